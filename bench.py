@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Benchmark of the phoneme_to_articulation hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--scaling weak|strong] [--per-gpu-batch b]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--scaling weak|strong] [--per-gpu-batch b] [--dump-outputs DIR]
 
 With --gpus N > 1 and no torchrun environment, bench.py starts the N ranks itself as CHILD processes
 (`python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ... bench.py ...`)
@@ -225,6 +225,27 @@ def self_launch(args):
     return subprocess.call(cmd, env=env)
 
 
+DUMP_LIMIT_BYTES = 64 * 10**6   # --dump-outputs: at most this much in all
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: write each array as out_dir/<name>.npy.  Should the arrays exceed DUMP_LIMIT_BYTES together, the
+    largest one is replaced by <name>_sample.npy, a fixed seeded sample of its elements (flat order) that fits the rest."""
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {k: np.ascontiguousarray(v) for k, v in arrays.items()}
+    header = 1024 * len(arrays)   # room for the .npy headers
+    total = sum(a.nbytes for a in arrays.values())
+    if total + header > DUMP_LIMIT_BYTES:
+        big = max(arrays, key=lambda k: arrays[k].nbytes)
+        a = arrays.pop(big).reshape(-1)
+        keep = (DUMP_LIMIT_BYTES - header - (total - a.nbytes)) // a.itemsize
+        idx = np.sort(np.random.default_rng(0).choice(a.size, size=keep, replace=False))
+        arrays[big + "_sample"] = a[idx]
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    log(f"outputs of the last timed step -> {out_dir}: " + ", ".join(f"{k} {tuple(a.shape)}" for k, a in arrays.items()))
+
+
 def make_batch(n_utt, seed):
     g = torch.Generator().manual_seed(seed)
     tokens = torch.randint(1, V, (n_utt, T), generator=g)
@@ -248,7 +269,12 @@ def main():
     ap.add_argument("--no-profile", action="store_true", help="skip the instrumented pass (roofline = null)")
     ap.add_argument("--no-extras", action="store_true", help="skip the configs[3] / configs[4] measurements (N = 1)")
     ap.add_argument("--no-exact", action="store_true", help="skip the second run on the exact fp32 matrix instruction (N = 1)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (rank 0: contours, loss, flat gradients, "
+                         "updated flat parameters; float32) as DIR/<name>.npy, at most 64 MB in all")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         raise SystemExit(self_launch(args))
@@ -294,8 +320,9 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
 
-    def measure(mode, b_one=None):
-        """W warm-up + K timed steps of `mode`; returns (elapsed max over ranks, loss, TrainStep, inputs)."""
+    def measure(mode, b_one=None, dump=False):
+        """W warm-up + K timed steps of `mode`; returns (elapsed max over ranks, loss, TrainStep, inputs).
+        dump: rank 0 writes the outputs of the last timed step to --dump-outputs (before any other run reuses the buffers)."""
         model.flat.data.copy_(flat0)  # every run starts from the same parameters
         if mode == "weak":     # each rank holds its own batch of B utterances (b_one: --per-gpu-batch, N = 1)
             tokens, targets, lengths = make_batch(b_one or B, seed=1 + rank)
@@ -330,6 +357,9 @@ def main():
             elapsed = float(tt.item())
             dist.all_reduce(loss_t)  # shard losses are scaled by the global frame count: their SUM is the batch loss
         loss = float(loss_t.item())
+        if dump and rank == 0:
+            dump_outputs(args.dump_outputs, {"contours": step.out.cpu().numpy(), "loss": loss_t.cpu().numpy(),
+                                             "grads": step.grads.cpu().numpy(), "params": model.flat.data.cpu().numpy()})
         assert np.isfinite(loss), "loss is not finite"
         frames = b_local * T * world * args.steps
         rec = {"scaling": mode, "value": round(frames / elapsed, 1), "ms_per_step": round(1e3 * elapsed / args.steps, 4),
@@ -341,7 +371,7 @@ def main():
     runs = {}
     head_step = head_inputs = None
     for m in modes:
-        rec, st, inp = measure(m, args.per_gpu_batch if world == 1 else None)
+        rec, st, inp = measure(m, args.per_gpu_batch if world == 1 else None, dump=(m == args.scaling and args.dump_outputs is not None))
         runs[m] = rec
         if m == args.scaling:
             head_step, head_inputs = st, inp

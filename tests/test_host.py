@@ -432,3 +432,26 @@ def test_bench_self_launch_builds_a_child_torchrun_command(monkeypatch):
     monkeypatch.setattr(bench.torch.cuda, "device_count", lambda: 1)
     with pytest.raises(SystemExit):
         bench.self_launch(args)                               # 8 ranks on one card: refused
+
+
+def test_bench_dump_outputs_writes_npy_within_the_size_limit(tmp_path):
+    """`bench.py --dump-outputs DIR`: every array as DIR/<name>.npy, dtype kept; over 64 MB in all the largest array becomes
+    <name>_sample.npy, the same seeded sample of its elements on every call, and the files stay within the limit."""
+    import importlib
+    bench = importlib.import_module("bench")
+    rng = np.random.default_rng(1)
+    small = {"contours": rng.random((4, 8, 11, 2, 50), dtype=np.float32), "loss": np.float32([0.25]),
+             "grads": rng.random(1000, dtype=np.float32)}
+    bench.dump_outputs(str(tmp_path / "a"), small)
+    assert sorted(os.listdir(tmp_path / "a")) == ["contours.npy", "grads.npy", "loss.npy"]
+    for k, v in small.items():
+        got = np.load(tmp_path / "a" / f"{k}.npy")
+        assert got.dtype == v.dtype and np.array_equal(got, v)
+    big = {"contours": np.arange(10_000_000, dtype=np.float64), "params": rng.random(1000)}
+    for d in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / d), big)
+        assert sorted(os.listdir(tmp_path / d)) == ["contours_sample.npy", "params.npy"]
+        assert sum(os.path.getsize(tmp_path / d / f) for f in os.listdir(tmp_path / d)) <= bench.DUMP_LIMIT_BYTES
+    s = np.load(tmp_path / "b" / "contours_sample.npy")
+    assert np.array_equal(s, np.load(tmp_path / "c" / "contours_sample.npy")) and (np.diff(s) > 0).all()
+    assert np.array_equal(np.load(tmp_path / "b" / "params.npy"), big["params"])
