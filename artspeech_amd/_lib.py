@@ -57,6 +57,16 @@ class Gemm(C.Structure):
                 ("k_seg", C.c_int32), ("a_seg_off", C.c_void_p), ("b_seg_off", C.c_void_p), ("k_tri", C.c_int32)]
 
 
+class MultiMlp(C.Structure):
+    _fields_ = [("groups", C.c_int32), ("rows", C.c_int32), ("layers", C.c_int32), ("h1", C.c_int32), ("h2", C.c_int32),
+                ("k_max", C.c_int32), ("n_max", C.c_int32), ("latent", C.c_int32),
+                ("dims", C.c_void_p), ("params", C.c_void_p), ("in_mode", C.c_int32), ("in_scale", C.c_float),
+                ("x", C.c_void_p), ("x_r", C.c_int64), ("x_g", C.c_int64), ("in_idx", C.c_void_p),
+                ("out_mode", C.c_int32), ("act", C.c_int32), ("y", C.c_void_p), ("y_r", C.c_int64), ("y_g", C.c_int64),
+                ("out_idx", C.c_void_p), ("own_ptr", C.c_void_p), ("own", C.c_void_p), ("win", C.c_void_p),
+                ("ws", C.c_void_p), ("ws_floats", C.c_int64), ("dy", C.c_void_p), ("dx", C.c_void_p), ("dparams", C.c_void_p)]
+
+
 _P, _I32, _I64, _F, _D = C.c_void_p, C.c_int32, C.c_int64, C.c_float, C.c_double
 _DIMS, _LAY = C.POINTER(Dims), C.POINTER(Layout)
 
@@ -125,6 +135,13 @@ PROTOTYPES = {
     "as_gather_pad_rows": (_I32, [_P, _P, _P, _I32, _I32, _I64, _I32, _D, _P, _P]),
     "as_lin_debug_stamps": (None, [_P, _I64]),
     "as_gru_debug_stamps": (None, [_P]),
+    "as_multi_mlp_supported": (_I32, [_I32, _I32, _I32, _I32, _I32]),
+    "as_multi_mlp_param_floats": (_I64, [_I32, _I32, _I32, _I32, _I32]),
+    "as_multi_mlp_workspace_floats": (_I64, [C.POINTER(MultiMlp), _I32]),
+    "as_multi_mlp_fwd": (_I32, [C.POINTER(MultiMlp), _P]),
+    "as_multi_mlp_bwd": (_I32, [C.POINTER(MultiMlp), _P]),
+    "as_masked_mse_partials": (_I32, []),
+    "as_masked_mse_fwd_bwd": (_I32, [_P, _P, _I64, _I64, _P, _I32, _P, _F, _P, _P, _P, _P]),
     "as_profile_enable": (None, [_I32]),
     "as_profile_reset": (None, []),
     "as_profile_report": (_I32, [C.c_char_p, _I32]),

@@ -34,6 +34,7 @@ SOURCES = {
     "conv.hip": [],
     "attention.hip": [],
     "metrics.hip": ["-ffp-contract=off"],
+    "multi_mlp.hip": [],
     "artspeech.hip": [],
 }
 

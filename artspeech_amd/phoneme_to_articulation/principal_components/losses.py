@@ -1,13 +1,21 @@
-"""Critical-distance loss of the principal-components method (reference principal_components/losses.py:23-99): for every
+"""Losses of the principal-components method (reference principal_components/losses.py).
+
+``CriticalLoss`` (:23-99): for every
 tract variable the minimum pairwise distance between two predicted articulators per frame, averaged over the frames where
 the constriction is critical.  The reference materialises ``cdist`` (bs, T, N, N) per variable and takes ``min``; here one
 launch of the tract-variable tile kernel (``as_tract_variables_fwd``) yields the minima and their arg-min points for all
 variables and frames, and the backward sends the gradient to those two points (what ``torch.min`` / ``cdist`` do).
+
+``AutoencoderLoss2`` (:102-251) and ``RegularizedLatentsMSELoss2`` (:254-285): their masked / weighted mean squared errors are
+one pass each of ``as_masked_mse_fwd_bwd`` (loss and gradient together, deterministic sum), the frozen encoder / decoder the
+fused multi-articulator MLP kernel.
 """
 import torch
 import torch.nn as nn
 
 from ... import _lib
+from .models.autoencoder import Decoder, Encoder, MultiDecoder, MultiEncoder
+from .transforms import InputTransform
 
 LOWER_LIP, PHARYNX, SOFT_PALATE, TONGUE = "lower-lip", "pharynx", "soft-palate", "tongue"
 UPPER_INCISOR, UPPER_LIP = "upper-incisor", "upper-lip"
@@ -81,3 +89,114 @@ class CriticalLoss(nn.Module):
         pairs = torch.stack(sets, dim=2).reshape(bs * seq_len, 2 * len(self.TVs), 2, num_samples)
         critical = _MinPairDistance.apply(pairs).view(bs, seq_len, len(self.TVs)).permute(0, 2, 1)  # (bs, n_TVs, T)
         return critical[critical_mask.to(critical.device) == 1].mean()
+
+
+class _MaskedMSEFn(torch.autograd.Function):
+    """scale * sum_r w_r sum_f (a - b)^2 over rows [rows][feat]; w_r = [t < lengths[b]] (row r = b * T + t) and / or
+    row_weights[r].  The gradient w.r.t. a is written in the same pass; b is a target (no gradient)."""
+
+    @staticmethod
+    def forward(ctx, a, b, lengths_dev, T, row_weights, scale):
+        _lib.require_gpu(a, "a")
+        a, b = a.contiguous().float(), b.contiguous().float()
+        if a.shape != b.shape:
+            raise ValueError(f"shapes differ: {tuple(a.shape)} vs {tuple(b.shape)}")
+        L = _lib.lib()
+        rows = a.shape[0] * a.shape[1] if lengths_dev is not None else a.shape[0]   # (B, T, ...) or (rows, ...)
+        feat = a.numel() // rows
+        loss = torch.empty((), dtype=torch.float32, device=a.device)
+        grad = torch.empty_like(a) if ctx.needs_input_grad[0] else None
+        partial = torch.empty(L.as_masked_mse_partials(), dtype=torch.float32, device=a.device)
+        w = None if row_weights is None else row_weights.contiguous().float()
+        _lib.check(L.as_masked_mse_fwd_bwd(_lib.ptr(a), _lib.ptr(b), rows, feat, _lib.ptr(lengths_dev), int(T), _lib.ptr(w),
+                                           float(scale), _lib.ptr(loss), _lib.ptr(grad), _lib.ptr(partial), _lib.stream_ptr()),
+                   "as_masked_mse_fwd_bwd")
+        if grad is not None:
+            ctx.save_for_backward(grad)
+        return loss
+
+    @staticmethod
+    def backward(ctx, dloss):
+        (grad,) = ctx.saved_tensors
+        return grad * dloss, None, None, None, None, None
+
+
+def masked_mse(a, b, lengths):
+    """mean of (a - b)^2 over the valid frames (t < lengths[b]) of a, b (B, T, ...) and all their features: the
+    ``loss[padding_mask].mean()`` of AutoencoderLoss2 (losses.py:215-225).  lengths: host sequence / CPU tensor."""
+    lengths_cpu = torch.as_tensor(lengths, dtype=torch.int32).cpu()
+    B, T = a.shape[0], a.shape[1]
+    valid = int(lengths_cpu.sum())
+    feat = a.numel() // (B * T)
+    return _MaskedMSEFn.apply(a, b, lengths_cpu.to(a.device, non_blocking=True), T, None, 1.0 / (valid * feat))
+
+
+class AutoencoderLoss2(nn.Module):
+    """AutoencoderLoss adapted to several articulators (reference :102-251): beta1 * latent MSE (output_pcs against the frozen
+    encoder's tanh latents of the targets) + beta2 * shape MSE (the frozen decoder on rescale_factor * output_pcs against the
+    targets) + beta3 * CriticalLoss on the decoded shapes, means over the valid frames.  The phoneme-recognizer term (beta4)
+    needs a differentiable scorer, which this engine does not have: a ``recognizer`` is refused."""
+
+    def __init__(self, indices_dict, TVs, in_features, hidden_features, encoder_state_dict_filepath,
+                 decoder_state_dict_filepath, device, encoder_cls=Encoder, decoder_cls=Decoder, denormalize_fn=None,
+                 beta1=1.0, beta2=1.0, beta3=1.0, beta4=0.0, rescale_factor=1.0, recognizer=None, **kwargs):
+        super().__init__()
+        if recognizer is not None:
+            raise NotImplementedError("AutoencoderLoss2: the recognition term needs a backward through the phoneme "
+                                      "recognizer, which this engine does not provide (recognizer must be None)")
+        self.beta1, self.beta2, self.beta3, self.beta4 = self.normalize_betas([beta1, beta2, beta3, beta4])
+        encoder = MultiEncoder(indices_dict, in_features, hidden_features, encoder_cls=encoder_cls)
+        encoder.load_state_dict(torch.load(encoder_state_dict_filepath, map_location=device))
+        self.encode = InputTransform(transform=encoder, device=device, activation=torch.tanh)
+        decoder = MultiDecoder(indices_dict, in_features, hidden_features, decoder_cls=decoder_cls)
+        decoder.load_state_dict(torch.load(decoder_state_dict_filepath, map_location=device))
+        self.decode = InputTransform(transform=decoder, device=device)
+        self.rescale_factor = rescale_factor
+        articulators = sorted(indices_dict.keys())
+        self.critical = CriticalLoss(TVs, articulators, denormalize_fn)
+        self.recognizer = recognizer
+
+    @staticmethod
+    def normalize_betas(betas):
+        return betas
+
+    def forward(self, output_pcs, target_shapes, reference_arrays, lengths, critical_mask, voicing=None):
+        """output_pcs (B, T, n_pcs), target_shapes (B, T, n_articulators, 2, N), reference_arrays (B, T, 1, 2, N),
+        lengths (B,) on the host, critical_mask (B, n_TVs, T) -> scalar."""
+        _lib.require_gpu(output_pcs, "output_pcs")
+        bs, seq_len, num_articulators, _, num_samples = target_shapes.shape
+        with torch.no_grad():
+            target_pcs = self.encode.transform._forward(
+                target_shapes.reshape(bs * seq_len, num_articulators, 2 * num_samples), tanh=True)
+        target_pcs = target_pcs.reshape(bs, seq_len, -1)
+        output_shapes = self.decode.transform(output_pcs, scale=self.rescale_factor)
+        output_shapes = output_shapes.reshape(bs, seq_len, num_articulators, 2, num_samples)
+        latent_loss = masked_mse(output_pcs, target_pcs, lengths)
+        reconstruction_loss = masked_mse(output_shapes, target_shapes, lengths)
+        critical_loss = self.critical(output_shapes, target_shapes, reference_arrays, critical_mask)
+        return self.beta1 * latent_loss + self.beta2 * reconstruction_loss + self.beta3 * critical_loss
+
+
+class RegularizedLatentsMSELoss2(nn.Module):
+    """mean over (bs, A, F) of sample_weights[bs] * (outputs - target)^2 + alpha * the off-diagonal squared covariance of
+    each articulator's latents (reference :254-285).  The reference builds the covariance term through torch.tensor([...]),
+    which detaches it: it counts in the value, never in the gradient.  Kept so (on the device, no host sync)."""
+
+    def __init__(self, alpha, indices_dict):
+        super().__init__()
+        self.alpha = alpha
+        self.indices_dict = indices_dict
+
+    def forward(self, outputs, latents, target, sample_weights=None):
+        _lib.require_gpu(outputs, "outputs")
+        rows = outputs.shape[0]
+        scale = 1.0 / outputs.numel()
+        mse = _MaskedMSEFn.apply(outputs.reshape(rows, -1), target.reshape(rows, -1), None, 0, sample_weights, scale)
+        with torch.no_grad():
+            terms = []
+            for _, indices in self.indices_dict.items():
+                if len(indices) > 1:
+                    cov = torch.cov(latents.T[indices])
+                    terms.append(cov.square().sum() - cov.diag().square().sum())
+            cov_loss = torch.stack(terms).sum() if terms else torch.zeros((), device=outputs.device)
+        return mse + self.alpha * cov_loss

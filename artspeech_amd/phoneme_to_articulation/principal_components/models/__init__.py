@@ -1,6 +1,7 @@
 import torch.nn as nn
 
-from .autoencoder import Decoder, Encoder, MultiArticulatorAutoencoder, MultiDecoder, MultiEncoder  # noqa: F401
+from .autoencoder import (Decoder, DecoderType, Encoder, EncoderType, MultiArticulatorAutoencoder, MultiDecoder,  # noqa: F401
+                          MultiEncoder, PCADecoder, PCAEncoder)
 from .rnn import PrincipalComponentsArtSpeech, PrincipalComponentsPredictor  # noqa: F401
 
 

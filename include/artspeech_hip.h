@@ -519,6 +519,62 @@ int as_adam_step(float* params, const float* grads, float* exp_avg, float* exp_a
 int as_gather_pad_rows(const void* src, const int64_t* first_row, const int32_t* lengths, int32_t B, int32_t T,
                        int64_t row_elems, int32_t elem_bytes, double pad_value, void* out, void* stream);
 
+/* All articulator MLPs of a MultiEncoder / MultiDecoder in one launch per direction (principal_components/models/
+ * autoencoder.py:153-173 MultiEncoder.forward, :203-213 MultiDecoder.forward; the per-articulator stacks are Encoder / Decoder
+ * :83-111, layers = 3: Linear-ReLU-Linear-ReLU-Linear, and PCAEncoder / PCADecoder :10-80, layers = 1: one projection).
+ * Group g (sorted-articulator order) maps K_g = dims[2g] inputs through the hidden widths h1, h2 (common to all groups) to
+ * N_g = dims[2g + 1] outputs; params[6g + 2l], params[6g + 2l + 1] are the device addresses of W_l [wout][win] (row-major,
+ * nn.Linear's layout) and b_l [wout] (0: no bias).  k_max / n_max bound every K_g / N_g.
+ *   in_mode 0 (slice):  input_g[r][k] = x[r * x_r + g * x_g + k]                       (the encoder on (rows, A, 2N) targets)
+ *   in_mode 1 (gather): input_g[r][k] = in_scale * x[r * x_r + in_idx[g * k_max + k]]  (the decoder on the latent vector;
+ *                       in_scale is AutoencoderLoss2's rescale_factor, losses.py:204)
+ *   out_mode 0 (stack): y[r * y_r + g * y_g + n] = output_g[r][n]                       (the decoder's torch.concat)
+ *   out_mode 1 (max-scatter): y[r * y_r + j] = act(max over the groups g that own j of output_g[r][n], j = out_idx[g * n_max
+ *                       + n]), act 0 none / 1 tanh (MultiArticulatorAutoencoder.forward :251); ties go to the first group,
+ *                       as torch.max does; an index no group owns is -inf (tanh: -1, zero gradient).  win[r * latent + j]
+ *                       records the winning g * n_max + n (-1: none) for the backward.
+ * own_ptr [latent + 1] / own (CSR over the latent index j, entries in group order): the (g, n) = g * n_max + n that write j
+ * (max-scatter) or the (g, k) = g * k_max + k that read it (gather).  Gather input with max-scatter output is refused.
+ * Backward: dy in y's layout (max-scatter: the gradient of the activated latent; y = the forward's output, needed for tanh),
+ * dx (optional) in x's layout -- slice: only the slices are written; gather: every j < latent of each row, the readers summed
+ * in group order, times in_scale.  dparams (optional; NULL for frozen weights, InputTransform's requires_grad = False,
+ * transforms.py:5-14): [groups][as_multi_mlp_param_floats] = per layer W_l [wout_g][win_g] at the start of a slot of
+ * [wout_max][win_max], then b_l [wout_max].  Weight gradients are per-row-chunk partials summed in a fixed order; the hidden
+ * activations are recomputed from x, nothing is saved between the calls.  Exact fp32 FMA chains, no atomics: bit-identical
+ * across runs.  ws: as_multi_mlp_workspace_floats(p, backward) floats.  Limits: every width <= 256 and at most 96 KB of LDS
+ * per workgroup for the backward (weights + 32 rows of activations and their gradients): outside them both calls return
+ * AS_ERR_UNSUPPORTED before any launch (as_multi_mlp_supported tells in advance). */
+typedef struct as_multi_mlp {
+    int32_t groups, rows, layers, h1, h2, k_max, n_max, latent;
+    const int32_t* dims;
+    const int64_t* params;
+    int32_t in_mode; float in_scale;
+    const float* x; int64_t x_r, x_g;
+    const int32_t* in_idx;
+    int32_t out_mode, act;
+    float* y; int64_t y_r, y_g;
+    const int32_t* out_idx;
+    const int32_t* own_ptr; const int32_t* own;
+    int32_t* win;
+    float* ws; int64_t ws_floats;
+    const float* dy; float* dx; float* dparams;
+} as_multi_mlp;
+int32_t as_multi_mlp_supported(int32_t layers, int32_t k_max, int32_t h1, int32_t h2, int32_t n_max);
+int64_t as_multi_mlp_param_floats(int32_t layers, int32_t k_max, int32_t h1, int32_t h2, int32_t n_max);
+int64_t as_multi_mlp_workspace_floats(const as_multi_mlp* p, int32_t backward);
+int as_multi_mlp_fwd(const as_multi_mlp* p, void* stream);
+int as_multi_mlp_bwd(const as_multi_mlp* p, void* stream);
+
+/* Masked / weighted MSE with its gradient in one pass (nn.MSELoss(reduction="none") + mask / weights + mean of
+ * principal_components/losses.py:215-225 AutoencoderLoss2 and :274-279 RegularizedLatentsMSELoss2):
+ *   loss = scale * sum_r w_r sum_f (a[r][f] - b[r][f])^2,   grad[r][f] = 2 * scale * w_r * (a - b)
+ * w_r = [r % T < lengths[r / T]] if lengths != NULL (else 1), times row_weights[r] if given.  a, b, grad [rows][feat]
+ * contiguous; grad may be NULL; partial: as_masked_mse_partials() floats; the sum is per-workgroup partials, then one fixed-order
+ * final sum (deterministic). */
+int32_t as_masked_mse_partials(void);
+int as_masked_mse_fwd_bwd(const float* a, const float* b, int64_t rows, int64_t feat, const int32_t* lengths, int32_t T,
+                          const float* row_weights, float scale, float* loss, float* grad, float* partial, void* stream);
+
 /* Optional per-kernel-phase timing with HIP events recorded on the launch stream (for bench.py's
  * roofline object).  as_profile_report writes "name count total_ms\n" lines (NUL terminated, truncated
  * to buflen) and returns the untruncated length; it waits for the recorded events to complete. */
