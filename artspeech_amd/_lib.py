@@ -130,6 +130,11 @@ PROTOTYPES = {
     "as_lstm_bidir_fwd": (_I32, [_P, _P, _I64, _P, _P, _P, _I32, _I32, _I32, _P, _P, _P]),
     "as_lstm_bidir_bwd": (_I32, [_P, _P, _P, _P, _I32, _I32, _I32, _P, _P]),
     "as_gru_unidir_fwd": (_I32, [_P, _P, _P, _P, _I32, _I32, _I32, _P, _P]),
+    "as_gru_unidir_fwd_gates": (_I32, [_P, _P, _P, _P, _I32, _I32, _I32, _P, _P, _P]),
+    "as_gru_unidir_bwd": (_I32, [_P, _P, _P, _P, _P, _I32, _I32, _I32, _P, _P, _P]),
+    "as_ln_feat_gelu_bwd": (_I32, [_P, _P, _P, _P, _P, _P, _I64, _I32, _I32, _P]),
+    "as_conv3x3_stem_bwd": (_I32, [_P, _P, _P, _I64, _I64, _I64, _I64, _I32, _I32, _I32, _I32, _P]),
+    "as_gelu_bwd": (_I32, [_P, _P, _P, _P, _I64, _I32, _P]),
     "as_intersect_semipolar_grid": (_I32, [_P, _P, _I64, _I32, _I32, _I32, _P, _P, _P, _P]),
     "as_artspeech_wait_head_grads": (_I32, [_P, _P]),
     "as_gather_pad_rows": (_I32, [_P, _P, _P, _I32, _I32, _I64, _I32, _D, _P, _P]),

@@ -16,6 +16,11 @@
 //   ln_feat_gelu_kernel  : LayerNorm over the FEATURE axis d (the reference transposes (B, C, D, T) -> (B, C, T, D),
 //                          normalises, transposes back: deepspeech2.py:31-34) followed by exact GELU, in place of four
 //                          transposes and two elementwise passes; coalesced over c.
+// Backward (input gradients only: the scorer is frozen wherever it is differentiated, principal_components/losses.py):
+//   ln_feat_gelu_bwd_kernel : d/dx of ln_feat_gelu, mean and rstd recomputed from x; optional residual gradient added.
+//   conv3x3_stem_bwd_kernel : d/dx of the stem; the 32 -> 32 convolutions' data gradient is as_conv3x3_c32 itself over
+//                             flipped, transposed taps (see as_conv3x3_c32's header comment).
+//   gelu_bwd_kernel         : dy * gelu'(x), optionally times a per-column scale (a following affine LayerNorm's gamma).
 #include "as_common.h"
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
@@ -25,6 +30,10 @@ namespace {
 constexpr int CO = 32;  // output channels of every convolution of the scorer (deepspeech2.py:104)
 
 __device__ __forceinline__ float gelu_exact(float x) { return 0.5f * x * (1.0f + erff(x * 0.70710678118654752440f)); }
+// d gelu / dx = Phi(x) + x phi(x)
+__device__ __forceinline__ float gelu_exact_grad(float x) {
+    return 0.5f * (1.0f + erff(x * 0.70710678118654752440f)) + x * 0.39894228040143267794f * __expf(-0.5f * x * x);
+}
 
 __global__ __launch_bounds__(256) void conv3x3_mfma_kernel(const float* __restrict__ x, const float* __restrict__ w,
                                                            const float* __restrict__ bias, const float* __restrict__ res,
@@ -314,6 +323,153 @@ __global__ __launch_bounds__(256) void gelu_kernel(const float* __restrict__ x, 
     for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += stride) y[i] = gelu_exact(x[i]);
 }
 
+// Backward of ln_feat_gelu over one (r, c) column: with xhat = (x - mean) * rstd, a = xhat * gamma + beta and
+// g = dy * gelu'(a) * gamma (the gradient reaching xhat),  dx = rstd * (g - mean(g) - xhat * mean(g * xhat)) [+ res].
+// The column (x, then xhat) and g stay in registers: one read of x and dy, one write of dx.
+template <int MAXD>
+__global__ __launch_bounds__(256) void ln_feat_gelu_bwd_kernel(const float* __restrict__ x, const float* __restrict__ gamma,
+                                                               const float* __restrict__ beta, const float* __restrict__ dy,
+                                                               const float* __restrict__ res, float* __restrict__ dx, long R, int D,
+                                                               int Cc, float eps) {
+    const long col = (long)blockIdx.x * 256 + threadIdx.x;
+    if (col >= R * Cc) return;
+    const long r = col / Cc;
+    const int c = (int)(col - r * Cc);
+    const long o = r * D * Cc + c;
+    float v[MAXD], g[MAXD];
+    float s = 0.f;
+#pragma unroll
+    for (int d = 0; d < MAXD; ++d) {
+        const long e = o + (long)(d < D ? d : D - 1) * Cc;   // branch-free: all loads in flight together
+        v[d] = x[e];
+        g[d] = dy[e];
+    }
+#pragma unroll
+    for (int d = 0; d < MAXD; ++d) {
+        if (d >= D) v[d] = 0.f;
+        s += v[d];
+    }
+    const float mean = s / D;
+    float q = 0.f;
+#pragma unroll
+    for (int d = 0; d < MAXD; ++d) {
+        const float e = v[d] - mean;
+        q += d < D ? e * e : 0.f;
+    }
+    const float rs = 1.0f / sqrtf(q / D + eps);
+    float sg = 0.f, sgx = 0.f;
+#pragma unroll
+    for (int d = 0; d < MAXD; ++d) {
+        if (d < D) {
+            const float xh = (v[d] - mean) * rs;
+            const float ga = gamma[d];
+            const float gd = g[d] * gelu_exact_grad(xh * ga + beta[d]) * ga;
+            v[d] = xh;
+            g[d] = gd;
+            sg += gd;
+            sgx += gd * xh;
+        }
+    }
+    const float mg = sg / D, mgx = sgx / D;
+#pragma unroll
+    for (int d = 0; d < MAXD; ++d)
+        if (d < D) {
+            const long e = o + (long)d * Cc;
+            const float out = rs * (g[d] - mg - v[d] * mgx);
+            dx[e] = res ? out + res[e] : out;
+        }
+}
+
+// any D: the same arithmetic in four strided passes (x and dy re-read from the caches)
+__global__ __launch_bounds__(256) void ln_feat_gelu_bwd_loop_kernel(const float* __restrict__ x, const float* __restrict__ gamma,
+                                                                    const float* __restrict__ beta, const float* __restrict__ dy,
+                                                                    const float* __restrict__ res, float* __restrict__ dx, long R,
+                                                                    int D, int Cc, float eps) {
+    const long col = (long)blockIdx.x * 256 + threadIdx.x;
+    if (col >= R * Cc) return;
+    const long r = col / Cc;
+    const int c = (int)(col - r * Cc);
+    const long o = r * D * Cc + c;
+    float s = 0.f;
+    for (int d = 0; d < D; ++d) s += x[o + (long)d * Cc];
+    const float mean = s / D;
+    float q = 0.f;
+    for (int d = 0; d < D; ++d) {
+        const float e = x[o + (long)d * Cc] - mean;
+        q += e * e;
+    }
+    const float rs = 1.0f / sqrtf(q / D + eps);
+    float sg = 0.f, sgx = 0.f;
+    for (int d = 0; d < D; ++d) {
+        const long e = o + (long)d * Cc;
+        const float xh = (x[e] - mean) * rs;
+        const float gd = dy[e] * gelu_exact_grad(xh * gamma[d] + beta[d]) * gamma[d];
+        sg += gd;
+        sgx += gd * xh;
+    }
+    const float mg = sg / D, mgx = sgx / D;
+    for (int d = 0; d < D; ++d) {
+        const long e = o + (long)d * Cc;
+        const float xh = (x[e] - mean) * rs;
+        const float gd = dy[e] * gelu_exact_grad(xh * gamma[d] + beta[d]) * gamma[d];
+        const float out = rs * (gd - mg - xh * mgx);
+        dx[e] = res ? out + res[e] : out;
+    }
+}
+
+// Input gradient of the stem: dx[b][ci][d][t] = sum_tap sum_co w[tap][co][ci] * dy[b][t - kt][d - kd][co] (zero outside the
+// map).  Half a wave per position: lane c reads channel c of the (up to) nine neighbouring dy rows -- each row one coalesced
+// 128-byte line, re-read by the neighbours from the caches -- against its own 9 x CIN weights (registers for the whole
+// launch), and a fixed xor-butterfly over the 32 lanes sums the channels: deterministic.  dx goes to the forward's planar
+// strides, so with the adapter it lands in the (B, C, T, D) rows the adapter produced.
+template <int CIN>
+__global__ __launch_bounds__(256) void conv3x3_stem_bwd_kernel(const float* __restrict__ dy, const float* __restrict__ w,
+                                                               float* __restrict__ dx, int B, int D, int T, long sb, long sc, long sd,
+                                                               long st) {
+    const int c = threadIdx.x & 31;
+    float wr[9][CIN];
+#pragma unroll
+    for (int tap = 0; tap < 9; ++tap)
+#pragma unroll
+        for (int ci = 0; ci < CIN; ++ci) wr[tap][ci] = w[(tap * CO + c) * CIN + ci];
+    const long P = (long)B * D * T;
+    const long step = (long)gridDim.x * 8;
+    for (long p = (long)blockIdx.x * 8 + (threadIdx.x >> 5); p < P; p += step) {   // (half-wave uniform: the shuffles are whole)
+        const int d = (int)(p % D), t = (int)((p / D) % T);
+        const long b = p / ((long)D * T);
+        float acc[CIN];
+#pragma unroll
+        for (int ci = 0; ci < CIN; ++ci) acc[ci] = 0.f;
+#pragma unroll
+        for (int tap = 0; tap < 9; ++tap) {
+            const int dd = d - (tap / 3 - 1), tt = t - (tap % 3 - 1);
+            const bool ok = dd >= 0 && dd < D && tt >= 0 && tt < T;
+            float v = dy[ok ? ((b * T + tt) * D + dd) * CO + c : 0L];
+            v = ok ? v : 0.f;
+#pragma unroll
+            for (int ci = 0; ci < CIN; ++ci) acc[ci] = fmaf(wr[tap][ci], v, acc[ci]);
+        }
+        float mine = 0.f;
+#pragma unroll
+        for (int ci = 0; ci < CIN; ++ci) {
+            float a = acc[ci];
+#pragma unroll
+            for (int m = 16; m >= 1; m >>= 1) a += __shfl_xor(a, m, 32);
+            mine = c == ci ? a : mine;
+        }
+        if (c < CIN) dx[b * sb + c * sc + d * sd + t * st] = mine;
+    }
+}
+
+__global__ __launch_bounds__(256) void gelu_bwd_kernel(const float* dy, const float* __restrict__ x, const float* __restrict__ scale,
+                                                       float* dx, long n, int row_len) {   // dy == dx allowed
+    const long stride = (long)gridDim.x * 256;
+    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += stride) {
+        const float g = dy[i] * gelu_exact_grad(x[i]);
+        dx[i] = scale ? g * scale[i % row_len] : g;
+    }
+}
+
 }  // namespace
 
 extern "C" int as_conv3x3_c32(const float* x, const float* w, const float* bias, const float* res, float* y, int32_t B,
@@ -383,5 +539,48 @@ extern "C" int as_gelu(const float* x, float* y, int64_t n, void* stream) {
     if (blocks > 2048) blocks = 2048;
     hipLaunchKernelGGL(gelu_kernel, dim3((int)blocks), dim3(256), 0, (hipStream_t)stream, x, y, (long)n);
     AS_LAUNCH_CHECK("as_gelu");
+    return 0;
+}
+
+extern "C" int as_ln_feat_gelu_bwd(const float* x, const float* gamma, const float* beta, const float* dy, const float* res, float* dx,
+                                   int64_t rows, int32_t D, int32_t Cc, void* stream) {
+    AS_REQUIRE(x && gamma && beta && dy && dx && rows > 0 && D > 0 && Cc > 0, AS_ERR_BAD_ARG, "as_ln_feat_gelu_bwd: bad argument");
+    const dim3 grid(as_cdiv((long)rows * Cc, 256));
+    hipStream_t st = (hipStream_t)stream;
+    if (D <= 80)
+        hipLaunchKernelGGL(ln_feat_gelu_bwd_kernel<80>, grid, dim3(256), 0, st, x, gamma, beta, dy, res, dx, (long)rows, D, Cc, 1e-5f);
+    else
+        hipLaunchKernelGGL(ln_feat_gelu_bwd_loop_kernel, grid, dim3(256), 0, st, x, gamma, beta, dy, res, dx, (long)rows, D, Cc, 1e-5f);
+    AS_LAUNCH_CHECK("as_ln_feat_gelu_bwd");
+    return 0;
+}
+
+extern "C" int as_conv3x3_stem_bwd(const float* dy, const float* w, float* dx, int64_t sb, int64_t sc, int64_t sd, int64_t st,
+                                   int32_t B, int32_t T, int32_t D, int32_t Cin, void* stream) {
+    AS_REQUIRE(dy && w && dx && B > 0 && D > 0 && T > 0, AS_ERR_BAD_ARG, "as_conv3x3_stem_bwd: bad argument");
+    AS_REQUIRE(Cin >= 1 && Cin <= 4, AS_ERR_UNSUPPORTED, "as_conv3x3_stem_bwd: %d input planes (1 to 4 supported)", Cin);
+    const long P = (long)B * D * T;
+    const long blocks = as_cdiv(P, 8);
+    const dim3 grid((unsigned)(blocks < 16384 ? blocks : 16384));
+    hipStream_t s = (hipStream_t)stream;
+#define AS_STEM_BWD(CIN) \
+    hipLaunchKernelGGL(conv3x3_stem_bwd_kernel<CIN>, grid, dim3(256), 0, s, dy, w, dx, B, D, T, (long)sb, (long)sc, (long)sd, (long)st)
+    switch (Cin) {
+        case 1: AS_STEM_BWD(1); break;
+        case 2: AS_STEM_BWD(2); break;
+        case 3: AS_STEM_BWD(3); break;
+        default: AS_STEM_BWD(4);
+    }
+#undef AS_STEM_BWD
+    AS_LAUNCH_CHECK("as_conv3x3_stem_bwd");
+    return 0;
+}
+
+extern "C" int as_gelu_bwd(const float* dy, const float* x, const float* scale, float* dx, int64_t n, int32_t row_len, void* stream) {
+    AS_REQUIRE(dy && x && dx && n > 0 && (!scale || row_len > 0), AS_ERR_BAD_ARG, "as_gelu_bwd: bad argument");
+    long blocks = (n + 255) / 256;
+    if (blocks > 2048) blocks = 2048;
+    hipLaunchKernelGGL(gelu_bwd_kernel, dim3((int)blocks), dim3(256), 0, (hipStream_t)stream, dy, x, scale, dx, (long)n, row_len);
+    AS_LAUNCH_CHECK("as_gelu_bwd");
     return 0;
 }

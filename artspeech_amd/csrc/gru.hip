@@ -341,7 +341,9 @@ __global__ __launch_bounds__(LPU * H) void gru_bwd_kernel(const float* __restric
 // read-modify-write per lane and step, off the recurrence's dependency chain; each word has one owner lane, so the order
 // of additions is the frame order: reproducible) and stores it once at the end into part [B][V][2 * 3H]; dgi is not
 // touched.  A fixed-order reduction over the B tables follows (token_segsum_reduce_kernel).
-template <int H, bool TOK, int AHEAD>
+// ND: directions interleaved per frame in y / dy ([frame][ND][H]), gates ([frame][ND][4H]) and dgi / dgh ([frame][ND][3H]);
+// 2 = the bidirectional layer, 1 = a unidirectional one (its only direction walks the sequence backwards, as direction 0).
+template <int H, bool TOK, int AHEAD, int ND = 2>
 __global__ __launch_bounds__(4 * H) void gru_bwd_row_kernel(const float* __restrict__ dy, const float* __restrict__ y,
                                                             const float* __restrict__ gates, const float* __restrict__ w_hh,
                                                             const int* __restrict__ lengths, int T, float* __restrict__ dgi,
@@ -385,7 +387,7 @@ __global__ __launch_bounds__(4 * H) void gru_bwd_row_kernel(const float* __restr
     }
     for (long i = (long)len * 3 * H + tid; i < (long)T * 3 * H; i += NT) {  // padded frames feed the time-batched GEMMs as zeros
         const long t = i / (3 * H), c = i % (3 * H);
-        const long o = (((long)b * T + t) * 2 + dir) * 3 * H + c;
+        const long o = (((long)b * T + t) * ND + dir) * 3 * H + c;
         if constexpr (!TOK) dgi[o] = 0.f;
         dgh[o] = 0.f;
     }
@@ -416,19 +418,19 @@ __global__ __launch_bounds__(4 * H) void gru_bwd_row_kernel(const float* __restr
     const char* dy_c = reinterpret_cast<const char*>(dy);
     char* dgi_c = reinterpret_cast<char*>(dgi);
     char* dgh_c = reinterpret_cast<char*>(dgh);
-    const unsigned gto = (unsigned)(dir * 4 * H + k) * 4u;   // + frame * 8H * 4; planes at +0, +H, +2H, +3H floats
-    const unsigned yo = (unsigned)(dir * H + k) * 4u;        // + frame * 2H * 4   (y and dy)
+    const unsigned gto = (unsigned)(dir * 4 * H + k) * 4u;   // + frame * 4H * ND * 4; planes at +0, +H, +2H, +3H floats
+    const unsigned yo = (unsigned)(dir * H + k) * 4u;        // + frame * H * ND * 4   (y and dy)
     const int sel = pl < 2 ? pl : 2;                     // planes r, z, n; rows 2 and 3 of the quad store the same n word
-    const unsigned dgo = (unsigned)(dir * 3 * H + sel * H + k) * 4u;   // + frame * 6H * 4   (dgi and dgh)
+    const unsigned dgo = (unsigned)(dir * 3 * H + sel * H + k) * 4u;   // + frame * 3H * ND * 4   (dgi and dgh)
     struct In { float r, z, n, hn, hprev, dyv; bool has_prev; };
     auto load = [&](long fr, bool has_prev) {
         In v;
         const unsigned f = (unsigned)fr;
-        const float* gp = reinterpret_cast<const float*>(g_c + (f * (8u * H * 4u) + gto));
+        const float* gp = reinterpret_cast<const float*>(g_c + (f * (ND * 4u * H * 4u) + gto));
         v.r = gp[0]; v.z = gp[H]; v.n = gp[2 * H]; v.hn = gp[3 * H];
-        v.hprev = *reinterpret_cast<const float*>(y_c + ((f + (unsigned)(has_prev ? dt : 0)) * (2u * H * 4u) + yo));
+        v.hprev = *reinterpret_cast<const float*>(y_c + ((f + (unsigned)(has_prev ? dt : 0)) * (ND * H * 4u) + yo));
         v.has_prev = has_prev;
-        v.dyv = *reinterpret_cast<const float*>(dy_c + (f * (2u * H * 4u) + yo));
+        v.dyv = *reinterpret_cast<const float*>(dy_c + (f * (ND * H * 4u) + yo));
         return v;
     };
     // Reduce-scatter of the four partial sums over the 16 lanes of a DPP row: the lane at quad position qp needs only the
@@ -481,7 +483,7 @@ __global__ __launch_bounds__(4 * H) void gru_bwd_row_kernel(const float* __restr
         const float vi = dht * c_vi;
         const float vh = dht * c_vh;
         gbuf[cur][sel * H + k] = vh;
-        const unsigned dfo = (unsigned)fr * (6u * H * 4u) + dgo;
+        const unsigned dfo = (unsigned)fr * (ND * 3u * H * 4u) + dgo;
         if constexpr (!TOK) *reinterpret_cast<float*>(dgi_c + dfo) = vi;
         *reinterpret_cast<float*>(dgh_c + dfo) = vh;
         __syncthreads();
@@ -693,7 +695,7 @@ __global__ __launch_bounds__(GEN_THREADS) void gru_fwd_generic_kernel(const floa
 __global__ __launch_bounds__(GEN_THREADS) void gru_bwd_generic_kernel(const float* __restrict__ dy, const float* __restrict__ y,
                                                                      const float* __restrict__ gates, const float* __restrict__ w_hh,
                                                                      const int* __restrict__ lengths, int T, int H,
-                                                                     float* __restrict__ dgi, float* __restrict__ dgh) {
+                                                                     float* __restrict__ dgi, float* __restrict__ dgh, int nd) {
     extern __shared__ __attribute__((aligned(16))) float gsm[];   // g [3H], dh carried [H], dht * z [H], partial sums [4][H]
     float* gb = gsm;
     float* dhb = gsm + 3 * H;
@@ -703,7 +705,7 @@ __global__ __launch_bounds__(GEN_THREADS) void gru_bwd_generic_kernel(const floa
     const int len = lengths[b];
     for (long i = (long)len * 3 * H + tid; i < (long)T * 3 * H; i += GEN_THREADS) {   // padded frames feed time-batched GEMMs
         const long t = i / (3 * H), c = i % (3 * H);
-        const long o = (((long)b * T + t) * 2 + dir) * 3 * H + c;
+        const long o = (((long)b * T + t) * nd + dir) * 3 * H + c;
         dgi[o] = 0.f;
         dgh[o] = 0.f;
     }
@@ -719,18 +721,18 @@ __global__ __launch_bounds__(GEN_THREADS) void gru_bwd_generic_kernel(const floa
         const long frame = (long)b * T + t;
         const bool has_prev = s + 1 < len;
         for (int j = tid; j < H; j += GEN_THREADS) {
-            const float* gp = gates + (frame * 2 + dir) * 4L * H + j;
+            const float* gp = gates + (frame * nd + dir) * 4L * H + j;
             const float r = gp[0], z = gp[H], n = gp[2 * H], hn = gp[3 * H];
-            const float hprev = has_prev ? y[((frame + dt) * 2 + dir) * H + j] : 0.f;
-            const float dht = dhb[j] + dy[(frame * 2 + dir) * H + j];
+            const float hprev = has_prev ? y[((frame + dt) * nd + dir) * H + j] : 0.f;
+            const float dht = dhb[j] + dy[(frame * nd + dir) * H + j];
             const float dn = dht * (1.f - z);
             const float dz = dht * (hprev - n);
             const float dnt = dn * (1.f - n * n);
             const float g_r = dnt * hn * r * (1.f - r);
             const float g_z = dz * z * (1.f - z);
             const float g_hn = dnt * r;
-            float* di = dgi + (frame * 2 + dir) * 3L * H + j;
-            float* dh = dgh + (frame * 2 + dir) * 3L * H + j;
+            float* di = dgi + (frame * nd + dir) * 3L * H + j;
+            float* dh = dgh + (frame * nd + dir) * 3L * H + j;
             di[0] = g_r; di[H] = g_z; di[2 * H] = dnt;
             dh[0] = g_r; dh[H] = g_z; dh[2 * H] = g_hn;
             gb[j] = g_r; gb[H + j] = g_z; gb[2 * H + j] = g_hn;
@@ -878,15 +880,21 @@ extern "C" int as_gru_unidir_fwd(const float* gi, const float* w_hh, const float
     return gru_fwd_launch(gi, nullptr, 0, w_hh, b_hh, lengths, B, T, H, y, nullptr, 1, stream);
 }
 
+extern "C" int as_gru_unidir_fwd_gates(const float* gi, const float* w_hh, const float* b_hh, const int32_t* lengths, int32_t B,
+                                       int32_t T, int32_t H, float* y, float* gates, void* stream) {
+    AS_REQUIRE(gates, AS_ERR_BAD_ARG, "as_gru_unidir_fwd_gates: null pointer");
+    return gru_fwd_launch(gi, nullptr, 0, w_hh, b_hh, lengths, B, T, H, y, gates, 1, stream);
+}
+
 static int gru_bwd_launch(const float* dy, const float* y, const float* gates, const float* w_hh, const int32_t* lengths,
                           int32_t B, int32_t T, int32_t H, float* dgi, float* dgh, const int64_t* tokens, int64_t tok_stride,
-                          int32_t V, float* part, void* stream) {
+                          int32_t V, float* part, void* stream, int nd = 2) {
     AS_REQUIRE(dy && y && gates && w_hh && lengths && (dgi || tokens) && dgh, AS_ERR_BAD_ARG, "as_gru_bidir_bwd: null pointer");
     AS_REQUIRE(B > 0 && T > 0, AS_ERR_BAD_ARG, "as_gru_bidir_bwd: B=%d T=%d", B, T);
-    AS_REQUIRE(!tokens || (part && V > 0 && tok_stride >= T), AS_ERR_BAD_ARG, "as_gru_bidir_bwd: token table arguments");
-    AS_REQUIRE((long)B * T * 8 * H * 4 < (1L << 32), AS_ERR_UNSUPPORTED, "as_gru_bidir_bwd: B*T=%ld frames exceed the 32-bit offsets", (long)B * T);
+    AS_REQUIRE(!tokens || (part && V > 0 && tok_stride >= T && nd == 2), AS_ERR_BAD_ARG, "as_gru_bidir_bwd: token table arguments");
+    AS_REQUIRE((long)B * T * nd * 4 * H * 4 < (1L << 32), AS_ERR_UNSUPPORTED, "as_gru_bidir_bwd: B*T=%ld frames exceed the 32-bit offsets", (long)B * T);
     hipStream_t st = (hipStream_t)stream;
-    dim3 grid(B, 2);
+    dim3 grid(B, nd);
     // diagnostic stamps (as_gru_debug_stamps): 2 x (2 B workgroups x 4 words); launch k writes half k % 2, so that the two
     // backward recurrences of one training step (layer 1, then layer 0) can both be read afterwards
     unsigned long long* dbg_now = g_gru_dbg ? g_gru_dbg + (size_t)(g_gru_dbg_launch++ & 1u) * 8u * (size_t)B : nullptr;
@@ -894,23 +902,24 @@ static int gru_bwd_launch(const float* dy, const float* y, const float* gates, c
     static const bool unit_layout = AS_DIAG_SET("AS_GRU_BWD_UNIT");  // ablation: the 4-lanes-per-unit layout
 #endif
     hipEvent_t stop_ev = (H == 32 || H == 64 || H == 128) ? as_stop_event_take() : nullptr;
-    const size_t pad = gru_lds_pad(B * 2);
+    const size_t pad = gru_lds_pad(B * nd);
     const size_t need = tokens ? ((size_t)V * 3 * H + 4 * H + T) * sizeof(float) : 0;   // + one dummy word per lane + T offsets
 #ifdef AS_DIAG
     static const int ahead = AS_DIAG_INT("AS_GRU_AHEAD", 2);   // look-ahead of the operand loads (steps)
 #endif
-#define AS_GRU_BWD_ROW(HH, TK, AH)                                                                                            \
+#define AS_GRU_BWD_ROW_ND(HH, TK, AH, ND)                                                                                     \
     do {                                                                                                                      \
-        const bool big = gru_lds_attr(gru_bwd_row_kernel<HH, TK, AH>);                                                        \
+        const bool big = gru_lds_attr(gru_bwd_row_kernel<HH, TK, AH, ND>);                                                    \
         AS_REQUIRE(big || need <= 64 * 1024, AS_ERR_UNSUPPORTED, "as_gru_bidir_bwd: cannot reserve %zu bytes of LDS", need);   \
         const size_t shm = big && pad > need ? pad : need;                                                                    \
         if (stop_ev)   /* a fork event rides on this dispatch (gemm_internal.h, as_stop_event_set) */                         \
-            hipExtLaunchKernelGGL((gru_bwd_row_kernel<HH, TK, AH>), grid, dim3(4 * HH), (unsigned)shm, st, nullptr, stop_ev, 0, dy, y, \
-                                  gates, w_hh, lengths, T, dgi, dgh, dbg_now, tokens, (long)tok_stride, V, part);             \
+            hipExtLaunchKernelGGL((gru_bwd_row_kernel<HH, TK, AH, ND>), grid, dim3(4 * HH), (unsigned)shm, st, nullptr, stop_ev, 0, dy, \
+                                  y, gates, w_hh, lengths, T, dgi, dgh, dbg_now, tokens, (long)tok_stride, V, part);          \
         else                                                                                                                  \
-            hipLaunchKernelGGL((gru_bwd_row_kernel<HH, TK, AH>), grid, dim3(4 * HH), shm, st, dy, y, gates, w_hh,             \
+            hipLaunchKernelGGL((gru_bwd_row_kernel<HH, TK, AH, ND>), grid, dim3(4 * HH), shm, st, dy, y, gates, w_hh,         \
                                lengths, T, dgi, dgh, dbg_now, tokens, (long)tok_stride, V, part);                             \
     } while (0)
+#define AS_GRU_BWD_ROW(HH, TK, AH) AS_GRU_BWD_ROW_ND(HH, TK, AH, 2)
 #ifdef AS_DIAG   // other look-aheads and the 4-lanes-per-unit layout exist in the diagnostic build only
 #define AS_GRU_BWD(HH)                                                                                                        \
     if (tokens) {                                                                                                             \
@@ -925,7 +934,11 @@ static int gru_bwd_launch(const float* dy, const float* y, const float* gates, c
 #define AS_GRU_BWD(HH) \
     if (tokens) AS_GRU_BWD_ROW(HH, true, 2); else AS_GRU_BWD_ROW(HH, false, 2)
 #endif
-    switch (H) {
+    if (nd == 1 && (H == 32 || H == 64 || H == 128)) {   // unidirectional: the product look-ahead, no token table
+        if (H == 32) AS_GRU_BWD_ROW_ND(32, false, 2, 1);
+        else if (H == 64) AS_GRU_BWD_ROW_ND(64, false, 2, 1);
+        else AS_GRU_BWD_ROW_ND(128, false, 2, 1);
+    } else switch (H) {
         case 32: AS_GRU_BWD(32); break;
         case 64: AS_GRU_BWD(64); break;
         case 128: AS_GRU_BWD(128); break;
@@ -933,11 +946,12 @@ static int gru_bwd_launch(const float* dy, const float* y, const float* gates, c
             AS_REQUIRE(!tokens && dgi, AS_ERR_UNSUPPORTED, "as_gru_bidir_bwd: token sums need a hidden size in {32, 64, 128}");
             const size_t gshm = (size_t)9 * H * sizeof(float);
             AS_REQUIRE(H > 0 && H % 4 == 0 && gshm <= 64 * 1024, AS_ERR_UNSUPPORTED, "as_gru_bidir_bwd: hidden size %d (a multiple of 4 up to 1820)", H);
-            hipLaunchKernelGGL(gru_bwd_generic_kernel, grid, dim3(GEN_THREADS), gshm, st, dy, y, gates, w_hh, lengths, T, H, dgi, dgh);
+            hipLaunchKernelGGL(gru_bwd_generic_kernel, grid, dim3(GEN_THREADS), gshm, st, dy, y, gates, w_hh, lengths, T, H, dgi, dgh, nd);
         }
     }
 #undef AS_GRU_BWD
 #undef AS_GRU_BWD_ROW
+#undef AS_GRU_BWD_ROW_ND
     AS_LAUNCH_CHECK("as_gru_bidir_bwd");
     return 0;
 }
@@ -962,4 +976,10 @@ int as_gru_bidir_bwd_tokens(const float* dy, const float* y, const float* gates,
     if (!tokens || !as_gru_bwd_tokens_fits(V, H, T)) return 0;
     const int rc = gru_bwd_launch(dy, y, gates, w_hh, lengths, B, T, H, nullptr, dgh, tokens, tok_stride, V, part, st);
     return rc == 0 ? 1 : rc;
+}
+
+extern "C" int as_gru_unidir_bwd(const float* dy, const float* y, const float* gates, const float* w_hh, const int32_t* lengths,
+                                 int32_t B, int32_t T, int32_t H, float* dgi, float* dgh, void* stream) {
+    AS_REQUIRE(dgi, AS_ERR_BAD_ARG, "as_gru_unidir_bwd: null pointer");
+    return gru_bwd_launch(dy, y, gates, w_hh, lengths, B, T, H, dgi, dgh, nullptr, 0, 0, nullptr, stream, 1);
 }

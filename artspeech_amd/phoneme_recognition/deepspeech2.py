@@ -15,6 +15,13 @@ called.  ``DeepSpeech2.forward`` runs (deepspeech2.py:159-195)
 on channels-last feature maps ``[B][T][D][32]``: a frame's 32*D features are one contiguous row, so the reference's
 ``view(B, C*D, T).permute(2, 0, 1)`` (:183-185) costs nothing -- the Linear weight's columns are permuted once instead.
 Inference only (``eval()`` mode, the way ``phoneme_recognition/__init__.py:213-236`` scores); there is no CPU path.
+
+Input gradients (a FROZEN scorer inside a loss, principal_components/losses.py:228-243): when grad mode is on and ``x``
+requires grad, ``forward`` runs through ``_ScorerInputGrad``, which keeps the activations its backward needs (block inputs
+and pre-LN2 maps, GRU outputs and gates, row-LayerNorm ``xhat`` / ``rstd``) and returns the same values, bit for bit.  Its
+backward walks the layers in reverse on the HIP library: as_gemm_f32 for every dX = dY . W, as_gelu_bwd /
+as_layernorm_bwd, as_gru_unidir_bwd, as_conv3x3_c32 over flipped taps, as_ln_feat_gelu_bwd and as_conv3x3_stem_bwd.  The
+scorer's own parameters get no gradient: if any of them requires grad, that path raises instead.
 """
 import ctypes as C
 
@@ -70,7 +77,7 @@ def _slab(dev):
 
 
 def _gemm(A, W, bias, out, act=0, split_k=False):
-    """out[M][N] = act(A[M][K] . W[N][K]^T + bias).  split_k (act == 0 only): few output tiles under a long reduction --
+    """out[M][N] = act(A[M][K] . W[N][K]^T + bias) (bias None: none).  split_k (act == 0 only): few output tiles under a long reduction --
     the bias is laid down first and the GEMM accumulates onto it, its K range split over workgroups (deterministic slabs)."""
     assert A.is_contiguous() and W.is_contiguous() and out.is_contiguous(), "bare pointers below: dense row-major operands"
     g = _lib.Gemm()
@@ -82,18 +89,56 @@ def _gemm(A, W, bias, out, act=0, split_k=False):
         out.copy_(bias.expand_as(out))
         slab = _slab(out.device)
         g.accumulate, g.splitk_ws, g.splitk_ws_floats = 1, slab.data_ptr(), slab.numel()
-    else:
+    elif bias is not None:
         g.bias = bias.data_ptr()
     _lib.check(_lib.lib().as_gemm_f32(C.byref(g), _lib.stream_ptr()), "as_gemm_f32")
     return out
 
 
-def _ln(x, ln, out):
+def _ln(x, ln, out, keep=None):
+    """out = LayerNorm(x) (affine); keep: a list that receives the normalised rows xhat and their rstd (for the backward)."""
     rows, D = x.shape
     assert x.is_contiguous() and out.is_contiguous(), "bare pointers below: dense row-major operands"
-    _lib.check(_lib.lib().as_layernorm_fwd(_lib.ptr(x), None, _lib.ptr(ln.weight), _lib.ptr(ln.bias), _lib.ptr(out), None, None,
-                                           rows, D, 0, _lib.stream_ptr()), "as_layernorm_fwd")
+    xhat = rstd = None
+    if keep is not None:
+        xhat, rstd = torch.empty_like(x), torch.empty(rows, device=x.device, dtype=torch.float32)
+        keep += [xhat, rstd]
+    _lib.check(_lib.lib().as_layernorm_fwd(_lib.ptr(x), None, _lib.ptr(ln.weight), _lib.ptr(ln.bias), _lib.ptr(out), _lib.ptr(xhat),
+                                           _lib.ptr(rstd), rows, D, 0, _lib.stream_ptr()), "as_layernorm_fwd")
     return out
+
+
+def _ln_bwd(dxhat, xhat, rstd, out):
+    rows, D = xhat.shape
+    _lib.check(_lib.lib().as_layernorm_bwd(_lib.ptr(dxhat), _lib.ptr(xhat), _lib.ptr(rstd), None, _lib.ptr(out), rows, D,
+                                           _lib.stream_ptr()), "as_layernorm_bwd")
+    return out
+
+
+def _gelu_bwd(dy, x, scale, out):
+    _lib.check(_lib.lib().as_gelu_bwd(_lib.ptr(dy), _lib.ptr(x), _lib.ptr(scale), _lib.ptr(out), dy.numel(),
+                                      scale.numel() if scale is not None else 0, _lib.stream_ptr()), "as_gelu_bwd")
+    return out
+
+
+class _ScorerInputGrad(torch.autograd.Function):
+    """(x, voicing) -> (logits, features) of a frozen DeepSpeech2 in eval mode, differentiable with respect to x only."""
+
+    @staticmethod
+    def forward(ctx, x, voicing, model):
+        saved = {}
+        logits, features = model._run(x, voicing, saved)
+        ctx.model, ctx.saved, ctx.x_dtype = model, saved, x.dtype
+        ctx.set_materialize_grads(False)
+        return logits, features
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dlogits, dfeatures):
+        if dlogits is None and dfeatures is None:
+            return None, None, None
+        dx = ctx.model._input_grad(ctx.saved, dlogits, dfeatures)
+        return dx.to(ctx.x_dtype), None, None
 
 
 def top1_phonemes(logits):
@@ -119,6 +164,7 @@ class DeepSpeech2(nn.Module):
         self.dropout_p = dropout  # nn.Dropout holds no state; eval-mode forward never applies it
         self.num_features, self.hidden, self.num_classes, self.in_channels = num_features, rnn_hidden_size, num_classes, in_channels
         self._prepared = None
+        self._prepared_bwd = None
 
     @property
     def total_parameters(self):
@@ -148,13 +194,48 @@ class DeepSpeech2(nn.Module):
                      # column c*D + d of the reference's (B, C*D, T) view -> column d*32 + c of a channels-last frame row
                      linear=self.linear.weight.view(self.hidden, OUT_CHANNELS, D).permute(0, 2, 1).reshape(self.hidden, -1).contiguous())
         self._prepared = (key, w, keep)
+        self._prepared_bwd = None
         return w
 
+    def _prepare_bwd(self):
+        """Operands of the input gradient, cached like _prepare: every dX = dY . W as out = dY . W'^T with W' = W^T dense;
+        the gammas of the adapter's LayerNorms folded into the Linear behind them (its dX is then d xhat); the 32 -> 32
+        convolutions' taps flipped and transposed, w'[kd][kt][ci][co] = w[2 - kd][2 - kt][co][ci] (their data gradient is the
+        same convolution); a zero bias for as_conv3x3_c32, which requires one."""
+        w = self._prepare()
+        if self._prepared_bwd is not None:
+            return self._prepared_bwd
+        with torch.no_grad():
+            tr = lambda m: m.t().contiguous()
+            flip = lambda conv: conv.weight.flip(2, 3).transpose(0, 1).permute(2, 3, 0, 1).contiguous()
+            wb = dict(classifier=tr(self.classifier.weight), fe=tr(self.feature_extractor[0].weight),
+                      w_ih=[tr(blk.rnn.weight_ih_l0) for blk in self.recurrent_layers], linear=tr(w["linear"]),
+                      res=[(flip(r.cnn1), flip(r.cnn2)) for r in self.residual_layers],
+                      zero_bias=torch.zeros(OUT_CHANNELS, device=self.cnn.weight.device, dtype=torch.float32))
+            if self.adapter is not None:
+                ad = self.adapter.adapter
+                wb["adapter"] = (tr(ad[1].weight * ad[0].weight[None, :]), tr(ad[3].weight * ad[2].weight[None, :]))
+        self._prepared_bwd = wb
+        return wb
+
     def forward(self, x, voicing=None, return_features=False):
-        """x (B, C, D, T) float32 on the GPU, voicing (B, T) or None -> logits (B, T, classes) [, features (B, T, H)]."""
+        """x (B, C, D, T) float32 on the GPU, voicing (B, T) or None -> logits (B, T, classes) [, features (B, T, H)].
+        Differentiable with respect to x (only) when grad mode is on and x requires grad."""
         if self.training:
             raise RuntimeError("DeepSpeech2 (HIP): inference only -- call .eval() (the reference scores in eval mode)")
         _lib.require_gpu(x, "x")
+        if torch.is_grad_enabled() and x.requires_grad:
+            if any(p.requires_grad for p in self.parameters()):
+                raise NotImplementedError(
+                    "DeepSpeech2 (HIP): gradients reach the scorer's input only, not its parameters -- freeze the recognizer "
+                    "(`for p in recognizer.parameters(): p.requires_grad = False`, as the reference trainer does)")
+            logits, features = _ScorerInputGrad.apply(x, voicing, self)
+        else:
+            logits, features = self._run(x, voicing)
+        return (logits, features) if return_features else logits
+
+    def _run(self, x, voicing, keep=None):
+        """The forward on the HIP library; keep (a dict) receives what _input_grad needs."""
         L, st = _lib.lib(), _lib.stream_ptr()
         B, Cin, Din, T = x.shape
         assert Cin == self.in_channels
@@ -162,15 +243,17 @@ class DeepSpeech2(nn.Module):
         dev, f32 = x.device, torch.float32
         w = self._prepare()
         D, H = self.num_features, self.hidden
+        kad = None
         with torch.no_grad():
             if self.adapter is not None:
                 ad = self.adapter.adapter
                 # the reference's own transpose (:84); glue copy of the input.  (.contiguous(): with B = C = 1 the reshape of the
                 # transposed view is itself a VIEW with strides (1, T) -- the kernels below take bare pointers)
                 rows = x.transpose(2, 3).reshape(B * Cin * T, Din).contiguous()
-                a = _ln(rows, ad[0], torch.empty_like(rows))
+                kad = [] if keep is not None else None
+                a = _ln(rows, ad[0], torch.empty_like(rows), kad)
                 a = _gemm(a, ad[1].weight, ad[1].bias, torch.empty(rows.shape[0], D, device=dev, dtype=f32))
-                a = _ln(a, ad[2], torch.empty_like(a))
+                a = _ln(a, ad[2], torch.empty_like(a), kad)
                 planes = _gemm(a, ad[3].weight, ad[3].bias, torch.empty_like(a))  # (B, C, T, D)
                 strides = (Cin * T * D, T * D, 1, D)
             else:
@@ -184,7 +267,11 @@ class DeepSpeech2(nn.Module):
                                          _lib.ptr(voicing) if voicing is not None else None, _lib.ptr(fmap), B, T, D, Cin, st),
                        "as_conv3x3_stem")
             act, mid = torch.empty_like(fmap), torch.empty_like(fmap)
+            kres = []
             for r, (w1, w2) in zip(self.residual_layers, w["res"]):
+                if keep is not None:   # the block's input and its pre-LN2 map
+                    mid = torch.empty_like(fmap)
+                    kres.append((fmap, mid))
                 _lib.check(L.as_ln_feat_gelu(_lib.ptr(fmap), _lib.ptr(r.layer_norm1.weight), _lib.ptr(r.layer_norm1.bias), _lib.ptr(act),
                                              B * T, D, OUT_CHANNELS, st), "as_ln_feat_gelu")
                 _lib.check(L.as_conv3x3_c32(_lib.ptr(act), _lib.ptr(w1), _lib.ptr(r.cnn1.bias), None, _lib.ptr(mid), B, T, D, st),
@@ -199,16 +286,96 @@ class DeepSpeech2(nn.Module):
                       split_k=True)  # K = 32 * D (2560) against N = H (64) columns
             lengths = torch.full((B,), T, dtype=torch.int32, device=dev)
             gi = torch.empty(B * T, 3 * H, device=dev, dtype=f32)
+            krnn = []
             for blk in self.recurrent_layers:
-                a = _ln(h, blk.layer_norm, torch.empty_like(h))
-                _lib.check(L.as_gelu(_lib.ptr(a), _lib.ptr(a), a.numel(), st), "as_gelu")
-                _gemm(a, blk.rnn.weight_ih_l0, blk.rnn.bias_ih_l0, gi)
-                h = torch.empty_like(h)
-                _lib.check(L.as_gru_unidir_fwd(_lib.ptr(gi), _lib.ptr(blk.rnn.weight_hh_l0), _lib.ptr(blk.rnn.bias_hh_l0),
-                                               _lib.ptr(lengths), B, T, H, _lib.ptr(h), st), "as_gru_unidir_fwd")
+                if keep is None:
+                    a = _ln(h, blk.layer_norm, torch.empty_like(h))
+                    _lib.check(L.as_gelu(_lib.ptr(a), _lib.ptr(a), a.numel(), st), "as_gelu")
+                    _gemm(a, blk.rnn.weight_ih_l0, blk.rnn.bias_ih_l0, gi)
+                    h = torch.empty_like(h)
+                    _lib.check(L.as_gru_unidir_fwd(_lib.ptr(gi), _lib.ptr(blk.rnn.weight_hh_l0), _lib.ptr(blk.rnn.bias_hh_l0),
+                                                   _lib.ptr(lengths), B, T, H, _lib.ptr(h), st), "as_gru_unidir_fwd")
+                else:   # the same values, keeping the LayerNorm's xhat / rstd, the GELU's input and the GRU's gates
+                    kln = []
+                    a = _ln(h, blk.layer_norm, torch.empty_like(h), kln)
+                    ag = torch.empty_like(a)
+                    _lib.check(L.as_gelu(_lib.ptr(a), _lib.ptr(ag), a.numel(), st), "as_gelu")
+                    _gemm(ag, blk.rnn.weight_ih_l0, blk.rnn.bias_ih_l0, gi)
+                    h = torch.empty_like(h)
+                    gates = torch.empty(B * T, 4 * H, device=dev, dtype=f32)
+                    _lib.check(L.as_gru_unidir_fwd_gates(_lib.ptr(gi), _lib.ptr(blk.rnn.weight_hh_l0), _lib.ptr(blk.rnn.bias_hh_l0),
+                                                         _lib.ptr(lengths), B, T, H, _lib.ptr(h), _lib.ptr(gates), st),
+                               "as_gru_unidir_fwd_gates")
+                    krnn.append((kln[0], kln[1], a, h, gates))
             fe = self.feature_extractor[0]
             features = _gemm(h, fe.weight, fe.bias, torch.empty_like(h), act=3)
             logits = _gemm(features, self.classifier.weight, self.classifier.bias,
                            torch.empty(B * T, self.num_classes, device=dev, dtype=f32))
-        logits, features = logits.view(B, T, -1), features.view(B, T, H)
-        return (logits, features) if return_features else logits
+            if keep is not None:
+                keep.update(shape=(B, Cin, Din, T), planes=(tuple(planes.shape), strides), adapter=kad, res=kres, rnn=krnn,
+                            lengths=lengths, fe_pre=_gemm(h, fe.weight, fe.bias, torch.empty_like(h)))
+        return logits.view(B, T, -1), features.view(B, T, H)
+
+    def _input_grad(self, saved, dlogits, dfeatures):
+        """d(logits, features) -> dx (B, C, D, T): the layers of _run in reverse (no parameter gradients)."""
+        L, st = _lib.lib(), _lib.stream_ptr()
+        wb = self._prepare_bwd()
+        w = self._prepare()
+        B, Cin, Din, T = saved["shape"]
+        D, H, M = self.num_features, self.hidden, B * T
+        dev, f32 = saved["lengths"].device, torch.float32
+        with torch.no_grad():
+            # features = gelu(h W_fe^T + b_fe); logits = features W_cls^T + b_cls
+            if dlogits is not None:
+                df = _gemm(dlogits.reshape(M, -1).float().contiguous(), wb["classifier"], None, torch.empty(M, H, device=dev, dtype=f32))
+                if dfeatures is not None:
+                    dfc = dfeatures.reshape(M, H).float().contiguous()
+                    _lib.check(L.as_add(_lib.ptr(df), _lib.ptr(dfc), _lib.ptr(df), df.numel(), st), "as_add")
+            else:
+                df = dfeatures.reshape(M, H).float().contiguous().clone()
+            _gelu_bwd(df, saved["fe_pre"], None, df)
+            dh = _gemm(df, wb["fe"], None, torch.empty(M, H, device=dev, dtype=f32))
+            # recurrent blocks: h_out = GRU(gelu(LN(h_in)))
+            dgi = torch.empty(M, 3 * H, device=dev, dtype=f32)
+            dgh = torch.empty_like(dgi)
+            da = torch.empty(M, H, device=dev, dtype=f32)
+            for blk, w_ih_t, (xhat, rstd, a, h_out, gates) in zip(reversed(self.recurrent_layers), reversed(wb["w_ih"]),
+                                                                  reversed(saved["rnn"])):
+                _lib.check(L.as_gru_unidir_bwd(_lib.ptr(dh), _lib.ptr(h_out), _lib.ptr(gates), _lib.ptr(blk.rnn.weight_hh_l0),
+                                               _lib.ptr(saved["lengths"]), B, T, H, _lib.ptr(dgi), _lib.ptr(dgh), st),
+                           "as_gru_unidir_bwd")
+                _gemm(dgi, w_ih_t, None, da)
+                _gelu_bwd(da, a, blk.layer_norm.weight, da)     # d xhat = d gelu-out * gelu'(a) * gamma
+                dh = _ln_bwd(da, xhat, rstd, torch.empty_like(da))
+            # Linear(32 D -> H) over the channels-last frame rows
+            dmap = _gemm(dh, wb["linear"], None, torch.empty(M, D * OUT_CHANNELS, device=dev, dtype=f32))
+            # residual blocks: out = conv2(lngelu2(conv1(lngelu1(in)))) + in
+            dact, dmid = torch.empty_like(dmap), torch.empty_like(dmap)
+            zb = wb["zero_bias"]
+            for r, (f1, f2), (fin, mid) in zip(reversed(self.residual_layers), reversed(wb["res"]), reversed(saved["res"])):
+                _lib.check(L.as_conv3x3_c32(_lib.ptr(dmap), _lib.ptr(f2), _lib.ptr(zb), None, _lib.ptr(dact), B, T, D, st),
+                           "as_conv3x3_c32")
+                _lib.check(L.as_ln_feat_gelu_bwd(_lib.ptr(mid), _lib.ptr(r.layer_norm2.weight), _lib.ptr(r.layer_norm2.bias),
+                                                 _lib.ptr(dact), None, _lib.ptr(dmid), M, D, OUT_CHANNELS, st), "as_ln_feat_gelu_bwd")
+                _lib.check(L.as_conv3x3_c32(_lib.ptr(dmid), _lib.ptr(f1), _lib.ptr(zb), None, _lib.ptr(dact), B, T, D, st),
+                           "as_conv3x3_c32")
+                nxt = torch.empty_like(dmap)
+                _lib.check(L.as_ln_feat_gelu_bwd(_lib.ptr(fin), _lib.ptr(r.layer_norm1.weight), _lib.ptr(r.layer_norm1.bias),
+                                                 _lib.ptr(dact), _lib.ptr(dmap), _lib.ptr(nxt), M, D, OUT_CHANNELS, st),
+                           "as_ln_feat_gelu_bwd")
+                dmap = nxt
+            # stem: into the planes the forward read (voicing gets no gradient)
+            pshape, strides = saved["planes"]
+            dplanes = torch.empty(pshape, device=dev, dtype=f32)
+            _lib.check(L.as_conv3x3_stem_bwd(_lib.ptr(dmap), _lib.ptr(w["stem"]), _lib.ptr(dplanes), *strides, B, T, D, Cin, st),
+                       "as_conv3x3_stem_bwd")
+            if self.adapter is None:
+                return dplanes
+            # adapter: LN0 -> Linear1 -> LN2 -> Linear3 over (B, C, T, D) rows; the gammas sit in the folded weights
+            xhat0, rstd0, xhat2, rstd2 = saved["adapter"]
+            w1g_t, w3g_t = wb["adapter"]
+            dxhat2 = _gemm(dplanes, w3g_t, None, torch.empty_like(dplanes))
+            dl1 = _ln_bwd(dxhat2, xhat2, rstd2, dxhat2)
+            dxhat0 = _gemm(dl1, w1g_t, None, torch.empty(dl1.shape[0], Din, device=dev, dtype=f32))
+            drows = _ln_bwd(dxhat0, xhat0, rstd0, dxhat0)
+            return drows.view(B, Cin, T, Din).transpose(2, 3)

@@ -14,6 +14,7 @@ import torch
 import torch.nn as nn
 
 from ... import _lib
+from ...phoneme_recognition.deepspeech2 import DeepSpeech2
 from .models.autoencoder import Decoder, Encoder, MultiDecoder, MultiEncoder
 from .transforms import InputTransform
 
@@ -134,16 +135,20 @@ def masked_mse(a, b, lengths):
 class AutoencoderLoss2(nn.Module):
     """AutoencoderLoss adapted to several articulators (reference :102-251): beta1 * latent MSE (output_pcs against the frozen
     encoder's tanh latents of the targets) + beta2 * shape MSE (the frozen decoder on rescale_factor * output_pcs against the
-    targets) + beta3 * CriticalLoss on the decoded shapes, means over the valid frames.  The phoneme-recognizer term (beta4)
-    needs a differentiable scorer, which this engine does not have: a ``recognizer`` is refused."""
+    targets) + beta3 * CriticalLoss on the decoded shapes, means over the valid frames, + beta4 * the phoneme-recognition term
+    when a ``recognizer`` (this engine's frozen DeepSpeech2) is given: the MSE, over the valid frames, between the scorer's
+    features of the decoded shapes and of the targets (reference :226-243, including its raw ``.view`` of the (B, T, A, 2, N)
+    shapes as (B, 2, A * N, T)).  The scorer runs in eval mode (no dropout); the reference leaves it in training mode."""
 
     def __init__(self, indices_dict, TVs, in_features, hidden_features, encoder_state_dict_filepath,
                  decoder_state_dict_filepath, device, encoder_cls=Encoder, decoder_cls=Decoder, denormalize_fn=None,
                  beta1=1.0, beta2=1.0, beta3=1.0, beta4=0.0, rescale_factor=1.0, recognizer=None, **kwargs):
         super().__init__()
         if recognizer is not None:
-            raise NotImplementedError("AutoencoderLoss2: the recognition term needs a backward through the phoneme "
-                                      "recognizer, which this engine does not provide (recognizer must be None)")
+            if not isinstance(recognizer, DeepSpeech2):
+                raise NotImplementedError("AutoencoderLoss2: the recognizer must be this engine's DeepSpeech2 (the only scorer "
+                                          f"with an input gradient here), got {type(recognizer).__name__}")
+            recognizer.eval()
         self.beta1, self.beta2, self.beta3, self.beta4 = self.normalize_betas([beta1, beta2, beta3, beta4])
         encoder = MultiEncoder(indices_dict, in_features, hidden_features, encoder_cls=encoder_cls)
         encoder.load_state_dict(torch.load(encoder_state_dict_filepath, map_location=device))
@@ -174,7 +179,20 @@ class AutoencoderLoss2(nn.Module):
         latent_loss = masked_mse(output_pcs, target_pcs, lengths)
         reconstruction_loss = masked_mse(output_shapes, target_shapes, lengths)
         critical_loss = self.critical(output_shapes, target_shapes, reference_arrays, critical_mask)
-        return self.beta1 * latent_loss + self.beta2 * reconstruction_loss + self.beta3 * critical_loss
+        if self.recognizer is None:
+            return self.beta1 * latent_loss + self.beta2 * reconstruction_loss + self.beta3 * critical_loss
+        recognition_loss = self._recognition(output_shapes, target_shapes, lengths, voicing)
+        return self.beta1 * latent_loss + self.beta2 * reconstruction_loss + self.beta3 * critical_loss + self.beta4 * recognition_loss
+
+    def _recognition(self, output_shapes, target_shapes, lengths, voicing):
+        bs, seq_len, n_art, chann, n_samples = target_shapes.shape
+        self.recognizer.eval()   # (a .train() of this module reaches the registered recognizer; the scorer is eval-only)
+        with torch.no_grad():
+            _, target_features = self.recognizer(target_shapes.contiguous().view(bs, chann, n_art * n_samples, seq_len), voicing,
+                                                 return_features=True)
+        _, output_features = self.recognizer(output_shapes.contiguous().view(bs, chann, n_art * n_samples, seq_len), voicing,
+                                             return_features=True)
+        return masked_mse(output_features, target_features, lengths)
 
 
 class RegularizedLatentsMSELoss2(nn.Module):

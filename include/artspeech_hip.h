@@ -498,6 +498,29 @@ int as_gelu(const float* x, float* y, int64_t n, void* stream);
 int as_gru_unidir_fwd(const float* gi, const float* w_hh, const float* b_hh, const int32_t* lengths, int32_t B, int32_t T,
                       int32_t H, float* y, void* stream);
 
+/* ---- input gradients of the scorer (DeepSpeech2 above, frozen: no weight gradients).  Feature maps [B][T][D][32]. ----
+ * as_gru_unidir_fwd_gates : as_gru_unidir_fwd, also keeping gates [B][T][4][H] = (r, z, n, W_hn h + b_hn) for the backward;
+ *                           y is exactly as_gru_unidir_fwd's.
+ * as_gru_unidir_bwd       : backward of that recurrence: dy [B][T][H] -> dgi, dgh [B*T][3H], the gradients of W_ih x + b_ih and
+ *                           W_hh h + b_hh (gate order r, z, n; zeros at t >= lengths[b]); the input gradient is dgi . W_ih.
+ * as_ln_feat_gelu_bwd     : backward of as_ln_feat_gelu: x is the forward's input (mean and rstd are recomputed), dy the
+ *                           gradient of its output; dx = d/dx + res (res NULL or [rows][D][C]: a residual gradient fused in).
+ * as_conv3x3_stem_bwd     : input gradient of as_conv3x3_stem (w [9][32][Cin], 1 <= Cin <= 4): dy [B][T][D][32] -> dx in the
+ *                           forward's planar strides (sb, sc, sd, st); every element of the (B, Cin, D, T) planes is written.
+ *                           The 32 -> 32 convolutions need no entry point of their own: their input gradient is
+ *                           as_conv3x3_c32 over w'[tap][ci][co] = w[8 - tap][co][ci] with a zero bias.
+ * as_gelu_bwd             : dx = dy * gelu'(x) (* scale[i % row_len] if scale: the gamma of an affine LayerNorm before the
+ *                           GELU, giving the gradient of its normalised input); dy == dx allowed. */
+int as_gru_unidir_fwd_gates(const float* gi, const float* w_hh, const float* b_hh, const int32_t* lengths, int32_t B, int32_t T,
+                            int32_t H, float* y, float* gates, void* stream);
+int as_gru_unidir_bwd(const float* dy, const float* y, const float* gates, const float* w_hh, const int32_t* lengths, int32_t B,
+                      int32_t T, int32_t H, float* dgi, float* dgh, void* stream);
+int as_ln_feat_gelu_bwd(const float* x, const float* gamma, const float* beta, const float* dy, const float* res, float* dx,
+                        int64_t rows, int32_t D, int32_t C, void* stream);
+int as_conv3x3_stem_bwd(const float* dy, const float* w, float* dx, int64_t sb, int64_t sc, int64_t sd, int64_t st, int32_t B,
+                        int32_t T, int32_t D, int32_t Cin, void* stream);
+int as_gelu_bwd(const float* dy, const float* x, const float* scale, float* dx, int64_t n, int32_t row_len, void* stream);
+
 /* intersect_semipolar_grid (area_function.py:175-223), float64, batched over frames: air_column [frames][2 walls][2][n_pts]
  * (internal wall first, x row then y row -- the air-column file layout), grid [n_lines][grid_res][2].  For every frame and
  * grid line: flags bit 0 / 1 = the internal / external wall is crossed (0: the reference skips the line), bit 2 = more than

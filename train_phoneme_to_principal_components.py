@@ -27,6 +27,7 @@ from torch.optim.lr_scheduler import ReduceLROnPlateau
 from torch.utils.data import DataLoader
 
 from artspeech_amd.helpers import make_indices_dict, sequences_from_dict, set_seeds
+from artspeech_amd.phoneme_recognition import DeepSpeech2
 from artspeech_amd.phoneme_to_articulation import RNNType
 from artspeech_amd.phoneme_to_articulation.principal_components.dataset import (
     PrincipalComponentsPhonemeToArticulationDataset2,
@@ -118,9 +119,6 @@ def main(database_name, datadir, num_epochs, batch_size, patience, learning_rate
          synthetic=None, results_dir=None):
     device = torch.device("cuda", torch.cuda.current_device())
     logging.info(f"Running on '{device}'")
-    if recognizer_filepath:
-        raise NotImplementedError("recognizer_filepath: AutoencoderLoss2's recognition term needs a backward through the "
-                                  "DeepSpeech2 scorer, which this engine does not provide (beta4 = 0, no recognizer)")
     dataset_config = DATASET_CONFIG[database_name]
     results_dir = results_dir or RESULTS_DIR
     os.makedirs(results_dir, exist_ok=True)
@@ -158,6 +156,14 @@ def main(database_name, datadir, num_epochs, batch_size, patience, learning_rate
     _, valid_dataloader = loader(valid_seq_dict, True, seed + 1)
 
     TVs = sorted((TV_to_phoneme_map or {}).keys())
+    if recognizer_filepath:   # frozen: the recognition term differentiates through its input only (reference :267-276)
+        recognizer = DeepSpeech2(num_classes=len(vocabulary), **(recognizer_params or {}))
+        recognizer.load_state_dict(torch.load(recognizer_filepath, map_location=device))
+        recognizer.to(device)
+        for p in recognizer.parameters():
+            p.requires_grad = False
+    else:
+        recognizer = None
     denorm_fn = {articulator: normalize.inverse for articulator, normalize in train_dataset.normalize.items()}
     encoder_cls = EncoderType[encoder_type.upper()].value
     decoder_cls = DecoderType[decoder_type.upper()].value
@@ -165,7 +171,7 @@ def main(database_name, datadir, num_epochs, batch_size, patience, learning_rate
                                encoder_state_dict_filepath=encoder_state_dict_filepath,
                                decoder_state_dict_filepath=decoder_state_dict_filepath, denormalize_fn=denorm_fn, beta1=beta1,
                                beta2=beta2, beta3=beta3, beta4=beta4, rescale_factor=rescale_factor, encoder_cls=encoder_cls,
-                               decoder_cls=decoder_cls, recognizer=None, **autoencoder_kwargs)
+                               decoder_cls=decoder_cls, recognizer=recognizer, **autoencoder_kwargs)
     optimizer = Adam(model.parameters(), lr=learning_rate, weight_decay=weight_decay)
     scheduler = ReduceLROnPlateau(optimizer, factor=0.1, patience=10)
     fn_metrics = {"p2cp_mean": DecoderMeanP2CPDistance2(
