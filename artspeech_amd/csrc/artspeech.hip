@@ -487,8 +487,6 @@ struct StreamState {
     hipEvent_t heads = nullptr;                                   // recorded by as_artspeech_bwd
 };
 int g_overlap = -1;  // -1: not decided yet (environment), 0: off, 1: on
-// AS_ONE_SIDE_STREAM (ablation): the hidden-to-hidden weight gradients queue on the first side stream (round-2 start)
-const bool g_one_side = AS_DIAG_SET("AS_ONE_SIDE_STREAM");
 std::mutex g_state_mu;
 std::vector<StreamState*> g_states;
 
@@ -536,7 +534,7 @@ StreamState* side_for(hipStream_t st) {
             return nullptr;
         }
         // optional: without it, its work goes to `side`
-        if (!g_one_side && !p->side2 && hipStreamCreateWithFlags(&p->side2, hipStreamNonBlocking) != hipSuccess) p->side2 = nullptr;
+        if (!p->side2 && hipStreamCreateWithFlags(&p->side2, hipStreamNonBlocking) != hipSuccess) p->side2 = nullptr;
     }
     return p;
 }
@@ -710,28 +708,11 @@ extern "C" int as_artspeech_fwd(const as_dims* d, const float* P, const int64_t*
             AS_STEP("gru.dropout", st, as_dropout(ws + w.y0, ws + w.y0d, (long)R * 2 * H, pdrop, opts->dropout_seed, st));
             l1_in = ws + w.y0d;
         }
-        {
-            // input projection of GRU layer 1: [R][2H] . [6H][2H]^T + b.  (diagnostic build, AS_XPROJ_LIN = 64 | 32: the LDS-DMA
-            // kernel of the head layers on three 256-column blocks instead of the general kernel's 64 x 64 tiles)
-            static const int xproj_lin = AS_DIAG_INT("AS_XPROJ_LIN", 0);
-            int took = 0;
-            if (xproj_lin && 6 * H % 256 == 0) {
-                as_lin l{};
-                l.A = l1_in; l.lda = 2 * H; l.a_batch = 0;
-                l.B = P + L.w_ih[1]; l.ldb = 2 * H; l.b_batch = 256L * 2 * H; l.b_kc = 1;
-                l.C = ws + w.xp1; l.ldc = 6 * H; l.c_batch = 256;
-                l.bias = P + L.b_ih[1]; l.bias_batch = 256;
-                l.M = R; l.N = 256; l.K = 2 * H; l.batch = 6 * H / 256; l.tile_rows = xproj_lin;
-                AS_PROF("gru.xproj1", st);
-                took = as_lin_try(&l, st);
-                AS_REQUIRE(took >= 0, took, "gru.xproj1: launch failed");
-            }
-            // (split arithmetic measured here twice and not kept: the plane-fed kernel of the heads 39.5 vs 43 us + a 10-us plane
-            // launch in front of the step's first kernel; both operands split in the kernel, gemm_s6.hip, 35.3 vs 33.1 us alone,
-            // tools/bench_linear.py -- at 2.5 GFLOP the launch is bound by its prologue and fill, not by the matrix pipe)
-            if (!took)
-                AS_STEP("gru.xproj1", st, gemm_nt(l1_in, 2 * H, P + L.w_ih[1], 2 * H, ws + w.xp1, 6 * H, P + L.b_ih[1], R, 6 * H, 2 * H, 0, st));
-        }
+        // input projection of GRU layer 1: [R][2H] . [6H][2H]^T + b.
+        // (split arithmetic measured here twice and not kept: the plane-fed kernel of the heads 39.5 vs 43 us + a 10-us plane
+        // launch in front of the step's first kernel; both operands split in the kernel, gemm_s6.hip, 35.3 vs 33.1 us alone,
+        // tools/bench_linear.py -- at 2.5 GFLOP the launch is bound by its prologue and fill, not by the matrix pipe)
+        AS_STEP("gru.xproj1", st, gemm_nt(l1_in, 2 * H, P + L.w_ih[1], 2 * H, ws + w.xp1, 6 * H, P + L.b_ih[1], R, 6 * H, 2 * H, 0, st));
         AS_STEP("gru.fwd_l1", st, as_gru_bidir_fwd(ws + w.xp1, nullptr, 0, P + L.w_hh[1], P + L.b_hh[1], lengths, B, T, H, ws + w.y1,
                                 train ? ws + w.g1 : nullptr, st));
         // (trunk Linear: 10.5 us on the fp32 instruction, 14 - 23 us on either split kernel: 50 - 200 short workgroups)
@@ -818,12 +799,11 @@ extern "C" int as_artspeech_bwd(const as_dims* d, const float* P, const int64_t*
     // beside the head / input-projection ones instead of queueing behind them: -9 us per step
     hipStream_t s3 = (sd && sd->side2) ? sd->side2 : s2;
     float* sl3 = (sd && sd->side2) ? ws + w.head + hw.slab3 : sl2;
-    // ablation (AS_PLAIN_FORKS): every fork an event record on `st`.  Also while the per-phase timers are on (as_profile_enable):
-    // a timing event recorded right behind an event-carrying dispatch reads ~20 us late, which would inflate the phase.
-    static const bool plain_forks_env = AS_DIAG_SET("AS_PLAIN_FORKS");
+    // every fork an event record on `st` while the per-phase timers are on (as_profile_enable): a timing event recorded
+    // right behind an event-carrying dispatch reads ~20 us late, which would inflate the phase.
     hipStreamCaptureStatus cap_ = hipStreamCaptureStatusNone;   // inside a stream capture: ordinary event records (graph edges)
     const bool capturing = hipStreamIsCapturing(st, &cap_) != hipSuccess || cap_ != hipStreamCaptureStatusNone;
-    const bool plain_forks = plain_forks_env || as_profile_active() || capturing;
+    const bool plain_forks = as_profile_active() || capturing;
     // ---- fork 0: head + trunk weight gradients run beside the layer-1 recurrence.  The fork's event rides on the GEMM's own
     // dispatch (as_stop_event_set): no marker packet on `st` between it and the recurrence
     if (sd && !plain_forks) as_stop_event_set(sd->fork[0]);
@@ -833,38 +813,18 @@ extern "C" int as_artspeech_bwd(const as_dims* d, const float* P, const int64_t*
     const int side_cus = sd ? 192 : 0;  // the recurrence's 2 * B workgroups hold 64 CUs while the side stream works
     const TrunkJob trunk{dzlin, ws + w.y1, G + L.lin_w, G + L.lin_b, H};
     // with a side stream: layers 3, 1 and the trunk now, layer 2 + unfold beside the layer-0 recurrence (see head_bwd_dw)
-    static const bool dw_one = AS_DIAG_SET("AS_HEAD_DW_ONE");   // ablation: everything in one launch here
-    const bool defer = opts && opts->defer_dw2;                  // layer 2's is computed later by as_artspeech_dw2()
-    const bool two_parts = (sd != nullptr && !dw_one) || defer;
+    const bool defer = opts && opts->defer_dw2;   // layer 2's is computed later by as_artspeech_dw2()
+    const bool two_parts = sd != nullptr || defer;
     AS_TRY(head_bwd_dw(*d, L, P, R, G, hws, sl2, s2, dpre3, side_cus, sd ? SLAB2_FLOATS : SLAB_FLOATS, &trunk, two_parts ? 1 : 0,
                        defer ? 5 : -1));
     // [lin_w, total) of the flat gradient buffer is final from here on ([lin_w, ln2_g) with defer_dw2)
     if (!two_parts || defer) AS_TRY(record_heads_done(st, s2));
-    hipEvent_t fork1_left = nullptr;
-    bool fork1_armed = false;
-    {
-        // input gradient of GRU layer 1: [R][6H] . [6H][2H].  (diagnostic build, AS_DX1_LIN: the LDS-DMA kernel of the head
-        // layers on 32-row x 256-column tiles instead of the general kernel's 64 x 64 tiles + in-kernel split-K)
-        static const int dx1_lin = AS_DIAG_INT("AS_DX1_LIN", 0);   // 64 | 32 = tile rows
-        int took = 0;
-        if (dx1_lin && 2 * H == 256) {
-            as_lin l{};
-            l.A = ws + w.dgi1; l.lda = 6 * H;
-            l.B = P + L.w_ih[1]; l.ldb = 2 * H; l.b_kc = 0;
-            l.C = ws + w.dy0; l.ldc = 2 * H;
-            l.M = R; l.N = 2 * H; l.K = 6 * H; l.batch = 1; l.tile_rows = dx1_lin;
-            AS_PROF("grub.dx1", st);
-            took = as_lin_try(&l, st);
-            AS_REQUIRE(took >= 0, took, "grub.dx1: launch failed");
-        }
-        // (split arithmetic measured slower here, 56 vs 52 us: 200 workgroups x 1.2 MB of weight planes each from L2)
-        if (!took) {
-            if (sd && !plain_forks && !(pdrop > 0.f)) as_stop_event_set(sd->fork[1]);   // fork 1 rides on this GEMM (see fork 0)
-            AS_STEP("grub.dx1", st, gemm_nn(ws + w.dgi1, 6 * H, P + L.w_ih[1], 2 * H, ws + w.dy0, 2 * H, R, 2 * H, 6 * H, st, 1, 0, 0, 0, slab));
-            fork1_left = as_stop_event_take();
-            fork1_armed = sd && !plain_forks && !(pdrop > 0.f);
-        }
-    }
+    // input gradient of GRU layer 1: [R][6H] . [6H][2H]
+    // (split arithmetic measured slower here, 56 vs 52 us: 200 workgroups x 1.2 MB of weight planes each from L2)
+    const bool fork1_armed = sd && !plain_forks && !(pdrop > 0.f);
+    if (fork1_armed) as_stop_event_set(sd->fork[1]);   // fork 1 rides on this GEMM (see fork 0)
+    AS_STEP("grub.dx1", st, gemm_nn(ws + w.dgi1, 6 * H, P + L.w_ih[1], 2 * H, ws + w.dy0, 2 * H, R, 2 * H, 6 * H, st, 1, 0, 0, 0, slab));
+    const hipEvent_t fork1_left = as_stop_event_take();
     if (pdrop > 0.f)  // back through the inter-layer dropout: same mask, regenerated from the seed
         AS_STEP("gru.dropout", st, as_dropout(ws + w.dy0, ws + w.dy0, (long)R * 2 * H, pdrop, opts->dropout_seed, st));
     // ---- fork 1: layer-1 weight gradients run beside the layer-0 recurrence
@@ -903,9 +863,8 @@ extern "C" int as_artspeech_bwd(const as_dims* d, const float* P, const int64_t*
     //   otherwise: segmented sum + embedding grads (~40 us) here, the GEMM aside.
     // The first side stream has its last work of this call queued: the second one waits for it HERE, before its own tail work --
     // a wait that resolves while that stream idles through the recurrence -- so that the final join is one hop (second side
-    // stream -> `st`) instead of two (14.6 -> 11 us between the last kernel and Adam; chained form: AS_CHAIN_JOIN).
-    static const bool chain_join = AS_DIAG_SET("AS_CHAIN_JOIN");
-    if (sd && s3 != s2 && !chain_join) AS_TRY(fork_to(s2, s3, sd->join));
+    // stream -> `st`) instead of two (14.6 -> 11 us between the last kernel and Adam).
+    if (sd && s3 != s2) AS_TRY(fork_to(s2, s3, sd->join));
     hipStream_t s_hh = tok_sums ? st : s3, s_emb = tok_sums ? s3 : st;
     float* sl_hh = tok_sums ? slab : sl3;
     if (sd) AS_TRY(fork_after(st, s3, s3 != s2 ? sd->fork2[2] : sd->fork[2], fork2_left));
@@ -927,12 +886,9 @@ extern "C" int as_artspeech_bwd(const as_dims* d, const float* P, const int64_t*
     }
     // join: `st` continues only after the side streams' work.  One wait on `st` (each costs the tail a few microseconds):
     // the second side stream first waits for the first one, then `st` waits for it alone.
-    if (sd && s3 != s2 && !chain_join) {
+    if (sd && s3 != s2) {
         // the second side stream already waited for the first one (above, before its tail work): one record behind its last
         // kernel, one wait on `st`
-        AS_TRY(fork_to(s3, st, sd->join2));
-    } else if (sd && s3 != s2) {
-        AS_TRY(fork_to(s2, s3, sd->join));
         AS_TRY(fork_to(s3, st, sd->join2));
     } else if (sd) {
         AS_TRY(fork_to(s2, st, sd->join));

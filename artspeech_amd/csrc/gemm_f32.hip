@@ -747,8 +747,6 @@ int* counters_for(hipStream_t st) {
     struct Slot { int dev; hipStream_t st; int* p; };
     static std::mutex mu;
     static std::vector<Slot> slots;
-    static const bool off = AS_DIAG_SET("AS_GEMM_NO_FIXUP");  // ablation: always the separate reduce kernel
-    if (off) return nullptr;
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess) return nullptr;
     std::lock_guard<std::mutex> lock(mu);
@@ -923,11 +921,7 @@ extern "C" int as_gemm_f32(const as_gemm* g, void* stream) {
     }
     // 128x128 tiles once they fill the chip and N fills a tile (N = 100: 60 vs 72 us at 64x64), else 64x64 for more workgroups
     const long big = (long)as_cdiv(g->M, 128) * as_cdiv(g->N, 128) * g->batch;
-    static const char* force = AS_DIAG_STR("AS_GEMM_TILE");  // tuning aid: "128x128" | "64x128" | "128x64" | "64x64"
-    if (force && !strcmp(force, "128x128")) return launch<128, 128>(k, g->batch, a_kc, b_kc, st);
-    if (force && !strcmp(force, "64x128")) return launch<64, 128>(k, g->batch, a_kc, b_kc, st);
-    if (force && !strcmp(force, "128x64")) return launch<128, 64>(k, g->batch, a_kc, b_kc, st);
-    if (!force && big >= 512 && g->N >= 128) {  // fewer 128x128 tiles leave most of the 768 resident slots empty: 64x64 then
+    if (big >= 512 && g->N >= 128) {  // fewer 128x128 tiles leave most of the 768 resident slots empty: 64x64 then
                                                  // (measured 6400 x 768 x 256: 300 tiles 39.9 us, as 1200 64x64 tiles 30.1 us)
         // 128x128 tiles that do not fill the resident slots (3 per CU) with a long reduction: split K so that the persistent
         // workgroups get equal shares (measured: 440 tiles, K = 6400 run at 75 TF/s, 768 tiles of the same shape at 100)
@@ -953,8 +947,7 @@ extern "C" int as_gemm_f32(const as_gemm* g, void* stream) {
                 return 0;
             }
         }
-        static const bool no_panels = AS_DIAG_SET("AS_NO_XCD_PANELS");
-        k.xcd_panels = a_kc && g->N > 128 && g->k_tri == 0 && big >= 2048 && slots % 8 == 0 && !no_panels;
+        k.xcd_panels = a_kc && g->N > 128 && g->k_tri == 0 && big >= 2048 && slots % 8 == 0;
         return launch<128, 128>(k, g->batch, a_kc, b_kc, st);
     }
     // few output tiles and a long reduction (weight gradients): split K over workgroups
@@ -967,8 +960,7 @@ extern "C" int as_gemm_f32(const as_gemm* g, void* stream) {
         const long per = (long)g->batch * g->M * (g->N + (g->colsum ? 1 : 0));
         if (sk * per > g->splitk_ws_floats) sk = g->splitk_ws_floats / per;
         // weight-gradient shapes with many tiles per chunk: a multiple of 8 chunks, one XCD per chunk (GemmK::xcd_chunks)
-        static const bool no_xcd = AS_DIAG_SET("AS_NO_XCD_CHUNKS");
-        const bool want_xcd = !a_kc && !b_kc && sk >= 12 && tiles >= 16 && !no_xcd;
+        const bool want_xcd = !a_kc && !b_kc && sk >= 12 && tiles >= 16;
         if (want_xcd)   // the nearest multiple of 8 (downwards) whose BK-rounded chunks still number a multiple of 8
             for (long c = (sk + 4) / 8 * 8; c >= 8; c -= 8)
                 if (as_cdiv(g->K, as_round_up(as_cdiv(g->K, c), BK)) % 8 == 0) { sk = c; break; }

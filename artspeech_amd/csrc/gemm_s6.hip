@@ -168,10 +168,8 @@ __global__ __launch_bounds__(NTH, 3) void gemm_s6_kernel(S6K g) {
         }
     };
     auto load = [&](Regs& x) {
-#if !defined(AS_S6G_ABL) || AS_S6G_ABL != 1     // ablation 1 (diagnostic builds): no global loads
         load_op(IC2<ANC>{}, x.a, Au, la);
         load_op(IC2<BNC>{}, x.b, Bu, lb);
-#endif
         // advance (behind the last tile the loads repeat it: unconditional loads keep hipcc's vmcnt counts exact)
         if constexpr (!EXT) {
             ld_t = min(ld_t + 1, nk - 1);
@@ -278,11 +276,6 @@ __global__ __launch_bounds__(NTH, 3) void gemm_s6_kernel(S6K g) {
         for (int p = 0; p < 3; ++p)
 #pragma unroll
             for (int i = 0; i < 2; ++i) {
-#if defined(AS_S6G_ABL) && AS_S6G_ABL == 2      // ablation 2: plain 16-byte reads in place of the transposing ones (wrong numbers)
-                fa[i][p] = *reinterpret_cast<const bf16x8*>(a_rd + U * BUF + p * PLANE + i * 32 * 32);
-                fb[i][p] = *reinterpret_cast<const bf16x8*>(b_rd + U * BUF + p * PLANE + i * 32 * 32);
-                continue;
-#endif
                 if constexpr (ANC) fa[i][p] = frag_tr(tr_a[i][0], tr_a[i][1], U * BUF + p * PLANE);
                 else fa[i][p] = *reinterpret_cast<const bf16x8*>(a_rd + U * BUF + p * PLANE + i * 32 * 32);
                 if constexpr (BNC) fb[i][p] = frag_tr(tr_b[i][0], tr_b[i][1], U * BUF + p * PLANE);
@@ -296,9 +289,7 @@ __global__ __launch_bounds__(NTH, 3) void gemm_s6_kernel(S6K g) {
 #pragma unroll
                 for (int j = 0; j < 2; ++j)
                     acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[i][PA[o]], fb[j][PB[o]], acc[i][j], 0, 0, 0);
-#if !defined(AS_S6G_ABL) || AS_S6G_ABL != 3     // ablation 3: no split + LDS writes
         store(x[U ^ 1], U ^ 1);   // (behind the last tile: a clamped repeat into the idle buffer)
-#endif
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         __builtin_amdgcn_s_barrier();
     };
@@ -474,8 +465,7 @@ int as_gemm_s6_nt_ext(const as_gemm* g, hipStream_t st) {
     k.colsum = g->colsum; k.colsum_batch = g->colsum_batch;
     {
         auto al16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
-        static const bool no_vec = AS_DIAG_SET("AS_S6_SCALAR_EPI");   // ablation: the one-column-per-lane epilogue
-        k.vec_epi = !no_vec && g->N % 4 == 0 && g->ldc % 4 == 0 && al16(g->C) && (g->c_off || g->c_batch % 4 == 0) &&
+        k.vec_epi = g->N % 4 == 0 && g->ldc % 4 == 0 && al16(g->C) && (g->c_off || g->c_batch % 4 == 0) &&
                     (!g->bias || (al16(g->bias) && (g->bias_off || g->bias_batch % 4 == 0))) &&
                     (!g->res || (al16(g->res) && g->res_ld % 4 == 0 && (g->res_off || g->res_batch % 4 == 0)));
     }
@@ -484,7 +474,7 @@ int as_gemm_s6_nt_ext(const as_gemm* g, hipStream_t st) {
     k.batch = g->batch;
     if (anc) {
         // one workgroup walks the whole reduction of its tile: worth it once the tiles fill the chip (else wgrad_f32.hip's stream-K)
-        if (blocks < 256 && !AS_DIAG_SET("AS_S6_TN_ANY")) return 0;
+        if (blocks < 256) return 0;
         k.xcd_group = k.tiles_m * k.tiles_n;
         blocks = (long)as_round_up(g->batch, 8) * k.xcd_group;
     } else if (k.tiles_n > 1) {

@@ -21,8 +21,8 @@
 //     the same word) so that hipcc can count its loads and never waits for the step's own stores;
 //   * the input projections (time-parallel, W_ih x + b_ih) come precomputed; for layer 0 they are a
 //     [V] row table (embedding folded into W_ih) gathered by token id through an LDS copy of the ids.
-// The backward kernel mirrors this with W_hh^T in registers (lane owns a quarter of the 3H gate rows of
-// one hidden unit's column) and emits the pre-activation gradients; weight gradients are time-batched
+// The backward kernel mirrors this with W_hh^T in registers (a row of 16 lanes owns 4 hidden units' columns,
+// see gru_bwd_row_kernel) and emits the pre-activation gradients; weight gradients are time-batched
 // GEMMs over them (artspeech.hip).  (Tried and dropped: s_setprio(3) for these waves while weight-gradient GEMMs
 // share the CU from the side stream -- no measurable change, the interference is not VALU issue arbitration.)
 #include <cstdlib>
@@ -46,12 +46,9 @@ __device__ __forceinline__ float unit_sum(float v) {
     return v;
 }
 
-#ifdef AS_GRU_NO_GATE_SHARE
-constexpr bool GATE_SHARE = false;
-#else
-constexpr bool GATE_SHARE = true;
-#endif
-template <int H, int LPU, bool TRAIN, bool TOK, int AHEAD>
+constexpr int AHEAD = 2;   // steps of look-ahead of the operand loads (see the header)
+
+template <int H, int LPU, bool TRAIN, bool TOK>
 __global__ __launch_bounds__(LPU * H) void gru_fwd_kernel(const float* __restrict__ gi, const int64_t* __restrict__ tokens,
                                                           long tok_stride, const float* __restrict__ w_hh,
                                                           const float* __restrict__ b_hh, const int* __restrict__ lengths,
@@ -152,7 +149,7 @@ __global__ __launch_bounds__(LPU * H) void gru_fwd_kernel(const float* __restric
         }
         const float sr = unit_sum<LPU>(ar.x + ar.y), sz = unit_sum<LPU>(az.x + az.y), sn = unit_sum<LPU>(an.x + an.y);
         float r, z;
-        if constexpr (LPU == 4 && GATE_SHARE) {
+        if constexpr (LPU == 4) {
             // the four lanes of a unit hold the same sums: lane 0 takes r's sigmoid, lanes 1..3 z's -- ONE exp + rcp sequence per
             // lane instead of two (quarter-rate instructions: 32 of the step's ~410 issue cycles per wave) -- and two quad
             // broadcasts hand both to every lane.  Same operations on the same values: bit-identical.
@@ -191,147 +188,23 @@ __global__ __launch_bounds__(LPU * H) void gru_fwd_kernel(const float* __restric
     constexpr std::integral_constant<int, 0> c0{};
     constexpr std::integral_constant<int, 1> c1{};
     constexpr std::integral_constant<int, 2> c2{};
-    if constexpr (AHEAD == 1) {
-        Gi a = load_step(0), bn;
-        for (int s = 0; s < len; ++s) {
-            step(s % 3, s, a, bn);
-            a = bn;
-        }
-    } else {
-        // Two steps of look-ahead: three operand sets whose roles rotate by NAME through a loop unrolled by three.  A
-        // register-to-register rotation is a CONSUMER of the newest loads: the wave would wait for them at the end of the
-        // step that issued them, and the memory round trip (not the arithmetic) would set the step time.
-        Gi a = load_step(0), bq = load_step(1), c;
-        int s = 0;
-        for (; s + 2 < len; s += 3) {
-            step(c0, s, a, c);
-            step(c1, s + 1, bq, a);
-            step(c2, s + 2, c, bq);
-        }
-        if (s < len) step(c0, s, a, c);
-        if (s + 1 < len) step(c1, s + 1, bq, a);
+    // Two steps of look-ahead: three operand sets whose roles rotate by NAME through a loop unrolled by three.  A
+    // register-to-register rotation is a CONSUMER of the newest loads: the wave would wait for them at the end of the
+    // step that issued them, and the memory round trip (not the arithmetic) would set the step time.
+    Gi a = load_step(0), bq = load_step(1), c;
+    int s = 0;
+    for (; s + 2 < len; s += 3) {
+        step(c0, s, a, c);
+        step(c1, s + 1, bq, a);
+        step(c2, s + 2, c, bq);
     }
+    if (s < len) step(c0, s, a, c);
+    if (s + 1 < len) step(c1, s + 1, bq, a);
 }
 
-template <int H, int LPU>
-__global__ __launch_bounds__(LPU * H) void gru_bwd_kernel(const float* __restrict__ dy, const float* __restrict__ y,
-                                                          const float* __restrict__ gates, const float* __restrict__ w_hh,
-                                                          const int* __restrict__ lengths, int T, float* __restrict__ dgi,
-                                                          float* __restrict__ dgh) {
-    constexpr int CW = 4 * LPU;
-    constexpr int NC = 3 * H / CW;
-    constexpr int NT = LPU * H;
-    __shared__ __attribute__((aligned(16))) float gbuf[2][3 * H];
-    const int b = blockIdx.x, dir = blockIdx.y;
-    const int tid = threadIdx.x, k = tid / LPU, q = tid % LPU;
-    const int len = lengths[b];
-
-    // W_hh^T: this lane owns rows i = CW*c + 4q + ii of column k (packed pairs for v_pk_fma_f32)
-    f32x2 wt[NC * 2];
-    {
-        const float* wd = w_hh + (long)dir * 3 * H * H;
-#pragma unroll
-        for (int c = 0; c < NC; ++c) {
-            wt[2 * c] = f32x2{wd[(long)(CW * c + 4 * q) * H + k], wd[(long)(CW * c + 4 * q + 1) * H + k]};
-            wt[2 * c + 1] = f32x2{wd[(long)(CW * c + 4 * q + 2) * H + k], wd[(long)(CW * c + 4 * q + 3) * H + k]};
-        }
-    }
-    // zero the gradients of padded frames (rows feed time-batched GEMMs)
-    for (long i = (long)len * 3 * H + tid; i < (long)T * 3 * H; i += NT) {
-        const long t = i / (3 * H), c = i % (3 * H);
-        const long o = (((long)b * T + t) * 2 + dir) * 3 * H + c;
-        dgi[o] = 0.f;
-        dgh[o] = 0.f;
-    }
-    if (len <= 0) return;
-
-    // walk opposite to the forward: forward dir t = len-1..0, reverse dir t = 0..len-1; running offsets
-    const int t0 = dir ? 0 : len - 1;
-    const int dt = dir ? 1 : -1;
-    const float* gtb = gates + (long)dir * 4 * H + k;   // + frame * 8H, planes at +0, +H, +2H, +3H
-    const float* yb = y + dir * H + k;                   // + frame * 2H
-    const float* dyb = dy + dir * H + k;                 // + frame * 2H
-    float* dgib = dgi + (long)dir * 3 * H + k;           // + frame * 6H + plane * H
-    float* dghb = dgh + (long)dir * 3 * H + k;
-    // Plane(s) stored by this lane.  LPU = 4: lane q stores plane min(q, 2) of both arrays (lanes 2, 3 the same
-    // words).  LPU = 2: lane 0 stores planes r (both arrays) and n of dgi; lane 1 planes z (both) and n of dgh.
-    const int sel = LPU == 4 ? (q < 2 ? q : 2) : q;
-    const int m0 = q == 0 ? -1 : 0, m1 = q == 1 ? -1 : 0, m2 = q >= 2 ? -1 : 0;
-    struct In { float r, z, n, hn, hprev, dyv; };
-    // h_{prev} of frame t is the output of the frame this backward walk visits NEXT (t + dt): forward dir t-1,
-    // reverse dir t+1; zero beyond the sequence ends.
-    auto load = [&](long fr, bool has_prev) {
-        In v;
-        const float* gp = gtb + fr * 8 * H;
-        v.r = gp[0]; v.z = gp[H]; v.n = gp[2 * H]; v.hn = gp[3 * H];
-        const float hp = yb[(fr + (has_prev ? dt : 0)) * 2 * H];
-        v.hprev = has_prev ? hp : 0.f;
-        v.dyv = dyb[fr * 2 * H];
-        return v;
-    };
-    long fr = (long)b * T + t0;
-    float dh = 0.f;
-    In cur_in = load(fr, len > 1);
-    for (int s = 0; s < len; ++s) {
-        const int cur = s & 1;
-        // next step's operands: in flight during this step (last step re-reads its own frame)
-        const int adv = s + 1 < len ? dt : 0;
-        const In nxt = load(fr + adv, s + 2 < len);
-        const float r = cur_in.r, z = cur_in.z, n = cur_in.n, hn = cur_in.hn;
-        const float dht = dh + cur_in.dyv;
-        const float dn = dht * (1.f - z);
-        const float dz = dht * (cur_in.hprev - n);
-        const float dnt = dn * (1.f - n * n);
-        const float g_r = dnt * hn * r * (1.f - r);
-        const float g_z = dz * z * (1.f - z);
-        const float g_hn = dnt * r;
-        // planes r, z, n of d/d(W_ih x + b_ih) and d/d(W_hh h + b_hh): they differ in the n plane only
-        if (LPU == 4) {
-            const int rz = (__float_as_int(g_r) & m0) | (__float_as_int(g_z) & m1);
-            const float vi = __int_as_float(rz | (__float_as_int(dnt) & m2));
-            const float vh = __int_as_float(rz | (__float_as_int(g_hn) & m2));
-            gbuf[cur][sel * H + k] = vh;
-            dgib[fr * 6 * H + sel * H] = vi;
-            dghb[fr * 6 * H + sel * H] = vh;
-        } else {
-            const float rz = __int_as_float((__float_as_int(g_r) & m0) | (__float_as_int(g_z) & m1));
-            const float nn = __int_as_float((__float_as_int(dnt) & m0) | (__float_as_int(g_hn) & m1));
-            gbuf[cur][sel * H + k] = rz;
-            gbuf[cur][2 * H + k] = g_hn;  // both lanes write the same word
-            dgib[fr * 6 * H + sel * H] = rz;
-            dghb[fr * 6 * H + sel * H] = rz;
-            (q == 0 ? dgib : dghb)[fr * 6 * H + 2 * H] = nn;
-        }
-        __syncthreads();
-        const float4* gq = reinterpret_cast<const float4*>(gbuf[cur]);
-        f32x2 a0 = {0.f, 0.f}, a1 = {0.f, 0.f};
-#pragma unroll
-        for (int c0 = 0; c0 < NC; c0 += 8) {  // 8 LDS reads in flight, then their FMAs
-            float4 gv[8];
-#pragma unroll
-            for (int u = 0; u < 8; ++u)
-                if (c0 + u < NC) gv[u] = gq[LPU * (c0 + u) + q];
-            __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int u = 0; u < 8; ++u)
-                if (c0 + u < NC) {
-                    const int c = c0 + u;
-                    a0 = __builtin_elementwise_fma(wt[2 * c], f32x2{gv[u].x, gv[u].y}, a0);
-                    a1 = __builtin_elementwise_fma(wt[2 * c + 1], f32x2{gv[u].z, gv[u].w}, a1);
-                }
-        }
-        const float acc = unit_sum<LPU>((a0.x + a0.y) + (a1.x + a1.y));
-        dh = dht * z + acc;
-        cur_in = nxt;
-        fr += dt;
-        // gbuf is double buffered: the next step writes gbuf[cur^1]; all reads of it (two steps ago)
-        // precede the barrier above, so one barrier per step suffices.
-    }
-}
-
-// Backward recurrence, second layout: the LDS read of the step's 3H gate gradients is what bounds the layout above (every
-// lane reads 3H/4 floats: 24 ds_read_b128 per lane, 8 waves x 24 x 8 cycles = 1536 LDS cycles per step at H = 128, about
-// the whole measured step).  Here a ROW of 16 lanes owns 4 hidden units: each lane holds W_hh^T for those 4 columns over
+// Backward recurrence.  The LDS read of the step's 3H gate gradients bounded the earlier layout of 4 lanes per hidden unit
+// (every lane read 3H/4 floats: 24 ds_read_b128 per lane, 8 waves x 24 x 8 cycles = 1536 LDS cycles per step at H = 128,
+// about the whole measured step).  Here a ROW of 16 lanes owns 4 hidden units: each lane holds W_hh^T for those 4 columns over
 // 1/16 of the gate rows (the same 96 weight VGPRs), reads only 3H/16 gate gradients per step (6 ds_read_b128 at H = 128)
 // and the four partial sums are all-reduced across the row with 4 DPP steps each (quad xor 1, xor 2, half-row mirror,
 // row mirror).  Lane r of a row then plays the old role for unit 4*row + (r & 3), plane r >> 2.
@@ -343,7 +216,7 @@ __global__ __launch_bounds__(LPU * H) void gru_bwd_kernel(const float* __restric
 // touched.  A fixed-order reduction over the B tables follows (token_segsum_reduce_kernel).
 // ND: directions interleaved per frame in y / dy ([frame][ND][H]), gates ([frame][ND][4H]) and dgi / dgh ([frame][ND][3H]);
 // 2 = the bidirectional layer, 1 = a unidirectional one (its only direction walks the sequence backwards, as direction 0).
-template <int H, bool TOK, int AHEAD, int ND = 2>
+template <int H, bool TOK, int ND = 2>
 __global__ __launch_bounds__(4 * H) void gru_bwd_row_kernel(const float* __restrict__ dy, const float* __restrict__ y,
                                                             const float* __restrict__ gates, const float* __restrict__ w_hh,
                                                             const int* __restrict__ lengths, int T, float* __restrict__ dgi,
@@ -552,44 +425,24 @@ __global__ __launch_bounds__(4 * H) void gru_bwd_row_kernel(const float* __restr
     constexpr std::integral_constant<int, 0> c0{};
     constexpr std::integral_constant<int, 1> c1{};
     constexpr std::integral_constant<int, 2> c2{};
-    if constexpr (AHEAD == 1) {
-        In a = load_step(0), bnx;
-        for (int s = 0; s < len; ++s) {
-            step(std::false_type{}, s % 3, s, a, bnx);
-            a = bnx;
-        }
-    } else if constexpr (AHEAD == 3) {
-        In a = load_step(0), bq = load_step(1), c = load_step(2), d;
-        int s = 0;
-        for (; s + 3 < len; s += 4) {
-            step(std::false_type{}, s % 3, s, a, d);
-            step(std::false_type{}, (s + 1) % 3, s + 1, bq, a);
-            step(std::false_type{}, (s + 2) % 3, s + 2, c, bq);
-            step(std::false_type{}, (s + 3) % 3, s + 3, d, c);
-        }
-        if (s < len) step(std::false_type{}, s % 3, s, a, d);
-        if (s + 1 < len) step(std::false_type{}, (s + 1) % 3, s + 1, bq, a);
-        if (s + 2 < len) step(std::false_type{}, (s + 2) % 3, s + 2, c, bq);
-    } else {
-        // Two steps of look-ahead: three operand sets whose roles rotate by NAME through a loop unrolled by three (a
-        // register-to-register rotation would be a consumer of the newest loads and bring their wait back to this step)
-        In a = load_step(0), bq = load_step(1), c;
-        int s = 0;
-        constexpr std::true_type yes{};
-        constexpr std::false_type no{};
-        for (; s + 5 < len; s += 3) {   // every step of the group has s + AHEAD + 1 < len
-            step(yes, c0, s, a, c);
-            step(yes, c1, s + 1, bq, a);
-            step(yes, c2, s + 2, c, bq);
-        }
-        for (; s + 2 < len; s += 3) {
-            step(no, c0, s, a, c);
-            step(no, c1, s + 1, bq, a);
-            step(no, c2, s + 2, c, bq);
-        }
-        if (s < len) step(no, c0, s, a, c);
-        if (s + 1 < len) step(no, c1, s + 1, bq, a);
+    // Two steps of look-ahead: three operand sets whose roles rotate by NAME through a loop unrolled by three (a
+    // register-to-register rotation would be a consumer of the newest loads and bring their wait back to this step)
+    In a = load_step(0), bq = load_step(1), c;
+    int s = 0;
+    constexpr std::true_type yes{};
+    constexpr std::false_type no{};
+    for (; s + 5 < len; s += 3) {   // every step of the group has s + AHEAD + 1 < len
+        step(yes, c0, s, a, c);
+        step(yes, c1, s + 1, bq, a);
+        step(yes, c2, s + 2, c, bq);
     }
+    for (; s + 2 < len; s += 3) {
+        step(no, c0, s, a, c);
+        step(no, c1, s + 1, bq, a);
+        step(no, c2, s + 2, c, bq);
+    }
+    if (s < len) step(no, c0, s, a, c);
+    if (s + 1 < len) step(no, c1, s + 1, bq, a);
     if constexpr (TOK) {
         __syncthreads();
         for (int i = tid; i < V * 3 * H; i += NT) part_wg[(long)(i / (3 * H)) * 6 * H + i % (3 * H)] = tab[i];
@@ -812,29 +665,12 @@ static int gru_fwd_launch(const float* gi, const int64_t* tokens, int64_t tok_st
     dim3 grid(B, nd);
     const size_t pad = gru_lds_pad(B * nd);
     const size_t need = tokens ? (size_t)T * sizeof(int) : 0;
-#ifdef AS_DIAG
-    static const int ahead = AS_DIAG_INT("AS_GRU_AHEAD", 2);   // look-ahead of the operand loads (steps)
-#endif
-#ifdef AS_DIAG   // the one-step look-ahead instantiation exists in the diagnostic build only
-#define AS_GRU_LAUNCH(HH, TR, TK)                                                                                         \
-    do {                                                                                                                  \
-        const size_t shm = pad > need && gru_lds_attr(gru_fwd_kernel<HH, lpu_of(HH), TR, TK, 1>) &&                       \
-                           gru_lds_attr(gru_fwd_kernel<HH, lpu_of(HH), TR, TK, 2>) ? pad : need;                          \
-        if (ahead == 1)                                                                                                   \
-            hipLaunchKernelGGL((gru_fwd_kernel<HH, lpu_of(HH), TR, TK, 1>), grid, dim3(lpu_of(HH) * HH), shm, st, gi, tokens, \
-                               (long)tok_stride, w_hh, b_hh, lengths, T, y, gates, nd, V);                                   \
-        else                                                                                                              \
-            hipLaunchKernelGGL((gru_fwd_kernel<HH, lpu_of(HH), TR, TK, 2>), grid, dim3(lpu_of(HH) * HH), shm, st, gi, tokens, \
-                               (long)tok_stride, w_hh, b_hh, lengths, T, y, gates, nd, V);                                   \
+#define AS_GRU_LAUNCH(HH, TR, TK)                                                                                      \
+    do {                                                                                                               \
+        const size_t shm = pad > need && gru_lds_attr(gru_fwd_kernel<HH, lpu_of(HH), TR, TK>) ? pad : need;            \
+        hipLaunchKernelGGL((gru_fwd_kernel<HH, lpu_of(HH), TR, TK>), grid, dim3(lpu_of(HH) * HH), shm, st, gi, tokens, \
+                           (long)tok_stride, w_hh, b_hh, lengths, T, y, gates, nd, V);                                 \
     } while (0)
-#else
-#define AS_GRU_LAUNCH(HH, TR, TK)                                                                                         \
-    do {                                                                                                                  \
-        const size_t shm = pad > need && gru_lds_attr(gru_fwd_kernel<HH, lpu_of(HH), TR, TK, 2>) ? pad : need;            \
-        hipLaunchKernelGGL((gru_fwd_kernel<HH, lpu_of(HH), TR, TK, 2>), grid, dim3(lpu_of(HH) * HH), shm, st, gi, tokens, \
-                           (long)tok_stride, w_hh, b_hh, lengths, T, y, gates, nd, V);                                    \
-    } while (0)
-#endif
 #define AS_GRU_FWD(HH)                                      \
     if (gates && tokens) AS_GRU_LAUNCH(HH, true, true);     \
     else if (gates) AS_GRU_LAUNCH(HH, true, false);         \
@@ -898,46 +734,27 @@ static int gru_bwd_launch(const float* dy, const float* y, const float* gates, c
     // diagnostic stamps (as_gru_debug_stamps): 2 x (2 B workgroups x 4 words); launch k writes half k % 2, so that the two
     // backward recurrences of one training step (layer 1, then layer 0) can both be read afterwards
     unsigned long long* dbg_now = g_gru_dbg ? g_gru_dbg + (size_t)(g_gru_dbg_launch++ & 1u) * 8u * (size_t)B : nullptr;
-#ifdef AS_DIAG
-    static const bool unit_layout = AS_DIAG_SET("AS_GRU_BWD_UNIT");  // ablation: the 4-lanes-per-unit layout
-#endif
     hipEvent_t stop_ev = (H == 32 || H == 64 || H == 128) ? as_stop_event_take() : nullptr;
     const size_t pad = gru_lds_pad(B * nd);
     const size_t need = tokens ? ((size_t)V * 3 * H + 4 * H + T) * sizeof(float) : 0;   // + one dummy word per lane + T offsets
-#ifdef AS_DIAG
-    static const int ahead = AS_DIAG_INT("AS_GRU_AHEAD", 2);   // look-ahead of the operand loads (steps)
-#endif
-#define AS_GRU_BWD_ROW_ND(HH, TK, AH, ND)                                                                                     \
+#define AS_GRU_BWD_ROW(HH, TK, ND)                                                                                     \
     do {                                                                                                                      \
-        const bool big = gru_lds_attr(gru_bwd_row_kernel<HH, TK, AH, ND>);                                                    \
+        const bool big = gru_lds_attr(gru_bwd_row_kernel<HH, TK, ND>);                                                    \
         AS_REQUIRE(big || need <= 64 * 1024, AS_ERR_UNSUPPORTED, "as_gru_bidir_bwd: cannot reserve %zu bytes of LDS", need);   \
         const size_t shm = big && pad > need ? pad : need;                                                                    \
         if (stop_ev)   /* a fork event rides on this dispatch (gemm_internal.h, as_stop_event_set) */                         \
-            hipExtLaunchKernelGGL((gru_bwd_row_kernel<HH, TK, AH, ND>), grid, dim3(4 * HH), (unsigned)shm, st, nullptr, stop_ev, 0, dy, \
+            hipExtLaunchKernelGGL((gru_bwd_row_kernel<HH, TK, ND>), grid, dim3(4 * HH), (unsigned)shm, st, nullptr, stop_ev, 0, dy, \
                                   y, gates, w_hh, lengths, T, dgi, dgh, dbg_now, tokens, (long)tok_stride, V, part);          \
         else                                                                                                                  \
-            hipLaunchKernelGGL((gru_bwd_row_kernel<HH, TK, AH, ND>), grid, dim3(4 * HH), shm, st, dy, y, gates, w_hh,         \
+            hipLaunchKernelGGL((gru_bwd_row_kernel<HH, TK, ND>), grid, dim3(4 * HH), shm, st, dy, y, gates, w_hh,         \
                                lengths, T, dgi, dgh, dbg_now, tokens, (long)tok_stride, V, part);                             \
     } while (0)
-#define AS_GRU_BWD_ROW(HH, TK, AH) AS_GRU_BWD_ROW_ND(HH, TK, AH, 2)
-#ifdef AS_DIAG   // other look-aheads and the 4-lanes-per-unit layout exist in the diagnostic build only
-#define AS_GRU_BWD(HH)                                                                                                        \
-    if (tokens) {                                                                                                             \
-        if (ahead == 3) AS_GRU_BWD_ROW(HH, true, 3); else if (ahead == 2) AS_GRU_BWD_ROW(HH, true, 2); else AS_GRU_BWD_ROW(HH, true, 1); \
-    } else if (unit_layout) {                                                                                                 \
-        hipLaunchKernelGGL((gru_bwd_kernel<HH, lpu_of(HH)>), grid, dim3(lpu_of(HH) * HH), 0, st, dy, y, gates, w_hh, lengths, \
-                           T, dgi, dgh);                                                                                      \
-        if (stop_ev) (void)hipEventRecord(stop_ev, st);                                                                       \
-    }                                                                                                                         \
-    else if (ahead == 3) AS_GRU_BWD_ROW(HH, false, 3); else if (ahead == 2) AS_GRU_BWD_ROW(HH, false, 2); else AS_GRU_BWD_ROW(HH, false, 1)
-#else
 #define AS_GRU_BWD(HH) \
     if (tokens) AS_GRU_BWD_ROW(HH, true, 2); else AS_GRU_BWD_ROW(HH, false, 2)
-#endif
-    if (nd == 1 && (H == 32 || H == 64 || H == 128)) {   // unidirectional: the product look-ahead, no token table
-        if (H == 32) AS_GRU_BWD_ROW_ND(32, false, 2, 1);
-        else if (H == 64) AS_GRU_BWD_ROW_ND(64, false, 2, 1);
-        else AS_GRU_BWD_ROW_ND(128, false, 2, 1);
+    if (nd == 1 && (H == 32 || H == 64 || H == 128)) {   // unidirectional: no token table
+        if (H == 32) AS_GRU_BWD_ROW(32, false, 1);
+        else if (H == 64) AS_GRU_BWD_ROW(64, false, 1);
+        else AS_GRU_BWD_ROW(128, false, 1);
     } else switch (H) {
         case 32: AS_GRU_BWD(32); break;
         case 64: AS_GRU_BWD(64); break;
@@ -951,7 +768,6 @@ static int gru_bwd_launch(const float* dy, const float* y, const float* gates, c
     }
 #undef AS_GRU_BWD
 #undef AS_GRU_BWD_ROW
-#undef AS_GRU_BWD_ROW_ND
     AS_LAUNCH_CHECK("as_gru_bidir_bwd");
     return 0;
 }
@@ -967,8 +783,7 @@ extern "C" int as_gru_bidir_bwd(const float* dy, const float* y, const float* ga
 // part [B][V][6H], instead of dgi.  0 = not a case for it (V * 3H floats must fit the LDS budget): the caller takes
 // as_gru_bidir_bwd + as_token_segsum.
 bool as_gru_bwd_tokens_fits(int32_t V, int32_t H, int32_t T) {
-    static const bool off = AS_DIAG_SET("AS_NO_GRU_TOKSUM");   // ablation: dgi + the segmented-sum kernel
-    return !off && (H == 32 || H == 64 || H == 128) && ((long)V * 3 * H + 4 * H + T) * (long)sizeof(float) <= AS_GRU_TOK_LDS_MAX;
+    return (H == 32 || H == 64 || H == 128) && ((long)V * 3 * H + 4 * H + T) * (long)sizeof(float) <= AS_GRU_TOK_LDS_MAX;
 }
 int as_gru_bidir_bwd_tokens(const float* dy, const float* y, const float* gates, const float* w_hh, const int32_t* lengths,
                             int32_t B, int32_t T, int32_t H, float* dgh, const int64_t* tokens, int64_t tok_stride, int32_t V,

@@ -47,17 +47,7 @@ struct LinK {
     int M, N, K, ka_valid, batch, act;
     int n_big, big_per_batch, big_per_batch_rows, small_per_batch;   // tiles of 64 rows first, then tiles of 32 rows (see launch())
     int tile_rows;
-#ifdef AS_DIAG
-    int stagger;
-#else
-    static constexpr int stagger = 0;
-#endif
     unsigned long long* dbg; long dbg_max;   // diagnostic cycle stamps (as_lin_debug_stamps), normally null
-#ifdef AS_DIAG
-    int abl;  // diagnostic (AS_LIN_ABL): 1 = return before the epilogue, 2 = no DMA after the prologue
-#else
-    static constexpr int abl = 0;
-#endif
     float eps;
     float* rstd;                      // EPI_LNF out: [M][batch]
     unsigned long long* bits;         // EPI_LNF out: [M][batch][4]: v > 0 per feature
@@ -268,14 +258,14 @@ __device__ __forceinline__ void lin_epilogue(const LinK& g, f32x16 (&acc)[TM], f
     lin_ln_rows<TM, EPI, 8>(g, acc, smem, bz, m0, tm_eff, 1, wave, lane, bj);
 }
 
-// NB ring slots: 3 (two k-tiles in flight, 60 KB: two workgroups per CU) or 2 (one in flight, 40 KB: three per CU; diagnostic)
-template <int BM, bool B_KC, int EPI, int NB = NBUF>
-__global__ __launch_bounds__(NT, NB == 2 ? 6 : 4) void lin_f32_kernel(LinK g) {
+// NBUF ring slots: two k-tiles in flight, 60 KB: two workgroups per CU
+template <int BM, bool B_KC, int EPI>
+__global__ __launch_bounds__(NT, 4) void lin_f32_kernel(LinK g) {
     constexpr int TM = BM / 32;
     constexpr int TILE = BK * (BM + BN);
     constexpr int PA_TOTAL = BM / 16;    // 1-KiB DMA pieces of the A tile (16 rows x 16 k each)
-    constexpr int RING = NB * TILE, EPIT = 32 * BN;
-    constexpr int AHEADT = NB - 1;       // k-tiles in flight besides the one being multiplied
+    constexpr int RING = NBUF * TILE, EPIT = 32 * BN;
+    constexpr int AHEADT = NBUF - 1;     // k-tiles in flight besides the one being multiplied
     __shared__ __attribute__((aligned(16))) float smem[RING > EPIT ? RING : EPIT];
 
     // tile list: the 64-row tiles of every head first, then 32-row tiles over the remaining rows of every head
@@ -321,7 +311,7 @@ __global__ __launch_bounds__(NT, NB == 2 ? 6 : 4) void lin_f32_kernel(LinK g) {
     const unsigned smem_base = lds_addr(smem);
     // piece 0 = this wave's A piece, pieces 1, 2 = its two B pieces of k-tile kt
     auto issue_piece = [&](int kt, int piece) {
-        const unsigned base = smem_base + (unsigned)((kt % NB) * TILE) * 4u;
+        const unsigned base = smem_base + (unsigned)((kt % NBUF) * TILE) * 4u;
         const int k0 = kt * BK;
         if (piece == 0) {
             const bool ok = k0 + a_gc + 4 <= g.ka_valid;
@@ -351,37 +341,12 @@ __global__ __launch_bounds__(NT, NB == 2 ? 6 : 4) void lin_f32_kernel(LinK g) {
         d[6] = 0;
         d[5] = __builtin_amdgcn_s_getreg((4 - 1) << 11 | 0 << 6 | 4) | ((unsigned long long)__builtin_amdgcn_s_getreg((32 - 1) << 11 | 0 << 6 | 20) << 32);
     }
-    // Two workgroups share a CU and would run in lockstep (same start, same tile time): both in their prologue, both in
-    // their main loop, both in their epilogue -- nothing overlaps.  The second wave of the first fill (blocks 256..511 under
-    // round-robin dispatch: speed only) starts half a tile late; every later workgroup inherits the phase of the slot it takes.
-    if (g.stagger > 0 && g.stagger < 10 && blockIdx.x >= 256 && blockIdx.x < 256 * NB) {
-        // NB = 3 (two per CU): the second starts half a tile late; NB = 2 (three per CU): a third and two thirds of a tile
-        const int steps = NB == 3 ? nk * g.stagger : (int)(blockIdx.x >> 8) * nk * g.stagger * 2 / 3;
-        for (int i = 0; i < steps; ++i) __builtin_amdgcn_s_sleep(16);  // 16 * 64 cycles = half a k-tile of MFMAs
-    }
-    // diagnostic (AS_LIN_STAGGER >= 10): the same delay, but for the workgroup that really is the SECOND tenant of its CU --
-    // told by the wave slot its first wave got on its SIMD (HW_ID.wave_id >= 2: slots 0, 1 belong to the first tenant) -- instead
-    // of by block index (the dispatcher need not place blocks b and b + 256 on one CU)
-    if (g.stagger >= 10 && blockIdx.x < 512) {
-        const unsigned slot = __builtin_amdgcn_s_getreg((4 - 1) << 11 | 0 << 6 | 4);   // HW_REG_HW_ID[3:0] = wave slot on the SIMD
-        __shared__ int second;
-        if (tid == 0) second = slot >= 2;
-        __syncthreads();
-        if (second)
-            for (int i = 0; i < nk * (g.stagger - 9); ++i) __builtin_amdgcn_s_sleep(16);
-    }
-    // diagnostic (AS_LIN_STAGGER < 0): de-phase the XCDs instead -- the first-fill workgroups of XCD x start x * |stagger| / 8
-    // of a 16-k-tile main loop late, so that the epilogues' store bursts of the eight dies do not coincide chip-wide
-    if (g.stagger < 0 && blockIdx.x < 512) {
-        const int steps = (int)(blockIdx.x & 7) * (-g.stagger) * 2;          // x * |stagger| * 2 sleeps of 1024 cycles
-        for (int i = 0; i < steps; ++i) __builtin_amdgcn_s_sleep(16);
-    }
     const int swz = (l31 >> 2) & 3;   // rows i * 32 + l31 and wave * 32 + l31 share it (32 = 0 mod 16)
     // two k-tiles in flight; the older one is retired with vmcnt(3).  (A 2-slot ring with three workgroups per CU was no
     // faster: 108-118 us against 108-114 for head GEMM 2.)
     issue(0);
-    if (AHEADT > 1 && nk > 1) issue(1);
-    if (AHEADT > 1 && nk > 1) asm volatile("s_waitcnt vmcnt(3)" ::: "memory");
+    if (nk > 1) issue(1);
+    if (nk > 1) asm volatile("s_waitcnt vmcnt(3)" ::: "memory");
     else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();
     if (stamp) g.dbg[8L * blockIdx.x + 1] = __builtin_amdgcn_s_memtime();
@@ -392,7 +357,7 @@ __global__ __launch_bounds__(NT, NB == 2 ? 6 : 4) void lin_f32_kernel(LinK g) {
     // with all eight waves waiting for their first fragments, ~10 % of a 2048-cycle tile with the pipe idle).
     struct Frag { float4 av[TM]; float bv[4]; };
     auto load = [&](Frag& f, int kt_, int cc) {
-        const float* tile = smem + (kt_ % NB) * TILE;
+        const float* tile = smem + (kt_ % NBUF) * TILE;
         const float* a_s = tile + l31 * BK;
         const float* b_s = tile + BK * BM;
         const int slot = ((2 * cc + lh) ^ swz) * 4;
@@ -435,9 +400,9 @@ __global__ __launch_bounds__(NT, NB == 2 ? 6 : 4) void lin_f32_kernel(LinK g) {
         __builtin_amdgcn_sched_barrier(0);
         mma(f0, kt + AHEADT < nk ? kt + AHEADT : -1);
         __builtin_amdgcn_sched_barrier(0);
-        if (AHEADT > 1 && kt + 2 < nk) asm volatile("s_waitcnt vmcnt(3)" ::: "memory");
+        if (kt + 2 < nk) asm volatile("s_waitcnt vmcnt(3)" ::: "memory");
         else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");     // this wave's reads of slot kt % NB are in registers
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");     // this wave's reads of slot kt % NBUF are in registers
         __builtin_amdgcn_s_barrier();
         if (kt + 1 < nk) load(f0, kt + 1, 0);
         __builtin_amdgcn_sched_barrier(0);
@@ -445,10 +410,6 @@ __global__ __launch_bounds__(NT, NB == 2 ? 6 : 4) void lin_f32_kernel(LinK g) {
         __builtin_amdgcn_sched_barrier(0);
     }
     if (stamp) g.dbg[8L * blockIdx.x + 2] = __builtin_amdgcn_s_memtime();
-    if (g.abl == 1) {
-        if (acc[0][0] == 123.456f) g.C[0] = acc[0][0];  // keep the loop alive
-        return;
-    }
 
     lin_epilogue<TM, EPI>(g, acc, smem, bz, m0, tm_eff, wave, lane);
     if (stamp) {
@@ -512,14 +473,6 @@ template <int NW, int TME>   // TME: row blocks of 32 the tile really has (a 32-
 __device__ __forceinline__ void s6_main_loop(f32x16 (&acc)[2], unsigned char* sm, const float* __restrict__ A, long lda, int rows_valid,
                                              int K, int ka_valid, const uint16_t* __restrict__ bp, unsigned b_lane, long bp_plane,
                                              long bp_step, int tid, int lane, bool late, unsigned long long* stamp1 = nullptr) {
-    // compile-time ablations of a diagnostic build (python -m artspeech_amd.build --diag -DAS_S6_ABL=n): 1 = no epilogue,
-    // 2 = no B loads inside the loop, 3 = no A loads / splits / LDS stores inside the loop, 4 = no MFMAs, 5 = every tile reads
-    // the fragments of plane image 0.  (A run-time switch here costs the loop its register arrays: 16 x slower.)
-#ifdef AS_S6_ABL
-    constexpr int abl = AS_S6_ABL;
-#else
-    constexpr int abl = 0;
-#endif
     constexpr int NTH = NW * 64;
     constexpr int AL = 512 / NTH;         // float4 loads per thread and k-tile (64 rows x 8 chunks of 4 k)
     const int l31 = lane & 31, lh = lane >> 5;
@@ -578,20 +531,13 @@ __device__ __forceinline__ void s6_main_loop(f32x16 (&acc)[2], unsigned char* sm
     lds_barrier();
     if (stamp1) *stamp1 = __builtin_amdgcn_s_memtime();
     // k-tile kt (kt % 3 == U): its plane image is in buffer kt & 1, its B fragments in sets (2 kt) % 3 and (2 kt + 1) % 3
-#ifdef AS_S6_TRACE   // diagnostic build: per-tile cycle stamps of every wave of the stamped workgroups (tools/s6_trace.py)
-    unsigned long long* tr = stamp1 ? stamp1 - 1 + 8L * 4096 + ((long)blockIdx.x * 8 + (tid >> 6)) * 64 : nullptr;
-#define AS_TR(slot) if (tr && lane == 0) tr[(kt < 10 ? kt : 9) * 6 + (slot)] = __builtin_amdgcn_s_memtime();
-#else
-#define AS_TR(slot)
-#endif
     auto tile = [&](auto Uc, int kt) {
         constexpr int U = decltype(Uc)::value;
-        const unsigned char* img = a_rd + (abl == 5 ? 0 : (kt & 1) * S6_BUF);
-        AS_TR(0)
-        if (abl != 3) a_load(aq[(U + 2) % 3], kt + 2);
+        const unsigned char* img = a_rd + (kt & 1) * S6_BUF;
+        a_load(aq[(U + 2) % 3], kt + 2);
 #pragma unroll
         for (int s = 0; s < 2; ++s) {
-            if (abl != 2) b_load(bq[(2 * U + s + 2) % 3], 2 * kt + s + 2);
+            b_load(bq[(2 * U + s + 2) % 3], 2 * kt + s + 2);
             __builtin_amdgcn_sched_barrier(0);   // the look-ahead loads stay HERE, two k-steps in front of their first use
             bf16x8 fa[TME][3];
 #pragma unroll
@@ -600,7 +546,6 @@ __device__ __forceinline__ void s6_main_loop(f32x16 (&acc)[2], unsigned char* sm
                 for (int i = 0; i < TME; ++i)
                     fa[i][p] = *reinterpret_cast<const bf16x8*>(img + p * S6_PLANE + i * 32 * 64 + (((2 * s + lh) ^ sw) * 16));
             const u32x4(&bs)[3] = bq[(2 * U + s) % 3];
-            if (s == 0) { AS_TR(1) }
             bf16x8 fb[3];
 #pragma unroll
             for (int p = 0; p < 3; ++p) fb[p] = __builtin_bit_cast(bf16x8, bs[p]);
@@ -612,21 +557,16 @@ __device__ __forceinline__ void s6_main_loop(f32x16 (&acc)[2], unsigned char* sm
             for (int o = 0; o < 6; ++o)
 #pragma unroll
                 for (int i = 0; i < TME; ++i)
-                    if (abl != 4) acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[i][PA[o]], fb[PB[o]], acc[i], 0, 0, 0);
-                    else acc[i][o] += (float)fa[i][PA[o]][0] * (float)fb[PB[o]][0];
+                    acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[i][PA[o]], fb[PB[o]], acc[i], 0, 0, 0);
             __builtin_amdgcn_sched_barrier(0);
             // The split of the NEXT tile (vector + LDS-store work, no matrix work) sits at a different place in the two halves of
             // the workgroup: waves 0-3 behind the tile's second k-step, waves 4-7 between the two.  Waves w and w + 4 share a
             // SIMD and, running the same program between the same barriers, would otherwise do their vector work at the same
             // moment and their matrix work at the same moment -- the matrix pipe idles through the former.
-            if (s == 0) { AS_TR(2) } else { AS_TR(3) }
-            if (abl != 3 && late == (s == 0)) a_store(aq[(U + 1) % 3], (kt & 1) ^ 1);   // (behind the last tile: a clamped repeat)
+            if (late == (s == 0)) a_store(aq[(U + 1) % 3], (kt & 1) ^ 1);   // (behind the last tile: a clamped repeat)
         }
-        AS_TR(4)
         lds_barrier();
-        AS_TR(5)
     };
-#undef AS_TR
     int kt = 0;
     for (; kt + 3 <= nk; kt += 3) {
         tile(IC<0>{}, kt);
@@ -672,172 +612,15 @@ __global__ __launch_bounds__(NT, 4) void lin_s6_kernel(LinK g) {
         d[4] = __builtin_amdgcn_s_memrealtime();
         d[5] = __builtin_amdgcn_s_getreg((4 - 1) << 11 | 0 << 6 | 4) | ((unsigned long long)__builtin_amdgcn_s_getreg((32 - 1) << 11 | 0 << 6 | 20) << 32);
     }
-    // diagnostic (AS_LIN_STAGGER = n > 0): the workgroups of the second fill (blocks 256..511 under round-robin dispatch, the
-    // second tenant of each CU) start n x 1024 cycles late, so that the two tenants' epilogues (and the chip's store bursts)
-    // do not coincide; n < 0: the same for blocks whose CU-slot parity ... (see lin_f32_kernel)
-    if (g.stagger > 0 && blockIdx.x >= 256 && blockIdx.x < 512)
-        for (int i = 0; i < g.stagger; ++i) __builtin_amdgcn_s_sleep(16);
     if (tm_eff == 2) s6_main_loop<8, 2>(acc, sm, A, g.lda, g.M - m0, g.K, g.ka_valid, bp, b_lane, g.bp_plane, (long)g.bp_rows * 16, tid, lane, late, stamp ? d + 1 : nullptr);
     else s6_main_loop<8, 1>(acc, sm, A, g.lda, g.M - m0, g.K, g.ka_valid, bp, b_lane, g.bp_plane, (long)g.bp_rows * 16, tid, lane, late, stamp ? d + 1 : nullptr);
     if (stamp) d[2] = __builtin_amdgcn_s_memtime();
-#if defined(AS_S6_ABL) && AS_S6_ABL == 1
-    if (acc[0][0] == 123.456f) g.C[0] = acc[0][0] + acc[1][0];  // keep the loop alive
-    return;
-#endif
     lin_epilogue<2, EPI>(g, acc, smem, bz, m0, tm_eff, wave, lane);
     if (stamp) {
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         d[3] = __builtin_amdgcn_s_memtime();
         d[6] = __builtin_amdgcn_s_memrealtime();
     }
-}
-
-// ---------------------------------------------------------------------------------------------------------------------
-// The wide form of lin_s6_kernel: ONE workgroup of 16 waves per CU owns 128 rows x 256 columns (two row groups of 8 column
-// waves; wave = 64 rows x 32 columns as before) and the weight planes go through the LDS too, staged once per workgroup.
-// Why: the 64-row kernel's main loop is bound by what the CUs pull from L2, not by the matrix pipe -- every wave loads its
-// own B fragments, 24 KB per 64 rows and 16-deep k-step, 432 MB per launch of head Linear 2 against 72 MB of activations;
-// removing the matrix instructions from that loop changed its time by 4 % (profiles/r04_s6_ablation.log).  Here a k-tile's
-// planes (48 KB) are fetched once per 128 rows: a quarter of the bytes per row.  LDS: two A images (2 x 24 KB) + two B
-// images (2 x 48 KB) = 144 KB; one barrier per 32-deep k-tile; A two tiles ahead in registers, B one tile ahead (load at the
-// top of a tile, ds_write_b128 at its end: one register set).  The epilogue stages 64 rows at a time ([64][256] floats in the
-// images' memory), every wave normalising four rows (lin_ln_rows).
-// Tile list: 128-row tiles first (whole rounds of one workgroup per CU), then 32-row tiles over the remaining rows (row group
-// 0 multiplies one row block, row group 1 only helps with the loads): the partly filled last round costs a third of a tile.
-constexpr int SW_NT = 1024;
-constexpr int SW_AIMG = 3 * 128 * 64;      // bytes of one A image: 3 planes x 128 rows x 32 bf16
-constexpr int SW_BIMG = 3 * 256 * 64;      // bytes of one B image: 3 planes x 256 rows x 32 bf16
-constexpr int SW_LDS = 2 * SW_AIMG + 2 * SW_BIMG;
-
-template <int TME>   // row blocks of 32 this wave multiplies per k-step: 2 (128-row tile), 1 (32-row tile, row group 0), 0 (loads only)
-__device__ __forceinline__ void s6w_main_loop(f32x16 (&acc)[2], unsigned char* sm, const float* __restrict__ A, long lda, int rows_valid, int K,
-                                              int ka_valid, const uint16_t* __restrict__ bp, long bp_plane, int bp_rows, int tid, int lane,
-                                              int wm, int wn, bool late) {
-    const int l31 = lane & 31, lh = lane >> 5;
-    // A: thread -> row tid >> 3 (0..127), 16-byte chunk tid & 7 of the row's 32 k
-    const int a_row = tid >> 3, a_chunk = tid & 7;
-    const unsigned a_off = (unsigned)(min(a_row, rows_valid - 1) * (int)lda + a_chunk * 4) * 4u;   // bytes
-    const int a_wr = a_row * 64 + (((a_chunk >> 1) ^ ((a_row >> 2) & 3)) * 16) + (a_chunk & 1) * 8;
-    // B: thread -> image row tid >> 2 (0..255), chunk tid & 3 = 8 consecutive k (k-step chunk >> 1, half chunk & 1)
-    const int b_row = tid >> 2, b_chunk = tid & 3;
-    const unsigned b_off = (unsigned)((((b_chunk >> 1) * bp_rows + b_row) * 16 + (b_chunk & 1) * 8) * 2);   // bytes
-    const int b_wr = b_row * 64 + ((b_chunk ^ ((b_row >> 2) & 3)) * 16);
-    const int nk = K / S6_BK;
-    const gptr Au = uniform_ptr(A);
-    const long bp_tile = 2L * bp_rows * 16;     // elements per 32-deep k-tile of one plane
-    auto a_load = [&](f32x4& dst, int kt) {
-        kt = min(kt, nk - 1);
-        const unsigned ko = kt * S6_BK + a_chunk * 4 + 4 <= ka_valid ? (unsigned)(kt * S6_BK) * 4u : 0u - (unsigned)a_chunk * 16u;
-        dst = *reinterpret_cast<gptr_f4>(Au + (a_off + ko));
-    };
-    auto a_store = [&](const f32x4& src, int buf) {
-        unsigned h0, m0, l0, h1, m1, l1;
-        split_pair(src.x, src.y, h0, m0, l0);
-        split_pair(src.z, src.w, h1, m1, l1);
-        unsigned char* d = sm + buf * SW_AIMG + a_wr;
-        *reinterpret_cast<uint2*>(d) = make_uint2(h0, h1);
-        *reinterpret_cast<uint2*>(d + 128 * 64) = make_uint2(m0, m1);
-        *reinterpret_cast<uint2*>(d + 2 * 128 * 64) = make_uint2(l0, l1);
-    };
-    auto b_load = [&](u32x4 (&dst)[3], int kt) {
-        kt = min(kt, nk - 1);
-#pragma unroll
-        for (int p = 0; p < 3; ++p) dst[p] = *reinterpret_cast<gptr_u4>(uniform_ptr(bp + p * bp_plane + kt * bp_tile) + b_off);
-    };
-    auto b_store = [&](const u32x4 (&src)[3], int buf) {
-        unsigned char* d = sm + 2 * SW_AIMG + buf * SW_BIMG + b_wr;
-#pragma unroll
-        for (int p = 0; p < 3; ++p) *reinterpret_cast<u32x4*>(d + p * 256 * 64) = src[p];
-    };
-    const int sw = (l31 >> 2) & 3;
-    const unsigned char* a_rd = sm + (wm * 64 + l31) * 64;
-    const unsigned char* b_rd = sm + 2 * SW_AIMG + (wn * 32 + l31) * 64;
-
-    f32x4 aq[2];
-    u32x4 bq[3];
-    a_load(aq[0], 0);
-    b_load(bq, 0);
-    a_load(aq[1], 1);
-    a_store(aq[0], 0);
-    b_store(bq, 0);
-    lds_barrier();
-    // k-tile kt: images in buffers kt & 1; registers aq[(kt + 1) & 1] hold A of tile kt + 1
-    auto tile = [&](auto Uc, int kt) {
-        constexpr int U = decltype(Uc)::value;   // kt & 1
-        b_load(bq, kt + 1);
-        f32x4 a_next;
-        a_load(a_next, kt + 2);
-        __builtin_amdgcn_sched_barrier(0);
-        const unsigned char* ai = a_rd + U * SW_AIMG;
-        const unsigned char* bi = b_rd + U * SW_BIMG;
-#pragma unroll
-        for (int s = 0; s < 2; ++s) {
-            if (TME > 0) {
-                bf16x8 fa[TME > 0 ? TME : 1][3], fb[3];
-                const int ch = ((2 * s + lh) ^ sw) * 16;
-#pragma unroll
-                for (int p = 0; p < 3; ++p) {
-#pragma unroll
-                    for (int i = 0; i < TME; ++i) fa[i][p] = *reinterpret_cast<const bf16x8*>(ai + p * 128 * 64 + i * 32 * 64 + ch);
-                    fb[p] = *reinterpret_cast<const bf16x8*>(bi + p * 256 * 64 + ch);
-                }
-                constexpr int PA[6] = {0, 0, 0, 1, 1, 2}, PB[6] = {0, 1, 2, 0, 1, 0};
-#pragma unroll
-                for (int o = 0; o < 6; ++o)
-#pragma unroll
-                    for (int i = 0; i < TME; ++i) acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[i][PA[o]], fb[PB[o]], acc[i], 0, 0, 0);
-            }
-            __builtin_amdgcn_sched_barrier(0);
-            // the next tile's images are written between the two k-steps by half of the waves and behind the second by the other
-            // half (SIMD partners then do their vector / LDS-store work at different moments, see s6_main_loop)
-            if (late == (s == 0)) {
-                a_store(aq[U ^ 1], U ^ 1);
-                b_store(bq, U ^ 1);
-            }
-        }
-        aq[U] = a_next;
-        lds_barrier();
-    };
-    int kt = 0;
-    for (; kt + 2 <= nk; kt += 2) {
-        tile(IC<0>{}, kt);
-        tile(IC<1>{}, kt + 1);
-    }
-    if (kt < nk) tile(IC<0>{}, kt);
-}
-
-template <int EPI>
-__global__ __launch_bounds__(SW_NT, 4) void lin_s6w_kernel(LinK g) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smw[];
-    int bz, m0, rows;
-    const int tile = blockIdx.x;
-    if (tile < g.n_big) {
-        bz = tile / g.big_per_batch;
-        m0 = (tile - bz * g.big_per_batch) * 128;
-        rows = 128;
-    } else {
-        const int j = tile - g.n_big;
-        bz = j / g.small_per_batch;
-        m0 = g.big_per_batch_rows + (j - bz * g.small_per_batch) * 32;
-        rows = 32;
-    }
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int wave_u = __builtin_amdgcn_readfirstlane(wave);
-    const int wm = wave_u >> 3, wn = wave_u & 7;
-    f32x16 acc[2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[i][r] = 0.f;
-    const uint16_t* bp = g.Bp + (long)bz * g.bp_batch;
-    const float* A = g.A + (long)bz * g.a_batch + (long)m0 * g.lda;
-    const bool late = (wave_u >> 2) & 1;
-    if (rows == 128) s6w_main_loop<2>(acc, smw, A, g.lda, g.M - m0, g.K, g.ka_valid, bp, g.bp_plane, g.bp_rows, tid, lane, wm, wn, late);
-    else if (wm == 0) s6w_main_loop<1>(acc, smw, A, g.lda, g.M - m0, g.K, g.ka_valid, bp, g.bp_plane, g.bp_rows, tid, lane, wm, wn, late);
-    else s6w_main_loop<0>(acc, smw, A, g.lda, g.M - m0, g.K, g.ka_valid, bp, g.bp_plane, g.bp_rows, tid, lane, wm, wn, late);
-    const int col = wn * 32 + (lane & 31);
-    const float bj = (EPI == EPI_LNF && g.bias) ? g.bias[(long)bz * g.bias_batch + col] : 0.f;
-    lin_ln_rows<2, EPI, 8>(g, acc, reinterpret_cast<float*>(smw), bz, m0, rows == 128 ? 2 : 1, rows == 128 ? 2 : 1, wave, lane, bj);
 }
 
 // A plain Linear on the same main loop: C = act(A . B^T + bias), 64 (or 32) rows x 32 NW columns per workgroup (NW = 8:
@@ -1268,13 +1051,11 @@ inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 
 template <bool B_KC, int EPI>
 int launch(const LinK& k, hipStream_t st) {
     LinK kk = k;
-    static const int nbuf = AS_DIAG_INT("AS_LIN_NBUF", 3);      // 2: two ring slots, three workgroups per CU (diagnostic)
-    const int slots = nbuf == 2 ? 768 : 512;
+    constexpr int slots = 512;
     const long units = (long)as_cdiv(k.M, 64) * k.batch;      // work in 64-row tiles
     const long rounds = units / slots;
-    static const bool all_big = AS_DIAG_SET("AS_LIN_ALLBIG");  // ablation: 64-row tiles only (+ a ragged end)
     int x = (int)(rounds * slots / k.batch);                    // 64-row tiles per head that fill whole rounds
-    if (x > k.M / 64 || all_big || k.tile_rows == 64) x = k.M / 64;
+    if (x > k.M / 64 || k.tile_rows == 64) x = k.M / 64;
     if (k.tile_rows == 32) x = 0;
     const int rest = k.M - x * 64;
     kk.big_per_batch = x > 0 ? x : 1;
@@ -1283,45 +1064,11 @@ int launch(const LinK& k, hipStream_t st) {
     kk.small_per_batch = as_cdiv(rest, 32);
     const long total = (long)kk.n_big + (long)kk.small_per_batch * k.batch;
     if (kk.small_per_batch == 0) kk.small_per_batch = 1;
-    if (kk.Bp && EPI != EPI_PLAIN && k.tile_rows == 0 && (long)as_cdiv(k.M, 128) * k.batch >= 256 && k.bp_rows == BN) {
-        // at least one whole round of 128-row tiles: the wide kernel (one 16-wave workgroup per CU, B planes through LDS)
-        // MEASURED SLOWER than the 64-row kernel (head Linear 2: 77.5 vs 63.4 us, dx2 86.5 vs 80.2 us, gpurun_out/r04a): all 16
-        // waves of the CU meet at one barrier per k-tile, and a workgroup alone on its CU keeps the matrix pipe about half busy
-        // (per-tile stamps, tools/s6_trace.py: ~1000 cycles until a tile's first fragments are in registers, ~900 at the barrier,
-        // ~550 in the split, against 768 of matrix instructions per wave) -- two independent 8-wave workgroups fill each
-        // other's gaps, one 16-wave workgroup does not.  Kept for the diagnostic build only (AS_LIN_WIDE=1).
-        static const bool wide = AS_DIAG_SET("AS_LIN_WIDE");
-        if (wide) {
-            static const hipError_t attr =
-                hipFuncSetAttribute(reinterpret_cast<const void*>(lin_s6w_kernel<EPI>), hipFuncAttributeMaxDynamicSharedMemorySize, SW_LDS);
-            if (attr != hipSuccess) {
-                as_set_error("as_lin_s6w: cannot reserve %d bytes of LDS: %s", SW_LDS, hipGetErrorString(attr));
-                return (int)attr;
-            }
-            const long t128 = (long)(k.M / 128) * k.batch;          // whole 128-row tiles
-            int xw = (int)((t128 / 256) * 256 / k.batch);            // ... per head that fill whole rounds of the 256 CUs
-            if (xw > k.M / 128) xw = k.M / 128;
-            const int restw = k.M - xw * 128;
-            kk.big_per_batch = xw > 0 ? xw : 1;
-            kk.big_per_batch_rows = xw * 128;
-            kk.n_big = xw * k.batch;
-            kk.small_per_batch = as_cdiv(restw, 32);
-            const long totalw = (long)kk.n_big + (long)kk.small_per_batch * k.batch;
-            if (kk.small_per_batch == 0) kk.small_per_batch = 1;
-            hipLaunchKernelGGL((lin_s6w_kernel<EPI>), dim3((unsigned)totalw), dim3(SW_NT), SW_LDS, st, kk);
-            AS_LAUNCH_CHECK("as_lin_s6w");
-            return 0;
-        }
-    }
     if (kk.Bp) {   // the products on the bf16 matrix instruction, B as planes (lin_s6_kernel)
         hipLaunchKernelGGL((lin_s6_kernel<EPI>), dim3((unsigned)total), dim3(NT), 0, st, kk);
         AS_LAUNCH_CHECK("as_lin_s6");
         return 0;
     }
-#ifdef AS_DIAG
-    if (nbuf == 2) hipLaunchKernelGGL((lin_f32_kernel<64, B_KC, EPI, 2>), dim3((unsigned)total), dim3(NT), 0, st, kk);
-    else
-#endif
     hipLaunchKernelGGL((lin_f32_kernel<64, B_KC, EPI>), dim3((unsigned)total), dim3(NT), 0, st, kk);
     AS_LAUNCH_CHECK("as_lin_f32");
     return 0;
@@ -1340,8 +1087,6 @@ extern "C" void as_lin_debug_stamps(uint64_t* buf, int64_t max_workgroups) {
 // see gemm_internal.h.  Returns 1 if launched, 0 if the arguments are outside what the kernel is built for (the caller
 // then takes the general GEMM + row kernels), < 0 on a launch error.
 int as_lin_try(const as_lin* a, hipStream_t st) {
-    static const bool off = AS_DIAG_SET("AS_NO_LIN");  // ablation: the round-1 path
-    if (off) return 0;
     if (a->K % BK || a->K < BK || a->N > BN || a->N < 4 || a->M < 1 || a->batch < 1) return 0;
     if (!aligned16(a->A) || !aligned16(a->B) || a->lda % 4 || a->ldb % 4 || a->a_batch % 4 || a->b_batch % 4) return 0;
     if (!a->b_kc && a->N % 4) return 0;
@@ -1356,14 +1101,6 @@ int as_lin_try(const as_lin* a, hipStream_t st) {
     k.M = a->M; k.N = a->N; k.K = a->K; k.ka_valid = a->ka_valid > 0 ? a->ka_valid : a->K; k.batch = a->batch; k.act = a->act;
     k.tile_rows = a->tile_rows;
     k.eps = 1e-5f;
-#ifdef AS_DIAG
-    static const int abl = AS_DIAG_INT("AS_LIN_ABL", 0);
-    k.abl = abl;
-    // round 3: 1 (second workgroup of a CU half a tile late) is -3 % on one box and +3 % on the next: noise; < 0 = XCD de-phasing
-    // (strictly slower); with AS_LIN_NBUF=2 (three workgroups per CU on a 2-slot ring) thirds of a tile: no change either
-    static const int stagger = AS_DIAG_INT("AS_LIN_STAGGER", 0);
-    k.stagger = stagger;
-#endif
     k.dbg = g_dbg; k.dbg_max = g_dbg_max;
     k.rstd = a->rstd; k.bits = a->bits;
     k.xhat = a->xhat; k.ldx = a->ldx; k.x_batch = a->x_batch; k.rstd_in = a->rstd_in; k.bits_in = a->bits_in;
@@ -1387,8 +1124,7 @@ int as_lin_try(const as_lin* a, hipStream_t st) {
 
 // see gemm_internal.h
 int as_lin_plain_s6(const as_lin* a, int ksplit, long c_split, hipStream_t st) {
-    static const bool off = AS_DIAG_SET("AS_NO_PLAIN_S6");   // diagnostic: callers fall back to the general fp32 kernel
-    if (off || as_matrix_arith() != AS_ARITH_BF16X6 || !a->Bp) return 0;
+    if (as_matrix_arith() != AS_ARITH_BF16X6 || !a->Bp) return 0;
     if (a->epi != EPI_PLAIN || a->K % S6_BK || a->K < S6_BK || a->N > BN || a->N < 1 || a->M < 1 || a->batch < 1 || !a->C) return 0;
     if (!aligned16(a->A) || a->lda % 4 || a->a_batch % 4 || a->lda >= (1L << 23)) return 0;
     if ((reinterpret_cast<uintptr_t>(a->Bp) & 15) || a->bp_plane % 8 || a->bp_batch % 8) return 0;
@@ -1427,8 +1163,6 @@ int as_lin_plain_s6(const as_lin* a, int ksplit, long c_split, hipStream_t st) {
 // Output layer of the heads, optionally with the masked Euclidean criterion and its gradient fused in (see lin_out_kernel).
 // 1 = launched (fused: *n_partials workgroup sums were written to `partial`), 0 = not a case, < 0 = error.
 int as_lin_out_try(const as_lin_out* a, int* n_partials, hipStream_t st) {
-    static const bool off = AS_DIAG_SET("AS_NO_LIN_OUT");  // ablation: the general GEMM (+ the separate criterion kernel)
-    if (off) return 0;
     if (a->K % BK || a->K < BK || a->N > ON || a->N < 4 || a->N % 2 || a->M < 1 || a->batch < 1) return 0;
     if (!aligned16(a->A) || !aligned16(a->B) || a->lda % 4 || a->ldb % 4 || a->a_batch % 4 || a->b_batch % 4) return 0;
     if (a->b_rows < a->N) return 0;
@@ -1456,14 +1190,12 @@ int as_lin_out_try(const as_lin_out* a, int* n_partials, hipStream_t st) {
     const long total = (long)k.n_big + (long)k.small_per_batch * k.batch;
     if (k.small_per_batch == 0) k.small_per_batch = 1;
     if (k.tgt && total > a->partial_capacity) return 0;
-    static const bool no_tail = AS_DIAG_SET("AS_NO_LOSS_TAIL");   // ablation: the separate final-sum kernel
-    if (k.tgt && a->loss && !no_tail) {
+    if (k.tgt && a->loss) {
         k.counter = as_arrival_counter(st);
         k.loss = k.counter ? a->loss : nullptr;
     }
     const int left = k.counter ? 0 : (int)total;   // partials that still await as_loss_final
-    static const bool no_s6 = AS_DIAG_SET("AS_NO_LIN_OUT_S6");   // diagnostic: the output layer on the fp32 instruction
-    if (!no_s6 && a->Bp && as_matrix_arith() == AS_ARITH_BF16X6 && a->K % S6_BK == 0 && a->bp_rows >= ON && (reinterpret_cast<uintptr_t>(a->Bp) & 15) == 0 &&
+    if (a->Bp && as_matrix_arith() == AS_ARITH_BF16X6 && a->K % S6_BK == 0 && a->bp_rows >= ON && (reinterpret_cast<uintptr_t>(a->Bp) & 15) == 0 &&
         a->bp_plane % 8 == 0 && a->bp_batch % 8 == 0 && a->lda < (1L << 23)) {
         k.Bp = a->Bp; k.bp_plane = a->bp_plane; k.bp_batch = a->bp_batch; k.bp_rows = a->bp_rows;
         hipLaunchKernelGGL(lin_out_s6_kernel, dim3((unsigned)total), dim3(256), 0, st, k);

@@ -133,94 +133,8 @@ __global__ __launch_bounds__(LPU * H) void lstm_fwd_kernel(const float* __restri
     if (s + 1 < len) step(s + 1, bq, a);
 }
 
-template <int H>
-__global__ __launch_bounds__(LPU * H) void lstm_bwd_kernel(const float* __restrict__ dy, const float* __restrict__ gates,
-                                                           const float* __restrict__ w_hh, const int* __restrict__ lengths, int T,
-                                                           float* __restrict__ dg) {
-    constexpr int CW = 4 * LPU, NC = 4 * H / CW, NT = LPU * H;
-    __shared__ __attribute__((aligned(16))) float gbuf[2][4 * H];
-    const int b = blockIdx.x, dir = blockIdx.y;
-    const int tid = threadIdx.x, k = tid / LPU, q = tid % LPU;
-    const int len = lengths[b];
-
-    f32x2 wt[NC * 2];  // W_hh^T: rows i = CW*c + 4q + ii of column k
-    {
-        const float* wd = w_hh + (long)dir * 4 * H * H;
-#pragma unroll
-        for (int c = 0; c < NC; ++c) {
-            wt[2 * c] = f32x2{wd[(long)(CW * c + 4 * q) * H + k], wd[(long)(CW * c + 4 * q + 1) * H + k]};
-            wt[2 * c + 1] = f32x2{wd[(long)(CW * c + 4 * q + 2) * H + k], wd[(long)(CW * c + 4 * q + 3) * H + k]};
-        }
-    }
-    for (long i = (long)len * 4 * H + tid; i < (long)T * 4 * H; i += NT) {  // padded frames feed the time-batched GEMMs as zeros
-        const long t = i / (4 * H), c = i % (4 * H);
-        dg[(((long)b * T + t) * 2 + dir) * 4 * H + c] = 0.f;
-    }
-    if (len <= 0) return;
-
-    const int t0 = dir ? 0 : len - 1;  // opposite to the forward walk
-    const int dt = dir ? 1 : -1;
-    const float* gtb = gates + (long)dir * 5 * H + k;  // + frame * 10H
-    const float* dyb = dy + dir * H + k;               // + frame * 2H
-    float* dgb = dg + (long)dir * 4 * H + k;           // + frame * 8H + plane * H
-    const int m0 = q == 0 ? -1 : 0, m1 = q == 1 ? -1 : 0, m2 = q == 2 ? -1 : 0, m3 = q == 3 ? -1 : 0;
-    struct In { float i, f, g, o, c, cprev, dyv; };
-    // c_{prev} of frame t is the cell state of the frame this walk visits next (t + dt); zero beyond the sequence start
-    auto load = [&](long fr, bool has_prev) {
-        In v;
-        const float* gp = gtb + fr * 10 * H;
-        v.i = gp[0]; v.f = gp[H]; v.g = gp[2 * H]; v.o = gp[3 * H]; v.c = gp[4 * H];
-        const float cp = gtb[(fr + (has_prev ? dt : 0)) * 10 * H + 4 * H];
-        v.cprev = has_prev ? cp : 0.f;
-        v.dyv = dyb[fr * 2 * H];
-        return v;
-    };
-    long fr = (long)b * T + t0;
-    float dh = 0.f, dc = 0.f;
-    In cur_in = load(fr, len > 1);
-    for (int s = 0; s < len; ++s) {
-        const int cur = s & 1;
-        const int adv = s + 1 < len ? dt : 0;
-        const In nxt = load(fr + adv, s + 2 < len);
-        const float dht = dh + cur_in.dyv;
-        const float tc = as_tanh(cur_in.c);
-        const float dct = dc + dht * cur_in.o * (1.f - tc * tc);
-        const float p_o = dht * tc * cur_in.o * (1.f - cur_in.o);
-        const float p_i = dct * cur_in.g * cur_in.i * (1.f - cur_in.i);
-        const float p_f = dct * cur_in.cprev * cur_in.f * (1.f - cur_in.f);
-        const float p_g = dct * cur_in.i * (1.f - cur_in.g * cur_in.g);
-        dc = dct * cur_in.f;
-        const float v = __int_as_float((__float_as_int(p_i) & m0) | (__float_as_int(p_f) & m1) | (__float_as_int(p_g) & m2) |
-                                       (__float_as_int(p_o) & m3));
-        gbuf[cur][q * H + k] = v;
-        dgb[fr * 8 * H + q * H] = v;
-        __syncthreads();
-        const float4* gq = reinterpret_cast<const float4*>(gbuf[cur]);
-        f32x2 a0 = {0.f, 0.f}, a1 = {0.f, 0.f};
-#pragma unroll
-        for (int c0 = 0; c0 < NC; c0 += 8) {
-            float4 gv[8];
-#pragma unroll
-            for (int u = 0; u < 8; ++u)
-                if (c0 + u < NC) gv[u] = gq[LPU * (c0 + u) + q];
-            __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int u = 0; u < 8; ++u)
-                if (c0 + u < NC) {
-                    const int c = c0 + u;
-                    a0 = __builtin_elementwise_fma(wt[2 * c], f32x2{gv[u].x, gv[u].y}, a0);
-                    a1 = __builtin_elementwise_fma(wt[2 * c + 1], f32x2{gv[u].z, gv[u].w}, a1);
-                }
-        }
-        dh = quad_sum((a0.x + a0.y) + (a1.x + a1.y));
-        cur_in = nxt;
-        fr += dt;
-        // gbuf is double buffered: the next step writes gbuf[cur^1], whose readers all passed the barrier above
-    }
-}
-
-// Backward recurrence, row layout (as gru_bwd_row_kernel): the unit layout above reads all 4H gate gradients per lane quad
-// (32 ds_read_b128 per lane and step at H = 128: 8 waves x 32 x 8 cycles = 2048 LDS cycles, the whole measured step).  Here a
+// Backward recurrence, row layout (as gru_bwd_row_kernel): the earlier layout of 4 lanes per unit read all 4H gate gradients
+// per lane quad (32 ds_read_b128 per lane and step at H = 128: 8 waves x 32 x 8 cycles = 2048 LDS cycles, the whole measured step).  Here a
 // ROW of 16 lanes owns 4 hidden units: a lane holds W_hh^T for those 4 columns over 1/16 of the gate rows (the same 128
 // weight VGPRs), reads 4H/16 gate gradients per step (8 ds_read_b128) and the four partial sums are reduce-scattered over
 // the row (rotated accumulator slots: 5 DPP adds, every lane ends with the total of ITS unit).  Lane r of a row plays
@@ -525,14 +439,7 @@ extern "C" int as_lstm_bidir_bwd(const float* dy, const float* gates, const floa
     AS_REQUIRE(B > 0 && T > 0, AS_ERR_BAD_ARG, "as_lstm_bidir_bwd: B=%d T=%d", B, T);
     hipStream_t st = (hipStream_t)stream;
     const dim3 grid(B, 2);
-#ifdef AS_DIAG
-    static const bool unit_layout = AS_DIAG_SET("AS_LSTM_BWD_UNIT");  // ablation: the older 4-lanes-per-unit layout
-#define AS_LSTM_BWD(HH)                                                                                                     \
-    if (unit_layout) hipLaunchKernelGGL((lstm_bwd_kernel<HH>), grid, dim3(LPU * HH), 0, st, dy, gates, w_hh, lengths, T, dg); \
-    else hipLaunchKernelGGL((lstm_bwd_row_kernel<HH>), grid, dim3(4 * HH), 0, st, dy, gates, w_hh, lengths, T, dg)
-#else
 #define AS_LSTM_BWD(HH) hipLaunchKernelGGL((lstm_bwd_row_kernel<HH>), grid, dim3(4 * HH), 0, st, dy, gates, w_hh, lengths, T, dg)
-#endif
     switch (H) {
         case 32: AS_LSTM_BWD(32); break;
         case 64: AS_LSTM_BWD(64); break;

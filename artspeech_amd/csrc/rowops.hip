@@ -677,51 +677,6 @@ __global__ __launch_bounds__(256) void layernorm_fwd_kernel(const float* __restr
 // register for all of them (wave-uniform offsets).  NV = max float4 per lane (D <= 1024 NV).
 constexpr int WIDE_NV = 11;   // 2816 = A d at A = 11, d = 256
 
-// x_hat = affine-free LayerNorm(x [+ res]); res_block > 0: block-major residual (as_layernorm_fwd_blockres)
-__global__ __launch_bounds__(256) void layernorm_fwd_wide_kernel(const float* __restrict__ x, const float* __restrict__ res,
-                                                                 float* __restrict__ xhat, float* __restrict__ rstd, long rows, int D,
-                                                                 float eps, int res_block, long res_rows) {
-    const long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
-    const int lane = threadIdx.x & 63;
-    if (row >= rows) return;
-    const int nv = D >> 8;   // float4 per lane
-    const float4* xr = reinterpret_cast<const float4*>(x + row * D) + lane;
-    const float* rr = res ? res + (res_block > 0 ? ((row / res_rows) * (D / res_block) * res_rows + row % res_rows) * res_block : row * D) : nullptr;
-    const long res_jstride = res_block > 0 ? res_rows * res_block - res_block : 0;
-    float4 v[WIDE_NV];
-#pragma unroll
-    for (int c = 0; c < WIDE_NV; ++c) {
-        const int cc = c < nv ? c : 0;                       // (wave-uniform: lanes beyond the row re-read its first chunk)
-        v[c] = xr[64 * cc];
-        if (rr) {
-            const int e = 4 * lane + 256 * cc;               // first feature of this float4 (never straddles a block: block % 4 == 0)
-            const float4 t = *reinterpret_cast<const float4*>(rr + e + (res_block > 0 ? (e / res_block) * res_jstride : 0));
-            v[c].x += t.x; v[c].y += t.y; v[c].z += t.z; v[c].w += t.w;
-        }
-    }
-    float sum = 0.f;
-#pragma unroll
-    for (int c = 0; c < WIDE_NV; ++c) {
-        if (c >= nv) v[c] = make_float4(0.f, 0.f, 0.f, 0.f);
-        sum += (v[c].x + v[c].y) + (v[c].z + v[c].w);
-    }
-    const float mean = as_wave_sum(sum) / D;
-    float q = 0.f;
-#pragma unroll
-    for (int c = 0; c < WIDE_NV; ++c) {
-        if (c < nv) {
-            v[c].x -= mean; v[c].y -= mean; v[c].z -= mean; v[c].w -= mean;
-            q += (v[c].x * v[c].x + v[c].y * v[c].y) + (v[c].z * v[c].z + v[c].w * v[c].w);
-        }
-    }
-    const float rs = 1.0f / sqrtf(as_wave_sum(q) / D + eps);
-    float4* o = reinterpret_cast<float4*>(xhat + row * D) + lane;
-#pragma unroll
-    for (int c = 0; c < WIDE_NV; ++c)
-        if (c < nv) o[64 * c] = make_float4(v[c].x * rs, v[c].y * rs, v[c].z * rs, v[c].w * rs);
-    if (rstd && lane == 0) rstd[row] = rs;
-}
-
 // dx = rstd * (dy - mean(dy) - xhat * mean(dy * xhat)), no ReLU mask
 __global__ __launch_bounds__(256) void normalize_bwd_wide_kernel(const float* dy, const float* __restrict__ xhat,
                                                                  const float* __restrict__ rstd, float* dx, long rows, int D) {
@@ -1054,16 +1009,9 @@ extern "C" int as_layernorm_fwd(const float* x, const float* res, const float* g
                                 float* rstd, int64_t rows, int32_t D, int64_t group_rows, void* stream) {
     AS_REQUIRE(x && (y || xhat) && rows > 0 && D > 0 && (!gamma == !beta), AS_ERR_BAD_ARG, "as_layernorm_fwd: bad argument");
     AS_REQUIRE(D <= 64 * 44, AS_ERR_UNSUPPORTED, "as_layernorm_fwd: row length %d > %d", D, 64 * 44);
-    // (the 16-byte forward kernel is built and tested, but not dispatched: it sums a row in a different order, and the full-width
-    // transformer's contours -- 0.89 of the 1e-4 band against the reference with the scalar kernel -- land at 1.03 with it:
-    // rounding noise either way, but the band is the contract; the gain was 0.6 ms of a 70 ms forward)
-    static const bool wide_fwd = AS_DIAG_SET("AS_LN_WIDE_FWD");
-    if (wide_fwd && !gamma && !y && wide_ok(D, x, res, xhat)) {   // wide affine-free rows: 16-byte accesses
-        hipLaunchKernelGGL(layernorm_fwd_wide_kernel, dim3(as_cdiv(rows, 4)), dim3(256), 0, (hipStream_t)stream, x, res, xhat, rstd, (long)rows,
-                           D, 1e-5f, 0, 0L);
-        AS_LAUNCH_CHECK("as_layernorm_fwd");
-        return 0;
-    }
+    // (a 16-byte forward kernel like normalize_bwd_wide_kernel was measured and dropped: it sums a row in a different order,
+    // and the full-width transformer's contours -- 0.89 of the 1e-4 band against the reference with the scalar kernel -- landed
+    // at 1.03 with it: rounding noise either way, but the band is the contract; the gain was 0.6 ms of a 70 ms forward)
 #define AS_LN_FWD(NW)                                                                                                                  \
     do {                                                                                                                               \
         if (gamma)                                                                                                                     \
@@ -1093,13 +1041,6 @@ extern "C" int as_layernorm_fwd_blockres(const float* x, const float* res, float
     const int D = per * block;
     AS_REQUIRE(D <= 64 * 44, AS_ERR_UNSUPPORTED, "as_layernorm_fwd_blockres: row length %d > %d", D, 64 * 44);
     const long total = (long)channels * rows;
-    static const bool wide_fwd = AS_DIAG_SET("AS_LN_WIDE_FWD");   // (see as_layernorm_fwd)
-    if (wide_fwd && block % 4 == 0 && wide_ok(D, x, res, xhat)) {
-        hipLaunchKernelGGL(layernorm_fwd_wide_kernel, dim3(as_cdiv(total, 4)), dim3(256), 0, (hipStream_t)stream, x, res, xhat, rstd, total, D,
-                           1e-5f, block, (long)rows);
-        AS_LAUNCH_CHECK("as_layernorm_fwd_blockres");
-        return 0;
-    }
 #define AS_LN_FWD(NW)                                                                                                                \
     do {                                                                                                                             \
         if (block % 64 == 0)                                                                                                         \

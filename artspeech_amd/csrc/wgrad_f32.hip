@@ -35,8 +35,8 @@ typedef unsigned u32x4w __attribute__((ext_vector_type(4)));
 
 namespace {
 
-constexpr int BM = 128, NT = 512, NBUF = 3;
-constexpr int KALIGN = 32;   // reduction chunks are multiples of both k-tile depths
+constexpr int BM = 128, BK = 32, NT = 512, NBUF = 3;
+constexpr int KALIGN = BK;   // reduction chunks are multiples of the k-tile depth
 
 // source of the shifted B operand's out-of-sequence rows (b_kT > 0): one row of zeros the DMA can read
 __device__ __attribute__((aligned(16))) float g_zero_row[256];
@@ -63,16 +63,11 @@ struct WgradK {
     float* colsum_b; long colsum_b_batch; float* csb_slab;
     int c_trans;
     long tile0;   // stream-K launches: first output tile of this problem in the launch's tile numbering
-#ifdef AS_DIAG
-    int abl;  // diagnostic ablation (AS_WGRAD_ABL=1): no global loads after the first two k-tiles (matrix work only)
-#else
-    static constexpr int abl = 0;
-#endif
 };
 
 // LDS-DMA helper: one wave-instruction copies 64 x 16 B from per-lane global addresses to 1 KiB of LDS starting at the
 // wave-uniform `dst` (global_load_lds_dwordx4: no VGPR destination, counted by vmcnt).  Inline asm: with the builtin hipcc
-// may put an s_waitcnt vmcnt(0) in front of the next ds_read (it did in the BK = 16 instantiation), which drains the ring.
+// may put an s_waitcnt vmcnt(0) in front of the next ds_read (it did in a 16-deep k-tile version), which drains the ring.
 __device__ __forceinline__ void glds16(const float* src, float* dst) {
     unsigned keep;
     const unsigned lds = __builtin_amdgcn_readfirstlane((unsigned)(uintptr_t)(const __attribute__((address_space(3))) float*)dst);
@@ -82,8 +77,7 @@ __device__ __forceinline__ void glds16(const float* src, float* dst) {
                  : "memory");
 }
 
-// BK = 32: one workgroup per CU (144 KB of LDS at BN = 256, two k-tiles = 96 KB in flight).  BK = 16: 72 KB, two workgroups
-// per CU -- the partner's MFMAs cover this one's barriers, prologue and epilogue.
+// One workgroup per CU (144 KB of LDS at BN = 256, two k-tiles = 96 KB in flight).
 // Stream-K (streamk = 1): the launch's work is the flat sequence of k-tiles (32 frames) of all its output tiles, tile after
 // tile; workgroup w takes units [w U, (w + 1) U).  A tile that one workgroup covers from its first k-tile to its last is
 // written as usual; a tile cut by a workgroup boundary leaves one PIECE per workgroup in the slab (slot 0: the piece a
@@ -102,7 +96,7 @@ struct WgradMulti {
 };
 
 // SK: the stream-K instantiation (mm.streamk launches); the plain one compiles to a single pass of the segment loop.
-// S6 (BK = 32): the products on the bfloat16 matrix instruction (as_set_matrix_arith(1): three planes per operand, six plane
+// S6: the products on the bfloat16 matrix instruction (as_set_matrix_arith(1): three planes per operand, six plane
 //   products per fp32 product, fp32 accumulation; see lin_f32.hip).  The fp32 image in LDS stays as it is ([k][m]: what the
 //   DMA delivers); a lane's MFMA fragment -- 8 consecutive frames of one column -- is read down the image (8 ds_read_b32,
 //   conflict-free) and split in registers (36 vector instructions).  Every wave splits the fragments it multiplies: the A
@@ -111,9 +105,8 @@ struct WgradMulti {
 //   the matrix instructions of k-step s (about seven vector instructions fit under one 32-cycle MFMA), and the barrier
 //   that publishes k-tile t + 1 sits in the MIDDLE of tile t, so that the first fragments of t + 1 are split under the second
 //   half of t's matrix work.  Per 32-frame k-tile a wave issues 48 MFMAs of 32 cycles instead of 64 of 64.
-template <int BN, int BK, bool SK = false, bool S6 = false>
-__global__ __launch_bounds__(NT, BK == 16 ? 4 : 2) void wgrad_f32_kernel(WgradMulti mm) {
-    static_assert(!S6 || BK == 32, "split arithmetic: 32-deep k-tiles");
+template <int BN, bool SK = false, bool S6 = false>
+__global__ __launch_bounds__(NT, 2) void wgrad_f32_kernel(WgradMulti mm) {
     constexpr int WN = BN / 4, TN = WN / 32, TM = 2;   // 2 x 4 waves; a wave owns 64 rows x WN columns
     constexpr int TILE = BK * (BM + BN);                // floats per ring slot: A image [BK][BM] then B image [BK][BN]
     constexpr int PA = BK * BM / 256 / 8;               // 1-KiB DMA pieces of A per wave and k-tile (2)
@@ -276,7 +269,7 @@ __global__ __launch_bounds__(NT, BK == 16 ? 4 : 2) void wgrad_f32_kernel(WgradMu
         load_frags(fa0, fb0, 0, 0);
         for (int kt = 0; kt < nk; ++kt) {
             // slot (kt + 2) % 3 was last read (k-step 1 of tile kt - 1) before the barrier in the middle of tile kt - 1
-            if (kt + 2 < nk && g.abl != 1) issue(kt + 2);
+            if (kt + 2 < nk) issue(kt + 2);
             const float* tile = smem + (kt % NBUF) * TILE;
             if (do_cs) {
                 const float* c_s = tile + (tid >> 7) * CSR * BM + (tid & 127);
@@ -294,7 +287,7 @@ __global__ __launch_bounds__(NT, BK == 16 ? 4 : 2) void wgrad_f32_kernel(WgradMu
             interleave();
             __builtin_amdgcn_sched_barrier(0);
             // retire tile kt + 1 (leave kt + 2 in flight) and publish it; this wave's reads of tile kt are all issued
-            if (kt + 2 < nk && g.abl != 1) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(PA + PB) : "memory");
+            if (kt + 2 < nk) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(PA + PB) : "memory");
             else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
             __builtin_amdgcn_s_barrier();
@@ -318,7 +311,7 @@ __global__ __launch_bounds__(NT, BK == 16 ? 4 : 2) void wgrad_f32_kernel(WgradMu
     __builtin_amdgcn_s_barrier();
     for (int kt = 0; kt < nk; ++kt) {
         // slot (kt + 2) % 3 was read in iteration kt - 1; every wave passed the barrier that ended it
-        if (kt + 2 < nk && g.abl != 1) issue(kt + 2);
+        if (kt + 2 < nk) issue(kt + 2);
         const float* tile = smem + (kt % NBUF) * TILE;
         const float* a_s = tile + wm * 64 + l31;
         const float* b_s = tile + BK * BM + wn * WN + l31;
@@ -355,7 +348,7 @@ __global__ __launch_bounds__(NT, BK == 16 ? 4 : 2) void wgrad_f32_kernel(WgradMu
                     acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[c][i], bv[c][j], acc[i][j], 0, 0, 0);
         }
         // retire tile kt + 1 (leave kt + 2 in flight), then publish it
-        if (kt + 2 < nk && g.abl != 1) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(PA + PB) : "memory");
+        if (kt + 2 < nk) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(PA + PB) : "memory");
         else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // this wave's fragment reads of slot kt % 3 are done
         __builtin_amdgcn_s_barrier();
@@ -571,14 +564,13 @@ bool describe(const as_gemm* g, WgradK& k) {
 }
 
 template <int BNT>
-int launch_multi(WgradMulti& mm, int bk, hipStream_t st, bool exact = false) {
+int launch_multi(WgradMulti& mm, hipStream_t st, bool exact = false) {
     const dim3 grid((unsigned)(8 * mm.per_xcd));
-    const bool s6 = !exact && as_matrix_arith() == AS_ARITH_BF16X6 && bk == 32;
-    if (mm.streamk && s6) hipLaunchKernelGGL((wgrad_f32_kernel<BNT, 32, true, true>), grid, dim3(NT), 0, st, mm);
-    else if (mm.streamk) hipLaunchKernelGGL((wgrad_f32_kernel<BNT, 32, true>), grid, dim3(NT), 0, st, mm);
-    else if (bk == 16) hipLaunchKernelGGL((wgrad_f32_kernel<BNT, 16>), grid, dim3(NT), 0, st, mm);
-    else if (s6) hipLaunchKernelGGL((wgrad_f32_kernel<BNT, 32, false, true>), grid, dim3(NT), 0, st, mm);
-    else hipLaunchKernelGGL((wgrad_f32_kernel<BNT, 32>), grid, dim3(NT), 0, st, mm);
+    const bool s6 = !exact && as_matrix_arith() == AS_ARITH_BF16X6;
+    if (mm.streamk && s6) hipLaunchKernelGGL((wgrad_f32_kernel<BNT, true, true>), grid, dim3(NT), 0, st, mm);
+    else if (mm.streamk) hipLaunchKernelGGL((wgrad_f32_kernel<BNT, true>), grid, dim3(NT), 0, st, mm);
+    else if (s6) hipLaunchKernelGGL((wgrad_f32_kernel<BNT, false, true>), grid, dim3(NT), 0, st, mm);
+    else hipLaunchKernelGGL((wgrad_f32_kernel<BNT>), grid, dim3(NT), 0, st, mm);
     AS_LAUNCH_CHECK("as_gemm_f32(wgrad)");
     if (mm.streamk) {
         constexpr long PER_TILE = BM * BNT / 4 + BM + BNT;
@@ -601,51 +593,36 @@ int launch_multi(WgradMulti& mm, int bk, hipStream_t st, bool exact = false) {
 // Takes the GEMM if it is a weight-gradient shape this kernel is built for (returns 1 and launches), else returns 0;
 // negative = error.  Called by as_gemm_f32 ahead of its general tile selection.
 int as_wgrad_try(const as_gemm* g, hipStream_t st) {
-    static const bool off = AS_DIAG_SET("AS_NO_WGRAD");  // ablation: the general kernel
-    if (off) return 0;
     WgradMulti mm{};
     WgradK& k = mm.p[0];
     if (!describe(g, k)) return 0;
-#ifdef AS_DIAG
-    static const int abl = AS_DIAG_INT("AS_WGRAD_ABL", 0);
-    k.abl = abl;
-#endif
     const int bn = g->N > 128 ? 256 : 128;
     k.tiles_m = as_cdiv(g->M, BM);
     k.tiles_n = as_cdiv(g->N, bn);
     const long tiles = (long)k.tiles_m * k.tiles_n * g->batch;
-    static const bool all_shapes = AS_DIAG_SET("AS_WGRAD_ALL");  // tuning aid: also the shapes below
     // too little work to give every CU a 128-row tile over >= 256 frames: the general kernel's 64 x 64 tiles spread it better
-    static const int min_work = AS_DIAG_INT("AS_WGRAD_MIN_WORK", 256);   // tiles x 256-deep k-chunks
-    if (!all_shapes && tiles * (g->K / 256) < min_work) return 0;
+    if (tiles * (g->K / 256) < 256) return 0;
     // split K so that the launch has about `target` workgroups (one per CU and round); cost model in DESIGN.md 5
-    static const int target_env = AS_DIAG_INT("AS_WGRAD_TARGET", 0);
-    static const int bk = AS_DIAG_INT("AS_WGRAD_BK", 32);
-    const int cus = (g->cu_budget > 0 ? g->cu_budget : 256) * (bk == 16 ? 2 : 1);   // slots: two workgroups per CU at BK = 16
+    const int cus = g->cu_budget > 0 ? g->cu_budget : 256;
     long S = 1;
     const long per = (long)g->batch * g->M * g->N, per_cs = g->colsum ? (long)g->batch * g->M : 0;
     if (g->splitk_ws && tiles < cus) {
-        if (target_env > 0) {
-            S = target_env / tiles;
-        } else {
-            // time ~ rounds * k-steps per workgroup * c1 + slab traffic; c1 = us per k of one 128 x bn tile on one CU
-            const double c1 = (bn == 256 ? 256.0 : 128.0) / 2400.0 * (bk == 16 ? 2 : 1), c2 = 8.0 / 4.0e6;  // write + read of a float at ~4 TB/s
-            double best = 1e30;
-            for (long s = 1; s <= 64 && s * 128 <= g->K; ++s) {
-                const long chunk = as_round_up(as_cdiv(g->K, s), KALIGN);
-                const long rounds = (tiles * s + cus - 1) / cus;
-                const double cost = rounds * chunk * c1 + (s > 1 ? s * (per + per_cs) * c2 : 0.0);
-                if (cost < best - 1e-9) best = cost, S = s;
-            }
+        // time ~ rounds * k-steps per workgroup * c1 + slab traffic; c1 = us per k of one 128 x bn tile on one CU
+        const double c1 = (bn == 256 ? 256.0 : 128.0) / 2400.0, c2 = 8.0 / 4.0e6;  // write + read of a float at ~4 TB/s
+        double best = 1e30;
+        for (long s = 1; s <= 64 && s * 128 <= g->K; ++s) {
+            const long chunk = as_round_up(as_cdiv(g->K, s), KALIGN);
+            const long rounds = (tiles * s + cus - 1) / cus;
+            const double cost = rounds * chunk * c1 + (s > 1 ? s * (per + per_cs) * c2 : 0.0);
+            if (cost < best - 1e-9) best = cost, S = s;
         }
         if (S > g->K / 128) S = g->K / 128;
         if (S * (per + per_cs) > g->splitk_ws_floats) S = g->splitk_ws_floats / (per + per_cs);
         if (S < 1) S = 1;
     }
     // Many tiles that do not fill whole rounds of the CUs: stream-K (see WgradMulti) instead of whole tiles per workgroup
-    static const bool no_sk = AS_DIAG_SET("AS_WGRAD_NO_STREAMK");
     const long rounds = (tiles + cus - 1) / cus;
-    if (!no_sk && bk == 32 && g->splitk_ws && tiles * 2 >= cus && tiles * 100 < rounds * cus * 95 && g->K / 32 >= 16 &&
+    if (g->splitk_ws && tiles * 2 >= cus && tiles * 100 < rounds * cus * 95 && g->K / 32 >= 16 &&
         (long)cus * 2 * PIECE_FLOATS <= g->splitk_ws_floats) {
         k.kchunk = g->K; k.splitk = 1; k.tile0 = 0;
         k.ncombos = (long)g->batch * k.tiles_n;
@@ -658,7 +635,7 @@ int as_wgrad_try(const as_gemm* g, hipStream_t st) {
         mm.total_items = (mm.total_units + mm.unit_per_wg - 1) / mm.unit_per_wg;   // workgroups
         mm.per_xcd = (int)((mm.total_items + 7) / 8);
         mm.pieces = g->splitk_ws;
-        const int rc = bn == 256 ? launch_multi<256>(mm, bk, st) : launch_multi<128>(mm, bk, st);
+        const int rc = bn == 256 ? launch_multi<256>(mm, st) : launch_multi<128>(mm, st);
         return rc == 0 ? 1 : rc;
     }
     k.kchunk = (int)as_round_up(as_cdiv(g->K, S), KALIGN);
@@ -672,7 +649,7 @@ int as_wgrad_try(const as_gemm* g, hipStream_t st) {
     mm.total_items = k.ncombos * k.tiles_m;
     mm.per_xcd = (int)((mm.total_items + 7) / 8);
     mm.total_red = per / 4 + per_cs;
-    const int rc = bn == 256 ? launch_multi<256>(mm, bk, st) : launch_multi<128>(mm, bk, st);
+    const int rc = bn == 256 ? launch_multi<256>(mm, st) : launch_multi<128>(mm, st);
     return rc == 0 ? 1 : rc;
 }
 
@@ -682,8 +659,7 @@ int as_wgrad_try(const as_gemm* g, hipStream_t st) {
 // per CU, so the dispatcher fills every free CU and other streams' kernels get CUs as workgroups retire.
 // 1 = launched, 0 = not a case (nothing launched: the caller issues the problems one by one), < 0 = error.
 int as_wgrad_multi(const as_wgrad_job* jobs, int n, float* slab, long slab_floats, int cu_budget, hipStream_t st, bool exact) {
-    static const bool off = AS_DIAG_SET("AS_NO_WGRAD_MULTI");  // ablation: one launch per problem
-    if (off || n < 1 || n > MAXP || !slab) return 0;
+    if (n < 1 || n > MAXP || !slab) return 0;
     WgradMulti mm{};
     long tiles = 0;
     const int K = jobs[0].g.K;
@@ -700,7 +676,6 @@ int as_wgrad_multi(const as_wgrad_job* jobs, int n, float* slab, long slab_float
     // chunk length: a multiple of 32 frames, at least 256; cost = rounds of `cus` workgroups x (chunk + fixed cost per
     // workgroup) + slab traffic, all in units of one k-tile of 32 frames (~4 us for a 128 x 256 tile)
     const int cus = cu_budget > 0 ? cu_budget : 256;
-    static const int chunk_env = AS_DIAG_INT("AS_WGRAD_MULTI_CHUNK", 0);   // k-tiles per workgroup (tuning aid)
     const int nkt = K / 32;
     int best_chunk = nkt;
     double best = 1e30;
@@ -711,7 +686,6 @@ int as_wgrad_multi(const as_wgrad_job* jobs, int n, float* slab, long slab_float
         const double cost = rounds * (chunk + 1.0) + 0.016 * W;   // 128 KB of slab written + read per workgroup at ~4 TB/s
         if (cost < best - 1e-9) best = cost, best_chunk = chunk;
     }
-    if (chunk_env > 0) best_chunk = chunk_env < nkt ? chunk_env : nkt;
     long off_f = 0, item0 = 0, red0 = 0;
     for (int i = 0; i < n; ++i) {
         WgradK& k = mm.p[i];
@@ -736,6 +710,6 @@ int as_wgrad_multi(const as_wgrad_job* jobs, int n, float* slab, long slab_float
     mm.total_items = item0;
     mm.total_red = red0;
     mm.per_xcd = (int)((item0 + 7) / 8);
-    const int rc = launch_multi<256>(mm, 32, st, exact);
+    const int rc = launch_multi<256>(mm, st, exact);
     return rc == 0 ? 1 : rc;
 }

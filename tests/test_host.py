@@ -26,8 +26,8 @@ def test_header_symbols_are_exported_and_bound():
 
 
 def test_product_library_has_no_ablation_switches():
-    """The shipped library reads no AS_* environment variable: ablations, tuning aids and legacy kernels exist only in the
-    -DAS_DIAG flavour (libartspeech_hip_diag.so, `python -m artspeech_amd.build --diag`) that tools/ load on request."""
+    """The library reads no AS_* environment variable and its sources hold no ablation switch: there is one flavour, and
+    only the documented ARTSPEECH_* options can be read from the environment."""
     from artspeech_amd import _lib
     assert _lib.LIB_PATH.endswith("libartspeech_hip.so")
     blob = open(_lib.LIB_PATH, "rb").read()
@@ -35,11 +35,13 @@ def test_product_library_has_no_ablation_switches():
     switches = {n for n in names if not n.startswith((b"AS_ERR_", b"AS_HEAD_", b"AS_WAVE"))}
     assert not switches, f"environment switches compiled into the product library: {sorted(switches)}"
     csrc = os.path.join(ROOT, "artspeech_amd", "csrc")
+    removed = re.compile(r"\b(AS_DIAG\w*|AS_S6_ABL|AS_S6G_ABL|AS_S6_TRACE|AS_GRU_NO_GATE_SHARE)\b")
     for f in os.listdir(csrc):
         if f.endswith((".hip", ".cpp", ".h")):
             for line in open(os.path.join(csrc, f)):
-                if "getenv(" in line and "#define AS_DIAG_" not in line:
-                    assert "ARTSPEECH_" in line, f"{f}: raw getenv outside the AS_DIAG macros: {line.strip()}"
+                if "getenv(" in line:
+                    assert "ARTSPEECH_" in line, f"{f}: getenv of a variable that is not an ARTSPEECH_ option: {line.strip()}"
+                assert not removed.search(line), f"{f}: diagnostic switch in the library sources: {line.strip()}"
 
 
 def test_layout_is_disjoint_and_counts_parameters():

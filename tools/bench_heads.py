@@ -1,5 +1,5 @@
 """The ArticulatorPredictor heads alone (as_head_fwd + as_head_bwd, A = 11, 6400 frames): per-phase microseconds from the
-library's own HIP-event table.  AS_NO_LIN=1 = general GEMMs + row kernels (round-1 path); AS_LIN_ABL=1/2 ablations.
+library's own HIP-event table.
 usage: python tools/bench_heads.py [iters]"""
 import ctypes as C
 import os

@@ -1,7 +1,7 @@
 """Weight-gradient GEMM shapes of the BiGRU training step (and the transformer's grouped 256 x 256 x 6400 one) through
 as_gemm_f32, alone on the chip: microseconds, TFLOP/s, fraction of the fp32 MFMA peak, and a check against fp64.
-AS_NO_WGRAD=1 in the environment routes the same calls to the general kernel (the round-1 path) for comparison.
-usage: python tools/bench_wgrad.py [iters] [cu_budget]"""
+precision (default 0): as_gemm.precision; 3 = gemm_s6.hip's kernel where it takes the shape.
+usage: python tools/bench_wgrad.py [iters] [cu_budget] [precision]"""
 import ctypes as C
 import os
 import sys
@@ -33,10 +33,9 @@ SHAPES = {
     "transformer dW x11 block-major": (256, 256, 11, 256, R * 256, 256, R * 256, 0, 0, 0),
     "transformer dW x1": (256, 256, 1, 256, 0, 256, 0, 0, 0, 0),
 }
-PREC = int(os.environ.get("AS_BENCH_PRECISION", "0"))   # 3: as_gemm.precision = 3 (gemm_s6.hip's kernel where it takes the shape)
+PREC = int(sys.argv[3]) if len(sys.argv) > 3 else 0
 
-label = "general kernel (AS_NO_WGRAD)" if os.environ.get("AS_NO_WGRAD") else "wgrad_f32_kernel"
-print(f"--- {label}, K = {R}, cu_budget = {cu_budget or 'chip'}, {iters} launches each")
+print(f"--- as_gemm_f32 (precision {PREC}), K = {R}, cu_budget = {cu_budget or 'chip'}, {iters} launches each")
 total_us = 0.0
 for name, (M, N, batch, lda, ab, ldb, bb, ksh, kT, kshb) in SHAPES.items():
     block_major = ab >= R * M
