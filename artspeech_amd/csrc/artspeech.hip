@@ -180,9 +180,11 @@ int head_fold(const as_dims& d, const as_layout& L, const float* P, int64_t rows
     AS_STEP("head.fold", st, as_fold(P + L.w1, P + L.ln1_g, P + L.ln1_b, P + L.b1, ws + w.w1f, ws + w.b1f, A, D, H, st));
     AS_STEP("head.fold", st, as_fold(P + L.w2, P + L.ln2_g, P + L.ln2_b, P + L.b2, ws + w.w2f, ws + w.b2f, A, D, D, st));
     AS_STEP("head.fold", st, as_fold(P + L.w3, P + L.ln3_g, P + L.ln3_b, P + L.b3, ws + w.w3f, ws + w.b3f, A, O, D, st, (int)as_round_up(O, 32)));
-    if (as_matrix_arith() == AS_ARITH_BF16X6 && H % 4 == 0) {
+    {
         // the folded weights as bfloat16 planes for the split-arithmetic kernels: forward orientation, and transposed for
-        // the input-gradient chain (d(x_hat) = dz . W': the reduction runs over W' rows)
+        // the input-gradient chain (d(x_hat) = dz . W': the reduction runs over W' rows).  Emitted for every hidden size and
+        // in both arithmetics: the head layers hand them to the split kernels whatever H is, and the arithmetic is read at
+        // each launch, so a backward may run in the split arithmetic after a forward in the exact one.
         const int Opad = (int)as_round_up(O, 32), Hp = (int)as_round_up(H, 32);
         auto up = [&](int64_t off) { return reinterpret_cast<uint16_t*>(ws + off); };
         as_planes_job j[6] = {

@@ -313,6 +313,8 @@ __global__ __launch_bounds__(NTH, 3) void gemm_s6_kernel(S6K g) {
                 // (a clamped quad -- M % 128 != 0 -- repeats valid columns at the tile's end: those lanes hold other columns' sums)
                 if (m0 + tid < g.M && (m0 + (tid & ~3) + 4 <= g.M)) g.colsum[(long)bz * g.colsum_batch + m0 + tid] = t8;
             }
+            // the epilogue below reuses `sm` from its start (es): every wave's reads of the partials end here
+            __syncthreads();
         }
     }
     // ---- epilogue: D[i][j] block (i, j) of the wave: row = m0 + wm * 64 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh, col = n0 + wn * 64 + j * 32 + l31

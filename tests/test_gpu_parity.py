@@ -539,11 +539,14 @@ def test_weight_gradient_stream_k(dev, M, N, K, batch, grouped):
     assert (acc - (c0 + outs[0][0])).abs().max().item() <= 2e-6 * scale
 
 
-@pytest.mark.parametrize("M,N,K,batch,grouped", [(256, 256, 6400, 110, False), (200, 132, 2048, 7, True), (128, 384, 160, 3, False)])
+@pytest.mark.parametrize("M,N,K,batch,grouped", [(256, 256, 6400, 110, False), (200, 132, 2048, 7, True), (128, 384, 160, 3, False),
+                                                    (256, 256, 6400, 110, True)])
 def test_weight_gradient_split_arithmetic_tiles(dev, M, N, K, batch, grouped):
     """as_gemm.precision = 3 on a weight-gradient shape (both operands reduction-strided): gemm_s6.hip's kernel with both operand
     tiles transposed on their way into the plane images, one workgroup per 128 x 128 output tile over the whole reduction, the
-    bias gradient (column sums of A) from the registers the tile loads pass through.  Same bounds as the stream-K kernel's test."""
+    bias gradient (column sums of A) from the registers the tile loads pass through.  Same bounds as the stream-K kernel's test.
+    (256, 256, 6400, 110, grouped) is the transformer's grouped bias gradient (ops.py): 440 tiles whose column-sum partials
+    share LDS with the float4 epilogue's staging image, bit-identical over the launches and against an fp64 column sum."""
     from artspeech_amd import _lib
     L = _lib.lib()
     rng = np.random.RandomState(M + K + batch)
@@ -702,18 +705,39 @@ def test_single_head_vs_reference_fixture(dev, name):
         assert_grad_close(got, grads[k], f"{name}: {k}")
 
 
-def test_head_stack_fused_weight_gradients_vs_oracle(dev):
-    """as_head_fwd / as_head_bwd at a row count that takes the fused paths (lin_f32_kernel layers, ONE multi-problem
-    weight-gradient launch incl. the transposed layer-1 problem and its B-side column sums) against the fp64 oracle:
-    A = 3 heads, 1536 frames, non-trivial LayerNorm affines, every parameter gradient element-wise."""
+def _take_the_devices_relu_decisions(got, zs, keys, grads, where, flips, tau=5e-6, max_flips=8):
+    """conftest.oracle_gradients_with_the_devices_relu_decisions' rule for caches it does not know: an oracle ReLU input z in
+    zs[k] (modified in place) within tau of zero takes the other decision only if row z's last index of the weight gradient
+    got[keys[k]] is off by more than 2e-5 of the tensor's maximum and the flip at least halves that row's error.
+    grads() returns the oracle's weight gradients in the order of keys; flips collects (where, index, z)."""
+    def row_err(key, g, j):
+        return float(np.abs(np.asarray(got[key][j], np.float64) - g[j]).max()) / max(float(np.abs(g).max()), 1e-30)
+
+    cand = sorted((abs(float(z[i])), k, i) for k, z in enumerate(zs) for i in zip(*np.nonzero(np.abs(z) < tau)))
+    for _, k, i in cand[:64]:
+        if len(flips) >= max_flips:
+            break
+        e = row_err(keys[k], grads()[k], i[-1])
+        if e < 2e-5:
+            continue
+        keep = float(zs[k][i])
+        zs[k][i] = -abs(keep) if keep > 0 else max(abs(keep), 1e-300)
+        if row_err(keys[k], grads()[k], i[-1]) < 0.5 * e:
+            flips.append((f"{where}, ReLU {k + 1}", tuple(int(j) for j in i), keep))
+        else:
+            zs[k][i] = keep
+
+
+def _head_stack_vs_oracle(dev, H, rows, set_arith=None, fwd_mode=1, bwd_mode=1, A=3, N=50, seed=7):
+    """as_head_fwd in arithmetic fwd_mode, then as_head_bwd in bwd_mode (set_arith: the matrix_arith fixture; None keeps the
+    default), on a workspace filled with NaN -- a kernel that reads something the library never wrote fails here -- against
+    the fp64 oracle: contours, dx and every head parameter gradient element-wise, non-trivial LayerNorm affines."""
     from artspeech_amd import _lib
     from artspeech_amd.phoneme_to_articulation.encoder_decoder.models import _build_views, _numel
-    from oracle import artspeech_oracle as O
     L = _lib.lib()
-    A, H, N, rows = 3, 128, 50, 1536
     dims = _lib.Dims(1, A, 1, H, N, 1)
     lay = _lib.layout(dims)
-    rng = np.random.RandomState(7)
+    rng = np.random.RandomState(seed)
     views = {k: v for k, v in _build_views(dims, lay).items() if k.startswith("predictors.")}
     flat = torch.zeros(lay.total)
     params = {}
@@ -731,26 +755,69 @@ def test_head_stack_fused_weight_gradients_vs_oracle(dev):
     x = rng.randn(rows, H).astype(np.float32)
     dsig = (rng.randn(rows, A, 2, N) * 1e-3).astype(np.float32)
     flat_d, x_d, dsig_d = flat.to(dev), T_(x, dev), T_(dsig, dev)
-    out = torch.empty((rows, A, 2, N), device=dev)
-    ws = torch.empty(L.as_head_workspace_floats(C.byref(dims), rows), device=dev)
+    out = torch.full((rows, A, 2, N), float("nan"), device=dev)
+    ws = torch.full((L.as_head_workspace_floats(C.byref(dims), rows),), float("nan"), device=dev)
+    if set_arith is not None:
+        set_arith(fwd_mode)
     _lib.check(L.as_head_fwd(C.byref(dims), C.byref(lay), _lib.ptr(flat_d), _lib.ptr(x_d), rows, _lib.ptr(out), _lib.ptr(ws), 1, _lib.stream_ptr()))
     G = torch.zeros_like(flat_d)
-    dx = torch.empty((rows, H), device=dev)
+    dx = torch.full((rows, H), float("nan"), device=dev)
+    if set_arith is not None:
+        set_arith(bwd_mode)
     _lib.check(L.as_head_bwd(C.byref(dims), C.byref(lay), _lib.ptr(flat_d), _lib.ptr(out), _lib.ptr(dsig_d), rows, _lib.ptr(dx), _lib.ptr(G),
                              _lib.ptr(ws), _lib.stream_ptr()))
     torch.cuda.synchronize()
+    what = f"head stack H={H} rows={rows} arithmetic {fwd_mode}/{bwd_mode}"
     Gc, dx_ref = G.cpu(), np.zeros((rows, H))
+    got = {k: Gc[off:off + _numel(shape)].view(shape).numpy() for k, (off, shape) in views.items()}
+    flips = []
     for a in range(A):
         p = {k[len(f"predictors.{a}."):]: v.astype(np.float64) for k, v in params.items() if k.startswith(f"predictors.{a}.")}
         pre, cache = O.predictor_fwd(x.astype(np.float64), p)
         sig = 1 / (1 + np.exp(-pre))
-        assert_close(out[:, a].cpu().numpy(), sig, what=f"head {a} out")
-        dxa, ga = O.predictor_bwd(dsig[:, a].astype(np.float64) * sig * (1 - sig), cache, p)
+        assert_close(out[:, a].cpu().numpy(), sig, what=f"{what}: head {a} out")
+        dpre = dsig[:, a].astype(np.float64) * sig * (1 - sig)
+
+        def grads():
+            g = O.predictor_bwd(dpre, cache, p)[1]
+            return g["linear.1.weight"], g["linear.4.weight"]
+        # (a ReLU input within rounding of zero: the device's decision, as in the model-level tests)
+        _take_the_devices_relu_decisions(got, [cache[3], cache[6]], [f"predictors.{a}.linear.1.weight", f"predictors.{a}.linear.4.weight"],
+                                         grads, f"head {a}", flips)
+        dxa, ga = O.predictor_bwd(dpre, cache, p)
         dx_ref += dxa
         for k, gref in ga.items():
-            off, shape = views[f"predictors.{a}.{k}"]
-            assert_grad_close(Gc[off:off + _numel(shape)].view(shape).numpy(), gref, f"fused head stack: predictors.{a}.{k}")
-    assert_grad_close(dx.cpu().numpy(), dx_ref, "fused head stack: dx")
+            assert_grad_close(got[f"predictors.{a}.{k}"], gref, f"{what} (ReLU decisions taken from the device: {flips}): predictors.{a}.{k}")
+    assert len(flips) <= 2 and all(abs(z) < 5e-6 for _, _, z in flips), flips
+    assert_grad_close(dx.cpu().numpy(), dx_ref, f"{what}: dx")
+
+
+def test_head_stack_fused_weight_gradients_vs_oracle(dev):
+    """as_head_fwd / as_head_bwd at a row count that takes the fused paths (lin_f32_kernel layers, ONE multi-problem
+    weight-gradient launch incl. the transposed layer-1 problem and its B-side column sums) against the fp64 oracle:
+    A = 3 heads, 1536 frames, non-trivial LayerNorm affines, every parameter gradient element-wise."""
+    _head_stack_vs_oracle(dev, 128, 1536)
+
+
+@pytest.mark.parametrize("mode", [1, 0])
+@pytest.mark.parametrize("rows", [1536, 37])
+@pytest.mark.parametrize("H", [128, 64, 50, 7, 130, 300])
+def test_head_stack_any_input_width_vs_oracle(dev, matrix_arith, H, rows, mode):
+    """The head stack at any input width H (the reference: nn.Linear(embed_dim, hidden_size), any size; SimpleArtSpeech feeds
+    it hidden_size directly) in both matrix arithmetics: H a multiple of 32 (layer 1 on the planes too), of 4 only, of
+    neither, and above 256 (the input-gradient chain declines its split path); 1536 rows take the fused multi-problem weight
+    gradient (as_wgrad_multi), 37 the plain one.  In the split arithmetic layers 2 and 3 and the input-gradient chain read
+    the bfloat16 planes of the folded weights whatever H is: on the NaN-filled workspace a plane head_fold did not emit
+    fails every check."""
+    _head_stack_vs_oracle(dev, H, rows, matrix_arith, mode, mode)
+
+
+@pytest.mark.parametrize("fwd_mode,bwd_mode", [(0, 1), (1, 0)])
+@pytest.mark.parametrize("H", [128, 50])
+def test_head_stack_arithmetic_switched_between_forward_and_backward(dev, matrix_arith, H, fwd_mode, bwd_mode):
+    """as_set_matrix_arith between as_head_fwd and as_head_bwd: the arithmetic is read at every launch, so the backward
+    takes the kernels of the new one, on planes the forward's head_fold left in the workspace."""
+    _head_stack_vs_oracle(dev, H, 1536, matrix_arith, fwd_mode, bwd_mode)
 
 
 # ------------------------------------------------------------------------------------------- models
@@ -800,6 +867,13 @@ def test_artspeech_matches_reference_fixture(dev, name):
     assert abs(p2cp.item() - oracle_p2cp) / oracle_p2cp < 1e-5
 
 
+@pytest.mark.parametrize("name", ["artspeech_c1", "artspeech_small", "artspeech_h64"])
+def test_artspeech_matches_reference_fixture_exact_fp32(dev, matrix_arith, name):
+    """The same checks in the exact-fp32 matrix arithmetic (as_set_matrix_arith(0), ARTSPEECH_MATRIX_ARITH=fp32)."""
+    matrix_arith(0)
+    test_artspeech_matches_reference_fixture(dev, name)
+
+
 def test_artspeech_eval_mode_and_errors(dev):
     from artspeech_amd.phoneme_to_articulation.encoder_decoder.models import ArtSpeech
     g = load_golden("artspeech_small")
@@ -830,6 +904,80 @@ def test_simple_artspeech_matches_reference_fixture(dev):
         assert_grad_close(v.cpu().numpy(), grads[k], f"simple_small: {k}")
 
 
+def test_simple_artspeech_matches_reference_fixture_exact_fp32(dev, matrix_arith):
+    matrix_arith(0)
+    test_simple_artspeech_matches_reference_fixture(dev)
+
+
+def _random_simple_configuration(seed):
+    """SimpleArtSpeech draws: the head stack's input width is hidden_size itself, so H cycles through widths that are multiples
+    of 32, of 4 only, of neither, and above 256; even seeds stay within 512 frames, odd ones go past them (up to 1920)."""
+    r = np.random.RandomState(2000 + seed)
+    HS = [1, 7, 32, 50, 64, 100, 128, 130, 300, 512]
+    B, T = (int(r.randint(1, 8)), int(r.randint(1, 74))) if seed % 2 == 0 else (int(r.randint(8, 17)), int(r.randint(65, 121)))
+    return dict(V=int(r.randint(2, 130)), A=int(r.randint(1, 13)), E=int(r.choice([1, 5, 8, 13, 24, 30, 64, 100, 129])),
+                H=HS[seed % len(HS)], N=int(r.choice([1, 3, 10, 25, 33, 50, 50, 64, 70])), B=B, T=T)
+
+
+def _simple_oracle_gradients_with_the_devices_relu_decisions(dout, cache, n_art, got):
+    """conftest.oracle_gradients_with_the_devices_relu_decisions for O.simple_artspeech_fwd's cache (no lengths: every frame
+    counts), ReLU inputs of the heads and of the trunk.  Returns (gradients, flips)."""
+    p, _, _, zlin, head_caches, out, _ = cache
+    dpre = dout * out * (1.0 - out)
+    flips = []
+    for a in range(n_art):
+        def grads(a=a):
+            g = O.predictor_bwd(dpre[:, :, a], head_caches[a], O._sub(p, f"predictors.{a}."))[1]
+            return g["linear.1.weight"], g["linear.4.weight"]
+        _take_the_devices_relu_decisions(got, [head_caches[a][3], head_caches[a][6]],
+                                         [f"predictors.{a}.linear.1.weight", f"predictors.{a}.linear.4.weight"], grads, f"head {a}", flips)
+    _take_the_devices_relu_decisions(got, [zlin], ["linear.0.weight"],
+                                     lambda: (O.simple_artspeech_bwd(dout, cache, n_art)["linear.0.weight"],), "trunk", flips)
+    return O.simple_artspeech_bwd(dout, cache, n_art), flips
+
+
+def _simple_artspeech_vs_oracle(dev, c, seed, set_arith=None, fwd_mode=1, bwd_mode=1):
+    """SimpleArtSpeech of configuration c: forward in arithmetic fwd_mode, d(sum(out * dout)) / d(every parameter) in
+    bwd_mode, against the fp64 oracle (models.py:75-96 of the reference)."""
+    from artspeech_amd.phoneme_to_articulation.encoder_decoder.models import SimpleArtSpeech
+    V, A, N, B, T = c["V"], c["A"], c["N"], c["B"], c["T"]
+    torch.manual_seed(seed)
+    model = SimpleArtSpeech(V, A, embed_dim=c["E"], hidden_size=c["H"], num_samples=N)
+    sd = {k: v.numpy() for k, v in model.state_dict().items()}
+    model = model.to(dev)
+    rng = np.random.RandomState(seed)
+    x = rng.randint(1, V, (B, T))
+    dout = rng.randn(B, T, A, 2, N).astype(np.float32)
+    if set_arith is not None:
+        set_arith(fwd_mode)
+    out = model(T_(x, dev, torch.int64), None)
+    assert tuple(out.shape) == (B, T, A, 2, N), c
+    if set_arith is not None:
+        set_arith(bwd_mode)
+    (out * T_(dout, dev)).sum().backward()
+    what = f"{c}, arithmetic {fwd_mode}/{bwd_mode}"
+    o_out, cache = O.simple_artspeech_fwd(sd, x, A)
+    assert_close(out.detach().cpu().numpy(), o_out, what=f"contours {what}")
+    got = {k: v.cpu().numpy() for k, v in model.named_grad_views().items()}
+    og, flips = _simple_oracle_gradients_with_the_devices_relu_decisions(dout.astype(np.float64), cache, A, got)
+    assert len(flips) <= 4 and all(abs(z) < 5e-6 for _, _, z in flips), flips
+    assert set(got) == set(og)
+    for k, v in got.items():
+        assert_grad_close(v, og[k], f"{what} (ReLU decisions taken from the device: {flips}): {k}")
+
+
+_SIMPLE_SEEDS = int(os.environ.get("AS_FUZZ_SEEDS", "12"))
+
+
+@pytest.mark.parametrize("seed,mode", [(s, 1) for s in range(_SIMPLE_SEEDS)] + [(s, 0) for s in range(_SIMPLE_SEEDS) if s % 4 < 2])
+def test_simple_artspeech_random_configurations_vs_oracle(dev, matrix_arith, seed, mode):
+    """Seeded random SimpleArtSpeech architectures (vocabulary 2-129, 1-12 articulators, odd and even embedding widths, hidden
+    sizes 1-512 of every alignment, 1-70 samples per contour, up to 1920 frames) in the split arithmetic, and every other
+    pair of seeds in the exact one: contours and every parameter gradient against the oracle at the usual element-wise
+    bound (a wider sweep: AS_FUZZ_SEEDS=150)."""
+    _simple_artspeech_vs_oracle(dev, _random_simple_configuration(seed), seed, matrix_arith, mode, mode)
+
+
 def test_artspeech_vs_oracle_ragged_full_width(dev):
     """A=11, N=50, H=128 (the benchmark architecture) at B=6, T=40 ragged, against the fp64 oracle."""
     from artspeech_amd.phoneme_to_articulation.encoder_decoder.models import ArtSpeech
@@ -856,6 +1004,11 @@ def test_artspeech_vs_oracle_ragged_full_width(dev):
     og = O.artspeech_bwd(o_dout, cache, 11)
     for k, v in model.named_grad_views().items():
         assert_grad_close(v.cpu().numpy(), og[k], f"ragged full width vs oracle: {k}")
+
+
+def test_artspeech_vs_oracle_ragged_full_width_exact_fp32(dev, matrix_arith):
+    matrix_arith(0)
+    test_artspeech_vs_oracle_ragged_full_width(dev)
 
 
 @pytest.mark.parametrize("V", [45, 100])
@@ -892,6 +1045,12 @@ def test_artspeech_vs_oracle_more_than_1024_frames(dev, V):
     assert len(flips) <= 2 and all(abs(z) < 5e-6 for _, _, z in flips), flips
     for k, v in got.items():
         assert_grad_close(v, og[k], f"1280 frames, V={V}, vs oracle (ReLU decisions taken from the device: {flips}): {k}")
+
+
+@pytest.mark.parametrize("V", [45, 100])
+def test_artspeech_vs_oracle_more_than_1024_frames_exact_fp32(dev, matrix_arith, V):
+    matrix_arith(0)
+    test_artspeech_vs_oracle_more_than_1024_frames(dev, V)
 
 
 @pytest.mark.parametrize("E", [256, 320])
@@ -1013,6 +1172,63 @@ def test_artspeech_random_configurations_vs_oracle(dev, seed):
     assert len(flips) <= 4 and all(abs(z) < 5e-6 for _, _, z in flips), flips
     for k, v in got.items():
         assert_grad_close(v, og[k], f"{c} (ReLU decisions taken from the device: {flips}): {k}")
+
+
+@pytest.mark.parametrize("seed", [0, 1, 3, 6, 7, 10])
+def test_artspeech_random_configurations_exact_fp32_vs_oracle(dev, matrix_arith, seed):
+    """A fixed subset of the seeds above (hidden sizes 20, 32, 44, 72 and 128) in the exact-fp32 arithmetic."""
+    matrix_arith(0)
+    test_artspeech_random_configurations_vs_oracle(dev, seed)
+
+
+def _poison_next_workspace(dims, B, T, dev):
+    """Leave a NaN-filled block of the model's workspace size in torch's caching allocator: the model's forward
+    (torch.empty) gets it back, so whatever the library reads without having written it is NaN, not an earlier run's data."""
+    n = _lib.lib().as_artspeech_workspace_floats(C.byref(dims), B, T)
+    block = torch.full((n,), float("nan"), device=dev)
+    del block
+
+
+@pytest.mark.parametrize("fwd_mode,bwd_mode", [(0, 1), (1, 0)])
+def test_artspeech_arithmetic_switched_between_forward_and_backward(dev, matrix_arith, fwd_mode, bwd_mode):
+    """as_set_matrix_arith between the forward and its backward: the backward runs the new arithmetic's kernels on what the
+    forward left in the workspace (the bfloat16 planes of the head weights among it).  Every gradient against the oracle."""
+    from artspeech_amd.phoneme_to_articulation.encoder_decoder.models import ArtSpeech
+    from artspeech_amd.phoneme_to_articulation.metrics import masked_euclidean_loss
+    torch.manual_seed(5)
+    V, A, B, T = 30, 3, 5, 41
+    model = ArtSpeech(V, A)
+    sd = {k: v.numpy() for k, v in model.state_dict().items()}
+    model = model.to(dev)
+    lengths = np.array([41, 40, 22, 9, 1])
+    rng = np.random.RandomState(5)
+    x = rng.randint(1, V, (B, T))
+    tgt = rng.rand(B, T, A, 2, 50).astype(np.float32)
+    for b, l in enumerate(lengths):
+        x[b, l:] = 0
+        tgt[b, l:] = 0
+    _poison_next_workspace(model.dims, B, T, dev)
+    matrix_arith(fwd_mode)
+    out = model(T_(x, dev, torch.int64), torch.from_numpy(lengths))
+    loss = masked_euclidean_loss(out, T_(tgt, dev), lengths)
+    matrix_arith(bwd_mode)
+    loss.backward()
+    o_out, cache = O.artspeech_fwd(sd, x, lengths, A)
+    assert_close(out.detach().cpu().numpy(), o_out, what="contours")
+    _, o_dout = O.masked_euclid_loss(out.detach().cpu().numpy().astype(np.float64), tgt, lengths)
+    got = {k: v.cpu().numpy() for k, v in model.named_grad_views().items()}
+    og, flips = oracle_gradients_with_the_devices_relu_decisions(got, o_dout, cache, A, label=f"arithmetic {fwd_mode}/{bwd_mode}")
+    assert len(flips) <= 2 and all(abs(z) < 5e-6 for _, _, z in flips), flips
+    for k, v in got.items():
+        assert_grad_close(v, og[k], f"arithmetic {fwd_mode} forward, {bwd_mode} backward: {k}")
+
+
+@pytest.mark.parametrize("fwd_mode,bwd_mode", [(0, 1), (1, 0)])
+@pytest.mark.parametrize("H", [50, 128])
+def test_simple_artspeech_arithmetic_switched_between_forward_and_backward(dev, matrix_arith, H, fwd_mode, bwd_mode):
+    c = dict(V=40, A=4, E=24, H=H, N=50, B=6, T=100)
+    _poison_next_workspace(_lib.Dims(c["V"], c["A"], c["E"], H, c["N"], 1), c["B"], c["T"], dev)
+    _simple_artspeech_vs_oracle(dev, c, 9, matrix_arith, fwd_mode, bwd_mode)
 
 
 def test_entry_points_accept_strided_and_degenerate_views(dev):
@@ -1414,6 +1630,12 @@ def test_full_size_every_gradient_vs_oracle(dev):
         except AssertionError as e:
             bad.append(str(e)[:200])
     assert not bad, (f"ReLU decisions taken from the device: {flips}", bad)
+
+
+def test_full_size_every_gradient_vs_oracle_exact_fp32(dev, matrix_arith):
+    """The benchmark's exact_fp32 configuration: the same checks in the exact-fp32 matrix arithmetic."""
+    matrix_arith(0)
+    test_full_size_every_gradient_vs_oracle(dev)
 
 
 def test_evenly_spaced_fx_and_grid(dev):

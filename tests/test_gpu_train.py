@@ -18,6 +18,16 @@ def dev():
     return torch.device("cuda:0")
 
 
+@pytest.fixture
+def matrix_arith():
+    """tests that switch the library's matrix arithmetic restore the default (1 = split) afterwards"""
+    from artspeech_amd import _lib
+    L = _lib.lib()
+    keep = L.as_get_matrix_arith()
+    yield L.as_set_matrix_arith
+    L.as_set_matrix_arith(keep)
+
+
 def _loaders(n, bs, seed):
     from torch.utils.data import DataLoader
     from artspeech_amd.phoneme_to_articulation.encoder_decoder.dataset import SyntheticArtSpeechDataset, pad_sequence_collate_fn
@@ -200,6 +210,13 @@ def test_train_step_engine_equals_module_path(dev, n_samp):
     else:   # (the module path's criterion is a separate autograd node with its own rounding of the sigmoid's backward)
         assert torch.allclose(step.grads, ref_grad, rtol=1e-4, atol=1e-6 * float(ref_grad.abs().max()))
     assert torch.allclose(model.flat.data, after_torch, rtol=1e-5, atol=1e-7)  # fused Adam == torch.optim.Adam
+
+
+@pytest.mark.parametrize("n_samp", [50, 1, 70])
+def test_train_step_engine_equals_module_path_exact_fp32(dev, matrix_arith, n_samp):
+    """The same in the exact-fp32 matrix arithmetic: both paths take its kernels and still agree bit for bit (N = 50)."""
+    matrix_arith(0)
+    test_train_step_engine_equals_module_path(dev, n_samp)
 
 
 def test_two_models_interleaved_on_two_streams(dev):

@@ -18,6 +18,16 @@ def dev():
     return torch.device("cuda:0")
 
 
+@pytest.fixture
+def matrix_arith():
+    """tests that switch the library's matrix arithmetic restore the default (1 = split) afterwards"""
+    from artspeech_amd import _lib
+    L = _lib.lib()
+    keep = L.as_get_matrix_arith()
+    yield L.as_set_matrix_arith
+    L.as_set_matrix_arith(keep)
+
+
 @pytest.fixture(scope="module")
 def small(dev):
     from artspeech_amd.phoneme_to_articulation.transformer.models import ArtSpeechTransformer
@@ -383,6 +393,13 @@ def test_backward_matches_reference_fixture(small, dev):
         assert err < 1e-3, (k, err)
     print("worst gradient relative error:", worst)
     model.zero_grad()
+
+
+def test_backward_matches_reference_fixture_exact_fp32(small, dev, matrix_arith):
+    """The same in the exact-fp32 matrix arithmetic: the forward linears do not change, but every backward GEMM
+    (GRAD_PRECISION = lib) resolves to the fp32 matrix instruction instead of the split kernels."""
+    matrix_arith(0)
+    test_backward_matches_reference_fixture(small, dev)
 
 
 def test_split_forward_gemms_opt_in_matches_reference_fixture(small, dev):
