@@ -128,12 +128,14 @@ __global__ __launch_bounds__(ATT_THREADS) void attn_fwd_kernel(AttnK a) {
         float m = -INFINITY;
         if (a.mask_t) {  // uniform branch around the whole unrolled block, not one per element
             // uniform row pointer + one per-lane 32-bit offset: per-element 64-bit addresses would be hoisted out of the strip
-            // loop and cost 2 VGPRs each (the mask is padded to 32 NB key rows, so no clamping either)
-            const float* mt = a.mask_t + (long)b * (32 * NB) * a.T;
+            // loop and cost 2 VGPRs each.  The caller pads the key rows to Tk rounded up to 32 (the per-utterance pitch), not
+            // to 32 NB: a block that starts at or beyond Tk lies past the utterance's rows and is not read (its scores are
+            // -inf through kp); every block below it lies wholly inside the padded rows, so no clamping either
+            const float* mt = a.mask_t + (long)b * (32 * ((a.Tk + 31) / 32)) * a.T;
             const int moff = qc + 4 * lh * a.T;
 #pragma unroll
             for (int blk = 0; blk < NB; ++blk) {  // 16 loads in flight per block (all NB x 16 at once would not fit the registers)
-                if (blk > last_blk) continue;
+                if (blk > last_blk || blk * 32 >= a.Tk) continue;
                 float mv[16];
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
