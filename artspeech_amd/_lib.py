@@ -129,6 +129,14 @@ PROTOTYPES = {
     "as_ln_feat_gelu_bwd": (_I32, [_P, _P, _P, _P, _P, _P, _I64, _I32, _I32, _P]),
     "as_conv3x3_stem_bwd": (_I32, [_P, _P, _P, _I64, _I64, _I64, _I64, _I32, _I32, _I32, _I32, _P]),
     "as_gelu_bwd": (_I32, [_P, _P, _P, _P, _I64, _I32, _P]),
+    "as_conv3x3_c32_wgrad": (_I32, [_P, _P, _P, _P, _I32, _I32, _I32, _P, _I64, _P]),
+    "as_conv3x3_stem_wgrad": (_I32, [_P, _I64, _I64, _I64, _I64, _P, _P, _P, _I32, _I32, _I32, _I32, _P, _I64, _P]),
+    "as_ln_feat_gelu_param_grad": (_I32, [_P, _P, _P, _P, _I64, _I32, _I32, _P, _P, _P, _I64, _P]),
+    "as_layernorm_param_grad": (_I32, [_P, _P, _I64, _I32, _P, _P, _P, _I64, _P]),
+    "as_ctc_workspace_floats": (_I64, [_I32, _I32, _I32]),
+    "as_ctc_loss": (_I32, [_P, _I64, _I64, _I32, _I32, _I32, _I32, _P, _I64, _P, _P, _I32, _I32, _I32, _P, _I64, _P, _P]),
+    "as_ctc_grad": (_I32, [_P, _I64, _I64, _I32, _I32, _I32, _I32, _P, _I64, _P, _P, _I32, _I32, _P, _I64, _P, _P, _I32, _P, _I64,
+                           _I64, _P]),
     "as_intersect_semipolar_grid": (_I32, [_P, _P, _I64, _I32, _I32, _I32, _P, _P, _P, _P]),
     "as_artspeech_wait_head_grads": (_I32, [_P, _P]),
     "as_gather_pad_rows": (_I32, [_P, _P, _P, _I32, _I32, _I64, _I32, _D, _P, _P]),

@@ -25,6 +25,8 @@ SOURCES = {
     "gru.hip": [],
     "lstm.hip": [],
     "conv.hip": [],
+    "scorer_wgrad.hip": [],
+    "ctc.hip": [],
     "attention.hip": [],
     "metrics.hip": ["-ffp-contract=off"],
     "multi_mlp.hip": [],

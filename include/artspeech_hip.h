@@ -521,6 +521,52 @@ int as_conv3x3_stem_bwd(const float* dy, const float* w, float* dx, int64_t sb, 
                         int32_t T, int32_t D, int32_t Cin, void* stream);
 int as_gelu_bwd(const float* dy, const float* x, const float* scale, float* dx, int64_t n, int32_t row_len, void* stream);
 
+/* ---- training the scorer (train_phoneme_recognition.py): parameter gradients and the CTC loss ---------------------------
+ * Every split reduction below writes at most 256 partial rows to the caller's workspace `ws` (ws_floats floats; too small:
+ * AS_ERR_WORKSPACE, whose message names the size needed) and adds them in a fixed order: no atomics, bit-identical repeats.
+ * Exact fp32 whatever as_set_matrix_arith says.
+ * as_conv3x3_c32_wgrad  : weight and bias gradients of as_conv3x3_c32 (ResidualCNN's cnn1 / cnn2, deepspeech2.py:22, 25):
+ *                         dw[tap][co][ci] = sum_{b,t,d} dy[b][t][d][co] * x[b][t+kt-1][d+kd-1][ci] (zero padded, tap = kd*3 + kt,
+ *                         the forward's tap layout [9][32][32]), dbias[co] = sum dy; x, dy [B][T][D][32].  Implicit GEMM on the
+ *                         f32 MFMA, the positions split over waves.  ws: 256 * (9*1024 + 32) floats suffice.
+ * as_conv3x3_stem_wgrad : the same for as_conv3x3_stem (:104): dw [9][32][Cin] (1 <= Cin <= 4), dbias [32]; x is read through the
+ *                         forward's planar strides (sb, sc, sd, st); the voicing term has no parameter.  ws: 256 * (288*Cin + 32).
+ * as_ln_feat_gelu_param_grad : dgamma[d] = sum_{r,c} dz * xhat, dbeta[d] = sum_{r,c} dz of as_ln_feat_gelu (:31-35, 39-43), where
+ *                         dz = dy * gelu'(LN(x)) is the gradient of the LayerNorm's output; mean and rstd are recomputed from
+ *                         x [rows][D][C] (C == 32).  ws: 256 * 2 * D.
+ * as_layernorm_param_grad : dgamma = sum_r dz * xhat, dbeta = sum_r dz of a row LayerNorm (RecurrentBlock :64, the adapter :75-78)
+ *                         from the forward's saved xhat [rows][D] and the gradient dz of its affine output.  ws: 256 * 2 * D. */
+int as_conv3x3_c32_wgrad(const float* x, const float* dy, float* dw, float* dbias, int32_t B, int32_t T, int32_t D, float* ws,
+                         int64_t ws_floats, void* stream);
+int as_conv3x3_stem_wgrad(const float* x, int64_t sb, int64_t sc, int64_t sd, int64_t st, const float* dy, float* dw, float* dbias,
+                          int32_t B, int32_t T, int32_t D, int32_t Cin, float* ws, int64_t ws_floats, void* stream);
+int as_ln_feat_gelu_param_grad(const float* x, const float* gamma, const float* beta, const float* dy, int64_t rows, int32_t D, int32_t C,
+                               float* dgamma, float* dbeta, float* ws, int64_t ws_floats, void* stream);
+int as_layernorm_param_grad(const float* dz, const float* xhat, int64_t rows, int32_t D, float* dgamma, float* dbeta, float* ws,
+                            int64_t ws_floats, void* stream);
+
+/* torch.nn.CTCLoss (phoneme_recognition/__init__.py:114-120: criterion(log_softmax(outputs).permute(1, 0, 2), targets,
+ * input_lengths, target_lengths)).  x: rows of C classes at x[t*sx_t + b*sx_b + c] (the (T, B, C) view of a (B, T, C) tensor costs
+ * no copy); logits == 0: x holds log-probabilities, used as given (torch semantics); logits != 0: raw scores, normalised by a
+ * log-softmax inside.  targets: int64, padded rows targets[b*tgt_stride + j] (tgt_stride > 0; padding past target_lengths[b]
+ * is never read) or torch's concatenated 1-D form (tgt_stride == 0).  input_lengths[b] <= T, target_lengths[b] <=
+ * max_target_length <= 2047 (S = 2L + 1 <= 4095 states; AS_ERR_UNSUPPORTED beyond), all int64 on the device; inconsistent
+ * lengths give NaN.
+ * as_ctc_loss : nll[b] = -log p(target_b | x_b) (inf when no alignment exists), from log-space alpha / beta recursions kept in
+ *               ws (with_beta = 0: alpha only -- a loss without gradient); ws: as_ctc_workspace_floats(T, B, max_target_length).
+ * as_ctc_grad : from that workspace, grad[t*sg_t + b*sg_b + c] = (exp(lp) - gamma) * scale[b] (scale NULL: 1), gamma the class
+ *               occupancy sum_{s: l'_s = c} alpha_t(s) beta_t(s) / (p y_t^c) -- torch's CPU backward with log-probability input,
+ *               the gradient with respect to the logits in logits mode.  Zero for t >= input_lengths[b], and for a whole
+ *               utterance whose nll is inf when zero_infinity != 0. */
+int64_t as_ctc_workspace_floats(int32_t T, int32_t B, int32_t max_target_length);
+int as_ctc_loss(const float* x, int64_t sx_t, int64_t sx_b, int32_t T, int32_t B, int32_t C, int32_t logits, const int64_t* targets,
+                int64_t tgt_stride, const int64_t* input_lengths, const int64_t* target_lengths, int32_t max_target_length, int32_t blank,
+                int32_t with_beta, float* ws, int64_t ws_floats, float* nll, void* stream);
+int as_ctc_grad(const float* x, int64_t sx_t, int64_t sx_b, int32_t T, int32_t B, int32_t C, int32_t logits, const int64_t* targets,
+                int64_t tgt_stride, const int64_t* input_lengths, const int64_t* target_lengths, int32_t max_target_length, int32_t blank,
+                const float* ws, int64_t ws_floats, const float* nll, const float* scale, int32_t zero_infinity, float* grad, int64_t sg_t,
+                int64_t sg_b, void* stream);
+
 /* intersect_semipolar_grid (area_function.py:175-223), float64, batched over frames: air_column [frames][2 walls][2][n_pts]
  * (internal wall first, x row then y row -- the air-column file layout), grid [n_lines][grid_res][2].  For every frame and
  * grid line: flags bit 0 / 1 = the internal / external wall is crossed (0: the reference skips the line), bit 2 = more than

@@ -1,0 +1,203 @@
+####################################################################################################
+#
+# Train the DeepSpeech2 phoneme recogniser with CTC (reference train_phoneme_recognition.py) on the
+# MI355X engine:
+#   python train_phoneme_recognition.py --config cfg.yaml [--mlflow URI --experiment NAME
+#          --run_id ID --run_name NAME --checkpoint checkpoint.pt]
+# The YAML keys are the keyword arguments of main() (the reference's), plus the extras `datadir: synthetic`
+# (SyntheticPhonemeRecognitionDataset, sized by `synthetic:` and the sequence dicts' `num_sentences`) and
+# `results_dir`.  TrainableDeepSpeech2 + the engine's CTCLoss(**loss_params), Adam(lr, weight_decay) and
+# CyclicLR(lr / 25, lr, cycle_momentum=False) stepped per batch; early stopping on the validation edit
+# distance (greedy CTC decoding); best_model.pt, last_model.pt and checkpoint.pt like the reference, then
+# a test-split pass of the best model written to info_test.json.  CTC only (`loss: CE` raises).
+#
+####################################################################################################
+import argparse
+import json
+import logging
+import os
+import random
+import shutil
+import tempfile
+from functools import partial
+
+import numpy as np
+import torch
+import yaml
+from torch.optim import Adam
+from torch.optim.lr_scheduler import CyclicLR
+from torch.utils.data import DataLoader
+
+from artspeech_amd.helpers import sequences_from_dict, set_seeds
+from artspeech_amd.phoneme_recognition import (BLANK, SIL, UNKNOWN, Criterion, Feature, Target, TrainableDeepSpeech2, run_epoch,
+                                               run_test)
+from artspeech_amd.phoneme_recognition.datasets import PhonemeRecognitionDataset, SyntheticPhonemeRecognitionDataset, collate_fn
+from artspeech_amd.phoneme_recognition.decoders import GreedyCTCDecoder
+from artspeech_amd.phoneme_recognition.metrics import EditDistance
+from artspeech_amd.settings import TRAIN, VALID
+
+try:  # mlflow is optional here (absent from the MI355X image): same flags, no-op logging
+    import mlflow
+except ImportError:
+    mlflow = None
+
+
+def _mlflow(fn, *args, **kwargs):
+    if mlflow is not None:
+        return getattr(mlflow, fn)(*args, **kwargs)
+
+
+def build_vocabulary(vocab_filepath, criterion):
+    """{token: index}: blank (CTC) and unknown first, then the JSON list (reference :84-90); without a file, the 43 synthetic
+    phoneme names of the other synthetic configs (V = 45)."""
+    default_tokens = [BLANK, UNKNOWN] if criterion == Criterion.CTC else [UNKNOWN]
+    vocabulary = {token: i for i, token in enumerate(default_tokens)}
+    if vocab_filepath is not None:
+        with open(vocab_filepath) as f:
+            tokens = json.load(f)
+    else:
+        tokens = [f"ph{i:02d}" for i in range(43)]
+    for i, token in enumerate(tokens, start=len(vocabulary)):
+        vocabulary[token] = i
+    return vocabulary
+
+
+def _make_dataset(datadir, database_name, seq_dict, vocabulary, feature, voiced_tokens, synthetic, seed):
+    if datadir == "synthetic":
+        cfg = dict(synthetic or {})
+        n = (seq_dict or {}).get("num_sentences", cfg.pop("num_sentences", 32))
+        cfg.pop("num_sentences", None)
+        return SyntheticPhonemeRecognitionDataset(n, vocabulary, seed=seed, voiced_tokens=voiced_tokens, **cfg)
+    return PhonemeRecognitionDataset(datadir=datadir, database_name=database_name, sequences=sequences_from_dict(datadir, seq_dict),
+                                     vocabulary=vocabulary, features=[feature], voiced_tokens=voiced_tokens)
+
+
+def main(database_name, datadir, num_epochs, batch_size, patience, learning_rate, weight_decay, feature, target, vocab_filepath,
+         train_seq_dict, valid_seq_dict, test_seq_dict, model_params, loss, plot_target=None, loss_params=None, num_workers=0,
+         logits_large_margins=0.0, pretrained=False, voicing_filepath=None, state_dict_filepath=None, checkpoint_filepath=None,
+         seed=0, synthetic=None, results_dir=None):
+    criterion = Criterion[loss]
+    if criterion != Criterion.CTC:
+        raise NotImplementedError(f"train_phoneme_recognition: loss {loss!r} is not supported; only CTC is ported")
+    device = torch.device("cuda", torch.cuda.current_device())
+    logging.info(f"Running on '{device}'")
+    results_dir = results_dir or RESULTS_DIR
+    os.makedirs(results_dir, exist_ok=True)
+    best_model_path = os.path.join(results_dir, "best_model.pt")
+    last_model_path = os.path.join(results_dir, "last_model.pt")
+    save_checkpoint_path = os.path.join(results_dir, "checkpoint.pt")
+
+    feature = Feature(feature)
+    target = Target(target)
+    if pretrained:
+        raise NotImplementedError("train_phoneme_recognition: pretrained (the LibriSpeech checkpoint) is not supported")
+    vocabulary = build_vocabulary(vocab_filepath, criterion)
+    voiced_tokens = None
+    if voicing_filepath is not None:
+        with open(voicing_filepath) as f:
+            voiced_tokens = json.load(f)
+    tokens = [k for k, _ in sorted(vocabulary.items(), key=lambda t: t[1])]
+    decoder = GreedyCTCDecoder(tokens=tokens, sil_token=SIL, blank_token=BLANK, unk_word=UNKNOWN)
+
+    model = TrainableDeepSpeech2(num_classes=len(vocabulary), **model_params)
+    if state_dict_filepath is not None:
+        model.load_state_dict(torch.load(state_dict_filepath, map_location="cpu"))
+    model.to(device)
+    print(f"\nDeepSpeech2 -- {model.total_parameters} parameters\n")
+    _mlflow("log_param", "num_network_params", model.total_parameters)
+
+    gen = torch.Generator(device="cpu")
+    gen.manual_seed(seed)
+
+    def loader(seq_dict, ds_seed):
+        ds = _make_dataset(datadir, database_name, seq_dict, vocabulary, feature, voiced_tokens, synthetic, ds_seed)
+        return DataLoader(ds, batch_size=batch_size, shuffle=True, num_workers=num_workers, worker_init_fn=set_seeds,
+                          collate_fn=partial(collate_fn, features_names=[feature]), generator=gen)
+
+    train_dataloader = loader(train_seq_dict, seed)
+    valid_dataloader = loader(valid_seq_dict, seed + 1)
+
+    loss_fn = criterion.value(**(loss_params or {}))
+    optimizer = Adam(model.parameters(), lr=learning_rate, weight_decay=weight_decay)
+    scheduler = CyclicLR(optimizer, base_lr=learning_rate / 25, max_lr=learning_rate, cycle_momentum=False)
+    metrics = {"edit_distance": EditDistance(decoder)}
+    use_voicing = voicing_filepath is not None
+    common = dict(model=model, criterion=loss_fn, fn_metrics=metrics, device=device, feature=feature, target=target,
+                  use_voicing=use_voicing, normalize_outputs=True, use_log_prob=True, optimizer=optimizer, scheduler=scheduler)
+
+    best_metric = np.inf
+    epochs_since_best = 0
+    epochs = range(1, num_epochs + 1)
+    if checkpoint_filepath is not None:
+        checkpoint = torch.load(checkpoint_filepath, map_location=device)
+        model.load_state_dict(checkpoint["model"])
+        optimizer.load_state_dict(checkpoint["optimizer"])
+        epoch = checkpoint["epoch"] + 1
+        epochs = range(epoch, num_epochs + 1)
+        best_metric = checkpoint["best_metric"]
+        epochs_since_best = checkpoint["epochs_since_best"]
+        logging.info(f"Loaded checkpoint -- training from epoch {epoch}, best metric {best_metric} "
+                     f"seen {epochs_since_best} epochs ago.")
+
+    history = []
+    for epoch in epochs:
+        info_train = run_epoch(phase=TRAIN, epoch=epoch, dataloader=train_dataloader, logits_large_margins=logits_large_margins, **common)
+        _mlflow("log_metrics", {f"train_{m}": v for m, v in info_train.items()}, step=epoch)
+        info_valid = run_epoch(phase=VALID, epoch=epoch, dataloader=valid_dataloader, **common)
+        _mlflow("log_metrics", {f"valid_{m}": v for m, v in info_valid.items()}, step=epoch)
+        history.append({"epoch": epoch, "train": info_train, "valid": info_valid})
+        if info_valid["edit_distance"] < best_metric:
+            best_metric = info_valid["edit_distance"]
+            epochs_since_best = 0
+            torch.save(model.state_dict(), best_model_path)
+            _mlflow("log_artifact", best_model_path)
+        else:
+            epochs_since_best += 1
+        torch.save(model.state_dict(), last_model_path)
+        _mlflow("log_artifact", last_model_path)
+        checkpoint = {"epoch": epoch, "model": model.state_dict(), "optimizer": optimizer.state_dict(), "best_metric": float(best_metric),
+                      "epochs_since_best": epochs_since_best, "best_model_path": best_model_path, "last_model_path": last_model_path}
+        torch.save(checkpoint, save_checkpoint_path)
+        _mlflow("log_artifact", save_checkpoint_path)
+        print(f"\nFinished training epoch {epoch}\nBest metric: {'%0.4f' % best_metric}, Epochs since best: {epochs_since_best}\n")
+        if epochs_since_best > patience:
+            break
+
+    # test split: the best model (the reference's plots and confusion / substitution matrices are not part of this engine)
+    test_dataloader = loader(test_seq_dict, seed + 2)
+    best_model = TrainableDeepSpeech2(num_classes=len(vocabulary), **model_params)
+    best_model.load_state_dict(torch.load(best_model_path if os.path.exists(best_model_path) else last_model_path, map_location="cpu"))
+    best_model.to(device)
+    info_test = run_test(best_model, test_dataloader, metrics, target, feature=feature, use_voicing=use_voicing, device=device,
+                         criterion=loss_fn)
+    with open(os.path.join(results_dir, "info_test.json"), "w") as f:
+        json.dump(info_test, f, indent=2)
+    _mlflow("log_metrics", {f"test_{m}": v for m, v in info_test.items()}, step=0)
+    return {"history": history, "test": info_test, "results_dir": results_dir}
+
+
+TMP_DIR = tempfile.mkdtemp(prefix="artspeech_recognizer_")
+RESULTS_DIR = os.path.join(TMP_DIR, "results")
+
+if __name__ == "__main__":
+    parser = argparse.ArgumentParser()
+    parser.add_argument("--config", dest="config_filepath")
+    parser.add_argument("--mlflow", dest="mlflow_tracking_uri", default=None)
+    parser.add_argument("--experiment", dest="experiment_name", default="phoneme_recognition")
+    parser.add_argument("--run_id", dest="run_id", default=None)
+    parser.add_argument("--run_name", dest="run_name", default=None)
+    parser.add_argument("--checkpoint", dest="checkpoint_filepath", default=None)
+    args = parser.parse_args()
+    seed = 0
+    random.seed(seed)
+    torch.manual_seed(seed)
+    np.random.seed(seed)
+    with open(args.config_filepath) as f:
+        cfg = yaml.safe_load(f)
+    if mlflow is not None and args.mlflow_tracking_uri is not None:
+        mlflow.set_tracking_uri(args.mlflow_tracking_uri)
+        mlflow.set_experiment(args.experiment_name)
+    try:
+        main(**cfg, checkpoint_filepath=args.checkpoint_filepath, seed=seed)
+    finally:
+        shutil.rmtree(TMP_DIR, ignore_errors=True)
