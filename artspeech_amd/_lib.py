@@ -61,6 +61,15 @@ class MultiMlp(C.Structure):
                 ("ws", C.c_void_p), ("ws_floats", C.c_int64), ("dy", C.c_void_p), ("dx", C.c_void_p), ("dparams", C.c_void_p)]
 
 
+class Pca(C.Structure):
+    _fields_ = [("groups", C.c_int32), ("features", C.c_int32), ("k_max", C.c_int32), ("batch", C.c_int32),
+                ("k", C.c_void_p), ("x", C.c_void_p), ("rows", C.c_int64), ("x_r", C.c_int64), ("x_g", C.c_int64),
+                ("order", C.c_void_p), ("n_seen", C.c_int64), ("state", C.c_void_p),
+                ("components", C.c_void_p), ("singular_values", C.c_void_p), ("explained_variance", C.c_void_p),
+                ("explained_variance_ratio", C.c_void_p), ("noise_variance", C.c_void_p),
+                ("ws", C.c_void_p), ("ws_floats", C.c_int64)]
+
+
 _P, _I32, _I64, _F, _D = C.c_void_p, C.c_int32, C.c_int64, C.c_float, C.c_double
 _DIMS, _LAY = C.POINTER(Dims), C.POINTER(Layout)
 
@@ -147,6 +156,9 @@ PROTOTYPES = {
     "as_multi_mlp_workspace_floats": (_I64, [C.POINTER(MultiMlp), _I32]),
     "as_multi_mlp_fwd": (_I32, [C.POINTER(MultiMlp), _P]),
     "as_multi_mlp_bwd": (_I32, [C.POINTER(MultiMlp), _P]),
+    "as_pca_supported": (_I32, [_I32, _I32]),
+    "as_pca_workspace_floats": (_I64, [C.POINTER(Pca)]),
+    "as_pca_fit": (_I32, [C.POINTER(Pca), _P]),
     "as_masked_mse_partials": (_I32, []),
     "as_masked_mse_fwd_bwd": (_I32, [_P, _P, _I64, _I64, _P, _I32, _P, _F, _P, _P, _P, _P]),
     "as_profile_enable": (None, [_I32]),

@@ -30,6 +30,7 @@ SOURCES = {
     "attention.hip": [],
     "metrics.hip": ["-ffp-contract=off"],
     "multi_mlp.hip": [],
+    "pca.hip": [],
     "artspeech.hip": [],
 }
 

@@ -34,11 +34,26 @@ class PrincipalComponentsPhonemeToArticulationDataset2(Dataset):
         raise NotImplementedError(f"PrincipalComponentsPhonemeToArticulationDataset2 {_NEEDS_DATA_STACK}")
 
 
+def low_rank_frames(num_frames, channels, features, rank, generator):
+    """(num_frames, channels, features) float32 frames 0.5 + z diag(0.25 0.7^j) Q^T + 0.002 noise, j < min(rank, features), Q
+    orthonormal per channel: a geometric spectrum over a noise floor, so that the leading principal directions are well
+    separated.  Drawn and multiplied in float64 and rounded once, so that machines whose float32 matrix products differ in the
+    last bit still build the same frames."""
+    rank = min(rank, features)
+    z = torch.randn(num_frames, channels, rank, generator=generator, dtype=torch.float64)
+    q, _ = torch.linalg.qr(torch.randn(channels, features, rank, generator=generator, dtype=torch.float64))
+    scale = 0.25 * 0.7 ** torch.arange(rank, dtype=torch.float64)
+    noise = torch.randn(num_frames, channels, features, generator=generator, dtype=torch.float64)
+    return (0.5 + torch.einsum("nar,afr->naf", z * scale, q) + 0.002 * noise).float()
+
+
 class SyntheticPrincipalComponentsAutoencoderDataset(Dataset):
     """Frames of the autoencoder's dataset (reference :28-107): item = (frame_name, articulators (A, 2 N) float,
-    weight (phoneme_weights of the frame's phoneme), phoneme); contours U(0, 1) like normalised real data."""
+    weight (phoneme_weights of the frame's phoneme), phoneme); contours U(0, 1) like normalised real data, whose principal
+    directions are all equivalent, or, with ``rank=r``, low-rank frames with a decaying spectrum (``low_rank_frames``), which a PCA
+    can be fitted to."""
 
-    def __init__(self, num_frames, articulators, n_samples=50, seed=0, database_name="artspeech2", phonemes=None):
+    def __init__(self, num_frames, articulators, n_samples=50, seed=0, database_name="artspeech2", phonemes=None, rank=None):
         self.articulators = sorted(articulators)
         self.num_samples = n_samples
         self.dataset_config = DATASET_CONFIG[database_name]
@@ -46,7 +61,10 @@ class SyntheticPrincipalComponentsAutoencoderDataset(Dataset):
         self.normalize = _normalizers(self.articulators, n_samples, g)
         phonemes = phonemes or ["a", "l", "t", "#", "ih", "s", "k", "m"]
         self._phonemes = [phonemes[i] for i in torch.randint(0, len(phonemes), (num_frames,), generator=g).tolist()]
-        self._frames = torch.rand(num_frames, len(self.articulators), 2 * n_samples, generator=g)
+        if rank is None:
+            self._frames = torch.rand(num_frames, len(self.articulators), 2 * n_samples, generator=g)
+        else:
+            self._frames = low_rank_frames(num_frames, len(self.articulators), 2 * n_samples, rank, g)
 
     def __len__(self):
         return len(self._phonemes)

@@ -634,6 +634,44 @@ int64_t as_multi_mlp_workspace_floats(const as_multi_mlp* p, int32_t backward);
 int as_multi_mlp_fwd(const as_multi_mlp* p, void* stream);
 int as_multi_mlp_bwd(const as_multi_mlp* p, void* stream);
 
+/* Incremental PCA of the articulator contours on the device (artspeech_amd/csrc/pca.hip): the fit of
+ * train_articulatory_PCA.py:91-108 -- one sklearn.decomposition.IncrementalPCA(n_components = k[a]) per articulator,
+ * partial_fit once per loader batch on inputs[:, a, :] -- for all articulators and all batches of a call in one launch sequence:
+ * a time-parallel phase (batch means, centred sums of squares and, where the merge is solved on the feature side, the centred
+ * cross-products) and ONE launch of a persistent workgroup per articulator that walks the chain of batches.  A partial_fit with n
+ * samples seen and m new ones updates mean / variance (Chan), stacks S V (k rows), X - batch_mean (m rows) and the row
+ * sqrt(n m / (n + m)) (mean - batch_mean) (the first batch: X - mean only), and keeps the k leading singular values / right
+ * singular vectors of the stack, each vector signed so that its largest-magnitude entry is positive (svd_flip,
+ * u_based_decision = False).  All arithmetic after the fp32 loads is fp64 (symmetric eigen-solve by cyclic Jacobi with a fixed
+ * maximum sweep count); sums have a fixed order: bit-identical repeats.
+ *   x      frames, x[row * x_r + a * x_g + f], a < groups, f < features; `rows` rows are consumed in batches of `batch` (the last
+ *          may be short), row i of the call being order[i] if order != NULL (int32, the shuffled loader order) else i.
+ *   k      device [groups] components per articulator, 1 <= k[a] <= k_max.
+ *   n_seen samples seen before this call (0: a fresh fit; the first batch must then hold >= k_max rows).  The fit continues from
+ *          `state`, device fp64 [groups][2 features + k_max + k_max features] = mean | variance | singular values | components,
+ *          which the call updates: partial_fit is the same call with rows = batch = m.
+ *   components [groups][k_max][features], singular_values / explained_variance / explained_variance_ratio [groups][k_max],
+ *          noise_variance [groups]: the fp32 results after the last batch (entries >= k[a] are left untouched).
+ *   ws     as_pca_workspace_floats(p) floats, 8-byte aligned.
+ * Limits: features <= 256, k_max <= min(features, 64): outside them as_pca_fit returns AS_ERR_UNSUPPORTED before any launch
+ * (as_pca_supported tells in advance). */
+typedef struct as_pca {
+    int32_t groups, features, k_max, batch;
+    const int32_t* k;
+    const float* x; int64_t rows, x_r, x_g;
+    const int32_t* order;
+    int64_t n_seen;
+    double* state;
+    float* components; float* singular_values; float* explained_variance; float* explained_variance_ratio; float* noise_variance;
+    float* ws; int64_t ws_floats;
+} as_pca;
+/* the IncrementalPCA(n_components, ...) constructor's and partial_fit's shape checks (train_articulatory_PCA.py:98-101) */
+int32_t as_pca_supported(int32_t features, int32_t k_max);
+/* scratch of one as_pca_fit call (sklearn allocates its stacked matrix per partial_fit, train_articulatory_PCA.py:108) */
+int64_t as_pca_workspace_floats(const as_pca* p);
+/* transformers[articulator].partial_fit(inputs[:, i, :]) for every articulator and batch (train_articulatory_PCA.py:104-108) */
+int as_pca_fit(const as_pca* p, void* stream);
+
 /* Masked / weighted MSE with its gradient in one pass (nn.MSELoss(reduction="none") + mask / weights + mean of
  * principal_components/losses.py:215-225 AutoencoderLoss2 and :274-279 RegularizedLatentsMSELoss2):
  *   loss = scale * sum_r w_r sum_f (a[r][f] - b[r][f])^2,   grad[r][f] = 2 * scale * w_r * (a - b)
