@@ -159,6 +159,11 @@ PROTOTYPES = {
     "as_pca_supported": (_I32, [_I32, _I32]),
     "as_pca_workspace_floats": (_I64, [C.POINTER(Pca)]),
     "as_pca_fit": (_I32, [C.POINTER(Pca), _P]),
+    "as_token_runs_workspace_ints": (_I64, [_I64]),
+    "as_token_runs": (_I32, [_P, _P, _P, _I32, _I64, _P, _P, _P, _P, _P]),
+    "as_mean_contour_fit": (_I32, [_P, _P, _P, _P, _I32, _I32, _P, _P, _P, _P]),
+    "as_mean_contour_fwd": (_I32, [_P, _P, _P, _P, _I32, _I32, _I32, _I32, _P, _P, _P]),
+    "as_mean_contour_weighted_fwd": (_I32, [_P, _P, _P, _P, _P, _P, _I32, _I32, _I32, _I32, _P, _P, _P]),
     "as_masked_mse_partials": (_I32, []),
     "as_masked_mse_fwd_bwd": (_I32, [_P, _P, _I64, _I64, _P, _I32, _P, _F, _P, _P, _P, _P]),
     "as_profile_enable": (None, [_I32]),

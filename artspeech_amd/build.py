@@ -31,6 +31,7 @@ SOURCES = {
     "metrics.hip": ["-ffp-contract=off"],
     "multi_mlp.hip": [],
     "pca.hip": [],
+    "mean_contour.hip": [],
     "artspeech.hip": [],
 }
 

@@ -672,6 +672,39 @@ int64_t as_pca_workspace_floats(const as_pca* p);
 /* transformers[articulator].partial_fit(inputs[:, i, :]) for every articulator and batch (train_articulatory_PCA.py:104-108) */
 int as_pca_fit(const as_pca* p, void* stream);
 
+/* Phoneme-wise mean contour on the device (artspeech_amd/csrc/mean_contour.hip; reference
+ * phoneme_to_articulation/phoneme_wise_mean_contour/__init__.py).  Shared layout: `tokens` are int64 ids, a contour row is
+ * D = n_articulators * 2 * n_samples floats, and the bank is in CSR form by token: the rows bank_offsets[v] .. bank_offsets[v + 1] - 1
+ * of bank_x [M][D] / bank_rel [M] are the stored training frames of token v (bank_offsets int64 [vocab + 1]).
+ *
+ * as_token_runs: _calculate_tokens_lengths_and_positions (:19-29) and the pos / seq_len of process_sentence_with_pos (:43-47) for
+ * every frame of a flat buffer: utterance u holds the rows first_row[u] .. first_row[u] + lengths[u] - 1 (first_row ascending, the
+ * HBM-resident data set's layout; a padded (B, T) batch is first_row[b] = b * T).  A run is a maximal stretch of equal consecutive
+ * tokens inside one utterance; abs_pos = the frame's index in its run, seq_len = the run's length, rel_pos = abs_pos / seq_len
+ * (float32).  Frames outside every utterance (padding) get 0, 0, 0.  A segmented scan over the frames in three launches; ws:
+ * as_token_runs_workspace_ints(frames) int32. */
+int64_t as_token_runs_workspace_ints(int64_t frames);
+int as_token_runs(const int64_t* tokens, const int64_t* first_row, const int32_t* lengths, int32_t utterances, int64_t frames,
+                  int32_t* abs_pos, int32_t* seq_len, float* rel_pos, int32_t* ws, void* stream);
+/* The per-token mean of forward_mean_contour (:130-137: the mean over the sampled rows of the token), table [vocab][D] float32 from
+ * fp64 sums in a fixed order; an empty bank gives a NaN row.  rows != NULL (int64 [M], grouped by token like the bank): the bank is
+ * compacted in the same pass, bank_x[k] = src[rows[k]] (src [frames][D]) and bank_rel[k] = src_rel[rows[k]] -- the
+ * df[df.token == token].sample(...) of :103 / :130 done once at fit time.  rows == NULL: bank_x is read in place. */
+int as_mean_contour_fit(const float* src, const float* src_rel, const int64_t* rows, const int64_t* bank_offsets, int32_t vocab,
+                        int32_t D, float* bank_x, float* bank_rel, float* table, void* stream);
+/* forward_mean_contour (:125-145) for a padded batch: out [B][T][D] = table[tokens[b][t]] for t < lengths[b], zeros after.  A valid
+ * frame whose token lies outside [0, vocab) (NaN) or has an empty bank (the table's NaN row) adds 1 to *flag (device int32). */
+int as_mean_contour_fwd(const float* table, const int64_t* bank_offsets, const int64_t* tokens, const int32_t* lengths, int32_t B,
+                        int32_t T, int32_t vocab, int32_t D, float* out, int32_t* flag, void* stream);
+/* forward_weighted_mean_contour (:86-122) for a padded batch in one launch: for a valid frame q with token v and relative position
+ * r = rel_pos[q] (as_token_runs of the batch), out[q] = sum_k w_k bank_x[k] / sum_k w_k over the bank rows k of v with
+ * w_k = exp(-|bank_rel[k] - r|) (F.softmin of :107; every exponent lies in [-1, 0]).  The queries of one token inside a chunk of
+ * 256 frames share each bank row in tiles of 16; float32 FMAs in a fixed order.  Padded frames give zeros; an empty bank or a token
+ * outside [0, vocab) gives NaN and adds to *flag. */
+int as_mean_contour_weighted_fwd(const float* bank_x, const float* bank_rel, const int64_t* bank_offsets, const int64_t* tokens,
+                                 const float* rel_pos, const int32_t* lengths, int32_t B, int32_t T, int32_t vocab, int32_t D, float* out,
+                                 int32_t* flag, void* stream);
+
 /* Masked / weighted MSE with its gradient in one pass (nn.MSELoss(reduction="none") + mask / weights + mean of
  * principal_components/losses.py:215-225 AutoencoderLoss2 and :274-279 RegularizedLatentsMSELoss2):
  *   loss = scale * sum_r w_r sum_f (a[r][f] - b[r][f])^2,   grad[r][f] = 2 * scale * w_r * (a - b)
