@@ -247,12 +247,15 @@ _ROUTES = (("fused", True, True), ("unfused dS", True, False), ("unfused", False
 
 @pytest.mark.parametrize("T,Tk,dh,causal", [(80, 80, 32, True), (150, 150, 16, True), (200, 200, 64, True), (33, 33, 64, True),
                                             (300, 256, 32, True), (300, 300, 16, True), (70, 150, 64, False), (96, 80, 16, False),
-                                            (129, 129, 32, False)])
+                                            (129, 129, 32, False), (300, 513, 16, False), (64, 1024, 32, False), (257, 257, 64, True),
+                                            (40, 700, 24, False)])
 def test_attention_gradients_three_routes(dev, T, Tk, dh, causal):
     """(dQ, dK, dV) of ops.Attention against float64 autograd by the fused dS kernel, by the dP GEMM + as_attn_softmax_bwd_t
-    (its float4 kernel at T % 4 == 0, its scalar one otherwise) and by the unfused forward and backward (Tk > 256 has no
-    fused forward at all)."""
+    (its float4 kernel at T % 4 == 0, its scalar one otherwise) and by the unfused forward and backward.  Where
+    as_attention_supported says no -- Tk > 256 (every utterance longer than 256 frames: as_attn_softmax at NW = 8 and 16) or a
+    head width outside {16, 32, 64} (dh = 24) -- all three settings take the unfused route, the only one there is."""
     ops = _ops()
+    _lib, L = _L()
     G, B, h = 1, 3, 2
     d = dh * h
     Q, K, V = _qkv(G, B, T, Tk, d, dev, seed=T + 11 * Tk + dh)
@@ -261,7 +264,8 @@ def test_attention_gradients_three_routes(dev, T, Tk, dh, causal):
     go = torch.randn_like(Q)
     Qd, Kd, Vd = (t.double().requires_grad_() for t in (Q, K, V))
     gref = torch.autograd.grad(_ref(Qd, Kd, Vd, am, kpm, B, h)[0], (Qd, Kd, Vd), go.double())
-    fusable = Tk <= 256
+    fusable = bool(L.as_attention_supported(T, Tk, d, h))
+    assert fusable == (Tk <= 256 and dh in (16, 32, 64))
     for route, fused_att, fused_ds in _ROUTES:
         ops.FUSED_ATTENTION, ops.FUSED_DS = fused_att, fused_ds
         try:
@@ -274,6 +278,17 @@ def test_attention_gradients_three_routes(dev, T, Tk, dh, causal):
             ops.FUSED_ATTENTION, ops.FUSED_DS = True, True
         for name, a_, r_ in zip("QKV", got, gref):
             _close(a_, r_, 2e-5, f"{route} T={T} Tk={Tk} dh={dh}: d{name}")
+
+
+def test_attention_forward_refuses_more_than_1024_keys(dev):
+    """Tk = 1025 is beyond the unfused softmax's widest instantiation (16 values per lane): ops.attention_forward raises the
+    library's error, which names the limit, instead of returning whatever the score buffer held"""
+    ops = _ops()
+    G, B, h, T, Tk, d = 1, 2, 2, 8, 1025, 32
+    Q, K, V = _qkv(G, B, T, Tk, d, dev, seed=1)
+    with pytest.raises(RuntimeError, match=r"as_attn_softmax.*1025 > 1024"):
+        ops.attention_forward(Q, K, V, None, None, B, h, True)
+    torch.cuda.synchronize()
 
 
 @pytest.mark.parametrize("T,Tk,dh,causal,fused", [(80, 80, 32, True, True), (70, 150, 64, False, True), (160, 160, 16, True, False)])

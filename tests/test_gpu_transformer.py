@@ -219,7 +219,8 @@ def _drawn_training_configs(n):
 @pytest.mark.parametrize("A,d,h,lens,nf", [(2, 32, 2, [9, 5], 20), (3, 48, 4, [12, 12, 7], 20), (5, 64, 2, [20, 3], 20), (3, 32, 2, [11, 4], 6),
                                            (2, 64, 4, [7, 7], 10), (3, 28, 4, [9, 6], 6), (2, 12, 4, [8], 2), (3, 20, 2, [5, 5, 2], 10)]
                          + _drawn_training_configs(int(os.environ.get("AS_FUZZ_SEEDS", "8")))
-                         + [(2, 64, 2, [80, 41], 10)])   # padded length 80: nb = 3 key blocks, rounded up to the kernel's NB = 4
+                         + [(2, 64, 2, [80, 41], 10),   # padded length 80: nb = 3 key blocks, rounded up to the kernel's NB = 4
+                            (2, 32, 2, [300, 260], 6)])   # longer than 256 frames: every attention runs GEMM + as_attn_softmax (NW = 8)
 def test_edge_configs_vs_oracle_with_directional_derivative(dev, A, d, h, lens, nf):
     """Corners of the block-group node (ops.ChannelBlocks): two channels (ONE interaction block per channel: the
     concatenation is a single block wide), a head width the fused attention kernel does not take (48 / 4 = 12: the unfused

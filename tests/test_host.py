@@ -457,3 +457,19 @@ def test_bench_dump_outputs_writes_npy_within_the_size_limit(tmp_path):
     s = np.load(tmp_path / "b" / "contours_sample.npy")
     assert np.array_equal(s, np.load(tmp_path / "c" / "contours_sample.npy")) and (np.diff(s) > 0).all()
     assert np.array_equal(np.load(tmp_path / "b" / "params.npy"), big["params"])
+
+
+def test_every_row_kernel_entry_point_has_a_direct_test():
+    """Ledger: every `extern "C" int as_...` of csrc/rowops.hip is called by tests/test_gpu_rowops.py, except the two whose
+    direct tests live elsewhere.  A new row kernel cannot arrive without a test of its own."""
+    elsewhere = {"as_adam_step": "test_gpu_parity.py", "as_gather_pad_rows": "test_gpu_train.py"}
+    src = open(os.path.join(ROOT, "artspeech_amd", "csrc", "rowops.hip")).read()
+    names = re.findall(r'extern\s+"C"\s+int\s+(as_[a-z0-9_]+)\s*\(', src)
+    assert len(names) >= 16 and len(set(names)) == len(names), names
+    tests = os.path.join(ROOT, "tests")
+    rowops = open(os.path.join(tests, "test_gpu_rowops.py")).read()
+    for name in names:
+        if name in elsewhere:   # as_adam_step: called directly; as_gather_pad_rows: through HBMResidentDataset.collate, named there
+            assert re.search(rf"\b{name}\b", open(os.path.join(tests, elsewhere[name])).read()), f"{name}: not in tests/{elsewhere[name]}"
+        else:
+            assert re.search(rf"\bL\.{name}\(", rowops), f"{name} is exported by rowops.hip but tests/test_gpu_rowops.py never calls it"
