@@ -19,6 +19,7 @@
 #include <mutex>
 #include <vector>
 
+#include "as_launch.h"
 #include "gemm_internal.h"
 #include "rowops.h"
 
@@ -553,8 +554,8 @@ int record_heads_done(hipStream_t owner, hipStream_t s) {
     return 0;
 }
 
-// fork whose event the producing kernel may already carry (as_stop_event_set before its launch): `left` = what
-// as_stop_event_take() returned after the launch -- non-null: nobody consumed it, record it the ordinary way
+// fork whose event the producing kernel may already carry (an AsStopEventScope around its launch): `left` = what the
+// scope's take() returned after the launch -- non-null: nobody consumed it, record it the ordinary way
 int fork_after(hipStream_t from, hipStream_t to, hipEvent_t ev, hipEvent_t left) {
     hipError_t e = left ? hipEventRecord(ev, from) : hipSuccess;
     if (e == hipSuccess) e = hipStreamWaitEvent(to, ev, 0);
@@ -807,10 +808,12 @@ extern "C" int as_artspeech_bwd(const as_dims* d, const float* P, const int64_t*
     const bool capturing = hipStreamIsCapturing(st, &cap_) != hipSuccess || cap_ != hipStreamCaptureStatusNone;
     const bool plain_forks = as_profile_active() || capturing;
     // ---- fork 0: head + trunk weight gradients run beside the layer-1 recurrence.  The fork's event rides on the GEMM's own
-    // dispatch (as_stop_event_set): no marker packet on `st` between it and the recurrence
-    if (sd && !plain_forks) as_stop_event_set(sd->fork[0]);
-    AS_STEP("trunkb.dx", st, gemm_nn(dzlin, H, P + L.lin_w, 2 * H, ws + w.dy1, 2 * H, R, 2 * H, H, st));
-    if (sd) AS_TRY(fork_after(st, s2, sd->fork[0], plain_forks ? sd->fork[0] : as_stop_event_take()));
+    // dispatch (AsStopEventScope): no marker packet on `st` between it and the recurrence
+    {
+        AsStopEventScope fork0(sd && !plain_forks ? sd->fork[0] : nullptr);
+        AS_STEP("trunkb.dx", st, gemm_nn(dzlin, H, P + L.lin_w, 2 * H, ws + w.dy1, 2 * H, R, 2 * H, H, st));
+        if (sd) AS_TRY(fork_after(st, s2, sd->fork[0], plain_forks ? sd->fork[0] : fork0.take()));
+    }
     AS_STEP("gru.bwd_l1", st, as_gru_bidir_bwd(ws + w.dy1, ws + w.y1, ws + w.g1, P + L.w_hh[1], lengths, B, T, H, ws + w.dgi1, ws + w.dgh1, st));
     const int side_cus = sd ? 192 : 0;  // the recurrence's 2 * B workgroups hold 64 CUs while the side stream works
     const TrunkJob trunk{dzlin, ws + w.y1, G + L.lin_w, G + L.lin_b, H};
@@ -824,9 +827,12 @@ extern "C" int as_artspeech_bwd(const as_dims* d, const float* P, const int64_t*
     // input gradient of GRU layer 1: [R][6H] . [6H][2H]
     // (split arithmetic measured slower here, 56 vs 52 us: 200 workgroups x 1.2 MB of weight planes each from L2)
     const bool fork1_armed = sd && !plain_forks && !(pdrop > 0.f);
-    if (fork1_armed) as_stop_event_set(sd->fork[1]);   // fork 1 rides on this GEMM (see fork 0)
-    AS_STEP("grub.dx1", st, gemm_nn(ws + w.dgi1, 6 * H, P + L.w_ih[1], 2 * H, ws + w.dy0, 2 * H, R, 2 * H, 6 * H, st, 1, 0, 0, 0, slab));
-    const hipEvent_t fork1_left = as_stop_event_take();
+    hipEvent_t fork1_left = nullptr;
+    {
+        AsStopEventScope fork1(fork1_armed ? sd->fork[1] : nullptr);   // fork 1 rides on this GEMM (see fork 0)
+        AS_STEP("grub.dx1", st, gemm_nn(ws + w.dgi1, 6 * H, P + L.w_ih[1], 2 * H, ws + w.dy0, 2 * H, R, 2 * H, 6 * H, st, 1, 0, 0, 0, slab));
+        fork1_left = fork1.take();
+    }
     if (pdrop > 0.f)  // back through the inter-layer dropout: same mask, regenerated from the seed
         AS_STEP("gru.dropout", st, as_dropout(ws + w.dy0, ws + w.dy0, (long)R * 2 * H, pdrop, opts->dropout_seed, st));
     // ---- fork 1: layer-1 weight gradients run beside the layer-0 recurrence
@@ -840,16 +846,20 @@ extern "C" int as_artspeech_bwd(const as_dims* d, const float* P, const int64_t*
     // pass; else dgi0 + as_token_segsum below
     const int tok_sums = V <= T && as_gru_bwd_tokens_fits(V, H, T);
     // fork 2 (the tail's second job, below) rides on the recurrence's dispatch
-    if (sd && !plain_forks) as_stop_event_set(s3 != s2 ? sd->fork2[2] : sd->fork[2]);
-    if (tok_sums) {
-        AS_PROF("gru.bwd_l0", st);
-        const int rc = as_gru_bidir_bwd_tokens(ws + w.dy0, ws + w.y0, ws + w.g0, P + L.w_hh[0], lengths, B, T, H, ws + w.dgh0, tokens,
-                                               tok_stride, V, ws + w.dgi0, st);
-        AS_REQUIRE(rc == 1, rc < 0 ? rc : AS_ERR_UNSUPPORTED, "gru.bwd_l0: launch failed");
-    } else {
-        AS_STEP("gru.bwd_l0", st, as_gru_bidir_bwd(ws + w.dy0, ws + w.y0, ws + w.g0, P + L.w_hh[0], lengths, B, T, H, ws + w.dgi0, ws + w.dgh0, st));
+    const hipEvent_t fork2_ev = sd ? (s3 != s2 ? sd->fork2[2] : sd->fork[2]) : nullptr;
+    hipEvent_t fork2_left = fork2_ev;
+    {
+        AsStopEventScope fork2(plain_forks ? nullptr : fork2_ev);
+        if (tok_sums) {
+            AS_PROF("gru.bwd_l0", st);
+            const int rc = as_gru_bidir_bwd_tokens(ws + w.dy0, ws + w.y0, ws + w.g0, P + L.w_hh[0], lengths, B, T, H, ws + w.dgh0, tokens,
+                                                   tok_stride, V, ws + w.dgi0, st);
+            AS_REQUIRE(rc == 1, rc < 0 ? rc : AS_ERR_UNSUPPORTED, "gru.bwd_l0: launch failed");
+        } else {
+            AS_STEP("gru.bwd_l0", st, as_gru_bidir_bwd(ws + w.dy0, ws + w.y0, ws + w.g0, P + L.w_hh[0], lengths, B, T, H, ws + w.dgi0, ws + w.dgh0, st));
+        }
+        if (sd && !plain_forks) fork2_left = fork2.take();
     }
-    const hipEvent_t fork2_left = (sd && !plain_forks) ? as_stop_event_take() : (sd ? (s3 != s2 ? sd->fork2[2] : sd->fork[2]) : nullptr);
     if (two_parts && !defer) {
         AS_TRY(head_bwd_dw(*d, L, P, R, G, hws, sl2, s2, dpre3, side_cus, sd ? SLAB2_FLOATS : SLAB_FLOATS, nullptr, 2));
         AS_TRY(record_heads_done(st, s2));  // [lin_w, total) of the flat gradient buffer is final from here on
@@ -869,7 +879,7 @@ extern "C" int as_artspeech_bwd(const as_dims* d, const float* P, const int64_t*
     if (sd && s3 != s2) AS_TRY(fork_to(s2, s3, sd->join));
     hipStream_t s_hh = tok_sums ? st : s3, s_emb = tok_sums ? s3 : st;
     float* sl_hh = tok_sums ? slab : sl3;
-    if (sd) AS_TRY(fork_after(st, s3, s3 != s2 ? sd->fork2[2] : sd->fork[2], fork2_left));
+    if (sd) AS_TRY(fork_after(st, s3, fork2_ev, fork2_left));
     AS_STEP("grub.dw_hh", s_hh, gemm_tn(ws + w.dgh0, 6 * H, ws + w.y0, 2 * H, G + L.w_hh[0], H, 3 * H, H, R, s_hh, sl_hh, G + L.b_hh[0], 3 * H, 2,
                    3 * H, H, 3L * H * H, -1, T, 2));
     // embedding + layer-0 input projection through the token table

@@ -18,9 +18,10 @@
 #include <cmath>
 
 #include "as_common.h"
+#include "as_device.h"
+#include "as_launch.h"
 #include "artspeech_hip.h"
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 namespace {
 
@@ -361,8 +362,7 @@ __global__ __launch_bounds__(ATT_THREADS, 4) void attn_ds_kernel(AttnDsK a) {
 template <int DH, int NB>
 int launch_attn_ds(const AttnDsK& k, long Z, hipStream_t st) {
     constexpr size_t shm = (size_t)(32 * NB * (DH + 4)) * sizeof(float);
-    static const hipError_t attr =
-        hipFuncSetAttribute(reinterpret_cast<const void*>(attn_ds_kernel<DH, NB>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm);
+    const hipError_t attr = as_allow_dynamic_lds(attn_ds_kernel<DH, NB>, (int)shm);
     AS_REQUIRE(attr == hipSuccess, (int)attr, "as_attention_bwd_ds: cannot reserve %zu bytes of LDS: %s", shm, hipGetErrorString(attr));
     hipLaunchKernelGGL((attn_ds_kernel<DH, NB>), dim3((unsigned)Z), dim3(ATT_THREADS), shm, st, k);
     return 0;
@@ -526,8 +526,7 @@ template <int DH>
 int launch_attn_ds_causal(const AttnDsK& k, long Z, hipStream_t st) {
     const int nb = (k.Tk + 31) / 32, strips = (k.T + 31) / 32;
     const size_t shm = (size_t)(32 * nb * (DH + 4) + 32 * strips) * sizeof(float) + 80 * sizeof(int);
-    static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(attn_ds_causal_kernel<DH>),
-                                                       hipFuncAttributeMaxDynamicSharedMemorySize, 72 * 1024);
+    const hipError_t attr = as_allow_dynamic_lds(attn_ds_causal_kernel<DH>, 72 * 1024);
     AS_REQUIRE(attr == hipSuccess, (int)attr, "as_attention_bwd_ds: cannot reserve LDS: %s", hipGetErrorString(attr));
     hipLaunchKernelGGL((attn_ds_causal_kernel<DH>), dim3((unsigned)Z), dim3(ATT_THREADS), shm, st, k);
     return 0;
@@ -618,8 +617,7 @@ __global__ __launch_bounds__(256) void attn_softmax_bwd_t_scalar_kernel(const fl
 template <int DH, int NB>
 int launch_attn(const AttnK& k, long Z, hipStream_t st) {
     constexpr size_t shm = (size_t)(2 * 32 * NB * (DH + 4) + 32 * NB) * sizeof(float);
-    static const hipError_t attr =
-        hipFuncSetAttribute(reinterpret_cast<const void*>(attn_fwd_kernel<DH, NB>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm);
+    const hipError_t attr = as_allow_dynamic_lds(attn_fwd_kernel<DH, NB>, (int)shm);
     AS_REQUIRE(attr == hipSuccess, (int)attr, "as_attention_fwd: cannot reserve %zu bytes of LDS: %s", shm, hipGetErrorString(attr));
     hipLaunchKernelGGL((attn_fwd_kernel<DH, NB>), dim3((unsigned)Z), dim3(ATT_THREADS), shm, st, k);
     return 0;

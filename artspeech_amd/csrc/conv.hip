@@ -22,18 +22,11 @@
 //                             flipped, transposed taps (see as_conv3x3_c32's header comment).
 //   gelu_bwd_kernel         : dy * gelu'(x), optionally times a per-column scale (a following affine LayerNorm's gamma).
 #include "as_common.h"
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
+#include "as_device.h"
 
 namespace {
 
 constexpr int CO = 32;  // output channels of every convolution of the scorer (deepspeech2.py:104)
-
-__device__ __forceinline__ float gelu_exact(float x) { return 0.5f * x * (1.0f + erff(x * 0.70710678118654752440f)); }
-// d gelu / dx = Phi(x) + x phi(x)
-__device__ __forceinline__ float gelu_exact_grad(float x) {
-    return 0.5f * (1.0f + erff(x * 0.70710678118654752440f)) + x * 0.39894228040143267794f * __expf(-0.5f * x * x);
-}
 
 __global__ __launch_bounds__(256) void conv3x3_mfma_kernel(const float* __restrict__ x, const float* __restrict__ w,
                                                            const float* __restrict__ bias, const float* __restrict__ res,
@@ -293,7 +286,7 @@ __global__ __launch_bounds__(256) void ln_feat_gelu_kernel(const float* __restri
     float* yp = y + r * D * Cc + c;
 #pragma unroll
     for (int d = 0; d < MAXD; ++d)
-        if (d < D) yp[(long)d * Cc] = gelu_exact((v[d] - mean) * rs * gamma[d] + beta[d]);
+        if (d < D) yp[(long)d * Cc] = as_gelu((v[d] - mean) * rs * gamma[d] + beta[d]);
 }
 
 // any D: three strided passes
@@ -315,12 +308,12 @@ __global__ __launch_bounds__(256) void ln_feat_gelu_loop_kernel(const float* __r
     }
     const float rs = 1.0f / sqrtf(q / D + eps);
     float* yp = y + r * D * Cc + c;
-    for (int d = 0; d < D; ++d) yp[(long)d * Cc] = gelu_exact((xp[(long)d * Cc] - mean) * rs * gamma[d] + beta[d]);
+    for (int d = 0; d < D; ++d) yp[(long)d * Cc] = as_gelu((xp[(long)d * Cc] - mean) * rs * gamma[d] + beta[d]);
 }
 
 __global__ __launch_bounds__(256) void gelu_kernel(const float* __restrict__ x, float* __restrict__ y, long n) {
     const long stride = (long)gridDim.x * 256;
-    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += stride) y[i] = gelu_exact(x[i]);
+    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += stride) y[i] = as_gelu(x[i]);
 }
 
 // Backward of ln_feat_gelu over one (r, c) column: with xhat = (x - mean) * rstd, a = xhat * gamma + beta and
@@ -363,7 +356,7 @@ __global__ __launch_bounds__(256) void ln_feat_gelu_bwd_kernel(const float* __re
         if (d < D) {
             const float xh = (v[d] - mean) * rs;
             const float ga = gamma[d];
-            const float gd = g[d] * gelu_exact_grad(xh * ga + beta[d]) * ga;
+            const float gd = g[d] * as_gelu_grad(xh * ga + beta[d]) * ga;
             v[d] = xh;
             g[d] = gd;
             sg += gd;
@@ -403,7 +396,7 @@ __global__ __launch_bounds__(256) void ln_feat_gelu_bwd_loop_kernel(const float*
     for (int d = 0; d < D; ++d) {
         const long e = o + (long)d * Cc;
         const float xh = (x[e] - mean) * rs;
-        const float gd = dy[e] * gelu_exact_grad(xh * gamma[d] + beta[d]) * gamma[d];
+        const float gd = dy[e] * as_gelu_grad(xh * gamma[d] + beta[d]) * gamma[d];
         sg += gd;
         sgx += gd * xh;
     }
@@ -411,7 +404,7 @@ __global__ __launch_bounds__(256) void ln_feat_gelu_bwd_loop_kernel(const float*
     for (int d = 0; d < D; ++d) {
         const long e = o + (long)d * Cc;
         const float xh = (x[e] - mean) * rs;
-        const float gd = dy[e] * gelu_exact_grad(xh * gamma[d] + beta[d]) * gamma[d];
+        const float gd = dy[e] * as_gelu_grad(xh * gamma[d] + beta[d]) * gamma[d];
         const float out = rs * (gd - mg - xh * mgx);
         dx[e] = res ? out + res[e] : out;
     }
@@ -465,7 +458,7 @@ __global__ __launch_bounds__(256) void gelu_bwd_kernel(const float* dy, const fl
                                                        float* dx, long n, int row_len) {   // dy == dx allowed
     const long stride = (long)gridDim.x * 256;
     for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += stride) {
-        const float g = dy[i] * gelu_exact_grad(x[i]);
+        const float g = dy[i] * as_gelu_grad(x[i]);
         dx[i] = scale ? g * scale[i % row_len] : g;
     }
 }

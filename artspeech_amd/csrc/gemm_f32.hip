@@ -14,9 +14,9 @@
 
 #include <hip/hip_ext.h>
 
+#include "as_device.h"
+#include "as_launch.h"
 #include "gemm_internal.h"
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 namespace {
 
@@ -499,7 +499,7 @@ __global__ __launch_bounds__(256, (BM * BN >= 128 * 128 ? 3 : 4)) void gemm_f32_
                                 float v = acc[i][j][r] + bj;
                                 if (g.act == 1) v = as_relu(v);
                                 else if (g.act == 2) v = as_sigmoid(v);
-                                else if (g.act == 3) v = 0.5f * v * (1.0f + erff(v * 0.70710678118654752440f));
+                                else if (g.act == 3) v = as_gelu(v);
                                 c0[(long)(i * 32 + (r & 3) + 8 * (r >> 2)) * g.ldc + j * 32] = v;
                             }
                     }
@@ -519,7 +519,7 @@ __global__ __launch_bounds__(256, (BM * BN >= 128 * 128 ? 3 : 4)) void gemm_f32_
                             float v = acc[i][j][r] + bj;
                             if (g.act == 1) v = as_relu(v);
                             else if (g.act == 2) v = as_sigmoid(v);
-                            else if (g.act == 3) v = 0.5f * v * (1.0f + erff(v * 0.70710678118654752440f));
+                            else if (g.act == 3) v = as_gelu(v);
                             float* c = C + (long)row * g.ldc + col;
                             if (g.accumulate) v += *c;
                             *c = v;
@@ -538,9 +538,6 @@ __global__ __launch_bounds__(256, (BM * BN >= 128 * 128 ? 3 : 4)) void gemm_f32_
 // with fp32 accumulation:  PL = 3: hh + hm + mh + hl + lh + mm (6 MFMAs, drops terms below 2^-24 of |a||b|: fp32-grade);
 // PL = 2: hh + hm + mh (3 MFMAs, ~2^-16).  LDS image per piece: [row][40 bf16] (80-byte rows: conflict-free ds_read_b128 of
 // the 8-element k groups a lane of v_mfma_f32_32x32x16_bf16 owns).  Same persistent tile walk and epilogue as the fp32 kernel.
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-
 template <int PL>
 __device__ __forceinline__ void split_store(__bf16* __restrict__ img, int plane_elems, int off, const float4& v) {
     float x[4] = {v.x, v.y, v.z, v.w};
@@ -669,7 +666,7 @@ __global__ __launch_bounds__(256, 2) void gemm_split_nt_kernel(GemmK g) {
                     float v = acc[i][j][r] + bj;
                     if (g.act == 1) v = as_relu(v);
                     else if (g.act == 2) v = as_sigmoid(v);
-                    else if (g.act == 3) v = 0.5f * v * (1.0f + erff(v * 0.70710678118654752440f));
+                    else if (g.act == 3) v = as_gelu(v);
                     float* c = c0 + (long)rr * g.ldc + j * 32;
                     if (g.accumulate) v += *c;
                     *c = v;
@@ -733,11 +730,10 @@ __global__ __launch_bounds__(256) void splitk_reduce4_kernel(GemmK g) {
 // resident workgroups of one kernel instance on the whole device (queried once per instance)
 template <typename Kern>
 int resident_blocks(Kern kern) {
-    int per_cu = 0, dev = 0, cus = 0;
+    int per_cu = 0;
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, 256, 0) != hipSuccess || per_cu < 1) per_cu = 1;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 1)
-        cus = 256;
-    return per_cu * cus;
+    const int cus = as_cu_count();
+    return per_cu * (cus < 1 ? 256 : cus);
 }
 
 // Arrival counters for the in-kernel split-K reduction: one zeroed array per (device, stream), created on first use (like

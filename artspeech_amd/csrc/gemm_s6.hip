@@ -32,12 +32,6 @@
 #include "gemm_internal.h"
 #include "split_arith.h"
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef short s16x4 __attribute__((ext_vector_type(4)));
-
 namespace {
 
 constexpr int TB = 128, BK = 16, NTH = 256;
@@ -64,14 +58,6 @@ struct S6K {
     int xcd_group, batch;                  // > 0: tiles per batch member, all on one XCD (see the kernel)
     int vec_epi;                           // float4-clean output side (N, ldc, res_ld multiples of 4, 16-byte aligned bases): row-major epilogue
 };
-
-typedef const __attribute__((address_space(1))) char* gptr;
-typedef const __attribute__((address_space(1))) f32x4* gptr_f4;
-__device__ __forceinline__ gptr uniform_ptr(const void* p) {   // see lin_f32.hip
-    const uintptr_t v = reinterpret_cast<uintptr_t>(p);
-    const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)v), hi = __builtin_amdgcn_readfirstlane((unsigned)(v >> 32));
-    return reinterpret_cast<gptr>(((uintptr_t)hi << 32) | lo);
-}
 
 // BNC: the B operand is column-contiguous in memory, B[k][n] (an input gradient dx = dz . W with W as the forward stores it):
 // a thread then loads 8 consecutive k of ONE column (8 dword loads, each coalesced over the 64 columns of its wave) and writes
@@ -115,8 +101,8 @@ __global__ __launch_bounds__(NTH, 3) void gemm_s6_kernel(S6K g) {
     const bool seg = EXT && g.k_seg > 0;
     const long* a_seg = seg ? g.a_seg_off + (long)bz * g.nseg : nullptr;
     const long* b_seg = seg ? g.b_seg_off + (long)bz * g.nseg : nullptr;
-    gptr Au = uniform_ptr(g.A + (seg ? a_seg[0] : g.a_off ? g.a_off[bz] : (long)bz * g.a_batch));
-    gptr Bu = uniform_ptr(g.B + (seg ? b_seg[0] : g.b_off ? g.b_off[bz] : (long)bz * g.b_batch));
+    gptr Au = as_uniform_ptr(g.A + (seg ? a_seg[0] : g.a_off ? g.a_off[bz] : (long)bz * g.a_batch));
+    gptr Bu = as_uniform_ptr(g.B + (seg ? b_seg[0] : g.b_off ? g.b_off[bz] : (long)bz * g.b_batch));
     // the NEXT segment's bases are fetched a segment ahead (scalar loads that have 16 k-tiles to arrive)
     long a_next = seg ? a_seg[min(1, g.nseg - 1)] : 0, b_next = seg ? b_seg[min(1, g.nseg - 1)] : 0;
     // An operand tile is 128 rows (m or n) x 16 k.  Reduction-contiguous operand: thread -> rows (tid >> 2) and (tid >> 2) + 64,
@@ -180,8 +166,8 @@ __global__ __launch_bounds__(NTH, 3) void gemm_s6_kernel(S6K g) {
             if (ld_k == kspan) {
                 ld_k = 0;
                 ++ld_seg;
-                Au = uniform_ptr(g.A + a_next);
-                Bu = uniform_ptr(g.B + b_next);
+                Au = as_uniform_ptr(g.A + a_next);
+                Bu = as_uniform_ptr(g.B + b_next);
                 const int nx = min(ld_seg + 1, g.nseg - 1);
                 a_next = a_seg[nx];
                 b_next = b_seg[nx];
@@ -264,7 +250,7 @@ __global__ __launch_bounds__(NTH, 3) void gemm_s6_kernel(S6K g) {
         }
     }
     store(x[0], 0);
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    as_wait_lds();
     __builtin_amdgcn_s_barrier();
     // k-tile kt (U = kt & 1): images in buffer U; x[U ^ 1] holds tile kt + 1, x[U] is refilled with tile kt + 2
     auto tile = [&](auto Uc) {
@@ -290,7 +276,7 @@ __global__ __launch_bounds__(NTH, 3) void gemm_s6_kernel(S6K g) {
                 for (int j = 0; j < 2; ++j)
                     acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[i][PA[o]], fb[j][PB[o]], acc[i][j], 0, 0, 0);
         store(x[U ^ 1], U ^ 1);   // (behind the last tile: a clamped repeat into the idle buffer)
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        as_wait_lds();
         __builtin_amdgcn_s_barrier();
     };
     int kt = 0;

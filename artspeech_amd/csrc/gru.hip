@@ -32,19 +32,11 @@
 #include <hip/hip_ext.h>
 
 #include "as_common.h"
+#include "as_device.h"
+#include "as_launch.h"
 #include "gemm_internal.h"
 
 namespace {
-
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-
-// sum over the LPU (2 or 4) adjacent lanes that share a hidden unit: quad_perm [1,0,3,2] (then [2,3,0,1])
-template <int LPU>
-__device__ __forceinline__ float unit_sum(float v) {
-    v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0xB1, 0xF, 0xF, true));
-    if (LPU == 4) v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x4E, 0xF, 0xF, true));
-    return v;
-}
 
 constexpr int AHEAD = 2;   // steps of look-ahead of the operand loads (see the header)
 
@@ -147,7 +139,7 @@ __global__ __launch_bounds__(LPU * H) void gru_fwd_kernel(const float* __restric
                     an = __builtin_elementwise_fma(w[2][2 * c + 1], hi, an);
                 }
         }
-        const float sr = unit_sum<LPU>(ar.x + ar.y), sz = unit_sum<LPU>(az.x + az.y), sn = unit_sum<LPU>(an.x + an.y);
+        const float sr = as_quad_sum<LPU>(ar.x + ar.y), sz = as_quad_sum<LPU>(az.x + az.y), sn = as_quad_sum<LPU>(an.x + an.y);
         float r, z;
         if constexpr (LPU == 4) {
             // the four lanes of a unit hold the same sums: lane 0 takes r's sigmoid, lanes 1..3 z's -- ONE exp + rcp sequence per
@@ -310,9 +302,6 @@ __global__ __launch_bounds__(4 * H) void gru_bwd_row_kernel(const float* __restr
     // total of unit qp.  Its slot s holds unit (s + qp) & 3, so the partial for unit qp of the lane t positions further in the
     // quad sits in that lane's slot (4 - t) & 3: three rotating quad_perm reads, then row_ror 4 and 8 (which keep the quad
     // position) -- 5 DPP adds instead of 16 moves + 16 adds + the select that an all-reduce of all four sums needs.
-    auto dpp_add = [](float acc, float v, auto ctrl) {
-        return acc + __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), decltype(ctrl)::value, 0xF, 0xF, true));
-    };
     const long fbase = (long)b * T + t0;   // frame of step u: fbase + u * dt
     float dh = 0.f;
     const int tmask = pl < 3 ? -1 : 0;                                                      // dummy word: same for every token
@@ -414,11 +403,11 @@ __global__ __launch_bounds__(4 * H) void gru_bwd_row_kernel(const float* __restr
             }
         }
         float acc = a[0].x + a[0].y;
-        acc = dpp_add(acc, a[3].x + a[3].y, std::integral_constant<int, 0x39>{});   // quad_perm [1,2,3,0]
-        acc = dpp_add(acc, a[2].x + a[2].y, std::integral_constant<int, 0x4E>{});   // quad_perm [2,3,0,1]
-        acc = dpp_add(acc, a[1].x + a[1].y, std::integral_constant<int, 0x93>{});   // quad_perm [3,0,1,2]
-        acc = dpp_add(acc, acc, std::integral_constant<int, 0x124>{});              // row_ror 4
-        acc = dpp_add(acc, acc, std::integral_constant<int, 0x128>{});              // row_ror 8
+        acc = as_dpp_add<0x39>(acc, a[3].x + a[3].y);   // quad_perm [1,2,3,0]
+        acc = as_dpp_add<0x4E>(acc, a[2].x + a[2].y);   // quad_perm [2,3,0,1]
+        acc = as_dpp_add<0x93>(acc, a[1].x + a[1].y);   // quad_perm [3,0,1,2]
+        acc = as_dpp_add<0x124>(acc, acc);              // row_ror 4
+        acc = as_dpp_add<0x128>(acc, acc);              // row_ror 8
         dh = dht * z + acc;
         // the next step writes another buffer of gbuf, whose readers all passed the barrier above: one barrier per step
     };
@@ -522,9 +511,9 @@ __global__ __launch_bounds__(GEN_THREADS) void gru_fwd_generic_kernel(const floa
                     sn += e[u].x * hv[u].x + e[u].y * hv[u].y + e[u].z * hv[u].z + e[u].w * hv[u].w;
                 }
             }
-            sr = unit_sum<4>(sr) + bd[j];
-            sz = unit_sum<4>(sz) + bd[H + j];
-            sn = unit_sum<4>(sn) + bd[2 * H + j];
+            sr = as_quad_sum<4>(sr) + bd[j];
+            sz = as_quad_sum<4>(sz) + bd[H + j];
+            sn = as_quad_sum<4>(sn) + bd[2 * H + j];
             const float r = as_sigmoid(gr[j] + sr);
             const float z = as_sigmoid(gr[H + j] + sz);
             const float n = as_tanh(gr[2 * H + j] + r * sn);
@@ -631,22 +620,12 @@ constexpr int lpu_of(int) { return 4; }
 // recurrence workgroup asks for 144 KB of dynamic LDS it does not touch, so that nothing that needs LDS fits beside it and
 // the dispatcher places the side work on the other CUs.  Only while the grid leaves at least half of the CUs free;
 // ARTSPEECH_GRU_SHARED_CUS=1 turns it off.
-constexpr size_t GRU_LDS_PAD = 144 * 1024, GRU_LDS_ATTR = 152 * 1024;
+constexpr size_t GRU_LDS_PAD = 144 * 1024;
+constexpr int GRU_LDS_ATTR = 152 * 1024;
 static size_t gru_lds_pad(int workgroups) {
     static const bool off = getenv("ARTSPEECH_GRU_SHARED_CUS") != nullptr;
     if (off) return 0;
-    static const int cus = [] {
-        int dev = 0, n = 0;
-        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) n = 0;
-        return n;
-    }();
-    return workgroups * 2 <= cus ? GRU_LDS_PAD : 0;
-}
-// dynamic LDS beyond 64 KB needs the attribute, once per kernel; false: the kernel keeps the 64 KB limit (no padding then)
-template <typename K>
-static bool gru_lds_attr(K kernel) {
-    static const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)GRU_LDS_ATTR);
-    return e == hipSuccess;
+    return workgroups * 2 <= as_cu_count() ? GRU_LDS_PAD : 0;
 }
 
 static unsigned long long* g_gru_dbg = nullptr;
@@ -667,7 +646,9 @@ static int gru_fwd_launch(const float* gi, const int64_t* tokens, int64_t tok_st
     const size_t need = tokens ? (size_t)T * sizeof(int) : 0;
 #define AS_GRU_LAUNCH(HH, TR, TK)                                                                                      \
     do {                                                                                                               \
-        const size_t shm = pad > need && gru_lds_attr(gru_fwd_kernel<HH, lpu_of(HH), TR, TK>) ? pad : need;            \
+        /* not granted: the kernel keeps the 64 KB limit of dynamic LDS (no padding then) */                           \
+        const bool big = pad > need && as_allow_dynamic_lds(gru_fwd_kernel<HH, lpu_of(HH), TR, TK>, GRU_LDS_ATTR) == hipSuccess; \
+        const size_t shm = big ? pad : need;                                                                           \
         hipLaunchKernelGGL((gru_fwd_kernel<HH, lpu_of(HH), TR, TK>), grid, dim3(lpu_of(HH) * HH), shm, st, gi, tokens, \
                            (long)tok_stride, w_hh, b_hh, lengths, T, y, gates, nd, V);                                 \
     } while (0)
@@ -739,7 +720,7 @@ static int gru_bwd_launch(const float* dy, const float* y, const float* gates, c
     const size_t need = tokens ? ((size_t)V * 3 * H + 4 * H + T) * sizeof(float) : 0;   // + one dummy word per lane + T offsets
 #define AS_GRU_BWD_ROW(HH, TK, ND)                                                                                     \
     do {                                                                                                                      \
-        const bool big = gru_lds_attr(gru_bwd_row_kernel<HH, TK, ND>);                                                    \
+        const bool big = as_allow_dynamic_lds(gru_bwd_row_kernel<HH, TK, ND>, GRU_LDS_ATTR) == hipSuccess;                    \
         AS_REQUIRE(big || need <= 64 * 1024, AS_ERR_UNSUPPORTED, "as_gru_bidir_bwd: cannot reserve %zu bytes of LDS", need);   \
         const size_t shm = big && pad > need ? pad : need;                                                                    \
         if (stop_ev)   /* a fork event rides on this dispatch (gemm_internal.h, as_stop_event_set) */                         \

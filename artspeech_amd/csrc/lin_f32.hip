@@ -28,10 +28,6 @@
 #include "gemm_internal.h"
 #include "split_arith.h"
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-
 namespace {
 
 constexpr int BN = 256, BK = 16, NT = 512, NBUF = 3;
@@ -55,53 +51,6 @@ struct LinK {
     const float* rstd_in;             // EPI_LNB in: [M][batch]
     const unsigned long long* bits_in;
 };
-
-// One LDS-DMA wave-instruction: 64 lanes x 16 B from per-lane global addresses to 1 KiB of LDS at the wave-uniform byte
-// address `lds_dst` (+ lane * 16).  Inline asm on purpose: with the builtin hipcc knows that the instruction writes LDS and
-// puts an s_waitcnt vmcnt(0) in front of the next ds_read -- every k-tile then waits for the DMAs it has just issued (seen
-// in this kernel's ISA; the ring's counted waits + barriers below are what orders a slot's reads behind its DMAs).
-// M0 is compiler-reserved: saved and restored inside the one statement that uses it.
-__device__ __forceinline__ void glds16(const float* src, unsigned lds_dst) {
-    unsigned keep;
-    lds_dst = __builtin_amdgcn_readfirstlane(lds_dst);  // derived from the wave index: uniform, but only the hardware knows
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep)
-                 : "v"(src), "s"(lds_dst)
-                 : "memory");
-}
-__device__ __forceinline__ unsigned lds_addr(const float* p) {  // byte address inside the workgroup's LDS, wave-uniform
-    return __builtin_amdgcn_readfirstlane((unsigned)(uintptr_t)(const __attribute__((address_space(3))) float*)p);
-}
-
-// Sum over the 64 lanes, result in every lane.  Four DPP steps give every lane its 16-lane row total (xor 1, xor 2, mirror of
-// 8, mirror of 16: ~8 cycles each); the four row totals are read out with v_readlane and added as wave-uniform values.
-// (as_wave_sum's six __shfl_xor steps are six dependent LDS-crossbar round trips: 12 of them per LayerNorm row made the
-// epilogue longer than the GEMM's main loop.)
-__device__ __forceinline__ float wave_sum(float v) {
-    v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0xB1, 0xF, 0xF, true));    // quad_perm [1,0,3,2]
-    v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x4E, 0xF, 0xF, true));    // quad_perm [2,3,0,1]
-    v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x141, 0xF, 0xF, true));   // row_half_mirror
-    v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x140, 0xF, 0xF, true));   // row_mirror
-    const float a = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 0));
-    const float b = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 16));
-    const float c = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 32));
-    const float d = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 48));
-    return (a + b) + (c + d);
-}
-__device__ __forceinline__ void lds_barrier() {  // LDS hazards only: unlike __syncthreads() it leaves global stores in flight
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-}
-
-// Sum over the 16 lanes of a DPP row (lanes 16 k .. 16 k + 15), result in every lane of the row: four DPP steps, no
-// cross-row traffic, no v_readlane.
-__device__ __forceinline__ float row16_sum(float v) {
-    v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0xB1, 0xF, 0xF, true));    // quad_perm [1,0,3,2]
-    v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x4E, 0xF, 0xF, true));    // quad_perm [2,3,0,1]
-    v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x141, 0xF, 0xF, true));   // row_half_mirror
-    v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x140, 0xF, 0xF, true));   // row_mirror
-    return v;
-}
 
 // ---- the LayerNorm epilogues.  The accumulators of a block of 32 rows (per group of 8 column waves) go to LDS, then every
 // wave normalises FOUR rows at a time: lane = (row rr = lane >> 4, slot jj = lane & 15) holds the 16 features
@@ -150,7 +99,7 @@ __device__ __forceinline__ void lin_ln_rows(const LinK& g, f32x16 (&acc)[TM], fl
 #pragma unroll
     for (int i = 0; i < TM; ++i) {
         if (i >= tm_eff) break;
-        if (i > 0) lds_barrier();    // the previous block's rows are all read
+        if (i > 0) as_lds_barrier();    // the previous block's rows are all read
         float* st = smem + wm * 32 * BN;
         if (!stages) {
         } else if (EPI == EPI_LNF) {
@@ -176,7 +125,7 @@ __device__ __forceinline__ void lin_ln_rows(const LinK& g, f32x16 (&acc)[TM], fl
 #pragma unroll
             for (int r = 0; r < 16; ++r) st[((r & 3) + 8 * (r >> 2) + 4 * lh) * BN + col] = acc[i][r];
         }
-        lds_barrier();
+        as_lds_barrier();
         if (!normalises) continue;
         const long row = (long)m0 + trow_base + i * 32;
         f32x4 v[4];
@@ -187,14 +136,14 @@ __device__ __forceinline__ void lin_ln_rows(const LinK& g, f32x16 (&acc)[TM], fl
             float s = 0.f;
 #pragma unroll
             for (int c = 0; c < 4; ++c) s += (v[c].x + v[c].y) + (v[c].z + v[c].w);
-            const float mean = row16_sum(s) * inv_d;
+            const float mean = as_row16_sum(s) * inv_d;
             float q = 0.f;
 #pragma unroll
             for (int c = 0; c < 4; ++c) {
                 v[c] -= mean;
                 q += (v[c].x * v[c].x + v[c].y * v[c].y) + (v[c].z * v[c].z + v[c].w * v[c].w);
             }
-            const float rs = 1.0f / sqrtf(row16_sum(q) * inv_d + g.eps);
+            const float rs = 1.0f / sqrtf(as_row16_sum(q) * inv_d + g.eps);
             if (row < g.M) {
 #pragma unroll
                 for (int c = 0; c < 4; ++c) *reinterpret_cast<f32x4*>(o + 64 * c) = v[c] * rs;
@@ -207,7 +156,7 @@ __device__ __forceinline__ void lin_ln_rows(const LinK& g, f32x16 (&acc)[TM], fl
                 s1 += (v[c].x + v[c].y) + (v[c].z + v[c].w);
                 s2 += (v[c].x * h[i][c].x + v[c].y * h[i][c].y) + (v[c].z * h[i][c].z + v[c].w * h[i][c].w);
             }
-            const float m1 = row16_sum(s1) * inv_d, m2 = row16_sum(s2) * inv_d;
+            const float m1 = as_row16_sum(s1) * inv_d, m2 = as_row16_sum(s2) * inv_d;
             if (row < g.M) {
                 const float rs = rs_in[i];
 #pragma unroll
@@ -308,17 +257,17 @@ __global__ __launch_bounds__(NT, 4) void lin_f32_kernel(LinK g) {
             b_src[j] = B + (long)p * g.ldb + min(lane * 4, g.N - 4);
         }
     }
-    const unsigned smem_base = lds_addr(smem);
+    const unsigned smem_base = as_lds_addr(smem);
     // piece 0 = this wave's A piece, pieces 1, 2 = its two B pieces of k-tile kt
     auto issue_piece = [&](int kt, int piece) {
         const unsigned base = smem_base + (unsigned)((kt % NBUF) * TILE) * 4u;
         const int k0 = kt * BK;
         if (piece == 0) {
             const bool ok = k0 + a_gc + 4 <= g.ka_valid;
-            glds16(a_src + (ok ? k0 : -a_gc), base + (unsigned)(pa * 1024));
+            as_glds16(a_src + (ok ? k0 : -a_gc), base + (unsigned)(pa * 1024));
         } else {
             const int j = piece - 1;
-            glds16(b_src[j] + (B_KC ? (long)k0 : (long)k0 * g.ldb), base + (unsigned)((BK * BM + (wave * 2 + j) * 256) * 4));
+            as_glds16(b_src[j] + (B_KC ? (long)k0 : (long)k0 * g.ldb), base + (unsigned)((BK * BM + (wave * 2 + j) * 256) * 4));
         }
     };
     auto issue = [&](int kt) {
@@ -402,7 +351,7 @@ __global__ __launch_bounds__(NT, 4) void lin_f32_kernel(LinK g) {
         __builtin_amdgcn_sched_barrier(0);
         if (kt + 2 < nk) asm volatile("s_waitcnt vmcnt(3)" ::: "memory");
         else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");     // this wave's reads of slot kt % NBUF are in registers
+        as_wait_lds();     // this wave's reads of slot kt % NBUF are in registers
         __builtin_amdgcn_s_barrier();
         if (kt + 1 < nk) load(f0, kt + 1, 0);
         __builtin_amdgcn_sched_barrier(0);
@@ -438,18 +387,6 @@ __global__ __launch_bounds__(NT, 4) void lin_f32_kernel(LinK g) {
 //     {0-3, 12-15, 20-27}, {4-11, 16-19, 28-31} -- then touch each of the 64 banks once).  All eight
 //     waves read their A fragments from there: one barrier per 32-deep k-tile, two plane images (24 KB).
 //   * accumulator layout = that of the fp32 instruction: the LayerNorm epilogues above are shared.
-// a pointer the compiler must treat as wave-uniform (SGPR pair): base of the scalar-base form of a global load, whose lane
-// part is then a 32-bit byte offset.  (Without it hipcc re-associates base + lane offset into a loop-invariant 64-bit VECTOR
-// address and adds the uniform per-step part to that: two address registers and a 64-bit vector add per load.)
-typedef const __attribute__((address_space(1))) char* gptr;   // global address space (the integer round trip would lose it: flat loads)
-__device__ __forceinline__ gptr uniform_ptr(const void* p) {
-    const uintptr_t v = reinterpret_cast<uintptr_t>(p);
-    const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)v), hi = __builtin_amdgcn_readfirstlane((unsigned)(v >> 32));
-    return reinterpret_cast<gptr>(((uintptr_t)hi << 32) | lo);
-}
-typedef const __attribute__((address_space(1))) f32x4* gptr_f4;
-typedef const __attribute__((address_space(1))) u32x4* gptr_u4;
-
 // Workgroups go to the eight XCDs round-robin by block index, and each XCD has its own 4 MB L2.  With tiles numbered head
 // by head, block b -> tile b puts every head's weights into every L2 (11 heads x 393 KB of planes do not fit one).  This map
 // gives XCD x a CONTIGUOUS range of the tile list instead (two or three heads): block b = x + 8 i -> tile start(x) + i.
@@ -488,7 +425,7 @@ __device__ __forceinline__ void s6_main_loop(f32x16 (&acc)[2], unsigned char* sm
         a_wr[q] = row * 64 + (((a_chunk >> 1) ^ ((row >> 2) & 3)) * 16) + (a_chunk & 1) * 8;
     }
     const int nk = K / S6_BK, nj = 2 * nk;
-    const gptr Au = uniform_ptr(A);
+    const gptr Au = as_uniform_ptr(A);
     // every load below is unconditional (indices clamped to the last tile / k-step): straight-line code, so that hipcc's
     // s_waitcnt vmcnt counts are exact -- a load under a branch makes every later wait assume the branch was not taken,
     // i.e. wait for (nearly) everything in flight
@@ -516,7 +453,7 @@ __device__ __forceinline__ void s6_main_loop(f32x16 (&acc)[2], unsigned char* sm
     auto b_load = [&](u32x4 (&dst)[3], int j) {
         j = min(j, nj - 1);
 #pragma unroll
-        for (int p = 0; p < 3; ++p) dst[p] = *reinterpret_cast<gptr_u4>(uniform_ptr(bp + p * bp_plane + j * bp_step) + b_lane);
+        for (int p = 0; p < 3; ++p) dst[p] = *reinterpret_cast<gptr_u4>(as_uniform_ptr(bp + p * bp_plane + j * bp_step) + b_lane);
     };
     const int sw = (l31 >> 2) & 3;        // rows i * 32 + l31 share it (32 = 0 mod 16)
     const unsigned char* a_rd = sm + l31 * 64;
@@ -528,7 +465,7 @@ __device__ __forceinline__ void s6_main_loop(f32x16 (&acc)[2], unsigned char* sm
     b_load(bq[0], 0);
     b_load(bq[1], 1);
     a_store(aq[0], 0);
-    lds_barrier();
+    as_lds_barrier();
     if (stamp1) *stamp1 = __builtin_amdgcn_s_memtime();
     // k-tile kt (kt % 3 == U): its plane image is in buffer kt & 1, its B fragments in sets (2 kt) % 3 and (2 kt + 1) % 3
     auto tile = [&](auto Uc, int kt) {
@@ -565,7 +502,7 @@ __device__ __forceinline__ void s6_main_loop(f32x16 (&acc)[2], unsigned char* sm
             // moment and their matrix work at the same moment -- the matrix pipe idles through the former.
             if (late == (s == 0)) a_store(aq[(U + 1) % 3], (kt & 1) ^ 1);   // (behind the last tile: a clamped repeat)
         }
-        lds_barrier();
+        as_lds_barrier();
     };
     int kt = 0;
     for (; kt + 3 <= nk; kt += 3) {
@@ -763,11 +700,11 @@ __global__ __launch_bounds__(NT, 4) void lin_out_kernel(LinOutK g) {
     const int rb = wave * 16 + (lane >> 2);
     const int b_gc = ((lane & 3) ^ ((rb >> 2) & 3)) * 4;
     const float* b_src = B + (long)min(rb, g.b_rows - 1) * g.ldb + b_gc;   // rows beyond the head's own only feed columns >= N
-    const unsigned smem_base = lds_addr(smem);
+    const unsigned smem_base = as_lds_addr(smem);
     auto issue = [&](int kt) {
         const unsigned base = smem_base + (unsigned)((kt % NBUF) * TILE) * 4u;
-        glds16(a_src + kt * BK, base + (unsigned)(pa * 1024));
-        glds16(b_src + kt * BK, base + (unsigned)((BK * 64 + wave * 256) * 4));
+        as_glds16(a_src + kt * BK, base + (unsigned)(pa * 1024));
+        as_glds16(b_src + kt * BK, base + (unsigned)((BK * 64 + wave * 256) * 4));
     };
     f32x16 acc;
 #pragma unroll
@@ -799,7 +736,7 @@ __global__ __launch_bounds__(NT, 4) void lin_out_kernel(LinOutK g) {
         }
         if (kt + 2 < nk) asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
         else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        as_wait_lds();
         __builtin_amdgcn_s_barrier();
     }
     // ---- epilogue.  D[row][col]: col = wn * 32 + l31, row = wm * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh
@@ -821,7 +758,7 @@ __global__ __launch_bounds__(NT, 4) void lin_out_kernel(LinOutK g) {
 #pragma unroll
         for (int r = 0; r < 16; ++r) smem[(wm * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh) * ON + col] = as_sigmoid(acc[r] + bj);
     }
-    lds_barrier();
+    as_lds_barrier();
     const int Np = g.N >> 1;                                    // points per contour
     // one wave per frame (row) at a time, lanes over the points: frame index, utterance, validity and the target row are
     // wave-uniform (computed once per row on the scalar unit, no per-pair divisions); rows of a wave are independent, so
@@ -897,7 +834,7 @@ __global__ __launch_bounds__(NT, 4) void lin_out_kernel(LinOutK g) {
             dz[Np + n] = gy;
         }
     }
-    part = wave_sum(part);
+    part = as_wave_sum_dpp(part);
     __shared__ float red[8];
     if (lane == 0) red[wave] = part;
     __syncthreads();
@@ -961,7 +898,7 @@ __global__ __launch_bounds__(256, 4) void lin_out_s6_kernel(LinOutK g) {
 #pragma unroll
         for (int r = 0; r < 16; ++r)
             if (i < nblk) smem[(i * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh) * ON + col] = as_sigmoid(acc[i][r] + bj);
-    lds_barrier();
+    as_lds_barrier();
     const int Np = g.N >> 1;                                    // points per contour
     float part = 0.f;
     if (Np <= 64) {
@@ -1033,7 +970,7 @@ __global__ __launch_bounds__(256, 4) void lin_out_s6_kernel(LinOutK g) {
             dz[Np + n] = gy;
         }
     }
-    part = wave_sum(part);
+    part = as_wave_sum_dpp(part);
     __shared__ float red[4];
     if (lane == 0) red[wave] = part;
     __syncthreads();

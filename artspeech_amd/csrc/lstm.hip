@@ -8,19 +8,11 @@
 // The forward keeps i, f, g, o and c' per frame for the backward; the backward emits the pre-activation gradients (one
 // array: input- and hidden-side pre-activations share them), weight gradients are time-batched GEMMs over them.
 #include <cstdlib>
-#include <type_traits>
 
 #include "as_common.h"
+#include "as_device.h"
 
 namespace {
-
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ float quad_sum(float v) {
-    v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0xB1, 0xF, 0xF, true));
-    v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x4E, 0xF, 0xF, true));
-    return v;
-}
 
 constexpr int LPU = 4;  // lanes per hidden unit
 
@@ -107,10 +99,10 @@ __global__ __launch_bounds__(LPU * H) void lstm_fwd_kernel(const float* __restri
                     }
                 }
         }
-        const float gi_ = as_sigmoid(ci.x[0] + quad_sum(a[0].x + a[0].y));
-        const float gf = as_sigmoid(ci.x[1] + quad_sum(a[1].x + a[1].y));
-        const float gg = as_tanh(ci.x[2] + quad_sum(a[2].x + a[2].y));
-        const float go = as_sigmoid(ci.x[3] + quad_sum(a[3].x + a[3].y));
+        const float gi_ = as_sigmoid(ci.x[0] + as_quad_sum<4>(a[0].x + a[0].y));
+        const float gf = as_sigmoid(ci.x[1] + as_quad_sum<4>(a[1].x + a[1].y));
+        const float gg = as_tanh(ci.x[2] + as_quad_sum<4>(a[2].x + a[2].y));
+        const float go = as_sigmoid(ci.x[3] + as_quad_sum<4>(a[3].x + a[3].y));
         cst = gf * cst + gi_ * gg;
         const float hnew = go * as_tanh(cst);
         hbuf[cur ^ 1][j] = hnew;  // the lanes of a unit hold identical values: all store the same word
@@ -192,9 +184,6 @@ __global__ __launch_bounds__(4 * H) void lstm_bwd_row_kernel(const float* __rest
         v.dyv = dyb[fr * 2 * H];
         return v;
     };
-    auto dpp_add = [](float acc, float v, auto ctrl) {
-        return acc + __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), decltype(ctrl)::value, 0xF, 0xF, true));
-    };
     const long fbase = (long)b * T + t0;   // frame of step u: fbase + u * dt
     float dh = 0.f, dc = 0.f;
     auto load_step = [&](int u) {
@@ -235,11 +224,11 @@ __global__ __launch_bounds__(4 * H) void lstm_bwd_row_kernel(const float* __rest
             }
         }
         float acc = a[0].x + a[0].y;
-        acc = dpp_add(acc, a[3].x + a[3].y, std::integral_constant<int, 0x39>{});   // quad_perm [1,2,3,0]
-        acc = dpp_add(acc, a[2].x + a[2].y, std::integral_constant<int, 0x4E>{});   // quad_perm [2,3,0,1]
-        acc = dpp_add(acc, a[1].x + a[1].y, std::integral_constant<int, 0x93>{});   // quad_perm [3,0,1,2]
-        acc = dpp_add(acc, acc, std::integral_constant<int, 0x124>{});              // row_ror 4
-        acc = dpp_add(acc, acc, std::integral_constant<int, 0x128>{});              // row_ror 8
+        acc = as_dpp_add<0x39>(acc, a[3].x + a[3].y);   // quad_perm [1,2,3,0]
+        acc = as_dpp_add<0x4E>(acc, a[2].x + a[2].y);   // quad_perm [2,3,0,1]
+        acc = as_dpp_add<0x93>(acc, a[1].x + a[1].y);   // quad_perm [3,0,1,2]
+        acc = as_dpp_add<0x124>(acc, acc);              // row_ror 4
+        acc = as_dpp_add<0x128>(acc, acc);              // row_ror 8
         dh = acc;
         // gbuf is double buffered: the next step writes gbuf[cur^1], whose readers all passed the barrier above
     };
@@ -306,10 +295,10 @@ __global__ __launch_bounds__(GEN_THREADS) void lstm_fwd_generic_kernel(const flo
                     for (int g = 0; g < 4; ++g)
                         sg[g] += wv[g][u].x * hv[u].x + wv[g][u].y * hv[u].y + wv[g][u].z * hv[u].z + wv[g][u].w * hv[u].w;
             }
-            const float gi_ = as_sigmoid(gr[j] + quad_sum(sg[0]) + bd[j]);
-            const float gf = as_sigmoid(gr[H + j] + quad_sum(sg[1]) + bd[H + j]);
-            const float gg = as_tanh(gr[2 * H + j] + quad_sum(sg[2]) + bd[2 * H + j]);
-            const float go = as_sigmoid(gr[3 * H + j] + quad_sum(sg[3]) + bd[3 * H + j]);
+            const float gi_ = as_sigmoid(gr[j] + as_quad_sum<4>(sg[0]) + bd[j]);
+            const float gf = as_sigmoid(gr[H + j] + as_quad_sum<4>(sg[1]) + bd[H + j]);
+            const float gg = as_tanh(gr[2 * H + j] + as_quad_sum<4>(sg[2]) + bd[2 * H + j]);
+            const float go = as_sigmoid(gr[3 * H + j] + as_quad_sum<4>(sg[3]) + bd[3 * H + j]);
             const float cnew = gf * cb[j] + gi_ * gg;     // (the quad's lanes read c before lane 0 writes it: one wave, program order)
             const float hnew = go * as_tanh(cnew);
             if (q == 0) {

@@ -3,6 +3,7 @@
 //   P2CPDistance utterance means, tract variables (min pairwise distance + closest pair) and the
 //   vocal-tract area function (fp64).  One wave per tile/frame where a tile is small; coalesced
 //   4-byte lanes over the (.., 2, N) contour rows (N = 50 floats = 200 B rows are only 8-byte aligned).
+#include "as_device.h"
 #include "gemm_internal.h"
 
 namespace {
@@ -90,8 +91,6 @@ __global__ __launch_bounds__(256) void loss_final_kernel(const float* __restrict
 // one wave per (u, v) tile: both point sets staged in LDS; lane i scans all v for u_i (row minima),
 // lane j scans all u for v_j (column minima).  min over squared distances, sqrt once (monotone).
 constexpr int P2CP_MAXPTS = 256;
-
-typedef float f32x2 __attribute__((ext_vector_type(2)));
 
 // min_j |p - q_j|^2 over the n points (qx, qy) in LDS (padded to a multiple of 4 with +inf coordinates): four points per
 // step from two broadcast ds_read_b128, the arithmetic on float pairs (v_pk_add / v_pk_mul: half the instructions of the

@@ -12,9 +12,9 @@
 // forward) instead of saving them; one workgroup per (row chunk, articulator) walks the tiles t = chunk, chunk + chunks, ...
 // and keeps its weight-gradient partial in a global slot that only its own lanes read and write (fixed order), the chunks
 // are summed in chunk order by as_sum_partials.  No float atomics anywhere: two runs are bit-identical.
-#include <atomic>
 
 #include "as_common.h"
+#include "as_launch.h"
 #include "gemm_internal.h"
 
 namespace {
@@ -293,21 +293,6 @@ inline int mm_grid(int64_t n) {
     return (int)(b < 1 ? 1 : (b > 4096 ? 4096 : b));
 }
 
-// dynamic LDS beyond 64 KB needs the attribute; it is set for the current device, so success is remembered per device (and
-// per kernel: one instantiation per kernel type), a failure is not remembered (the next call asks again)
-template <typename K>
-bool mm_lds_attr(K kernel) {
-    constexpr int MAX_DEV = 64;
-    static std::atomic<bool> done[MAX_DEV];
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return false;
-    if (dev >= 0 && dev < MAX_DEV && done[dev].load(std::memory_order_acquire)) return true;
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, MM_MAX_LDS) != hipSuccess)
-        return false;
-    if (dev >= 0 && dev < MAX_DEV) done[dev].store(true, std::memory_order_release);
-    return true;
-}
-
 bool mm_fits(int32_t layers, int32_t k_max, int32_t h1, int32_t h2, int32_t n_max) {
     if (layers != 1 && layers != 3) return false;
     if (k_max < 1 || n_max < 1 || k_max > MM_MAX_WIDTH || n_max > MM_MAX_WIDTH) return false;
@@ -367,7 +352,7 @@ extern "C" int as_multi_mlp_fwd(const as_multi_mlp* p, void* stream) {
                (long)p->ws_floats, (long)need);
     hipStream_t st = (hipStream_t)stream;
     const int64_t shm = mm_lds_bytes(mm_geo(p->layers, p->k_max, p->n_max, p->h1, p->h2), false);
-    AS_REQUIRE(shm <= 64 * 1024 || mm_lds_attr(multi_mlp_fwd_kernel), AS_ERR_UNSUPPORTED, "as_multi_mlp_fwd: %ld B of LDS refused",
+    AS_REQUIRE(shm <= 64 * 1024 || as_allow_dynamic_lds(multi_mlp_fwd_kernel, MM_MAX_LDS) == hipSuccess, AS_ERR_UNSUPPORTED, "as_multi_mlp_fwd: %ld B of LDS refused",
                (long)shm);
     AS_PROF("multi_mlp_fwd", st);
     hipLaunchKernelGGL(multi_mlp_fwd_kernel, dim3((p->rows + MM_RT - 1) / MM_RT, p->groups), dim3(MM_THREADS), (size_t)shm, st, *p);
@@ -388,7 +373,7 @@ extern "C" int as_multi_mlp_bwd(const as_multi_mlp* p, void* stream) {
                (long)p->ws_floats, (long)need);
     hipStream_t st = (hipStream_t)stream;
     const int64_t shm = mm_lds_bytes(mm_geo(p->layers, p->k_max, p->n_max, p->h1, p->h2), true);
-    AS_REQUIRE(shm <= 64 * 1024 || mm_lds_attr(multi_mlp_bwd_kernel), AS_ERR_UNSUPPORTED, "as_multi_mlp_bwd: %ld B of LDS refused",
+    AS_REQUIRE(shm <= 64 * 1024 || as_allow_dynamic_lds(multi_mlp_bwd_kernel, MM_MAX_LDS) == hipSuccess, AS_ERR_UNSUPPORTED, "as_multi_mlp_bwd: %ld B of LDS refused",
                (long)shm);
     const int chunks = (int)mm_chunks(p->rows);
     const int64_t P = as_multi_mlp_param_floats(p->layers, p->k_max, p->h1, p->h2, p->n_max);

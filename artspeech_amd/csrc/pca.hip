@@ -15,9 +15,9 @@
 // The chain state (mean, variance, singular values, components) lives in fp64 in the caller's state buffer, so a fit continued
 // by a second call equals one call over all batches bit for bit.  No atomics: every sum has a fixed order.
 #include <algorithm>
-#include <atomic>
 
 #include "as_common.h"
+#include "as_launch.h"
 
 #define PCA_MAX_F 256
 #define PCA_MAX_K 64
@@ -373,20 +373,6 @@ __global__ __launch_bounds__(1024) void pca_chain_kernel(as_pca p, PcaWs w) {
     }
 }
 
-// dynamic LDS beyond 64 KB needs the attribute, per device and kernel instantiation
-template <typename K>
-bool pca_lds_attr(K kernel) {
-    constexpr int MAX_DEV = 64;
-    static std::atomic<bool> done[MAX_DEV];
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return false;
-    if (dev >= 0 && dev < MAX_DEV && done[dev].load(std::memory_order_acquire)) return true;
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, PCA_MAX_LDS) != hipSuccess)
-        return false;
-    if (dev >= 0 && dev < MAX_DEV) done[dev].store(true, std::memory_order_release);
-    return true;
-}
-
 struct PcaPlan {
     int64_t nb, cslots, ne, doubles;
 };
@@ -462,8 +448,8 @@ extern "C" int as_pca_fit(const as_pca* p, void* stream) {
     // where the matrix and the eigenvector accumulator live changes no arithmetic: a refused LDS size falls back to the next mode
     int mode = pl.ne <= PCA_LDS_BOTH ? 2 : (pl.ne <= PCA_LDS_ORDER ? 1 : 0);
     const size_t one = (size_t)pl.ne * pl.ne * 8;
-    if (mode == 2 && 2 * one > 64 * 1024 && !pca_lds_attr(pca_chain_kernel<2>)) mode = 1;
-    if (mode == 1 && one > 64 * 1024 && !pca_lds_attr(pca_chain_kernel<1>)) mode = 0;
+    if (mode == 2 && 2 * one > 64 * 1024 && as_allow_dynamic_lds(pca_chain_kernel<2>, PCA_MAX_LDS) != hipSuccess) mode = 1;
+    if (mode == 1 && one > 64 * 1024 && as_allow_dynamic_lds(pca_chain_kernel<1>, PCA_MAX_LDS) != hipSuccess) mode = 0;
     const int threads = pl.ne <= 48 ? 256 : 1024;
     AS_PROF("pca_chain", st);
     if (mode == 2)

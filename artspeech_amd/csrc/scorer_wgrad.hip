@@ -17,18 +17,13 @@
 //   ln_rows_param_grad_kernel : dgamma = sum_r dz * xhat, dbeta = sum_r dz of a row LayerNorm from its saved xhat, one
 //                               thread per column over a run of rows.
 #include "as_common.h"
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
+#include "as_device.h"
 
 namespace {
 
 constexpr int CO = 32;
 constexpr int WG_MAX_PARTS = 256;   // partial rows of every split reduction
 constexpr int LN_DT = 128;          // feature tile of ln_feat_gelu_param_grad_kernel
-
-__device__ __forceinline__ float gelu_exact_grad(float x) {
-    return 0.5f * (1.0f + erff(x * 0.70710678118654752440f)) + x * 0.39894228040143267794f * __expf(-0.5f * x * x);
-}
 
 // out[j] = sum_{i < n} part[i][j] (i ascending inside each of 16 contiguous row groups, then the groups in order); j < m0 goes
 // to out0[j], the rest to out1[j - m0]
@@ -207,7 +202,7 @@ __global__ __launch_bounds__(256) void ln_feat_gelu_param_grad_kernel(const floa
         __syncthreads();
         for (int d = d0 + dg; d < d1; d += 8) {
             const float xh = (xr[d * CO] - mean) * rs;
-            const float dz = gr[d * CO] * gelu_exact_grad(xh * gamma[d] + beta[d]);
+            const float dz = gr[d * CO] * as_gelu_grad(xh * gamma[d] + beta[d]);
             accg[d - d0][c] += dz * xh;
             accb[d - d0][c] += dz;
         }

@@ -30,9 +30,6 @@
 #include "gemm_internal.h"
 #include "split_arith.h"
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef unsigned u32x4w __attribute__((ext_vector_type(4)));
-
 namespace {
 
 constexpr int BM = 128, BK = 32, NT = 512, NBUF = 3;
@@ -64,18 +61,6 @@ struct WgradK {
     int c_trans;
     long tile0;   // stream-K launches: first output tile of this problem in the launch's tile numbering
 };
-
-// LDS-DMA helper: one wave-instruction copies 64 x 16 B from per-lane global addresses to 1 KiB of LDS starting at the
-// wave-uniform `dst` (global_load_lds_dwordx4: no VGPR destination, counted by vmcnt).  Inline asm: with the builtin hipcc
-// may put an s_waitcnt vmcnt(0) in front of the next ds_read (it did in a 16-deep k-tile version), which drains the ring.
-__device__ __forceinline__ void glds16(const float* src, float* dst) {
-    unsigned keep;
-    const unsigned lds = __builtin_amdgcn_readfirstlane((unsigned)(uintptr_t)(const __attribute__((address_space(3))) float*)dst);
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep)
-                 : "v"(src), "s"(lds)
-                 : "memory");
-}
 
 // One workgroup per CU (144 KB of LDS at BN = 256, two k-tiles = 96 KB in flight).
 // Stream-K (streamk = 1): the launch's work is the flat sequence of k-tiles (32 frames) of all its output tiles, tile after
@@ -190,19 +175,19 @@ __global__ __launch_bounds__(NT, 2) void wgrad_f32_kernel(WgradMulti mm) {
         float* base = smem + (kt % NBUF) * TILE;
         const long koff = (long)kt * BK;
 #pragma unroll
-        for (int j = 0; j < PA; ++j) glds16(a_src + (koff + j * 2) * g.lda, base + (a_dst - smem) + j * 256);
+        for (int j = 0; j < PA; ++j) as_glds16(a_src + (koff + j * 2) * g.lda, as_lds_addr(base + (a_dst - smem) + j * 256));
         if (g.b_kT > 0) {
 #pragma unroll
             for (int j = 0; j < PB; ++j) {
                 const int t = b_t[j] + kshift;
                 const bool ok = t >= 0 && t < g.b_kT;
-                glds16(ok ? b_src + (koff + j * RB + kshift) * g.ldb : zero_src, base + (b_dst - smem) + j * 256);
+                as_glds16(ok ? b_src + (koff + j * RB + kshift) * g.ldb : zero_src, as_lds_addr(base + (b_dst - smem) + j * 256));
                 b_t[j] += BK;
                 while (b_t[j] >= g.b_kT) b_t[j] -= g.b_kT;
             }
         } else {
 #pragma unroll
-            for (int j = 0; j < PB; ++j) glds16(b_src + (koff + j * RB) * g.ldb, base + (b_dst - smem) + j * 256);
+            for (int j = 0; j < PB; ++j) as_glds16(b_src + (koff + j * RB) * g.ldb, as_lds_addr(base + (b_dst - smem) + j * 256));
         }
     };
 
@@ -229,9 +214,9 @@ __global__ __launch_bounds__(NT, 2) void wgrad_f32_kernel(WgradMulti mm) {
 #pragma unroll
             for (int q = 0; q < 4; ++q) split_pair(v[2 * q], v[2 * q + 1], h[q], m[q], l[q]);
             Fr f;
-            f.p[0] = __builtin_bit_cast(bf16x8, (u32x4w){h[0], h[1], h[2], h[3]});
-            f.p[1] = __builtin_bit_cast(bf16x8, (u32x4w){m[0], m[1], m[2], m[3]});
-            f.p[2] = __builtin_bit_cast(bf16x8, (u32x4w){l[0], l[1], l[2], l[3]});
+            f.p[0] = __builtin_bit_cast(bf16x8, (u32x4){h[0], h[1], h[2], h[3]});
+            f.p[1] = __builtin_bit_cast(bf16x8, (u32x4){m[0], m[1], m[2], m[3]});
+            f.p[2] = __builtin_bit_cast(bf16x8, (u32x4){l[0], l[1], l[2], l[3]});
             return f;
         };
         auto load_frags = [&](Fr (&fa)[TM], Fr (&fb)[TN], int kt, int s) {
@@ -289,7 +274,7 @@ __global__ __launch_bounds__(NT, 2) void wgrad_f32_kernel(WgradMulti mm) {
             // retire tile kt + 1 (leave kt + 2 in flight) and publish it; this wave's reads of tile kt are all issued
             if (kt + 2 < nk) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(PA + PB) : "memory");
             else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+            as_wait_lds();
             __builtin_amdgcn_s_barrier();
             mma(fa1, fb1);
             if (kt + 1 < nk) {
@@ -298,7 +283,7 @@ __global__ __launch_bounds__(NT, 2) void wgrad_f32_kernel(WgradMulti mm) {
             }
             __builtin_amdgcn_sched_barrier(0);
         }
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        as_wait_lds();
         __builtin_amdgcn_s_barrier();   // the bias-gradient exchange below reuses the ring's memory
     } else {
     // Ring of NBUF = 3 slots: while k-tile t is multiplied, t + 1 and t + 2 are in flight (2 x 48 KB per CU at BN = 256).
@@ -350,7 +335,7 @@ __global__ __launch_bounds__(NT, 2) void wgrad_f32_kernel(WgradMulti mm) {
         // retire tile kt + 1 (leave kt + 2 in flight), then publish it
         if (kt + 2 < nk) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(PA + PB) : "memory");
         else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // this wave's fragment reads of slot kt % 3 are done
+        as_wait_lds();  // this wave's fragment reads of slot kt % 3 are done
         __builtin_amdgcn_s_barrier();
     }
     }   // !S6

@@ -137,7 +137,7 @@ class _ScorerInputGrad(torch.autograd.Function):
     def backward(ctx, dlogits, dfeatures):
         if dlogits is None and dfeatures is None:
             return None, None, None
-        dx = ctx.model._input_grad(ctx.saved, dlogits, dfeatures)
+        dx = ctx.model._backward(ctx.saved, dlogits, dfeatures)
         return dx.to(ctx.x_dtype), None, None
 
 
@@ -250,9 +250,10 @@ class DeepSpeech2(nn.Module):
         return (logits, features) if return_features else logits
 
     def _run(self, x, voicing, keep=None, drop=None):
-        """The forward on the HIP library; keep (a dict) receives what _input_grad needs -- and, when it holds a "train" entry,
-        what TrainableDeepSpeech2's parameter gradients need.  drop: None, or (p, seed): training-mode dropout at the reference's
-        sites, site k's mask being as_dropout_fwd's at _site_seed(seed, k) (TrainableDeepSpeech2)."""
+        """The forward on the HIP library; keep (a dict) receives what _backward needs -- and, when it holds a "train" entry,
+        what its parameter gradients need (without one those slots of the per-layer records are None).  drop: None, or (p, seed):
+        training-mode dropout at the reference's sites, site k's mask being as_dropout_fwd's at _site_seed(seed, k)
+        (TrainableDeepSpeech2)."""
         L, st = _lib.lib(), _lib.stream_ptr()
         train = keep is not None and "train" in keep
         B, Cin, Din, T = x.shape
@@ -294,7 +295,7 @@ class DeepSpeech2(nn.Module):
                     mid = torch.empty_like(fmap)
                     if train:
                         act, act2 = torch.empty_like(fmap), torch.empty_like(fmap)
-                    kres.append((fmap, mid, act, act2) if train else (fmap, mid))
+                    kres.append((fmap, mid, act, act2) if train else (fmap, mid, None, None))
                 _lib.check(L.as_ln_feat_gelu(_lib.ptr(fmap), _lib.ptr(r.layer_norm1.weight), _lib.ptr(r.layer_norm1.bias), _lib.ptr(act),
                                              B * T, D, OUT_CHANNELS, st), "as_ln_feat_gelu")
                 if drop:
@@ -318,27 +319,24 @@ class DeepSpeech2(nn.Module):
             krnn = []
             nres = len(self.residual_layers)
             for j, blk in enumerate(self.recurrent_layers):
+                # keep: the same values, keeping the LayerNorm's xhat / rstd, the GELU's input and the GRU's gates
+                kln = [] if keep is not None else None
+                a = _ln(h, blk.layer_norm, torch.empty_like(h), kln)
+                ag = torch.empty_like(a) if keep is not None else a
+                _lib.check(L.as_gelu(_lib.ptr(a), _lib.ptr(ag), a.numel(), st), "as_gelu")
+                _gemm(ag, blk.rnn.weight_ih_l0, blk.rnn.bias_ih_l0, gi)
+                h = torch.empty_like(h)
                 if keep is None:
-                    a = _ln(h, blk.layer_norm, torch.empty_like(h))
-                    _lib.check(L.as_gelu(_lib.ptr(a), _lib.ptr(a), a.numel(), st), "as_gelu")
-                    _gemm(a, blk.rnn.weight_ih_l0, blk.rnn.bias_ih_l0, gi)
-                    h = torch.empty_like(h)
                     _lib.check(L.as_gru_unidir_fwd(_lib.ptr(gi), _lib.ptr(blk.rnn.weight_hh_l0), _lib.ptr(blk.rnn.bias_hh_l0),
                                                    _lib.ptr(lengths), B, T, H, _lib.ptr(h), st), "as_gru_unidir_fwd")
                     if drop:
                         _dropout(h, drop, 2 * nres + j)
-                else:   # the same values, keeping the LayerNorm's xhat / rstd, the GELU's input and the GRU's gates
-                    kln = []
-                    a = _ln(h, blk.layer_norm, torch.empty_like(h), kln)
-                    ag = torch.empty_like(a)
-                    _lib.check(L.as_gelu(_lib.ptr(a), _lib.ptr(ag), a.numel(), st), "as_gelu")
-                    _gemm(ag, blk.rnn.weight_ih_l0, blk.rnn.bias_ih_l0, gi)
-                    h = torch.empty_like(h)
+                else:
                     gates = torch.empty(B * T, 4 * H, device=dev, dtype=f32)
                     _lib.check(L.as_gru_unidir_fwd_gates(_lib.ptr(gi), _lib.ptr(blk.rnn.weight_hh_l0), _lib.ptr(blk.rnn.bias_hh_l0),
                                                          _lib.ptr(lengths), B, T, H, _lib.ptr(h), _lib.ptr(gates), st),
                                "as_gru_unidir_fwd_gates")
-                    krnn.append((kln[0], kln[1], a, h, gates, ag) if train else (kln[0], kln[1], a, h, gates))
+                    krnn.append((kln[0], kln[1], a, h, gates, ag if train else None))
                     if drop:   # the GRU's own output stays in krnn (its backward and dW_hh read it); the next block reads the copy
                         h = _dropout(h, drop, 2 * nres + j, torch.empty_like(h))
             fe = self.feature_extractor[0]
@@ -353,49 +351,101 @@ class DeepSpeech2(nn.Module):
                             lengths=lengths, fe_pre=_gemm(h, fe.weight, fe.bias, torch.empty_like(h)))
         return logits.view(B, T, -1), features.view(B, T, H)
 
-    def _input_grad(self, saved, dlogits, dfeatures):
-        """d(logits, features) -> dx (B, C, D, T): the layers of _run in reverse (no parameter gradients)."""
+    def _backward(self, saved, dlogits, dfeatures, drop=None, grads=None, need_dx=True):
+        """d(logits, features) -> dx (B, C, D, T): the layers of _run in reverse.  drop: the forward's (p, seed) or None (its masks
+        are regenerated).  grads: None (a frozen scorer: no parameter gradients), or a dict that receives every parameter's gradient
+        by name -- as_gemm_f32 for the Linear / GRU weights and biases (dW_hh over h_{t-1}), as_conv3x3_c32_wgrad /
+        as_conv3x3_stem_wgrad for the convolutions, as_ln_feat_gelu_param_grad / as_layernorm_param_grad for the LayerNorms; it
+        needs the "train" entries of saved.  The launches that lead to dx are the same either way, so dx is too, bit for bit.
+        need_dx false (with grads only): the walk stops behind the first layer's parameter gradients and returns None."""
         L, st = _lib.lib(), _lib.stream_ptr()
         wb = self._prepare_bwd()
         w = self._prepare()
         B, Cin, Din, T = saved["shape"]
         D, H, M = self.num_features, self.hidden, B * T
         dev, f32 = saved["lengths"].device, torch.float32
+        nres, nrnn = len(self.residual_layers), len(self.recurrent_layers)
+        g, train = grads, grads is not None
+        empty = lambda *s: torch.empty(*s, device=dev, dtype=f32)
         with torch.no_grad():
-            # features = gelu(h W_fe^T + b_fe); logits = features W_cls^T + b_cls
+            # logits = dropout(features) W_cls^T + b_cls; features = gelu(h W_fe^T + b_fe)
             if dlogits is not None:
-                df = _gemm(dlogits.reshape(M, -1).float().contiguous(), wb["classifier"], None, torch.empty(M, H, device=dev, dtype=f32))
+                dl = dlogits.reshape(M, -1).float().contiguous()
+                if train:
+                    g["classifier.weight"] = _wgrad(dl, saved["cls_in"], empty(self.num_classes, H),
+                                                    g.setdefault("classifier.bias", empty(self.num_classes)))
+                df = _gemm(dl, wb["classifier"], None, empty(M, H))
+                if drop:
+                    _dropout(df, drop, 2 * nres + nrnn)
                 if dfeatures is not None:
                     dfc = dfeatures.reshape(M, H).float().contiguous()
                     _lib.check(L.as_add(_lib.ptr(df), _lib.ptr(dfc), _lib.ptr(df), df.numel(), st), "as_add")
             else:
                 df = dfeatures.reshape(M, H).float().contiguous().clone()
             _gelu_bwd(df, saved["fe_pre"], None, df)
-            dh = _gemm(df, wb["fe"], None, torch.empty(M, H, device=dev, dtype=f32))
-            # recurrent blocks: h_out = GRU(gelu(LN(h_in)))
-            dgi = torch.empty(M, 3 * H, device=dev, dtype=f32)
+            if train:
+                g["feature_extractor.0.weight"] = _wgrad(df, saved["fe_in"], empty(H, H), g.setdefault("feature_extractor.0.bias", empty(H)))
+            dh = _gemm(df, wb["fe"], None, empty(M, H))
+            # recurrent blocks: h_out = dropout(GRU(gelu(LN(h_in))))
+            dgi = empty(M, 3 * H)
             dgh = torch.empty_like(dgi)
-            da = torch.empty(M, H, device=dev, dtype=f32)
-            for blk, w_ih_t, (xhat, rstd, a, h_out, gates) in zip(reversed(self.recurrent_layers), reversed(wb["w_ih"]),
-                                                                  reversed(saved["rnn"])):
+            da = empty(M, H)
+            for j in reversed(range(nrnn)):
+                blk, w_ih_t = self.recurrent_layers[j], wb["w_ih"][j]
+                xhat, rstd, a, h_out, gates, ag = saved["rnn"][j]
+                pre = f"recurrent_layers.{j}."
+                if drop:
+                    _dropout(dh, drop, 2 * nres + j)
                 _lib.check(L.as_gru_unidir_bwd(_lib.ptr(dh), _lib.ptr(h_out), _lib.ptr(gates), _lib.ptr(blk.rnn.weight_hh_l0),
                                                _lib.ptr(saved["lengths"]), B, T, H, _lib.ptr(dgi), _lib.ptr(dgh), st),
                            "as_gru_unidir_bwd")
+                if train:
+                    g[pre + "rnn.weight_ih_l0"] = _wgrad(dgi, ag, empty(3 * H, H), g.setdefault(pre + "rnn.bias_ih_l0", empty(3 * H)))
+                    g[pre + "rnn.weight_hh_l0"] = _wgrad(dgh, h_out, empty(3 * H, H), g.setdefault(pre + "rnn.bias_hh_l0", empty(3 * H)),
+                                                         shift=T)
                 _gemm(dgi, w_ih_t, None, da)
+                if train:
+                    _ln_param_grad(_gelu_bwd(da, a, None, empty(M, H)), xhat, blk.layer_norm, g, pre + "layer_norm")
                 _gelu_bwd(da, a, blk.layer_norm.weight, da)     # d xhat = d gelu-out * gelu'(a) * gamma
                 dh = _ln_bwd(da, xhat, rstd, torch.empty_like(da))
-            # Linear(32 D -> H) over the channels-last frame rows
-            dmap = _gemm(dh, wb["linear"], None, torch.empty(M, D * OUT_CHANNELS, device=dev, dtype=f32))
-            # residual blocks: out = conv2(lngelu2(conv1(lngelu1(in)))) + in
+            # Linear(32 D -> H) over the channels-last frame rows; its weight gradient back in the reference's column order c*D + d
+            if train:
+                dwl = _wgrad(dh, saved["lin_in"].view(M, D * OUT_CHANNELS), empty(H, D * OUT_CHANNELS), g.setdefault("linear.bias", empty(H)))
+                g["linear.weight"] = dwl.view(H, D, OUT_CHANNELS).permute(0, 2, 1).reshape(H, OUT_CHANNELS * D)
+            dmap = _gemm(dh, wb["linear"], None, empty(M, D * OUT_CHANNELS))
+            # residual blocks: out = conv2(drop(lngelu2(conv1(drop(lngelu1(in)))))) + in
             dact, dmid = torch.empty_like(dmap), torch.empty_like(dmap)
             zb = wb["zero_bias"]
-            for r, (f1, f2), (fin, mid) in zip(reversed(self.residual_layers), reversed(wb["res"]), reversed(saved["res"])):
+            slab = _slab(dev) if train else None
+            taps_grad = lambda dwk, cin: dwk.view(3, 3, OUT_CHANNELS, cin).permute(2, 3, 0, 1).contiguous()   # [kd][kt][co][ci] -> torch
+
+            def c32_wgrad(x, dy, name):
+                dwk, dbk = empty(9, OUT_CHANNELS, OUT_CHANNELS), empty(OUT_CHANNELS)
+                _lib.check(L.as_conv3x3_c32_wgrad(_lib.ptr(x), _lib.ptr(dy), _lib.ptr(dwk), _lib.ptr(dbk), B, T, D, _lib.ptr(slab),
+                                                  slab.numel(), st), "as_conv3x3_c32_wgrad")
+                g[name + ".weight"], g[name + ".bias"] = taps_grad(dwk, OUT_CHANNELS), dbk
+
+            for i in reversed(range(nres)):
+                r, (f1, f2), (fin, mid, act1, act2) = self.residual_layers[i], wb["res"][i], saved["res"][i]
+                pre = f"residual_layers.{i}."
+                if train:
+                    c32_wgrad(act2, dmap, pre + "cnn2")
                 _lib.check(L.as_conv3x3_c32(_lib.ptr(dmap), _lib.ptr(f2), _lib.ptr(zb), None, _lib.ptr(dact), B, T, D, st),
                            "as_conv3x3_c32")
+                if drop:
+                    _dropout(dact, drop, 2 * i + 1)
+                if train:
+                    _ln_feat_param_grad(mid, r.layer_norm2, dact, g, pre + "layer_norm2")
                 _lib.check(L.as_ln_feat_gelu_bwd(_lib.ptr(mid), _lib.ptr(r.layer_norm2.weight), _lib.ptr(r.layer_norm2.bias),
                                                  _lib.ptr(dact), None, _lib.ptr(dmid), M, D, OUT_CHANNELS, st), "as_ln_feat_gelu_bwd")
+                if train:
+                    c32_wgrad(act1, dmid, pre + "cnn1")
                 _lib.check(L.as_conv3x3_c32(_lib.ptr(dmid), _lib.ptr(f1), _lib.ptr(zb), None, _lib.ptr(dact), B, T, D, st),
                            "as_conv3x3_c32")
+                if drop:
+                    _dropout(dact, drop, 2 * i)
+                if train:
+                    _ln_feat_param_grad(fin, r.layer_norm1, dact, g, pre + "layer_norm1")
                 nxt = torch.empty_like(dmap)
                 _lib.check(L.as_ln_feat_gelu_bwd(_lib.ptr(fin), _lib.ptr(r.layer_norm1.weight), _lib.ptr(r.layer_norm1.bias),
                                                  _lib.ptr(dact), _lib.ptr(dmap), _lib.ptr(nxt), M, D, OUT_CHANNELS, st),
@@ -403,17 +453,36 @@ class DeepSpeech2(nn.Module):
                 dmap = nxt
             # stem: into the planes the forward read (voicing gets no gradient)
             pshape, strides = saved["planes"]
-            dplanes = torch.empty(pshape, device=dev, dtype=f32)
+            if train:
+                dwk, dbk = empty(9, OUT_CHANNELS, Cin), empty(OUT_CHANNELS)
+                _lib.check(L.as_conv3x3_stem_wgrad(_lib.ptr(saved["planes_t"]), *strides, _lib.ptr(dmap), _lib.ptr(dwk), _lib.ptr(dbk), B, T, D,
+                                                   Cin, _lib.ptr(slab), slab.numel(), st), "as_conv3x3_stem_wgrad")
+                g["cnn.weight"], g["cnn.bias"] = taps_grad(dwk, Cin), dbk
+                if self.adapter is None and not need_dx:
+                    return None
+            dplanes = empty(*pshape)
             _lib.check(L.as_conv3x3_stem_bwd(_lib.ptr(dmap), _lib.ptr(w["stem"]), _lib.ptr(dplanes), *strides, B, T, D, Cin, st),
                        "as_conv3x3_stem_bwd")
             if self.adapter is None:
                 return dplanes
-            # adapter: LN0 -> Linear1 -> LN2 -> Linear3 over (B, C, T, D) rows; the gammas sit in the folded weights
+            # adapter: LN0 -> Linear1 -> LN2 -> Linear3 over (B, C, T, D) rows; for dx the gammas sit in the folded weights
+            ad = self.adapter.adapter
             xhat0, rstd0, xhat2, rstd2 = saved["adapter"]
             w1g_t, w3g_t = wb["adapter"]
+            if train:
+                a0, a2 = saved["adapter_in"]
+                g["adapter.adapter.3.weight"] = _wgrad(dplanes, a2, empty(D, D), g.setdefault("adapter.adapter.3.bias", empty(D)))
+                dz2 = _gemm(dplanes, ad[3].weight.t().contiguous(), None, empty(dplanes.shape[0], D))
+                _ln_param_grad(dz2, xhat2, ad[2], g, "adapter.adapter.2")
             dxhat2 = _gemm(dplanes, w3g_t, None, torch.empty_like(dplanes))
             dl1 = _ln_bwd(dxhat2, xhat2, rstd2, dxhat2)
-            dxhat0 = _gemm(dl1, w1g_t, None, torch.empty(dl1.shape[0], Din, device=dev, dtype=f32))
+            if train:
+                g["adapter.adapter.1.weight"] = _wgrad(dl1, a0, empty(D, Din), g.setdefault("adapter.adapter.1.bias", empty(D)))
+                dz0 = _gemm(dl1, ad[1].weight.t().contiguous(), None, empty(dl1.shape[0], Din))
+                _ln_param_grad(dz0, xhat0, ad[0], g, "adapter.adapter.0")
+                if not need_dx:
+                    return None
+            dxhat0 = _gemm(dl1, w1g_t, None, empty(dl1.shape[0], Din))
             drows = _ln_bwd(dxhat0, xhat0, rstd0, dxhat0)
             return drows.view(B, Cin, T, Din).transpose(2, 3)
 
@@ -445,6 +514,16 @@ def _ln_param_grad(dz, xhat, ln, grads, name):
     grads[name + ".weight"], grads[name + ".bias"] = dg, db
 
 
+def _ln_feat_param_grad(x, ln, dy, grads, name):
+    D = ln.weight.numel()
+    dg, db = torch.empty(D, device=x.device, dtype=torch.float32), torch.empty(D, device=x.device, dtype=torch.float32)
+    slab = _slab(x.device)
+    _lib.check(_lib.lib().as_ln_feat_gelu_param_grad(_lib.ptr(x), _lib.ptr(ln.weight), _lib.ptr(ln.bias), _lib.ptr(dy), x.numel() // (D * OUT_CHANNELS),
+                                                     D, OUT_CHANNELS, _lib.ptr(dg), _lib.ptr(db), _lib.ptr(slab), slab.numel(),
+                                                     _lib.stream_ptr()), "as_ln_feat_gelu_param_grad")
+    grads[name + ".weight"], grads[name + ".bias"] = dg, db
+
+
 class _ScorerTrain(torch.autograd.Function):
     """(x, voicing, *parameters) -> (logits, features) of TrainableDeepSpeech2, differentiable with respect to x and every
     parameter; drop: None or the forward's (p, seed)."""
@@ -463,7 +542,8 @@ class _ScorerTrain(torch.autograd.Function):
         names = [n for n, _ in ctx.model.named_parameters()]
         if dlogits is None and dfeatures is None:
             return (None, None, None, None) + (None,) * len(names)
-        dx, grads = ctx.model._train_grad(ctx.saved, dlogits, dfeatures, ctx.drop, ctx.needs_input_grad[0])
+        grads = {}
+        dx = ctx.model._backward(ctx.saved, dlogits, dfeatures, ctx.drop, grads, ctx.needs_input_grad[0])
         dx = dx.to(ctx.x_dtype) if dx is not None else None
         return (dx, None, None, None) + tuple(grads.get(n) for n in names)
 
@@ -473,9 +553,8 @@ class TrainableDeepSpeech2(DeepSpeech2):
     initialisation, so checkpoints load into either class.  ``forward(x, voicing=None, return_features=False)``:
 
     * with grad enabled and any parameter or x requiring grad it runs ``_ScorerTrain``, whose backward fills every parameter's
-      ``.grad`` (and x's): the walk of ``_input_grad`` with the parameter gradients added at every layer -- as_gemm_f32 for the
-      Linear / GRU weights and biases (dW_hh over h_{t-1}), as_conv3x3_c32_wgrad / as_conv3x3_stem_wgrad for the convolutions,
-      as_ln_feat_gelu_param_grad / as_layernorm_param_grad for the LayerNorms; otherwise ``_run``;
+      ``.grad`` (and x's): ``DeepSpeech2._backward``, the frozen scorer's walk, with the parameter gradients added at every
+      layer; otherwise ``_run``;
     * in ``train()`` mode -- with or without grad, as nn.Dropout -- the reference's dropout (deepspeech2.py:35, 43, 69, 190):
       after both GELUs of every ResidualCNN, after every RecurrentBlock's GRU, before the classifier (the returned features are
       not dropped).  Each forward draws one seed from torch's CPU generator (``int(torch.randint(0, 2**62, (1,)))``); site k
@@ -499,130 +578,3 @@ class TrainableDeepSpeech2(DeepSpeech2):
         else:
             logits, features = self._run(x, voicing, None, drop)
         return (logits, features) if return_features else logits
-
-    def _train_grad(self, saved, dlogits, dfeatures, drop, need_dx):
-        """d(logits, features) -> (dx or None, {parameter name: gradient}); dx is _input_grad's, bit for bit, without dropout."""
-        L, st = _lib.lib(), _lib.stream_ptr()
-        wb = self._prepare_bwd()
-        w = self._prepare()
-        B, Cin, Din, T = saved["shape"]
-        D, H, M = self.num_features, self.hidden, B * T
-        dev, f32 = saved["lengths"].device, torch.float32
-        nres, nrnn = len(self.residual_layers), len(self.recurrent_layers)
-        g = {}
-        empty = lambda *s: torch.empty(*s, device=dev, dtype=f32)
-        with torch.no_grad():
-            # logits = dropout(features) W_cls^T + b_cls; features = gelu(h W_fe^T + b_fe)
-            if dlogits is not None:
-                dl = dlogits.reshape(M, -1).float().contiguous()
-                g["classifier.weight"] = _wgrad(dl, saved["cls_in"], empty(self.num_classes, H), g.setdefault("classifier.bias", empty(self.num_classes)))
-                df = _gemm(dl, wb["classifier"], None, empty(M, H))
-                if drop:
-                    _dropout(df, drop, 2 * nres + nrnn)
-                if dfeatures is not None:
-                    dfc = dfeatures.reshape(M, H).float().contiguous()
-                    _lib.check(L.as_add(_lib.ptr(df), _lib.ptr(dfc), _lib.ptr(df), df.numel(), st), "as_add")
-            else:
-                df = dfeatures.reshape(M, H).float().contiguous().clone()
-            _gelu_bwd(df, saved["fe_pre"], None, df)
-            g["feature_extractor.0.weight"] = _wgrad(df, saved["fe_in"], empty(H, H), g.setdefault("feature_extractor.0.bias", empty(H)))
-            dh = _gemm(df, wb["fe"], None, empty(M, H))
-            # recurrent blocks: h_out = dropout(GRU(gelu(LN(h_in))))
-            dgi = empty(M, 3 * H)
-            dgh = torch.empty_like(dgi)
-            da = empty(M, H)
-            for j in reversed(range(nrnn)):
-                blk, w_ih_t = self.recurrent_layers[j], wb["w_ih"][j]
-                xhat, rstd, a, h_out, gates, ag = saved["rnn"][j]
-                pre = f"recurrent_layers.{j}."
-                if drop:
-                    _dropout(dh, drop, 2 * nres + j)
-                _lib.check(L.as_gru_unidir_bwd(_lib.ptr(dh), _lib.ptr(h_out), _lib.ptr(gates), _lib.ptr(blk.rnn.weight_hh_l0),
-                                               _lib.ptr(saved["lengths"]), B, T, H, _lib.ptr(dgi), _lib.ptr(dgh), st),
-                           "as_gru_unidir_bwd")
-                g[pre + "rnn.weight_ih_l0"] = _wgrad(dgi, ag, empty(3 * H, H), g.setdefault(pre + "rnn.bias_ih_l0", empty(3 * H)))
-                g[pre + "rnn.weight_hh_l0"] = _wgrad(dgh, h_out, empty(3 * H, H), g.setdefault(pre + "rnn.bias_hh_l0", empty(3 * H)),
-                                                     shift=T)
-                _gemm(dgi, w_ih_t, None, da)
-                _ln_param_grad(_gelu_bwd(da, a, None, empty(M, H)), xhat, blk.layer_norm, g, pre + "layer_norm")
-                _gelu_bwd(da, a, blk.layer_norm.weight, da)     # d xhat = d gelu-out * gelu'(a) * gamma
-                dh = _ln_bwd(da, xhat, rstd, torch.empty_like(da))
-            # Linear(32 D -> H) over the channels-last frame rows; its weight gradient back in the reference's column order c*D + d
-            dwl = _wgrad(dh, saved["lin_in"].view(M, D * OUT_CHANNELS), empty(H, D * OUT_CHANNELS), g.setdefault("linear.bias", empty(H)))
-            g["linear.weight"] = dwl.view(H, D, OUT_CHANNELS).permute(0, 2, 1).reshape(H, OUT_CHANNELS * D)
-            dmap = _gemm(dh, wb["linear"], None, empty(M, D * OUT_CHANNELS))
-            # residual blocks: out = conv2(drop(lngelu2(conv1(drop(lngelu1(in)))))) + in
-            dact, dmid = torch.empty_like(dmap), torch.empty_like(dmap)
-            zb = wb["zero_bias"]
-            slab = _slab(dev)
-            taps_grad = lambda dwk, cin: dwk.view(3, 3, OUT_CHANNELS, cin).permute(2, 3, 0, 1).contiguous()   # [kd][kt][co][ci] -> torch
-            for i in reversed(range(nres)):
-                r, (f1, f2), (fin, mid, act1, act2) = self.residual_layers[i], wb["res"][i], saved["res"][i]
-                pre = f"residual_layers.{i}."
-                dwk, dbk = empty(9, OUT_CHANNELS, OUT_CHANNELS), empty(OUT_CHANNELS)
-                _lib.check(L.as_conv3x3_c32_wgrad(_lib.ptr(act2), _lib.ptr(dmap), _lib.ptr(dwk), _lib.ptr(dbk), B, T, D, _lib.ptr(slab),
-                                                  slab.numel(), st), "as_conv3x3_c32_wgrad")
-                g[pre + "cnn2.weight"], g[pre + "cnn2.bias"] = taps_grad(dwk, OUT_CHANNELS), dbk
-                _lib.check(L.as_conv3x3_c32(_lib.ptr(dmap), _lib.ptr(f2), _lib.ptr(zb), None, _lib.ptr(dact), B, T, D, st),
-                           "as_conv3x3_c32")
-                if drop:
-                    _dropout(dact, drop, 2 * i + 1)
-                self._ln_feat_param_grad(mid, r.layer_norm2, dact, g, pre + "layer_norm2")
-                _lib.check(L.as_ln_feat_gelu_bwd(_lib.ptr(mid), _lib.ptr(r.layer_norm2.weight), _lib.ptr(r.layer_norm2.bias),
-                                                 _lib.ptr(dact), None, _lib.ptr(dmid), M, D, OUT_CHANNELS, st), "as_ln_feat_gelu_bwd")
-                dwk, dbk = empty(9, OUT_CHANNELS, OUT_CHANNELS), empty(OUT_CHANNELS)
-                _lib.check(L.as_conv3x3_c32_wgrad(_lib.ptr(act1), _lib.ptr(dmid), _lib.ptr(dwk), _lib.ptr(dbk), B, T, D, _lib.ptr(slab),
-                                                  slab.numel(), st), "as_conv3x3_c32_wgrad")
-                g[pre + "cnn1.weight"], g[pre + "cnn1.bias"] = taps_grad(dwk, OUT_CHANNELS), dbk
-                _lib.check(L.as_conv3x3_c32(_lib.ptr(dmid), _lib.ptr(f1), _lib.ptr(zb), None, _lib.ptr(dact), B, T, D, st),
-                           "as_conv3x3_c32")
-                if drop:
-                    _dropout(dact, drop, 2 * i)
-                self._ln_feat_param_grad(fin, r.layer_norm1, dact, g, pre + "layer_norm1")
-                nxt = torch.empty_like(dmap)
-                _lib.check(L.as_ln_feat_gelu_bwd(_lib.ptr(fin), _lib.ptr(r.layer_norm1.weight), _lib.ptr(r.layer_norm1.bias),
-                                                 _lib.ptr(dact), _lib.ptr(dmap), _lib.ptr(nxt), M, D, OUT_CHANNELS, st),
-                           "as_ln_feat_gelu_bwd")
-                dmap = nxt
-            # stem (voicing gets no gradient)
-            pshape, strides = saved["planes"]
-            planes = saved["planes_t"]
-            dwk, dbk = empty(9, OUT_CHANNELS, Cin), empty(OUT_CHANNELS)
-            _lib.check(L.as_conv3x3_stem_wgrad(_lib.ptr(planes), *strides, _lib.ptr(dmap), _lib.ptr(dwk), _lib.ptr(dbk), B, T, D, Cin,
-                                               _lib.ptr(slab), slab.numel(), st), "as_conv3x3_stem_wgrad")
-            g["cnn.weight"], g["cnn.bias"] = taps_grad(dwk, Cin), dbk
-            if self.adapter is None and not need_dx:
-                return None, g
-            dplanes = empty(*pshape)
-            _lib.check(L.as_conv3x3_stem_bwd(_lib.ptr(dmap), _lib.ptr(w["stem"]), _lib.ptr(dplanes), *strides, B, T, D, Cin, st),
-                       "as_conv3x3_stem_bwd")
-            if self.adapter is None:
-                return dplanes, g
-            # adapter: LN0 -> Linear1 -> LN2 -> Linear3 over (B, C, T, D) rows
-            ad = self.adapter.adapter
-            xhat0, rstd0, xhat2, rstd2 = saved["adapter"]
-            a0, a2 = saved["adapter_in"]
-            w1g_t, w3g_t = wb["adapter"]
-            rows = dplanes.view(-1, D)
-            g["adapter.adapter.3.weight"] = _wgrad(rows, a2, empty(D, D), g.setdefault("adapter.adapter.3.bias", empty(D)))
-            dz2 = _gemm(rows, ad[3].weight.t().contiguous(), None, empty(rows.shape[0], D))
-            _ln_param_grad(dz2, xhat2, ad[2], g, "adapter.adapter.2")
-            dxhat2 = _gemm(rows, w3g_t, None, torch.empty_like(rows))
-            dl1 = _ln_bwd(dxhat2, xhat2, rstd2, dxhat2)
-            g["adapter.adapter.1.weight"] = _wgrad(dl1, a0, empty(D, Din), g.setdefault("adapter.adapter.1.bias", empty(D)))
-            dz0 = _gemm(dl1, ad[1].weight.t().contiguous(), None, empty(dl1.shape[0], Din))
-            _ln_param_grad(dz0, xhat0, ad[0], g, "adapter.adapter.0")
-            if not need_dx:
-                return None, g
-            dxhat0 = _gemm(dl1, w1g_t, None, empty(dl1.shape[0], Din))
-            drows = _ln_bwd(dxhat0, xhat0, rstd0, dxhat0)
-            return drows.view(B, Cin, T, Din).transpose(2, 3), g
-
-    def _ln_feat_param_grad(self, x, ln, dy, grads, name):
-        D = self.num_features
-        dg, db = torch.empty(D, device=x.device, dtype=torch.float32), torch.empty(D, device=x.device, dtype=torch.float32)
-        slab = _slab(x.device)
-        _lib.check(_lib.lib().as_ln_feat_gelu_param_grad(_lib.ptr(x), _lib.ptr(ln.weight), _lib.ptr(ln.bias), _lib.ptr(dy), x.numel() // (D * OUT_CHANNELS),
-                                                         D, OUT_CHANNELS, _lib.ptr(dg), _lib.ptr(db), _lib.ptr(slab), slab.numel(),
-                                                         _lib.stream_ptr()), "as_ln_feat_gelu_param_grad")
-        grads[name + ".weight"], grads[name + ".bias"] = dg, db
