@@ -146,7 +146,12 @@ PROTOTYPES = {
     "as_ctc_loss": (_I32, [_P, _I64, _I64, _I32, _I32, _I32, _I32, _P, _I64, _P, _P, _I32, _I32, _I32, _P, _I64, _P, _P]),
     "as_ctc_grad": (_I32, [_P, _I64, _I64, _I32, _I32, _I32, _I32, _P, _I64, _P, _P, _I32, _I32, _P, _I64, _P, _P, _I32, _P, _I64,
                            _I64, _P]),
-    "as_intersect_semipolar_grid": (_I32, [_P, _P, _I64, _I32, _I32, _I32, _P, _P, _P, _P]),
+    "as_decode_top1": (_I32, [_P, _I64, _I64, _I32, _I32, _I32, _P, _I32, _P, _P, _P, _P]),
+    "as_edit_distance": (_I32, [_P, _I32, _P, _P, _I32, _P, _I32, _P, _I32, _P, _P]),
+    "as_align_workspace_bytes": (_I64, [_I32, _I32, _I32]),
+    "as_align_counts": (_I32, [_P, _I32, _P, _P, _I32, _P, _I32, _P, _I32, _I32, _P, _P, _P, _I64, _P]),
+    "as_confusion_counts": (_I32, [_P, _I32, _P, _I32, _P, _I32, _P, _I32, _I32, _P, _P]),
+    "as_intersect_semipolar_grid":(_I32, [_P, _P, _I64, _I32, _I32, _I32, _P, _P, _P, _P]),
     "as_artspeech_wait_head_grads": (_I32, [_P, _P]),
     "as_gather_pad_rows": (_I32, [_P, _P, _P, _I32, _I32, _I64, _I32, _D, _P, _P]),
     "as_lin_debug_stamps": (None, [_P, _I64]),

@@ -27,6 +27,7 @@ SOURCES = {
     "conv.hip": [],
     "scorer_wgrad.hip": [],
     "ctc.hip": [],
+    "recog_eval.hip": [],
     "attention.hip": [],
     "metrics.hip": ["-ffp-contract=off"],
     "multi_mlp.hip": [],

@@ -1,16 +1,42 @@
 """Phoneme recognition (reference ``phoneme_recognition``): the DeepSpeech2 scorer -- frozen (``DeepSpeech2``, the forward + top-1
 decoding that config 5 of BASELINE.json puts behind the phoneme-to-articulation models, with its input gradient) and trainable
 (``TrainableDeepSpeech2``) -- the CTC loss, the decoders, the edit-distance metric, the data sets and the training loop of
-train_phoneme_recognition.py (``run_epoch`` / ``run_test``, reference :63-153 and :156-...).  CTC only: the reference's CE
-criterion, the confusion / substitution matrices and their plots are not ported."""
+train_phoneme_recognition.py (``run_epoch`` / ``run_test``, reference :63-153 and :156-329), and the evaluation products of
+test_phoneme_recognition.py: the substitution matrix (``compute_substitution_matrix``, :470-526) and the frame-level confusion
+matrix (``compute_confusion_matrix``, :410-432), counted on the device (align.py) and normalised on the host in float64 as the
+reference does.  CTC only: the reference's CE criterion, the plots and the t-SNE feature plot are not ported."""
+import os
 from enum import Enum
 
 import numpy as np
 import torch
 
 from ..settings import BLANK, SIL, TRAIN, UNKNOWN  # noqa: F401
+from .align import align_counts, confusion_counts, decode_top1, edit_distance  # noqa: F401
 from .ctc import CTCLoss, ctc_loss
 from .deepspeech2 import DeepSpeech2, TrainableDeepSpeech2, top1_phonemes  # noqa: F401
+from .metrics import normalize_counts
+
+CLASSES_NAMES = {
+    0: "dental",
+    1: "labial",
+    2: "palatal",
+    3: "front vowels",
+    4: "back vowels",
+    5: "open vowels",
+    6: "rounded vowels",
+    7: "other",
+}
+
+PHONETIC_CLASSES = {
+    0: ["t", "d", "n", "l", "z", "s"],
+    1: ["p", "b", "m", "f", "v"],
+    2: ["k", "g", "Z", "S"],
+    3: ["i", "e", "E", "E/", "U~/", "j"],
+    4: ["u", "o", "O", "O/", "o~", "w"],
+    5: ["a", "a~"],
+    6: ["y", "2", "9", "H"],
+}
 
 
 class _CrossEntropyUnsupported:
@@ -83,13 +109,141 @@ def run_epoch(phase, epoch, model, dataloader, optimizer, criterion, normalize_o
     return info
 
 
-def run_test(model, dataloader, fn_metrics, target, feature=Feature.MELSPEC, use_voicing=False, device=None, criterion=None):
-    """The test pass of train_phoneme_recognition.py (reference run_test :156-...): eval-mode outputs, the metrics on their softmax
-    and, with a criterion, the loss on their log-softmax.  Returns {"loss": ..., metric: ...}."""
+def _groups_transposed(groups):
+    return {symbol: group for group, symbols in groups.items() for symbol in symbols}
+
+
+def _first_position(labels):
+    pos = {}
+    for k, label in enumerate(labels):
+        pos.setdefault(label, k)   # list.index: the first occurrence
+    return pos
+
+
+def _substitution_classes(vocabulary, groups):
+    """(class per token id 0 .. max id, number of classes) of the substitution matrix: without groups a token's class is its
+    position in list(vocabulary) (reference :483); with groups it is its group's position in list(groups) + [max(groups) + 1],
+    tokens outside every group falling into that last "other" class (:456, :486).  An id without a token gets -1."""
+    names = {i: token for token, i in vocabulary.items()}
+    if groups is None:
+        pos = _first_position(list(vocabulary))
+        token_class = lambda token: pos[token]   # noqa: E731
+        n = len(vocabulary)
+    else:
+        other = max(groups.keys()) + 1
+        pos = _first_position(list(groups.keys()) + [other])
+        groups_T = _groups_transposed(groups)
+        token_class = lambda token: pos[groups_T.get(token, other)]   # noqa: E731
+        n = len(groups) + 1
+    return [token_class(names[i]) if i in names else -1 for i in range(max(names) + 1)], n
+
+
+def _confusion_classes(vocabulary, groups):
+    """(class per token id 0 .. max id plus one last entry for every other id, sorted labels) of the confusion matrix: an id
+    without a token counts as UNKNOWN (reference :418-419); labels are the token names, or with groups the group numbers and
+    "other" = max(groups) + 1."""
+    names = {i: token for token, i in vocabulary.items()}
+    ids = list(range(max(names) + 1)) + [None]
+    tokens = [names.get(i, UNKNOWN) for i in ids]
+    if groups is not None:
+        other = max(groups.keys()) + 1
+        groups_T = _groups_transposed(groups)
+        tokens = [groups_T.get(token, other) for token in tokens]
+    labels = sorted(set(tokens))
+    pos = {label: k for k, label in enumerate(labels)}
+    return [pos[token] for token in tokens], labels
+
+
+def _pad(rows, value):
+    return torch.nn.utils.rnn.pad_sequence([torch.as_tensor(r) for r in rows], batch_first=True, padding_value=value)
+
+
+def substitution_counts(emissions, targets, input_lengths, target_lengths, decoder, class_map, n_classes, out=None):
+    """Decode on the device and add the batch's alignment counts to ``out`` ((n_classes + 1)-square int32 on the device; see
+    align.align_counts).  emissions: (B, T, C) on the device, or a list of per-utterance (T_b, C) tensors, each decoded over its
+    own rows (and no further than its input length when the decoder uses lengths); targets: (B, S) or a list of 1-D tensors."""
+    if not hasattr(decoder, "decode_device"):
+        raise TypeError("substitution_counts: the decoder has no decode_device (TopKDecoder and GreedyCTCDecoder have)")
+    if isinstance(emissions, (list, tuple)):
+        rows = torch.tensor([e.shape[0] for e in emissions], dtype=torch.int64)
+        if decoder.uses_lengths:
+            rows = torch.minimum(rows, torch.as_tensor([int(n) for n in input_lengths], dtype=torch.int64))
+        tokens, counts = decode_top1(_pad(emissions, 0.0), rows, decoder.blank_index)
+    else:
+        tokens, counts = decoder.decode_device(emissions, input_lengths)
+    if isinstance(targets, (list, tuple)):
+        targets = _pad(targets, -1)
+    target_lengths = torch.as_tensor([int(n) for n in target_lengths]).clamp(0, targets.shape[1])
+    return align_counts(tokens, counts, targets, target_lengths, n_classes, class_map, out)[0]
+
+
+def compute_substitution_matrix(emissions, targets, input_lengths, target_lengths, decoder, vocabulary, groups=None):
+    """The reference's compute_substitution_matrix (:470-526): substitution_matrix(decoded predictions, targets,
+    insertions_and_deletions="both", normalize="true") over the vocabulary's tokens or, with ``groups`` ({class: [tokens]}), over
+    the groups plus "other" = max(groups) + 1.  The counts are taken on the device (as_decode_top1 + as_align_counts); the row
+    normalisation and nan_to_num run on the host in float64.  Inputs as in ``substitution_counts``."""
+    class_map, n = _substitution_classes(vocabulary, groups)
+    counts = substitution_counts(emissions, targets, input_lengths, target_lengths, decoder, class_map, n)
+    return normalize_counts(counts.cpu().numpy(), "true")
+
+
+def _finish_confusion(counts, normalize):
+    """sklearn.metrics.confusion_matrix from the counts over every label: labels that occur neither as a target nor as a
+    prediction are dropped; normalize "true" / "pred" / "all" in float64 with NaN -> 0, else int64 counts."""
+    cm = np.asarray(counts, dtype=np.int64)
+    keep = (cm.sum(axis=0) + cm.sum(axis=1)) > 0
+    cm = cm[keep][:, keep]
+    return normalize_counts(cm, normalize) if normalize in ("true", "pred", "all") else cm
+
+
+def compute_confusion_matrix(predictions, targets, vocabulary, groups=None, normalize=None):
+    """The reference's compute_confusion_matrix (:410-432): sklearn's confusion_matrix of the per-frame target tokens (rows) and
+    predicted tokens (columns), labels sorted, or of their groups.  predictions, targets: flat per-frame token ids (device
+    tensors, or anything torch.as_tensor takes, which is uploaded); the counts are taken on the device (as_confusion_counts).
+
+    With ``groups`` the class of a token outside every group is ``max(groups) + 1``, as in the substitution matrix.  The
+    reference takes ``max`` over the symbol strings there, which scikit-learn rejects as soon as one token lies outside the
+    groups (labels of mixed type), so only the case in which every token is grouped can be compared with it."""
+    dev = predictions.device if torch.is_tensor(predictions) and predictions.is_cuda else torch.device("cuda", torch.cuda.current_device())
+    class_map, labels = _confusion_classes(vocabulary, groups)
+    n_ids = len(class_map) - 1
+
+    def ids(x):
+        x = torch.as_tensor(x).to(dev).reshape(1, -1).to(torch.int64)
+        return torch.where((x < 0) | (x >= n_ids), torch.full_like(x, n_ids), x)
+
+    predictions, targets = ids(predictions), ids(targets)
+    if predictions.shape != targets.shape:
+        raise ValueError(f"compute_confusion_matrix: {predictions.shape[1]} predictions but {targets.shape[1]} targets")
+    counts = confusion_counts(predictions, targets, None, len(labels), class_map)
+    return _finish_confusion(counts.cpu().numpy(), normalize)
+
+
+def run_test(model, dataloader, fn_metrics, target, feature=Feature.MELSPEC, use_voicing=False, device=None, criterion=None, *,
+             decoder=None, plot_target=None, save_dir=None, groups=PHONETIC_CLASSES):
+    """The test pass of train_phoneme_recognition.py / test_phoneme_recognition.py (reference run_test :156-329): eval-mode
+    outputs, the metrics on their softmax and, with a criterion, the loss on their log-softmax.  Returns {"loss": ..., metric: ...}.
+
+    With ``save_dir`` (and a ``decoder``) the counts of both matrices are accumulated on the device across the batches and
+    written as the reference writes them: ``substitution_matrix.npy`` (decoded predictions against ``target``, over ``groups``,
+    row-normalised) and, with a ``plot_target``, ``confusion_matrix.npy`` (the per-frame arg-max against ``plot_target``, frame by
+    frame, over ``groups``, normalize="true").  The plots are not ported."""
     if device is None:
         device = torch.device("cuda")
     model.eval()
     losses, metrics_values = [], {name: [] for name in fn_metrics}
+    sub_counts = conf_counts = None
+    if save_dir is not None:
+        if decoder is None:
+            raise ValueError("run_test: save_dir needs the decoder whose predictions the substitution matrix aligns")
+        vocabulary = dataloader.dataset.vocabulary
+        sub_map, n_sub = _substitution_classes(vocabulary, groups)
+        sub_map = torch.tensor(sub_map, dtype=torch.int32, device=device)
+        sub_counts = torch.zeros(n_sub + 1, n_sub + 1, dtype=torch.int32, device=device)
+        if plot_target is not None:
+            conf_map, conf_labels = _confusion_classes(vocabulary, groups)
+            conf_map = torch.tensor(conf_map[:-1], dtype=torch.int32, device=device)
+            conf_counts = torch.zeros(len(conf_labels), len(conf_labels), dtype=torch.int32, device=device)
     with torch.no_grad():
         for batch in dataloader:
             inputs = batch[feature.value].to(device)
@@ -103,6 +257,17 @@ def run_test(model, dataloader, fn_metrics, target, feature=Feature.MELSPEC, use
             norm_outputs = model.get_normalized_outputs(outputs)
             for name, fn_metric in fn_metrics.items():
                 metrics_values[name].append(float(fn_metric(norm_outputs, targets, input_lengths, target_lengths)))
+            if sub_counts is not None:
+                substitution_counts(norm_outputs, targets, input_lengths, target_lengths, decoder, sub_map, n_sub, sub_counts)
+            if conf_counts is not None:
+                plot_lengths = torch.minimum(torch.as_tensor(input_lengths), torch.as_tensor(batch[f"{plot_target.value}_length"]))
+                argmax = decode_top1(norm_outputs, plot_lengths, return_argmax=True)[2]
+                confusion_counts(argmax, batch[plot_target.value].to(device), plot_lengths, len(conf_labels), conf_map, conf_counts)
+    if sub_counts is not None:
+        os.makedirs(save_dir, exist_ok=True)
+        np.save(os.path.join(save_dir, "substitution_matrix.npy"), normalize_counts(sub_counts.cpu().numpy(), "true"))
+    if conf_counts is not None:
+        np.save(os.path.join(save_dir, "confusion_matrix.npy"), _finish_confusion(conf_counts.cpu().numpy(), "true"))
     info = {name: float(np.mean(v)) for name, v in metrics_values.items()}
     if criterion is not None:
         info["loss"] = float(np.mean(losses))

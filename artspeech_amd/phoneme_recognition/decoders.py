@@ -5,6 +5,9 @@
 * ``GreedyCTCDecoder``: best-path CTC decoding -- argmax per frame over the first ``lengths[b]`` frames, collapse repeats, drop
   blank.  It stands in for torchaudio's lexicon-free beam-search ``ctc_decoder``, which the reference uses for CTC and which this
   engine does not depend on.
+
+Both also have ``decode_device(emissions, lengths)``: the same decoding by the as_decode_top1 kernel, emissions and result on the
+device -- ``(tokens (B, T) int32 padded with -1, counts (B,) int32)`` -- which is what the metrics and the matrices consume.
 """
 from collections import namedtuple
 
@@ -27,6 +30,16 @@ class TopKDecoder:
         top = torch.topk(emissions, k=1, dim=-1).indices.squeeze(dim=-1)
         return [[Hypothesis(tokens=self.filter_blank(torch.unique_consecutive(t)))] for t in top]
 
+    uses_lengths = False   # like the reference's, it decodes every frame, padding included
+
+    @property
+    def blank_index(self):
+        return -1 if self.blank_token is None else int(self.blank_token)
+
+    def decode_device(self, emissions, lengths=None):
+        from .align import decode_top1
+        return decode_top1(emissions, None, self.blank_index)
+
 
 class GreedyCTCDecoder:
     """tokens: the vocabulary's token names in index order; blank_token: the blank's name (or index)."""
@@ -48,3 +61,13 @@ class GreedyCTCDecoder:
             seq = torch.unique_consecutive(seq)
             out.append([Hypothesis(tokens=seq[seq != self.blank])])
         return out
+
+    uses_lengths = True
+
+    @property
+    def blank_index(self):
+        return self.blank
+
+    def decode_device(self, emissions, lengths=None):
+        from .align import decode_top1
+        return decode_top1(emissions, lengths, self.blank)

@@ -567,6 +567,43 @@ int as_ctc_grad(const float* x, int64_t sx_t, int64_t sx_b, int32_t T, int32_t B
                 const float* ws, int64_t ws_floats, const float* nll, const float* scale, int32_t zero_infinity, float* grad, int64_t sg_t,
                 int64_t sg_b, void* stream);
 
+/* ---- evaluating the scorer (test_phoneme_recognition.py): decoding, edit distance, alignment, confusion counts -----------------
+ * Integer kernels (artspeech_amd/csrc/recog_eval.hip).  Token batches are int32 rows padded to a pitch (pred [B][P_max],
+ * target [B][L_max]) with int32 counts per row (clamped to [0, pitch]; entries past a count are never read).  class_map (int32
+ * [n_map], or NULL: identity) is applied to both sides before any comparison -- the reference's _make_tokenized_sequence
+ * (phoneme_recognition/__init__.py:435-467) ahead of substitution_matrix; a token outside [0, n_map) gets class -1.
+ *
+ * as_decode_top1: TopKDecoder.__call__ (decoders.py:36-42) and best-path CTC decoding.  emissions[b*s_b + t*s_t + c], class stride 1
+ *   (the (T, B, C) view of a tensor costs no copy); lengths int64 [B] on the device (clamped to [0, T]) or NULL: all T frames.  Per
+ *   frame the arg-max class in torch's order (a NaN is the maximum, the lowest index among equals); consecutive repeats of that
+ *   raw sequence collapse first, then `blank` is dropped (blank < 0: none), so "a _ a" keeps both a.  tokens [B][T] padded with
+ *   -1, counts [B]; argmax (optional, [B][T]): the raw per-frame arg-max, -1 past the length.  T <= 8192 (the row is staged in
+ *   LDS), else AS_ERR_UNSUPPORTED before any launch.
+ * as_edit_distance: torchmetrics' word_error_rate edit distance (metrics.py:135; insertions, deletions and substitutions cost 1)
+ *   of every pair, dist [B] int32; one wave per pair, the table row in registers.  P_max <= 4096, L_max <= 2047, else
+ *   AS_ERR_UNSUPPORTED before any launch.
+ * as_align_counts: substitution_matrix(..., insertions_and_deletions="both") counts (metrics.py:324-381) over the path of
+ *   compute_transitions (:295-321): from the corner, step to the predecessor with the smallest table entry, ties to the diagonal,
+ *   then to the previous prediction row, then to the previous target column.  ADDS into counts [(n_classes + 1)][(n_classes + 1)]
+ *   int32 (the caller zeroes it; integer atomics, so repeats are bit-identical): a diagonal move, match or not, to [target class]
+ *   [predicted class]; a move within one prediction row (a deletion) to [target class][n_classes]; a move within one target
+ *   column (an insertion) to [n_classes][predicted class]; a class outside [0, n_classes) takes part in the alignment but is not
+ *   counted.  Also writes dist [B].  The uint16 table lives in LDS when as_align_workspace_bytes(...) is 0, else in ws (that many
+ *   bytes; too small: AS_ERR_WORKSPACE).  The same size limits as as_edit_distance.
+ * as_confusion_counts: the counts of compute_confusion_matrix (__init__.py:410-432): for b < B and t < min(lengths[b], T, S)
+ *   (lengths int64 or NULL) ADDS 1 to counts[class(targets[b][t])][class(argmax[b][t])], counts [n][n] int32; frames whose
+ *   target or prediction class lies outside [0, n) (the -1 padding) are skipped.  argmax [B][T] (as_decode_top1's), targets [B][S]. */
+int as_decode_top1(const float* emissions, int64_t s_b, int64_t s_t, int32_t B, int32_t T, int32_t C, const int64_t* lengths,
+                   int32_t blank, int32_t* tokens, int32_t* counts, int32_t* argmax, void* stream);
+int as_edit_distance(const int32_t* pred, int32_t P_max, const int32_t* pred_counts, const int32_t* target, int32_t L_max,
+                     const int32_t* target_counts, int32_t B, const int32_t* class_map, int32_t n_map, int32_t* dist, void* stream);
+int64_t as_align_workspace_bytes(int32_t B, int32_t P_max, int32_t L_max);
+int as_align_counts(const int32_t* pred, int32_t P_max, const int32_t* pred_counts, const int32_t* target, int32_t L_max,
+                    const int32_t* target_counts, int32_t B, const int32_t* class_map, int32_t n_map, int32_t n_classes, int32_t* counts,
+                    int32_t* dist, void* ws, int64_t ws_bytes, void* stream);
+int as_confusion_counts(const int32_t* argmax, int32_t T, const int32_t* targets, int32_t S, const int64_t* lengths, int32_t B,
+                        const int32_t* class_map, int32_t n_map, int32_t n, int32_t* counts, void* stream);
+
 /* intersect_semipolar_grid (area_function.py:175-223), float64, batched over frames: air_column [frames][2 walls][2][n_pts]
  * (internal wall first, x row then y row -- the air-column file layout), grid [n_lines][grid_res][2].  For every frame and
  * grid line: flags bit 0 / 1 = the internal / external wall is crossed (0: the reference skips the line), bit 2 = more than

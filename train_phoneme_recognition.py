@@ -9,7 +9,8 @@
 # `results_dir`.  TrainableDeepSpeech2 + the engine's CTCLoss(**loss_params), Adam(lr, weight_decay) and
 # CyclicLR(lr / 25, lr, cycle_momentum=False) stepped per batch; early stopping on the validation edit
 # distance (greedy CTC decoding); best_model.pt, last_model.pt and checkpoint.pt like the reference, then
-# a test-split pass of the best model written to info_test.json.  CTC only (`loss: CE` raises).
+# a test-split pass of the best model written to info_test.json, with substitution_matrix.npy and (given `plot_target`)
+# confusion_matrix.npy beside it.  CTC only (`loss: CE` raises).
 #
 ####################################################################################################
 import argparse
@@ -89,6 +90,7 @@ def main(database_name, datadir, num_epochs, batch_size, patience, learning_rate
 
     feature = Feature(feature)
     target = Target(target)
+    plot_target = Target(plot_target) if plot_target is not None else None
     if pretrained:
         raise NotImplementedError("train_phoneme_recognition: pretrained (the LibriSpeech checkpoint) is not supported")
     vocabulary = build_vocabulary(vocab_filepath, criterion)
@@ -163,13 +165,14 @@ def main(database_name, datadir, num_epochs, batch_size, patience, learning_rate
         if epochs_since_best > patience:
             break
 
-    # test split: the best model (the reference's plots and confusion / substitution matrices are not part of this engine)
+    # test split: the best model, with the substitution matrix and (given a plot_target) the frame-level confusion matrix written
+    # to results_dir as the reference's closing run_test does (its plots are not part of this engine)
     test_dataloader = loader(test_seq_dict, seed + 2)
     best_model = TrainableDeepSpeech2(num_classes=len(vocabulary), **model_params)
     best_model.load_state_dict(torch.load(best_model_path if os.path.exists(best_model_path) else last_model_path, map_location="cpu"))
     best_model.to(device)
     info_test = run_test(best_model, test_dataloader, metrics, target, feature=feature, use_voicing=use_voicing, device=device,
-                         criterion=loss_fn)
+                         criterion=loss_fn, decoder=decoder, plot_target=plot_target, save_dir=results_dir)
     with open(os.path.join(results_dir, "info_test.json"), "w") as f:
         json.dump(info_test, f, indent=2)
     _mlflow("log_metrics", {f"test_{m}": v for m, v in info_test.items()}, step=0)
