@@ -13,7 +13,8 @@ LIB = os.path.join(HERE, "libartspeech_hip.so")
 ARCH = "gfx950"
 COMMON = ["-O3", "-fPIC", "-std=c++17", f"-I{os.path.join(ROOT, 'include')}", f"-I{CSRC}"]
 # per-file extra flags: metrics.hip keeps IEEE op-by-op arithmetic (arg-min pairs and the fp64 area
-# function must be bit-reproducible), so no fused multiply-add contraction there.
+# function must be bit-reproducible), so no fused multiply-add contraction there; pc_eval.hip likewise (its denormalisation
+# is torch's multiply, then add).
 SOURCES = {
     "error.cpp": [],
     "prof.hip": [],
@@ -33,6 +34,7 @@ SOURCES = {
     "multi_mlp.hip": [],
     "pca.hip": [],
     "mean_contour.hip": [],
+    "pc_eval.hip": ["-ffp-contract=off"],
     "artspeech.hip": [],
 }
 

@@ -89,6 +89,25 @@ __device__ __forceinline__ float as_wave_sum_dpp(float v) {
     return (a + b) + (c + d);
 }
 
+// ---- closest-point scan (MeanP2CPDistance: metrics.hip, pc_eval.hip)
+// min_j |p - q_j|^2 over the n points (qx, qy) in LDS (padded to a multiple of 4 with +inf coordinates): four points per
+// step from two broadcast ds_read_b128, the arithmetic on float pairs (v_pk_add / v_pk_mul: half the instructions of the
+// scalar form), v_min3 to fold two candidates at once.  The kernel lives on vector-instruction issue (50 x 50 pair
+// distances twice per 800-byte tile), not on HBM: ~3.5 instructions per pair instead of ~8.
+__device__ __forceinline__ float as_p2cp_scan(float px, float py, const float* __restrict__ qx, const float* __restrict__ qy, int n4) {
+    const f32x2 px2 = {px, px}, py2 = {py, py};
+    float m = INFINITY;
+    for (int j = 0; j < n4; j += 4) {
+        const float4 x4 = *reinterpret_cast<const float4*>(qx + j), y4 = *reinterpret_cast<const float4*>(qy + j);
+        const f32x2 dxa = px2 - f32x2{x4.x, x4.y}, dxb = px2 - f32x2{x4.z, x4.w};
+        const f32x2 dya = py2 - f32x2{y4.x, y4.y}, dyb = py2 - f32x2{y4.z, y4.w};
+        const f32x2 sa = dxa * dxa + dya * dya, sb = dxb * dxb + dyb * dyb;
+        m = fminf(fminf(m, sa.x), sa.y);
+        m = fminf(fminf(m, sb.x), sb.y);
+    }
+    return m;
+}
+
 // ---- exact (erf) GELU and d gelu / dx = Phi(x) + x phi(x)
 __device__ __forceinline__ float as_gelu(float x) { return 0.5f * x * (1.0f + erff(x * 0.70710678118654752440f)); }
 __device__ __forceinline__ float as_gelu_grad(float x) {

@@ -92,24 +92,6 @@ __global__ __launch_bounds__(256) void loss_final_kernel(const float* __restrict
 // lane j scans all u for v_j (column minima).  min over squared distances, sqrt once (monotone).
 constexpr int P2CP_MAXPTS = 256;
 
-// min_j |p - q_j|^2 over the n points (qx, qy) in LDS (padded to a multiple of 4 with +inf coordinates): four points per
-// step from two broadcast ds_read_b128, the arithmetic on float pairs (v_pk_add / v_pk_mul: half the instructions of the
-// scalar form), v_min3 to fold two candidates at once.  The kernel lives on vector-instruction issue (50 x 50 pair
-// distances twice per 800-byte tile), not on HBM: ~3.5 instructions per pair instead of ~8.
-__device__ __forceinline__ float p2cp_scan(float px, float py, const float* __restrict__ qx, const float* __restrict__ qy, int n4) {
-    const f32x2 px2 = {px, px}, py2 = {py, py};
-    float m = INFINITY;
-    for (int j = 0; j < n4; j += 4) {
-        const float4 x4 = *reinterpret_cast<const float4*>(qx + j), y4 = *reinterpret_cast<const float4*>(qy + j);
-        const f32x2 dxa = px2 - f32x2{x4.x, x4.y}, dxb = px2 - f32x2{x4.z, x4.w};
-        const f32x2 dya = py2 - f32x2{y4.x, y4.y}, dyb = py2 - f32x2{y4.z, y4.w};
-        const f32x2 sa = dxa * dxa + dya * dya, sb = dxb * dxb + dyb * dyb;
-        m = fminf(fminf(m, sa.x), sa.y);
-        m = fminf(fminf(m, sb.x), sb.y);
-    }
-    return m;
-}
-
 __global__ __launch_bounds__(256) void p2cp_kernel(const float* __restrict__ u, long u_tile, long u_pt, long u_xy, int nu,
                                                    const float* __restrict__ v, long v_tile, long v_pt, long v_xy, int nv,
                                                    long tiles, float* __restrict__ out) {
@@ -130,8 +112,8 @@ __global__ __launch_bounds__(256) void p2cp_kernel(const float* __restrict__ u, 
     __syncthreads();
     if (tile >= tiles) return;
     float su = 0.f, sv = 0.f;
-    for (int i = lane; i < nu; i += 64) su += sqrtf(p2cp_scan(ux[i], uy[i], vx, vy, nv4));   // row minima
-    for (int j = lane; j < nv; j += 64) sv += sqrtf(p2cp_scan(vx[j], vy[j], ux, uy, nu4));   // column minima
+    for (int i = lane; i < nu; i += 64) su += sqrtf(as_p2cp_scan(ux[i], uy[i], vx, vy, nv4));   // row minima
+    for (int j = lane; j < nv; j += 64) sv += sqrtf(as_p2cp_scan(vx[j], vy[j], ux, uy, nu4));   // column minima
     su = as_wave_sum(su);
     sv = as_wave_sum(sv);
     if (lane == 0) out[tile] = (su / nu + sv / nv) * 0.5f;

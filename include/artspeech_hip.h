@@ -752,6 +752,35 @@ int32_t as_masked_mse_partials(void);
 int as_masked_mse_fwd_bwd(const float* a, const float* b, int64_t rows, int64_t feat, const int32_t* lengths, int32_t T,
                           const float* row_weights, float scale, float* loss, float* grad, float* partial, void* stream);
 
+/* Evaluation of the principal-components method on the device (artspeech_amd/csrc/pc_eval.hip; reference
+ * phoneme_to_articulation/principal_components/evaluation.py and test_principal_components_autoencoder.py).  Rows are frames:
+ * rows = B * T with `lengths` (int32 [B], row b * T + t is valid iff t < lengths[b]; rows % T == 0), every row valid without.
+ *
+ * as_pc_shapes_eval: one launch for the per-articulator denormalise loops (evaluation.py:373-380,
+ * test_principal_components_autoencoder.py:156-160), the upper-incisor injection (evaluation.py:386-400) and the
+ * MeanP2CPDistance in mm (test_principal_components_autoencoder.py:166-169).
+ *   shapes  [rows][A][2 N]  normalised predictions (the MultiDecoder output);  targets [rows][A][2][N] normalised
+ *   mean, std [A][2][N]     the per-articulator Normalize statistics
+ *   reference [rows][1][2][N] with ref_idx in [0, A]: copied in at channel ref_idx of both outputs; ref_idx = -1: none
+ *   pred_out, tgt_out [rows][A + (ref_idx >= 0)][2][N]: x * std + mean, each operation rounded (bit-equal to the torch expression)
+ *   p2cp_mm [rows][A]: the mean point-to-closest-point distance of the denormalised pair (direct differences) times to_mm
+ * Each output may be NULL; invalid rows are written as zeros.  One wave per (row, articulator), the tile staged in LDS once.
+ * Limit: N <= 128 (AS_ERR_UNSUPPORTED before any launch beyond). */
+int as_pc_shapes_eval(const float* shapes, const float* targets, const float* mean, const float* std, const int32_t* lengths,
+                      int32_t T, const float* reference, int32_t ref_idx, int64_t rows, int32_t A, int32_t N, float to_mm,
+                      float* pred_out, float* tgt_out, float* p2cp_mm, void* stream);
+/* Running statistics of a split in device-resident fp64 states that the call updates (no host read per batch); a zero-filled
+ * state is the empty one.  Replaces the growing torch.concat + torch.cov of evaluation.py:208-249 and the pandas agg of
+ * test_principal_components_autoencoder.py:190-193.
+ *   err_state [5][A] = count | mean | M2 (centred sum of squares) | min | max of p2cp_mm [rows][A] over the valid rows
+ *   lat_state [1 + L + L L] = count | mean [L] | centred co-moments [L][L] of latents [rows][L] over the valid rows
+ * Either half may be absent (p2cp_mm / latents NULL).  A batch is reduced in two passes (mean, then centred sums) and merged by
+ * Chan's update; everything after the fp32 loads is fp64, every sum has a fixed order that does not depend on the launch
+ * geometry: repeats are bit-identical.  cov = M2 / (n - 1) is torch.cov of the concatenated latents; sqrt(M2 / (n - 1)) is
+ * pandas' std.  Limit: L <= 64 (AS_ERR_UNSUPPORTED before any launch beyond). */
+int as_pc_eval_accumulate(const float* p2cp_mm, int32_t A, double* err_state, const float* latents, int32_t L, double* lat_state,
+                          int64_t rows, const int32_t* lengths, int32_t T, void* stream);
+
 /* Optional per-kernel-phase timing with HIP events recorded on the launch stream (for bench.py's
  * roofline object).  as_profile_report writes "name count total_ms\n" lines (NUL terminated, truncated
  * to buflen) and returns the untruncated length; it waits for the recorded events to complete. */

@@ -8,7 +8,7 @@
 # (SyntheticPrincipalComponentsPhonemeToArticulationDataset, sized by `synthetic:` and the sequence dicts'
 # `num_sentences`) and `results_dir`.  The frozen encoder / decoder come from train_principal_components_autoencoder.py
 # (best_encoders.pt / best_decoders.pt).  Writes best_model.pt, last_model.pt and checkpoint.pt like the reference and
-# ends with a test-split pass of run_epoch (loss + p2cp_mean).
+# ends with run_phoneme_to_principal_components_test on the test split (loss + p2cp_mean).
 #
 ####################################################################################################
 import argparse
@@ -34,11 +34,12 @@ from artspeech_amd.phoneme_to_articulation.principal_components.dataset import (
     SyntheticPrincipalComponentsPhonemeToArticulationDataset,
     pad_sequence_collate_fn,
 )
+from artspeech_amd.phoneme_to_articulation.principal_components.evaluation import run_phoneme_to_principal_components_test
 from artspeech_amd.phoneme_to_articulation.principal_components.losses import AutoencoderLoss2
 from artspeech_amd.phoneme_to_articulation.principal_components.metrics import DecoderMeanP2CPDistance2
 from artspeech_amd.phoneme_to_articulation.principal_components.models import (DecoderType, EncoderType,
                                                                                PrincipalComponentsArtSpeech)
-from artspeech_amd.settings import BLANK, DATASET_CONFIG, TEST, TRAIN, UNKNOWN, VALID
+from artspeech_amd.settings import BLANK, DATASET_CONFIG, TRAIN, UNKNOWN, VALID
 
 try:  # mlflow is optional here (absent from the MI355X image): same flags, no-op logging
     import mlflow
@@ -222,15 +223,14 @@ def main(database_name, datadir, num_epochs, batch_size, patience, learning_rate
         if epochs_since_best > patience:
             break
 
-    # test split: the best model through run_epoch (the reference's plotting harness,
-    # run_phoneme_to_principal_components_test, is not part of this engine)
+    # test split: the best model through the test harness, as the reference does (:455), without the per-sentence dumps
     _, test_dataloader = loader(test_seq_dict, False, seed + 2)
     best_model = PrincipalComponentsArtSpeech(vocab_size=len(vocabulary), indices_dict=indices_dict,
                                               rnn=RNNType[rnn_type.upper()], **modelkwargs)
     best_model.load_state_dict(torch.load(best_model_path, map_location=device))
     best_model.to(device)
-    info_test = run_epoch(phase=TEST, epoch=0, model=best_model, dataloader=test_dataloader, optimizer=optimizer,
-                          criterion=loss_fn, device=device, fn_metrics=fn_metrics)
+    info_test = run_phoneme_to_principal_components_test(epoch=0, model=best_model, dataloader=test_dataloader, criterion=loss_fn,
+                                                         fn_metrics=fn_metrics, device=device)
     _mlflow("log_metrics", {f"test_{m}": v for m, v in info_test.items()}, step=0)
     return {"history": history, "test": info_test, "results_dir": results_dir}
 

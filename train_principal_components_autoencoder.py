@@ -7,7 +7,7 @@
 # The YAML keys are the keyword arguments of main() (the reference's), plus the extras `datadir: synthetic`
 # (SyntheticPrincipalComponentsAutoencoderDataset, sized by `synthetic:` and the sequence dicts' `num_frames`)
 # and `results_dir`.  Writes best_encoders.pt / best_decoders.pt, last_encoders.pt / last_decoders.pt and
-# checkpoint.pt like the reference, and ends with a test-split pass of the epoch loop (loss + p2cp_mm).
+# checkpoint.pt like the reference, and ends with run_multiart_autoencoder_test on the test split (loss + p2cp_mm).
 #
 ####################################################################################################
 import argparse
@@ -27,13 +27,14 @@ from torch.utils.data import DataLoader
 from artspeech_amd.helpers import make_indices_dict, sequences_from_dict, set_seeds
 from artspeech_amd.phoneme_to_articulation.metrics import MeanP2CPDistance
 from artspeech_amd.phoneme_to_articulation.principal_components import run_autoencoder_epoch
+from artspeech_amd.phoneme_to_articulation.principal_components.evaluation import run_multiart_autoencoder_test
 from artspeech_amd.phoneme_to_articulation.principal_components.dataset import (
     PrincipalComponentsAutoencoderDataset2,
     SyntheticPrincipalComponentsAutoencoderDataset,
 )
 from artspeech_amd.phoneme_to_articulation.principal_components.losses import RegularizedLatentsMSELoss2
 from artspeech_amd.phoneme_to_articulation.principal_components.models.autoencoder import MultiArticulatorAutoencoder
-from artspeech_amd.settings import DATASET_CONFIG, TEST, TRAIN, VALID
+from artspeech_amd.settings import DATASET_CONFIG, TRAIN, VALID
 
 try:  # mlflow is optional here (absent from the MI355X image): same flags, no-op logging
     import mlflow
@@ -168,15 +169,16 @@ def main(database_name, datadir, n_epochs, batch_size, patience, learning_rate, 
         if epochs_since_best > patience:
             break
 
-    # test split: the best encoders / decoders through the same epoch loop (the reference's plotting harness,
-    # run_multiart_autoencoder_test, is not part of this engine)
+    # test split: the best encoders / decoders through the test harness, as the reference does (:298): the
+    # latent covariance per articulator goes to results_dir
     _, test_dataloader = loader(test_seq_dict, False, seed + 2)
     best_autoencoder = MultiArticulatorAutoencoder(**model_params)
     best_autoencoder.encoders.load_state_dict(torch.load(best_encoders_path, map_location=device))
     best_autoencoder.decoders.load_state_dict(torch.load(best_decoders_path, map_location=device))
     best_autoencoder.to(device)
-    info_test = run_autoencoder_epoch(phase=TEST, epoch=0, model=best_autoencoder, dataloader=test_dataloader,
-                                      optimizer=optimizer, criterion=loss_fn, fn_metrics=metrics, device=device)
+    info_test = run_multiart_autoencoder_test(epoch=0, model=best_autoencoder, dataloader=test_dataloader, criterion=loss_fn,
+                                              dataset_config=dataset_config, plots_dir=results_dir, indices_dict=indices_dict,
+                                              fn_metrics=metrics, device=device)
     _mlflow("log_metrics", {f"test_{m}": v for m, v in info_test.items()}, step=0)
     return {"history": history, "test": info_test, "results_dir": results_dir}
 
