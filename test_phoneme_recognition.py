@@ -17,7 +17,6 @@ import argparse
 import json
 import logging
 import os
-import shutil
 from functools import partial
 
 import torch
@@ -29,7 +28,8 @@ from artspeech_amd.phoneme_recognition import BLANK, SIL, UNKNOWN, Criterion, De
 from artspeech_amd.phoneme_recognition.datasets import collate_fn
 from artspeech_amd.phoneme_recognition.decoders import GreedyCTCDecoder
 from artspeech_amd.phoneme_recognition.metrics import EditDistance, WordInfoLost
-from train_phoneme_recognition import TMP_DIR, _make_dataset, build_vocabulary
+from artspeech_amd.training import load_json
+from train_phoneme_recognition import _make_dataset, build_vocabulary
 
 
 def main(database_name, datadir, batch_size, seq_dict, vocab_filepath, pretrained, feature, loss, model_params, target,
@@ -46,10 +46,7 @@ def main(database_name, datadir, batch_size, seq_dict, vocab_filepath, pretraine
     plot_target = Target(plot_target) if plot_target else None
 
     vocabulary = build_vocabulary(vocab_filepath, criterion)
-    voiced_tokens = None
-    if voicing_filepath is not None:
-        with open(voicing_filepath) as f:
-            voiced_tokens = json.load(f)
+    voiced_tokens = load_json(voicing_filepath)
     tokens = [k for k, _ in sorted(vocabulary.items(), key=lambda t: t[1])]
     decoder = GreedyCTCDecoder(tokens=tokens, sil_token=SIL, blank_token=BLANK, unk_word=UNKNOWN)
 
@@ -76,7 +73,4 @@ if __name__ == "__main__":
     args = parser.parse_args()
     with open(args.config_filepath) as f:
         cfg = yaml.safe_load(f)
-    try:
-        print(json.dumps(main(**cfg), indent=2))
-    finally:
-        shutil.rmtree(TMP_DIR, ignore_errors=True)   # the trainer module's scratch directory, made on import
+    print(json.dumps(main(**cfg), indent=2))

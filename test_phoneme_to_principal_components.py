@@ -13,7 +13,6 @@
 import argparse
 import json
 import os
-import shutil
 
 import torch
 import yaml
@@ -27,10 +26,8 @@ from artspeech_amd.phoneme_to_articulation.principal_components.evaluation impor
 from artspeech_amd.phoneme_to_articulation.principal_components.losses import AutoencoderLoss2
 from artspeech_amd.phoneme_to_articulation.principal_components.models import (DecoderType, EncoderType,
                                                                                PrincipalComponentsArtSpeech)
-import train_phoneme_to_principal_components as _trainer
+from artspeech_amd.training import load_json
 from train_phoneme_to_principal_components import _make_dataset, build_vocabulary
-
-shutil.rmtree(_trainer.TMP_DIR, ignore_errors=True)   # the trainer's scratch directory, made at import: not used here
 
 
 def main(database_name, datadir, batch_size, seq_dict, indices_dict, vocab_filepath, state_dict_filepath, modelkwargs,
@@ -39,10 +36,7 @@ def main(database_name, datadir, batch_size, seq_dict, indices_dict, vocab_filep
          TV_to_phoneme_map=None, clip_tails=True, encoder_type="AE", decoder_type="AE", synthetic=None, seed=0):
     device = torch.device("cuda", torch.cuda.current_device())
     vocabulary = build_vocabulary(vocab_filepath)
-    voiced_tokens = None
-    if voicing_filepath is not None:
-        with open(voicing_filepath) as f:
-            voiced_tokens = json.load(f)
+    voiced_tokens = load_json(voicing_filepath)
     if isinstance(list(indices_dict.values())[0], int):
         indices_dict = make_indices_dict(indices_dict)
     articulators = sorted(indices_dict.keys())

@@ -14,7 +14,6 @@ import argparse
 import csv
 import json
 import os
-import shutil
 
 import numpy as np
 import torch
@@ -28,10 +27,7 @@ from artspeech_amd.phoneme_to_articulation.principal_components.evaluation impor
 from artspeech_amd.phoneme_to_articulation.principal_components.losses import RegularizedLatentsMSELoss2
 from artspeech_amd.phoneme_to_articulation.principal_components.models.autoencoder import MultiArticulatorAutoencoder
 from artspeech_amd.settings import DATASET_CONFIG
-import train_principal_components_autoencoder as _trainer
 from train_principal_components_autoencoder import _make_dataset
-
-shutil.rmtree(_trainer.TMP_DIR, ignore_errors=True)   # the trainer's scratch directory, made at import: not used here
 
 
 def _resolve_indices(model_params):

@@ -693,3 +693,49 @@ def test_rccl_single_rank_engine_is_bit_identical(dev):
     r = subprocess.run([sys.executable, worker], capture_output=True, text=True, timeout=240)
     assert r.returncode == 0 and "rccl single rank ok" in r.stdout, (r.returncode, r.stdout[-2000:], r.stderr[-4000:])
 
+
+
+CHECKPOINT_KEYS = {"epoch", "model", "optimizer", "scheduler", "best_metric", "epochs_since_best", "best_model_path", "last_model_path"}
+
+
+def _main_then_resume(trainer, cfg, tmp_path):
+    """main() for two epochs (two batches each, ragged lengths), its files and checkpoint, then a resume to a third epoch."""
+    first = trainer.main(**cfg)
+    for f in ("best_model.pt", "last_model.pt", "checkpoint.pt"):
+        assert os.path.exists(tmp_path / f), f
+    ckpt = torch.load(tmp_path / "checkpoint.pt")
+    assert set(ckpt) == CHECKPOINT_KEYS and ckpt["epoch"] == 2
+    assert np.isfinite(ckpt["best_metric"]) and ckpt["epochs_since_best"] in (0, 1)
+    assert ckpt["best_model_path"] == str(tmp_path / "best_model.pt") and ckpt["last_model_path"] == str(tmp_path / "last_model.pt")
+    assert set(ckpt["model"]) == set(torch.load(tmp_path / "last_model.pt"))
+    trainer.main(**dict(cfg, num_epochs=3), checkpoint_filepath=str(tmp_path / "checkpoint.pt"))
+    resumed = torch.load(tmp_path / "checkpoint.pt")
+    assert set(resumed) == CHECKPOINT_KEYS and resumed["epoch"] == 3
+    assert resumed["best_metric"] <= ckpt["best_metric"]
+    return first
+
+
+def test_trainer_main_writes_its_files_and_resumes(dev, tmp_path):
+    import json
+    import yaml
+    import train_phoneme_to_articulation as tr
+    with open(os.path.join(ROOT, "configs", "train_synthetic.yaml")) as f:
+        cfg = yaml.safe_load(f)
+    cfg.update(num_epochs=2, batch_size=3, train_seq_dict={"num_sentences": 6}, valid_seq_dict={"num_sentences": 3},
+               test_seq_dict={"num_sentences": 3}, synthetic={"min_len": 5, "max_len": 12}, results_dir=str(tmp_path))
+    res = _main_then_resume(tr, cfg, tmp_path)
+    with open(tmp_path / "test_results.json") as f:
+        assert json.load(f)["loss"] == pytest.approx(res["loss"])
+    assert np.isfinite(res["loss"]) and set(res) == {"loss", *cfg["articulators"]}
+
+
+def test_transformer_trainer_main_writes_its_files_and_resumes(dev, tmp_path):
+    import yaml
+    import train_phoneme_to_articulation_transformer as tr
+    with open(os.path.join(ROOT, "configs", "train_transformer_synthetic.yaml")) as f:
+        cfg = yaml.safe_load(f)
+    cfg.update(num_epochs=2, batch_size=2, train_seq_dict={"num_sentences": 4}, valid_seq_dict={"num_sentences": 2},
+               test_seq_dict={"num_sentences": 2}, synthetic={"min_len": 4, "max_len": 6}, results_dir=str(tmp_path),
+               model_kwargs={"embed_dim": 32, "num_heads": 4, "num_layers": 1, "num_feat": 100})
+    res = _main_then_resume(tr, cfg, tmp_path)
+    assert set(res) == {"best_p2cp_mean"} and np.isfinite(res["best_p2cp_mean"])

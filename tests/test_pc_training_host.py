@@ -120,19 +120,20 @@ def test_collate_matches_reference_fixture():
 
 
 def _script_signature(path):
-    """main()'s keyword names / defaults and the argparse flags (option, dest, default) of a training script."""
+    """main()'s keyword names / defaults and the argparse flags (option, dest, default) of a training script: the flags of
+    the parser its `run_cli(main, experiment)` call builds (artspeech_amd/training.py)."""
     import ast
+    from artspeech_amd.training import cli_parser
     tree = ast.parse(open(path).read())
     main = next(n for n in tree.body if isinstance(n, ast.FunctionDef) and n.name == "main")
     names = [a.arg for a in main.args.args]
     defaults = [ast.literal_eval(d) for d in main.args.defaults]
     keys = {n: None for n in names}
     keys.update(dict(zip(names[len(names) - len(defaults):], defaults)))
-    flags = []
-    for node in ast.walk(tree):
-        if isinstance(node, ast.Call) and getattr(node.func, "attr", "") == "add_argument":
-            kw = {k.arg: ast.literal_eval(k.value) for k in node.keywords}
-            flags.append([node.args[0].value, kw.get("dest"), kw.get("default")])
+    call, = [n for n in ast.walk(tree) if isinstance(n, ast.Call) and getattr(n.func, "id", "") == "run_cli"]
+    assert call.args[0].id == "main" and not call.keywords
+    parser = cli_parser(*(ast.literal_eval(a) for a in call.args[1:]))
+    flags = [[a.option_strings[0], a.dest, a.default] for a in parser._actions if a.option_strings[0] != "-h"]
     return keys, flags
 
 

@@ -12,17 +12,12 @@
 # sklearn objects (<articulator>_pca.pkl) have no counterpart here.
 #
 ####################################################################################################
-import argparse
 import csv
 import logging
 import os
-import random
-import shutil
-import tempfile
 
 import numpy as np
 import torch
-import yaml
 from torch.utils.data import DataLoader
 
 from artspeech_amd.helpers import sequences_from_dict
@@ -33,23 +28,12 @@ from artspeech_amd.phoneme_to_articulation.principal_components.dataset import (
 )
 from artspeech_amd.phoneme_to_articulation.principal_components.pca import MultiArticulatorPCA
 from artspeech_amd.settings import DATASET_CONFIG
-
-try:  # mlflow is optional here (absent from the MI355X image): same flags, no-op logging
-    import mlflow
-except ImportError:
-    mlflow = None
-
-
-def _mlflow(fn, *args, **kwargs):
-    if mlflow is not None:
-        return getattr(mlflow, fn)(*args, **kwargs)
+from artspeech_amd.training import mlflow_call, results_paths, run_cli, synthetic_size
 
 
 def _make_dataset(datadir, database_name, seq_dict, articulators, clip_tails, synthetic, seed):
     if datadir == "synthetic":
-        cfg = dict(synthetic or {})
-        n = (seq_dict or {}).get("num_frames", cfg.pop("num_frames", 256))
-        cfg.pop("num_frames", None)
+        n, cfg = synthetic_size(seq_dict, synthetic, "num_frames", 256)
         return SyntheticPrincipalComponentsAutoencoderDataset(n, articulators, seed=seed, database_name=database_name, **cfg)
     return PrincipalComponentsAutoencoderDataset2(database_name=database_name, datadir=datadir,
                                                   sequences=sequences_from_dict(datadir, seq_dict), articulators=articulators,
@@ -69,8 +53,8 @@ def main(database_name, datadir, batch_size, train_seq_dict, test_seq_dict, mode
          synthetic=None, results_dir=None, **kwargs):
     device = torch.device("cuda", torch.cuda.current_device())
     logging.info(f"Running on '{device}'")
-    results_dir = results_dir or RESULTS_DIR
-    os.makedirs(results_dir, exist_ok=True)
+    results_dir, best_encoders_path, best_decoders_path = results_paths(results_dir, "artspeech_pca_",
+                                                                       ("best_encoders.pt", "best_decoders.pt"))
     gen = torch.Generator(device="cpu")
     gen.manual_seed(seed)
 
@@ -104,12 +88,10 @@ def main(database_name, datadir, batch_size, train_seq_dict, test_seq_dict, mode
                  * dataset_config.PIXEL_SPACING * dataset_config.RES).cpu().numpy()
 
     encoders_dict, decoders_dict = pca.state_dicts()
-    best_encoders_path = os.path.join(results_dir, "best_encoders.pt")
     torch.save(encoders_dict, best_encoders_path)
-    _mlflow("log_artifact", best_encoders_path)
-    best_decoders_path = os.path.join(results_dir, "best_decoders.pt")
+    mlflow_call("log_artifact", best_encoders_path)
     torch.save(decoders_dict, best_decoders_path)
-    _mlflow("log_artifact", best_decoders_path)
+    mlflow_call("log_artifact", best_decoders_path)
 
     df_errors_filepath = os.path.join(results_dir, "reconstruction_errors.csv")
     with open(df_errors_filepath, "w", newline="") as f:
@@ -117,7 +99,7 @@ def main(database_name, datadir, batch_size, train_seq_dict, test_seq_dict, mode
         writer.writerow(["subject", "sequence", "frame"] + articulators)
         for name, row in zip(frame_names, data_p2cp):
             writer.writerow(name.split("_") + [repr(float(v)) for v in row])
-    _mlflow("log_artifact", df_errors_filepath)
+    mlflow_call("log_artifact", df_errors_filepath)
 
     aggregates = {"mean": data_p2cp.mean(axis=0), "std": data_p2cp.std(axis=0, ddof=1) if num_frames > 1 else np.full(n_articulators, np.nan),
                   "median": np.median(data_p2cp, axis=0), "min": data_p2cp.min(axis=0), "max": data_p2cp.max(axis=0)}
@@ -127,34 +109,11 @@ def main(database_name, datadir, batch_size, train_seq_dict, test_seq_dict, mode
         writer.writerow(["index"] + articulators)
         for name, row in aggregates.items():
             writer.writerow([name] + [repr(float(v)) for v in row])
-    _mlflow("log_artifact", df_errors_agg_filepath)
+    mlflow_call("log_artifact", df_errors_agg_filepath)
     return {"results_dir": results_dir, "num_train_frames": int(pca.n_samples_seen_), "num_test_frames": int(num_frames),
             "p2cp_mm": {a: float(v) for a, v in zip(articulators, aggregates["mean"])},
             "explained_variance_ratio": {a: float(v.sum()) for a, v in pca.explained_variance_ratio_.items()}}
 
 
-TMP_DIR = tempfile.mkdtemp(prefix="artspeech_pca_")
-RESULTS_DIR = os.path.join(TMP_DIR, "results")
-
 if __name__ == "__main__":
-    parser = argparse.ArgumentParser()
-    parser.add_argument("--config", dest="config_filepath")
-    parser.add_argument("--mlflow", dest="mlflow_tracking_uri", default=None)
-    parser.add_argument("--experiment", dest="experiment_name", default="articulatory_pca")
-    parser.add_argument("--run_id", dest="run_id", default=None)
-    parser.add_argument("--run_name", dest="run_name", default=None)
-    parser.add_argument("--checkpoint", dest="checkpoint_filepath", default=None)
-    args = parser.parse_args()
-    seed = 0
-    random.seed(seed)
-    torch.manual_seed(seed)
-    np.random.seed(seed)
-    with open(args.config_filepath) as f:
-        cfg = yaml.safe_load(f)
-    if mlflow is not None and args.mlflow_tracking_uri is not None:
-        mlflow.set_tracking_uri(args.mlflow_tracking_uri)
-        mlflow.set_experiment(args.experiment_name)
-    try:
-        print(main(**cfg, checkpoint_filepath=args.checkpoint_filepath, seed=seed))
-    finally:
-        shutil.rmtree(TMP_DIR, ignore_errors=True)
+    print(run_cli(main, "articulatory_pca"))

@@ -13,18 +13,12 @@
 # confusion_matrix.npy beside it.  CTC only (`loss: CE` raises).
 #
 ####################################################################################################
-import argparse
 import json
 import logging
 import os
-import random
-import shutil
-import tempfile
 from functools import partial
 
-import numpy as np
 import torch
-import yaml
 from torch.optim import Adam
 from torch.optim.lr_scheduler import CyclicLR
 from torch.utils.data import DataLoader
@@ -36,38 +30,18 @@ from artspeech_amd.phoneme_recognition.datasets import PhonemeRecognitionDataset
 from artspeech_amd.phoneme_recognition.decoders import GreedyCTCDecoder
 from artspeech_amd.phoneme_recognition.metrics import EditDistance
 from artspeech_amd.settings import TRAIN, VALID
-
-try:  # mlflow is optional here (absent from the MI355X image): same flags, no-op logging
-    import mlflow
-except ImportError:
-    mlflow = None
-
-
-def _mlflow(fn, *args, **kwargs):
-    if mlflow is not None:
-        return getattr(mlflow, fn)(*args, **kwargs)
+from artspeech_amd import training
+from artspeech_amd.training import fit, load_checkpoint, load_json, mlflow_call, results_paths, run_cli, synthetic_size
 
 
 def build_vocabulary(vocab_filepath, criterion):
-    """{token: index}: blank (CTC) and unknown first, then the JSON list (reference :84-90); without a file, the 43 synthetic
-    phoneme names of the other synthetic configs (V = 45)."""
-    default_tokens = [BLANK, UNKNOWN] if criterion == Criterion.CTC else [UNKNOWN]
-    vocabulary = {token: i for i, token in enumerate(default_tokens)}
-    if vocab_filepath is not None:
-        with open(vocab_filepath) as f:
-            tokens = json.load(f)
-    else:
-        tokens = [f"ph{i:02d}" for i in range(43)]
-    for i, token in enumerate(tokens, start=len(vocabulary)):
-        vocabulary[token] = i
-    return vocabulary
+    """{token: index}: blank (CTC only) and unknown first, then the JSON list (reference :84-90)"""
+    return training.build_vocabulary(vocab_filepath, (BLANK, UNKNOWN) if criterion == Criterion.CTC else (UNKNOWN,))
 
 
 def _make_dataset(datadir, database_name, seq_dict, vocabulary, feature, voiced_tokens, synthetic, seed):
     if datadir == "synthetic":
-        cfg = dict(synthetic or {})
-        n = (seq_dict or {}).get("num_sentences", cfg.pop("num_sentences", 32))
-        cfg.pop("num_sentences", None)
+        n, cfg = synthetic_size(seq_dict, synthetic, "num_sentences", 32)
         return SyntheticPhonemeRecognitionDataset(n, vocabulary, seed=seed, voiced_tokens=voiced_tokens, **cfg)
     return PhonemeRecognitionDataset(datadir=datadir, database_name=database_name, sequences=sequences_from_dict(datadir, seq_dict),
                                      vocabulary=vocabulary, features=[feature], voiced_tokens=voiced_tokens)
@@ -82,11 +56,7 @@ def main(database_name, datadir, num_epochs, batch_size, patience, learning_rate
         raise NotImplementedError(f"train_phoneme_recognition: loss {loss!r} is not supported; only CTC is ported")
     device = torch.device("cuda", torch.cuda.current_device())
     logging.info(f"Running on '{device}'")
-    results_dir = results_dir or RESULTS_DIR
-    os.makedirs(results_dir, exist_ok=True)
-    best_model_path = os.path.join(results_dir, "best_model.pt")
-    last_model_path = os.path.join(results_dir, "last_model.pt")
-    save_checkpoint_path = os.path.join(results_dir, "checkpoint.pt")
+    results_dir, best_model_path, last_model_path, save_checkpoint_path = results_paths(results_dir, "artspeech_recognizer_")
 
     feature = Feature(feature)
     target = Target(target)
@@ -94,10 +64,7 @@ def main(database_name, datadir, num_epochs, batch_size, patience, learning_rate
     if pretrained:
         raise NotImplementedError("train_phoneme_recognition: pretrained (the LibriSpeech checkpoint) is not supported")
     vocabulary = build_vocabulary(vocab_filepath, criterion)
-    voiced_tokens = None
-    if voicing_filepath is not None:
-        with open(voicing_filepath) as f:
-            voiced_tokens = json.load(f)
+    voiced_tokens = load_json(voicing_filepath)
     tokens = [k for k, _ in sorted(vocabulary.items(), key=lambda t: t[1])]
     decoder = GreedyCTCDecoder(tokens=tokens, sil_token=SIL, blank_token=BLANK, unk_word=UNKNOWN)
 
@@ -106,7 +73,7 @@ def main(database_name, datadir, num_epochs, batch_size, patience, learning_rate
         model.load_state_dict(torch.load(state_dict_filepath, map_location="cpu"))
     model.to(device)
     print(f"\nDeepSpeech2 -- {model.total_parameters} parameters\n")
-    _mlflow("log_param", "num_network_params", model.total_parameters)
+    mlflow_call("log_param", "num_network_params", model.total_parameters)
 
     gen = torch.Generator(device="cpu")
     gen.manual_seed(seed)
@@ -127,43 +94,17 @@ def main(database_name, datadir, num_epochs, batch_size, patience, learning_rate
     common = dict(model=model, criterion=loss_fn, fn_metrics=metrics, device=device, feature=feature, target=target,
                   use_voicing=use_voicing, normalize_outputs=True, use_log_prob=True, optimizer=optimizer, scheduler=scheduler)
 
-    best_metric = np.inf
-    epochs_since_best = 0
-    epochs = range(1, num_epochs + 1)
-    if checkpoint_filepath is not None:
-        checkpoint = torch.load(checkpoint_filepath, map_location=device)
-        model.load_state_dict(checkpoint["model"])
-        optimizer.load_state_dict(checkpoint["optimizer"])
-        epoch = checkpoint["epoch"] + 1
-        epochs = range(epoch, num_epochs + 1)
-        best_metric = checkpoint["best_metric"]
-        epochs_since_best = checkpoint["epochs_since_best"]
-        logging.info(f"Loaded checkpoint -- training from epoch {epoch}, best metric {best_metric} "
-                     f"seen {epochs_since_best} epochs ago.")
-
-    history = []
-    for epoch in epochs:
-        info_train = run_epoch(phase=TRAIN, epoch=epoch, dataloader=train_dataloader, logits_large_margins=logits_large_margins, **common)
-        _mlflow("log_metrics", {f"train_{m}": v for m, v in info_train.items()}, step=epoch)
-        info_valid = run_epoch(phase=VALID, epoch=epoch, dataloader=valid_dataloader, **common)
-        _mlflow("log_metrics", {f"valid_{m}": v for m, v in info_valid.items()}, step=epoch)
-        history.append({"epoch": epoch, "train": info_train, "valid": info_valid})
-        if info_valid["edit_distance"] < best_metric:
-            best_metric = info_valid["edit_distance"]
-            epochs_since_best = 0
-            torch.save(model.state_dict(), best_model_path)
-            _mlflow("log_artifact", best_model_path)
-        else:
-            epochs_since_best += 1
-        torch.save(model.state_dict(), last_model_path)
-        _mlflow("log_artifact", last_model_path)
-        checkpoint = {"epoch": epoch, "model": model.state_dict(), "optimizer": optimizer.state_dict(), "best_metric": float(best_metric),
-                      "epochs_since_best": epochs_since_best, "best_model_path": best_model_path, "last_model_path": last_model_path}
-        torch.save(checkpoint, save_checkpoint_path)
-        _mlflow("log_artifact", save_checkpoint_path)
-        print(f"\nFinished training epoch {epoch}\nBest metric: {'%0.4f' % best_metric}, Epochs since best: {epochs_since_best}\n")
-        if epochs_since_best > patience:
-            break
+    # CyclicLR steps per batch inside run_epoch and is not part of the checkpoint
+    first_epoch, best_metric, epochs_since_best, _ = load_checkpoint(checkpoint_filepath, model, optimizer, map_location=device)
+    history = fit(range(first_epoch, num_epochs + 1),
+                  lambda epoch: run_epoch(phase=TRAIN, epoch=epoch, dataloader=train_dataloader,
+                                          logits_large_margins=logits_large_margins, **common),
+                  lambda epoch: run_epoch(phase=VALID, epoch=epoch, dataloader=valid_dataloader, **common),
+                  metric="edit_distance", patience=patience, best_files=[(best_model_path, model.state_dict)],
+                  last_files=[(last_model_path, model.state_dict)], checkpoint_path=save_checkpoint_path,
+                  checkpoint_state=lambda: {"model": model.state_dict(), "optimizer": optimizer.state_dict(),
+                                            "best_model_path": best_model_path, "last_model_path": last_model_path},
+                  best_metric=best_metric, epochs_since_best=epochs_since_best)
 
     # test split: the best model, with the substitution matrix and (given a plot_target) the frame-level confusion matrix written
     # to results_dir as the reference's closing run_test does (its plots are not part of this engine)
@@ -175,32 +116,9 @@ def main(database_name, datadir, num_epochs, batch_size, patience, learning_rate
                          criterion=loss_fn, decoder=decoder, plot_target=plot_target, save_dir=results_dir)
     with open(os.path.join(results_dir, "info_test.json"), "w") as f:
         json.dump(info_test, f, indent=2)
-    _mlflow("log_metrics", {f"test_{m}": v for m, v in info_test.items()}, step=0)
+    mlflow_call("log_metrics", {f"test_{m}": v for m, v in info_test.items()}, step=0)
     return {"history": history, "test": info_test, "results_dir": results_dir}
 
 
-TMP_DIR = tempfile.mkdtemp(prefix="artspeech_recognizer_")
-RESULTS_DIR = os.path.join(TMP_DIR, "results")
-
 if __name__ == "__main__":
-    parser = argparse.ArgumentParser()
-    parser.add_argument("--config", dest="config_filepath")
-    parser.add_argument("--mlflow", dest="mlflow_tracking_uri", default=None)
-    parser.add_argument("--experiment", dest="experiment_name", default="phoneme_recognition")
-    parser.add_argument("--run_id", dest="run_id", default=None)
-    parser.add_argument("--run_name", dest="run_name", default=None)
-    parser.add_argument("--checkpoint", dest="checkpoint_filepath", default=None)
-    args = parser.parse_args()
-    seed = 0
-    random.seed(seed)
-    torch.manual_seed(seed)
-    np.random.seed(seed)
-    with open(args.config_filepath) as f:
-        cfg = yaml.safe_load(f)
-    if mlflow is not None and args.mlflow_tracking_uri is not None:
-        mlflow.set_tracking_uri(args.mlflow_tracking_uri)
-        mlflow.set_experiment(args.experiment_name)
-    try:
-        main(**cfg, checkpoint_filepath=args.checkpoint_filepath, seed=seed)
-    finally:
-        shutil.rmtree(TMP_DIR, ignore_errors=True)
+    run_cli(main, "phoneme_recognition")

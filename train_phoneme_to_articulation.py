@@ -11,19 +11,13 @@
 # all-reduced over RCCL before the optimizer step.
 #
 ####################################################################################################
-import argparse
 import json
 import logging
 import os
-import random
-import shutil
-import tempfile
-from collections import OrderedDict
 
 import numpy as np
 import torch
 import torch.distributed as dist
-import yaml
 from torch.optim import Adam
 from torch.optim.lr_scheduler import ReduceLROnPlateau
 from torch.utils.data import DataLoader
@@ -40,17 +34,9 @@ from artspeech_amd.phoneme_to_articulation.encoder_decoder.evaluation import run
 from artspeech_amd.phoneme_to_articulation.encoder_decoder.metrics import P2CPDistance
 from artspeech_amd.phoneme_to_articulation.encoder_decoder.models import ArtSpeech
 from artspeech_amd.phoneme_to_articulation.metrics import EuclideanDistance, masked_euclidean_loss
-from artspeech_amd.settings import BLANK, DATASET_CONFIG, TRAIN, UNKNOWN, VALID
-
-try:  # mlflow is optional here (absent from the MI355X image): same flags, no-op logging
-    import mlflow
-except ImportError:  # pragma: no cover
-    mlflow = None
-
-
-def _mlflow(fn, *args, **kwargs):
-    if mlflow is not None:
-        return getattr(mlflow, fn)(*args, **kwargs)
+from artspeech_amd.settings import DATASET_CONFIG, TRAIN, VALID
+from artspeech_amd.training import (build_vocabulary, fit, load_checkpoint, mlflow_call, results_paths, run_cli,
+                                    synthetic_size)
 
 
 def _world():
@@ -75,12 +61,15 @@ def run_epoch(phase, epoch, model, dataloader, optimizer, criterion, fn_metrics=
     if deferred:
         model.defer_token_check = True          # for this loop only: restored below, whatever happens
     try:
-        return _run_epoch_batches(phase, model, dataloader, optimizer, criterion, fn_metrics, scheduler, device, training, rank, world,
+        info = _run_epoch_batches(phase, model, dataloader, optimizer, criterion, fn_metrics, scheduler, device, training, rank, world,
                                   losses, metrics_values, fused, deferred)
+        if deferred:
+            model.check_tokens()                # the normal path only: never over an error of the loop
+        return info
     finally:
         if deferred:
             model.defer_token_check = keep_defer
-            model.check_tokens()                # nothing stays pending (and an id outside the vocabulary still raises)
+            model._pending_ws = []              # nothing stays pending; after an error the flag words are dropped unread
 
 
 def _run_epoch_batches(phase, model, dataloader, optimizer, criterion, fn_metrics, scheduler, device, training, rank, world, losses,
@@ -123,26 +112,11 @@ def _run_epoch_batches(phase, model, dataloader, optimizer, criterion, fn_metric
 
 def _make_dataset(datadir, database_name, seq_dict, vocabulary, articulators, clip_tails, synthetic, seed):
     if datadir == "synthetic":
-        cfg = dict(synthetic or {})
-        n = cfg.pop("num_sentences", 64) if not isinstance(seq_dict, dict) else seq_dict.get("num_sentences", cfg.pop("num_sentences", 64))
+        n, cfg = synthetic_size(seq_dict, synthetic, "num_sentences", 64)
         return SyntheticArtSpeechDataset(n, vocabulary, articulators, seed=seed, database_name=database_name, **cfg)
     from artspeech_amd.helpers import sequences_from_dict
     return ArtSpeechDataset(datadir, database_name, sequences_from_dict(datadir, seq_dict), vocabulary, articulators,
                             clip_tails=clip_tails)
-
-
-def build_vocabulary(vocab_filepath):
-    """{token: index}: the two default tokens first, then the JSON list (reference :151-156); without a file, 43 synthetic
-    phoneme names (V = 45)."""
-    vocabulary = {token: i for i, token in enumerate([BLANK, UNKNOWN])}
-    if vocab_filepath is not None:
-        with open(vocab_filepath) as f:
-            tokens = json.load(f)
-    else:
-        tokens = [f"ph{i:02d}" for i in range(43)]
-    for i, token in enumerate(tokens, start=len(vocabulary)):
-        vocabulary[token] = i
-    return vocabulary
 
 
 def main(datadir, database_name, num_epochs, batch_size, patience, learning_rate, weight_decay, train_seq_dict,
@@ -155,11 +129,7 @@ def main(datadir, database_name, num_epochs, batch_size, patience, learning_rate
     rank, world = _world()
     device = torch.device("cuda", torch.cuda.current_device())
     logging.info(f"Running on '{device}' (rank {rank}/{world})")
-    results_dir = results_dir or RESULTS_DIR
-    os.makedirs(results_dir, exist_ok=True)
-    best_model_path = os.path.join(results_dir, "best_model.pt")
-    last_model_path = os.path.join(results_dir, "last_model.pt")
-    save_checkpoint_path = os.path.join(results_dir, "checkpoint.pt")
+    results_dir, best_model_path, last_model_path, save_checkpoint_path = results_paths(results_dir, "artspeech_")
 
     vocabulary = build_vocabulary(vocab_filepath)
 
@@ -170,7 +140,7 @@ def main(datadir, database_name, num_epochs, batch_size, patience, learning_rate
     dp.broadcast_parameters(model)
     if rank == 0:
         print(f"\nArtSpeech -- {model.total_parameters} parameters\n")
-    _mlflow("log_param", "num_network_params", model.total_parameters)
+    mlflow_call("log_param", "num_network_params", model.total_parameters)
 
     loss_fn = EuclideanDistance(reduction="none")
     optimizer = Adam(model.parameters(), lr=learning_rate, weight_decay=weight_decay)
@@ -190,41 +160,18 @@ def main(datadir, database_name, num_epochs, batch_size, patience, learning_rate
     valid_dataloader = loader(valid_seq_dict, False, seed + 1)
     fn_metrics = {"p2cp_mean": P2CPDistance(dataset_config=DATASET_CONFIG[database_name])}
 
-    epochs = range(1, num_epochs + 1)
-    best_metric, epochs_since_best = np.inf, 0
-    if checkpoint_filepath is not None:
-        checkpoint = torch.load(checkpoint_filepath, map_location="cpu")
-        model.load_state_dict(checkpoint["model"])
-        optimizer.load_state_dict(checkpoint["optimizer"])
-        scheduler.load_state_dict(checkpoint["scheduler"])
-        epochs = range(checkpoint["epoch"] + 1, num_epochs + 1)
-        best_metric, epochs_since_best = checkpoint["best_metric"], checkpoint["epochs_since_best"]
-        best_model_path, last_model_path = checkpoint["best_model_path"], checkpoint["last_model_path"]
-
-    for epoch in epochs:
-        info_train = run_epoch(TRAIN, epoch, model, train_dataloader, optimizer, loss_fn, device=device)
-        _mlflow("log_metrics", {f"train_{k}": v for k, v in info_train.items()}, step=epoch)
-        info_valid = run_epoch(VALID, epoch, model, valid_dataloader, optimizer, loss_fn, fn_metrics=fn_metrics, device=device)
-        _mlflow("log_metrics", {f"valid_{k}": v for k, v in info_valid.items()}, step=epoch)
-        if rank == 0:
-            print(f"epoch {epoch}: train loss {info_train['loss']:.5f}  valid loss {info_valid['loss']:.5f}  "
-                  f"p2cp_mean {info_valid['p2cp_mean']:.3f} mm", flush=True)
-        scheduler.step(info_valid["loss"])          # LR schedule follows the validation LOSS (:290)
-        if info_valid["p2cp_mean"] < best_metric:   # model selection follows p2cp_mean (:292-298)
-            best_metric, epochs_since_best = info_valid["p2cp_mean"], 0
-            if rank == 0:
-                torch.save(model.state_dict(), best_model_path)
-        else:
-            epochs_since_best += 1
-        if rank == 0:
-            torch.save(model.state_dict(), last_model_path)
-            torch.save({
-                "epoch": epoch, "model": model.state_dict(), "optimizer": optimizer.state_dict(),
-                "scheduler": scheduler.state_dict(), "best_metric": best_metric, "epochs_since_best": epochs_since_best,
-                "best_model_path": best_model_path, "last_model_path": last_model_path,
-            }, save_checkpoint_path)
-        if epochs_since_best > patience:
-            break
+    first_epoch, best_metric, epochs_since_best, checkpoint = load_checkpoint(checkpoint_filepath, model, optimizer, scheduler)
+    best_model_path = checkpoint.get("best_model_path", best_model_path)   # a resumed run keeps writing where it started
+    last_model_path = checkpoint.get("last_model_path", last_model_path)
+    # the LR schedule follows the validation LOSS (:290), model selection follows p2cp_mean (:292-298)
+    fit(range(first_epoch, num_epochs + 1),
+        lambda epoch: run_epoch(TRAIN, epoch, model, train_dataloader, optimizer, loss_fn, device=device),
+        lambda epoch: run_epoch(VALID, epoch, model, valid_dataloader, optimizer, loss_fn, fn_metrics=fn_metrics, device=device),
+        metric="p2cp_mean", patience=patience, best_files=[(best_model_path, model.state_dict)],
+        last_files=[(last_model_path, model.state_dict)], checkpoint_path=save_checkpoint_path,
+        checkpoint_state=lambda: {"model": model.state_dict(), "optimizer": optimizer.state_dict(), "scheduler": scheduler.state_dict(),
+                                  "best_model_path": best_model_path, "last_model_path": last_model_path},
+        best_metric=best_metric, epochs_since_best=epochs_since_best, plateau=scheduler, rank=rank)
 
     results = None
     if rank == 0:
@@ -241,28 +188,5 @@ def main(datadir, database_name, num_epochs, batch_size, patience, learning_rate
     return results
 
 
-TMP_DIR = tempfile.mkdtemp(prefix="artspeech_")
-RESULTS_DIR = os.path.join(TMP_DIR, "results")
-
 if __name__ == "__main__":
-    parser = argparse.ArgumentParser()
-    parser.add_argument("--config", dest="config_filepath")
-    parser.add_argument("--mlflow", dest="mlflow_tracking_uri", default=None)
-    parser.add_argument("--experiment", dest="experiment_name", default="phoneme_to_articulation")
-    parser.add_argument("--run_id", dest="run_id", default=None)
-    parser.add_argument("--run_name", dest="run_name", default=None)
-    parser.add_argument("--checkpoint", dest="checkpoint_filepath", default=None)
-    args = parser.parse_args()
-    seed = 0
-    random.seed(seed)
-    torch.manual_seed(seed)
-    np.random.seed(seed)
-    with open(args.config_filepath) as f:
-        cfg = yaml.safe_load(f)
-    if mlflow is not None and args.mlflow_tracking_uri is not None:
-        mlflow.set_tracking_uri(args.mlflow_tracking_uri)
-        mlflow.set_experiment(args.experiment_name)
-    try:
-        main(**cfg, checkpoint_filepath=args.checkpoint_filepath, seed=seed)
-    finally:
-        shutil.rmtree(TMP_DIR, ignore_errors=True)
+    run_cli(main, "phoneme_to_articulation")

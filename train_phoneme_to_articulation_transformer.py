@@ -10,16 +10,11 @@
 # utterance and gradients are all-reduced over RCCL before the optimizer step.
 #
 ####################################################################################################
-import argparse
 import os
-import random
-import shutil
-import tempfile
 
 import numpy as np
 import torch
 import torch.distributed as dist
-import yaml
 from torch.optim import Adam
 from torch.optim.lr_scheduler import ReduceLROnPlateau
 from torch.utils.data import DataLoader
@@ -34,7 +29,7 @@ from artspeech_amd.phoneme_to_articulation.encoder_decoder.metrics import P2CPDi
 from artspeech_amd.phoneme_to_articulation.metrics import EuclideanDistance, masked_euclidean_loss
 from artspeech_amd.phoneme_to_articulation.transformer.models import ArtSpeechTransformer
 from artspeech_amd.settings import DATASET_CONFIG, TRAIN, VALID
-from train_phoneme_to_articulation import build_vocabulary
+from artspeech_amd.training import build_vocabulary, fit, load_checkpoint, results_paths, run_cli, synthetic_size
 
 
 def _world():
@@ -121,6 +116,14 @@ def run_epoch(phase, epoch, model, dataloader, optimizer, criterion, fn_metrics=
     return info
 
 
+def _make_dataset(datadir, database_name, seq_dict, vocabulary, articulators, clip_tails, synthetic, seed):
+    if datadir != "synthetic":
+        raise NotImplementedError("real-data loading needs the reference's database_collector / vt_shape_gen stack; "
+                                  "use `datadir: synthetic`")
+    n, cfg = synthetic_size(seq_dict, synthetic, "num_sentences", 64)
+    return SyntheticArtSpeechDataset(n, vocabulary, articulators, seed=seed, database_name=database_name, **cfg)
+
+
 def main(datadir, database_name, num_epochs, batch_size, patience, learning_rate, weight_decay, train_seq_dict, valid_seq_dict,
          test_seq_dict, vocab_filepath, articulators, model_kwargs=None, num_workers=0, clip_tails=True, state_dict_filepath=None,
          checkpoint_filepath=None, seed=0, synthetic=None, results_dir=None):
@@ -130,12 +133,8 @@ def main(datadir, database_name, num_epochs, batch_size, patience, learning_rate
         dist.init_process_group(backend)
     rank, world = _world()
     device = torch.device("cuda", torch.cuda.current_device())
-    results_dir = results_dir or RESULTS_DIR
-    os.makedirs(results_dir, exist_ok=True)
+    results_dir, best_model_path, last_model_path, save_checkpoint_path = results_paths(results_dir, "artspeech_tr_")
     vocabulary = build_vocabulary(vocab_filepath)
-    if datadir != "synthetic":
-        raise NotImplementedError("real-data loading needs the reference's database_collector / vt_shape_gen stack; "
-                                  "use `datadir: synthetic`")
     model = ArtSpeechTransformer(len(vocabulary), len(articulators), **(model_kwargs or {}))
     if state_dict_filepath is not None:
         model.load_state_dict(torch.load(state_dict_filepath, map_location="cpu"))
@@ -152,56 +151,28 @@ def main(datadir, database_name, num_epochs, batch_size, patience, learning_rate
     gen.manual_seed(seed)
 
     def loader(seq_dict, shuffle, ds_seed):
-        cfg = dict(synthetic or {})
-        n = seq_dict.get("num_sentences", 64) if isinstance(seq_dict, dict) else 64
-        ds = SyntheticArtSpeechDataset(n, vocabulary, articulators, seed=ds_seed, database_name=database_name, **cfg)
+        ds = _make_dataset(datadir, database_name, seq_dict, vocabulary, articulators, clip_tails, synthetic, ds_seed)
         return DataLoader(ds, batch_size=batch_size, shuffle=shuffle, num_workers=num_workers, worker_init_fn=set_seeds,
                           collate_fn=pad_sequence_transformer_collate_fn, generator=gen)
 
     train_dataloader, valid_dataloader = loader(train_seq_dict, True, seed), loader(valid_seq_dict, False, seed + 1)
     fn_metrics = {"p2cp_mean": P2CPDistance(dataset_config=DATASET_CONFIG[database_name])}
-    best_metric, epochs_since_best = np.inf, 0
-    for epoch in range(1, num_epochs + 1):
-        info_train = run_epoch(TRAIN, epoch, model, train_dataloader, optimizer, loss_fn, device=device)
-        info_valid = run_epoch(VALID, epoch, model, valid_dataloader, optimizer, loss_fn, fn_metrics=fn_metrics, device=device)
-        if rank == 0:
-            print(f"epoch {epoch}: train loss {info_train['loss']:.5f}  valid loss {info_valid['loss']:.5f}  "
-                  f"p2cp_mean {info_valid['p2cp_mean']:.3f} mm", flush=True)
-        scheduler.step(info_valid["loss"])
-        if info_valid["p2cp_mean"] < best_metric:
-            best_metric, epochs_since_best = info_valid["p2cp_mean"], 0
-            if rank == 0:
-                torch.save(model.state_dict(), os.path.join(results_dir, "best_model.pt"))
-        else:
-            epochs_since_best += 1
-        if rank == 0:
-            torch.save(model.state_dict(), os.path.join(results_dir, "last_model.pt"))
-        if epochs_since_best > patience:
-            break
+    first_epoch, best_metric, epochs_since_best, checkpoint = load_checkpoint(checkpoint_filepath, model, optimizer, scheduler)
+    best_model_path = checkpoint.get("best_model_path", best_model_path)   # a resumed run keeps writing where it started
+    last_model_path = checkpoint.get("last_model_path", last_model_path)
+    history = fit(range(first_epoch, num_epochs + 1),
+                  lambda epoch: run_epoch(TRAIN, epoch, model, train_dataloader, optimizer, loss_fn, device=device),
+                  lambda epoch: run_epoch(VALID, epoch, model, valid_dataloader, optimizer, loss_fn, fn_metrics=fn_metrics, device=device),
+                  metric="p2cp_mean", patience=patience, best_files=[(best_model_path, model.state_dict)],
+                  last_files=[(last_model_path, model.state_dict)], checkpoint_path=save_checkpoint_path,
+                  checkpoint_state=lambda: {"model": model.state_dict(), "optimizer": optimizer.state_dict(),
+                                            "scheduler": scheduler.state_dict(), "best_model_path": best_model_path,
+                                            "last_model_path": last_model_path},
+                  best_metric=best_metric, epochs_since_best=epochs_since_best, plateau=scheduler, rank=rank)
     if world > 1:
         dist.barrier()
-    return {"best_p2cp_mean": best_metric}
+    return {"best_p2cp_mean": min([best_metric] + [h["valid"]["p2cp_mean"] for h in history])}
 
-
-TMP_DIR = tempfile.mkdtemp(prefix="artspeech_tr_")
-RESULTS_DIR = os.path.join(TMP_DIR, "results")
 
 if __name__ == "__main__":
-    parser = argparse.ArgumentParser()
-    parser.add_argument("--config", dest="config_filepath")
-    parser.add_argument("--mlflow", dest="mlflow_tracking_uri", default=None)
-    parser.add_argument("--experiment", dest="experiment_name", default="phoneme_to_articulation_transformer")
-    parser.add_argument("--run_id", dest="run_id", default=None)
-    parser.add_argument("--run_name", dest="run_name", default=None)
-    parser.add_argument("--checkpoint", dest="checkpoint_filepath", default=None)
-    args = parser.parse_args()
-    seed = 0
-    random.seed(seed)
-    torch.manual_seed(seed)
-    np.random.seed(seed)
-    with open(args.config_filepath) as f:
-        cfg = yaml.safe_load(f)
-    try:
-        main(**cfg, checkpoint_filepath=args.checkpoint_filepath, seed=seed)
-    finally:
-        shutil.rmtree(TMP_DIR, ignore_errors=True)
+    run_cli(main, "phoneme_to_articulation_transformer")

@@ -11,17 +11,10 @@
 # ends with run_phoneme_to_principal_components_test on the test split (loss + p2cp_mean).
 #
 ####################################################################################################
-import argparse
-import json
 import logging
-import os
-import random
-import shutil
-import tempfile
 
 import numpy as np
 import torch
-import yaml
 from torch.optim import Adam
 from torch.optim.lr_scheduler import ReduceLROnPlateau
 from torch.utils.data import DataLoader
@@ -39,17 +32,9 @@ from artspeech_amd.phoneme_to_articulation.principal_components.losses import Au
 from artspeech_amd.phoneme_to_articulation.principal_components.metrics import DecoderMeanP2CPDistance2
 from artspeech_amd.phoneme_to_articulation.principal_components.models import (DecoderType, EncoderType,
                                                                                PrincipalComponentsArtSpeech)
-from artspeech_amd.settings import BLANK, DATASET_CONFIG, TRAIN, UNKNOWN, VALID
-
-try:  # mlflow is optional here (absent from the MI355X image): same flags, no-op logging
-    import mlflow
-except ImportError:
-    mlflow = None
-
-
-def _mlflow(fn, *args, **kwargs):
-    if mlflow is not None:
-        return getattr(mlflow, fn)(*args, **kwargs)
+from artspeech_amd.settings import DATASET_CONFIG, TRAIN, VALID
+from artspeech_amd.training import (build_vocabulary, fit, load_checkpoint, load_json, mlflow_call, results_paths, run_cli,
+                                    synthetic_size)
 
 
 def run_epoch(phase, epoch, model, dataloader, optimizer, criterion, scheduler=None, fn_metrics=None, device=None):
@@ -84,26 +69,10 @@ def run_epoch(phase, epoch, model, dataloader, optimizer, criterion, scheduler=N
     return info
 
 
-def build_vocabulary(vocab_filepath):
-    """{token: index}: the two default tokens first, then the JSON list (reference :186-191); without a file, 43 synthetic
-    phoneme names (V = 45)."""
-    vocabulary = {token: i for i, token in enumerate([BLANK, UNKNOWN])}
-    if vocab_filepath is not None:
-        with open(vocab_filepath) as f:
-            tokens = json.load(f)
-    else:
-        tokens = [f"ph{i:02d}" for i in range(43)]
-    for i, token in enumerate(tokens, start=len(vocabulary)):
-        vocabulary[token] = i
-    return vocabulary
-
-
 def _make_dataset(datadir, database_name, seq_dict, vocabulary, articulators, TV_to_phoneme_map, clip_tails, voiced_tokens,
                   synthetic, seed):
     if datadir == "synthetic":
-        cfg = dict(synthetic or {})
-        n = (seq_dict or {}).get("num_sentences", cfg.pop("num_sentences", 32))
-        cfg.pop("num_sentences", None)
+        n, cfg = synthetic_size(seq_dict, synthetic, "num_sentences", 32)
         return SyntheticPrincipalComponentsPhonemeToArticulationDataset(n, vocabulary, articulators, TV_to_phoneme_map, seed=seed,
                                                                         database_name=database_name, voiced_tokens=voiced_tokens,
                                                                         **cfg)
@@ -121,17 +90,10 @@ def main(database_name, datadir, num_epochs, batch_size, patience, learning_rate
     device = torch.device("cuda", torch.cuda.current_device())
     logging.info(f"Running on '{device}'")
     dataset_config = DATASET_CONFIG[database_name]
-    results_dir = results_dir or RESULTS_DIR
-    os.makedirs(results_dir, exist_ok=True)
-    best_model_path = os.path.join(results_dir, "best_model.pt")
-    last_model_path = os.path.join(results_dir, "last_model.pt")
-    save_checkpoint_path = os.path.join(results_dir, "checkpoint.pt")
+    results_dir, best_model_path, last_model_path, save_checkpoint_path = results_paths(results_dir, "artspeech_pc_")
 
     vocabulary = build_vocabulary(vocab_filepath)
-    voiced_tokens = None
-    if voicing_filepath is not None:
-        with open(voicing_filepath) as f:
-            voiced_tokens = json.load(f)
+    voiced_tokens = load_json(voicing_filepath)
     if isinstance(list(indices_dict.values())[0], int):
         indices_dict = make_indices_dict(indices_dict)
     articulators = sorted(indices_dict.keys())
@@ -142,7 +104,7 @@ def main(database_name, datadir, num_epochs, batch_size, patience, learning_rate
         model.load_state_dict(torch.load(state_dict_filepath, map_location=device))
     model.to(device)
     print(f"\nPrincipalComponentsArtSpeech -- {model.total_parameters} parameters\n")
-    _mlflow("log_param", "num_network_params", model.total_parameters)
+    mlflow_call("log_param", "num_network_params", model.total_parameters)
 
     gen = torch.Generator(device="cpu")
     gen.manual_seed(seed)
@@ -180,48 +142,19 @@ def main(database_name, datadir, num_epochs, batch_size, patience, learning_rate
         autoencoder_kwargs=autoencoder_kwargs, device=device, decoder_cls=decoder_cls,
         denorm_fns={articulator: train_dataset.normalize[articulator].inverse for articulator in articulators})}
 
-    best_metric = np.inf
-    epochs_since_best = 0
-    epochs = range(1, num_epochs + 1)
-    if checkpoint_filepath is not None:
-        checkpoint = torch.load(checkpoint_filepath, map_location=device)
-        model.load_state_dict(checkpoint["model"])
-        optimizer.load_state_dict(checkpoint["optimizer"])
-        scheduler.load_state_dict(checkpoint["scheduler"])
-        epoch = checkpoint["epoch"] + 1
-        epochs = range(epoch, num_epochs + 1)
-        best_metric = checkpoint["best_metric"]
-        epochs_since_best = checkpoint["epochs_since_best"]
-        logging.info(f"Loaded checkpoint -- training from epoch {epoch}, best metric {best_metric} "
-                     f"seen {epochs_since_best} epochs ago.")
-
-    history = []
-    for epoch in epochs:
-        info_train = run_epoch(phase=TRAIN, epoch=epoch, model=model, dataloader=train_dataloader, optimizer=optimizer,
-                               criterion=loss_fn, device=device)
-        _mlflow("log_metrics", {f"train_{m}": v for m, v in info_train.items()}, step=epoch)
-        info_valid = run_epoch(phase=VALID, epoch=epoch, model=model, dataloader=valid_dataloader, optimizer=optimizer,
-                               criterion=loss_fn, device=device, fn_metrics=fn_metrics)
-        _mlflow("log_metrics", {f"valid_{m}": v for m, v in info_valid.items()}, step=epoch)
-        history.append({"epoch": epoch, "train": info_train, "valid": info_valid})
-        scheduler.step(info_valid["loss"])
-        if info_valid["p2cp_mean"] < best_metric:
-            best_metric = info_valid["p2cp_mean"]
-            epochs_since_best = 0
-            torch.save(model.state_dict(), best_model_path)
-            _mlflow("log_artifact", best_model_path)
-        else:
-            epochs_since_best += 1
-        torch.save(model.state_dict(), last_model_path)
-        _mlflow("log_artifact", last_model_path)
-        checkpoint = {"epoch": epoch, "model": model.state_dict(), "optimizer": optimizer.state_dict(),
-                      "scheduler": scheduler.state_dict(), "best_metric": float(best_metric), "epochs_since_best": epochs_since_best,
-                      "best_model_path": best_model_path, "last_model_path": last_model_path}
-        torch.save(checkpoint, save_checkpoint_path)
-        _mlflow("log_artifact", save_checkpoint_path)
-        print(f"\nFinished training epoch {epoch}\nBest metric: {'%0.4f' % best_metric}, Epochs since best: {epochs_since_best}\n")
-        if epochs_since_best > patience:
-            break
+    first_epoch, best_metric, epochs_since_best, _ = load_checkpoint(checkpoint_filepath, model, optimizer, scheduler,
+                                                                     map_location=device)
+    history = fit(range(first_epoch, num_epochs + 1),
+                  lambda epoch: run_epoch(phase=TRAIN, epoch=epoch, model=model, dataloader=train_dataloader, optimizer=optimizer,
+                                          criterion=loss_fn, device=device),
+                  lambda epoch: run_epoch(phase=VALID, epoch=epoch, model=model, dataloader=valid_dataloader, optimizer=optimizer,
+                                          criterion=loss_fn, device=device, fn_metrics=fn_metrics),
+                  metric="p2cp_mean", patience=patience, best_files=[(best_model_path, model.state_dict)],
+                  last_files=[(last_model_path, model.state_dict)], checkpoint_path=save_checkpoint_path,
+                  checkpoint_state=lambda: {"model": model.state_dict(), "optimizer": optimizer.state_dict(),
+                                            "scheduler": scheduler.state_dict(), "best_model_path": best_model_path,
+                                            "last_model_path": last_model_path},
+                  best_metric=best_metric, epochs_since_best=epochs_since_best, plateau=scheduler)
 
     # test split: the best model through the test harness, as the reference does (:455), without the per-sentence dumps
     _, test_dataloader = loader(test_seq_dict, False, seed + 2)
@@ -231,32 +164,9 @@ def main(database_name, datadir, num_epochs, batch_size, patience, learning_rate
     best_model.to(device)
     info_test = run_phoneme_to_principal_components_test(epoch=0, model=best_model, dataloader=test_dataloader, criterion=loss_fn,
                                                          fn_metrics=fn_metrics, device=device)
-    _mlflow("log_metrics", {f"test_{m}": v for m, v in info_test.items()}, step=0)
+    mlflow_call("log_metrics", {f"test_{m}": v for m, v in info_test.items()}, step=0)
     return {"history": history, "test": info_test, "results_dir": results_dir}
 
 
-TMP_DIR = tempfile.mkdtemp(prefix="artspeech_pc_")
-RESULTS_DIR = os.path.join(TMP_DIR, "results")
-
 if __name__ == "__main__":
-    parser = argparse.ArgumentParser()
-    parser.add_argument("--config", dest="config_filepath")
-    parser.add_argument("--mlflow", dest="mlflow_tracking_uri", default=None)
-    parser.add_argument("--experiment", dest="experiment_name", default="phoneme_to_principal_components")
-    parser.add_argument("--run_id", dest="run_id", default=None)
-    parser.add_argument("--run_name", dest="run_name", default=None)
-    parser.add_argument("--checkpoint", dest="checkpoint_filepath", default=None)
-    args = parser.parse_args()
-    seed = 0
-    random.seed(seed)
-    torch.manual_seed(seed)
-    np.random.seed(seed)
-    with open(args.config_filepath) as f:
-        cfg = yaml.safe_load(f)
-    if mlflow is not None and args.mlflow_tracking_uri is not None:
-        mlflow.set_tracking_uri(args.mlflow_tracking_uri)
-        mlflow.set_experiment(args.experiment_name)
-    try:
-        main(**cfg, checkpoint_filepath=args.checkpoint_filepath, seed=seed)
-    finally:
-        shutil.rmtree(TMP_DIR, ignore_errors=True)
+    run_cli(main, "phoneme_to_principal_components")

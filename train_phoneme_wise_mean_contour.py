@@ -11,15 +11,12 @@
 # (the model's state_dict), then evaluates the test split: test_outputs/, test_results.json, test_results.csv.
 #
 ####################################################################################################
-import argparse
 import csv
 import json
 import logging
 import os
-import tempfile
 
 import torch
-import yaml
 
 from artspeech_amd.phoneme_to_articulation.encoder_decoder.dataset import ArtSpeechDataset
 from artspeech_amd.phoneme_to_articulation.phoneme_wise_mean_contour import (
@@ -28,38 +25,20 @@ from artspeech_amd.phoneme_to_articulation.phoneme_wise_mean_contour import (
     test,
     train,
 )
+from artspeech_amd import training
 from artspeech_amd.settings import UNKNOWN
-
-try:  # mlflow is optional here (absent from the MI355X image): same flags, no-op logging
-    import mlflow
-except ImportError:
-    mlflow = None
-
-
-def _mlflow(fn, *args, **kwargs):
-    if mlflow is not None:
-        return getattr(mlflow, fn)(*args, **kwargs)
+from artspeech_amd.training import cli_parser, mlflow_call, results_paths, run_cli, synthetic_size
 
 
 def build_vocabulary(vocab_filepath):
     """{token: index}: <unk> first, then the JSON list (reference :40-45); without a file, the synthetic vocabulary of
     train_phoneme_to_articulation.py (<blank>, <unk>, 43 phoneme names)."""
-    if vocab_filepath is None:
-        from train_phoneme_to_articulation import build_vocabulary as synthetic_vocabulary
-        return synthetic_vocabulary(None)
-    vocabulary = {token: i for i, token in enumerate([UNKNOWN])}
-    with open(vocab_filepath) as f:
-        tokens = json.load(f)
-    for i, token in enumerate(tokens, start=len(vocabulary)):
-        vocabulary[token] = i
-    return vocabulary
+    return training.build_vocabulary(vocab_filepath, (UNKNOWN,)) if vocab_filepath is not None else training.build_vocabulary(None)
 
 
 def make_dataset(datadir, database_name, seq_dict, vocabulary, articulators, clip_tails, synthetic, seed):
     if datadir == "synthetic":
-        cfg = dict(synthetic or {})
-        n = (seq_dict or {}).get("num_sentences", cfg.pop("num_sentences", 16))
-        cfg.pop("num_sentences", None)
+        n, cfg = synthetic_size(seq_dict, synthetic, "num_sentences", 16)
         return SyntheticSegmentedArtSpeechDataset(n, vocabulary, articulators, seed=seed, database_name=database_name, **cfg)
     from artspeech_amd.helpers import sequences_from_dict
     return ArtSpeechDataset(datadir, database_name, sequences_from_dict(datadir, seq_dict), vocabulary, articulators,
@@ -86,51 +65,38 @@ def write_results(test_results, articulators, results_dir):
 def main(database_name, datadir, train_seq_dict, test_seq_dict, vocab_filepath, articulators, state_dict_filepath=None,
          clip_tails=True, weighted=False, synthetic=None, seed=0, results_dir=None, frac=0.1, batch_size=32):
     device = torch.device("cuda", torch.cuda.current_device())
-    results_dir = results_dir or tempfile.mkdtemp(prefix="artspeech_mean_contour_")
-    os.makedirs(results_dir, exist_ok=True)
+    results_dir, = results_paths(results_dir, "artspeech_mean_contour_", ())
     vocabulary = build_vocabulary(vocab_filepath)
 
     if state_dict_filepath is None:
         train_dataset = make_dataset(datadir, database_name, train_seq_dict, vocabulary, articulators, clip_tails, synthetic, seed)
         save_to = os.path.join(results_dir, "phoneme_wise_articulators.csv")
         model = train(train_dataset, save_to=save_to, weighted=weighted, device=device)
-        _mlflow("log_artifact", save_to)
+        mlflow_call("log_artifact", save_to)
         state_dict_path = os.path.join(results_dir, "phoneme_wise_articulators.pt")
         torch.save(model.state_dict(), state_dict_path)
-        _mlflow("log_artifact", state_dict_path)
+        mlflow_call("log_artifact", state_dict_path)
     elif state_dict_filepath.endswith((".pt", ".pth")):
         model = PhonemeWiseMeanContour().load_state_dict(torch.load(state_dict_filepath, map_location="cpu"), device)
-        _mlflow("log_artifact", state_dict_filepath)
+        mlflow_call("log_artifact", state_dict_filepath)
     else:
         model = PhonemeWiseMeanContour.from_csv(state_dict_filepath, vocabulary, device)
-        _mlflow("log_artifact", state_dict_filepath)
+        mlflow_call("log_artifact", state_dict_filepath)
     logging.info("Finished training phoneme wise mean contour")
 
     test_dataset = make_dataset(datadir, database_name, test_seq_dict, vocabulary, articulators, clip_tails, synthetic, seed + 2)
     test_outputs_dir = os.path.join(results_dir, "test_outputs")
     os.makedirs(test_outputs_dir, exist_ok=True)
     test_results = test(test_dataset, model, test_outputs_dir, weighted=weighted, frac=frac, batch_size=batch_size, device=device)
-    _mlflow("log_artifact", test_outputs_dir)
+    mlflow_call("log_artifact", test_outputs_dir)
     for path in write_results(test_results, test_dataset.articulators, results_dir):
-        _mlflow("log_artifact", path)
+        mlflow_call("log_artifact", path)
     return {"results_dir": results_dir, "num_stored_frames": int(model.bank.shape[0]), **test_results}
 
 
 def parse_args(argv=None):
-    parser = argparse.ArgumentParser()
-    parser.add_argument("--config", dest="config_filepath")
-    parser.add_argument("--mlflow", dest="mlflow_tracking_uri", default=None)
-    parser.add_argument("--experiment", dest="experiment_name", default="phoneme_wise_mean_contour")
-    parser.add_argument("--run_id", dest="run_id", default=None)
-    parser.add_argument("--run_name", dest="run_name", default=None)
-    return parser.parse_args(argv)
+    return cli_parser("phoneme_wise_mean_contour", checkpoint=False).parse_args(argv)
 
 
 if __name__ == "__main__":
-    args = parse_args()
-    with open(args.config_filepath) as f:
-        cfg = yaml.safe_load(f)
-    if mlflow is not None and args.mlflow_tracking_uri is not None:
-        mlflow.set_tracking_uri(args.mlflow_tracking_uri)
-        mlflow.set_experiment(args.experiment_name)
-    print(main(**cfg))
+    print(run_cli(main, "phoneme_wise_mean_contour", checkpoint=False))

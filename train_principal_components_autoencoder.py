@@ -10,16 +10,10 @@
 # checkpoint.pt like the reference, and ends with run_multiart_autoencoder_test on the test split (loss + p2cp_mm).
 #
 ####################################################################################################
-import argparse
 import logging
-import os
-import random
-import shutil
-import tempfile
 
 import numpy as np
 import torch
-import yaml
 from torch.optim import Adam
 from torch.optim.lr_scheduler import ReduceLROnPlateau
 from torch.utils.data import DataLoader
@@ -35,16 +29,7 @@ from artspeech_amd.phoneme_to_articulation.principal_components.dataset import (
 from artspeech_amd.phoneme_to_articulation.principal_components.losses import RegularizedLatentsMSELoss2
 from artspeech_amd.phoneme_to_articulation.principal_components.models.autoencoder import MultiArticulatorAutoencoder
 from artspeech_amd.settings import DATASET_CONFIG, TRAIN, VALID
-
-try:  # mlflow is optional here (absent from the MI355X image): same flags, no-op logging
-    import mlflow
-except ImportError:
-    mlflow = None
-
-
-def _mlflow(fn, *args, **kwargs):
-    if mlflow is not None:
-        return getattr(mlflow, fn)(*args, **kwargs)
+from artspeech_amd.training import fit, load_checkpoint, mlflow_call, results_paths, run_cli, synthetic_size
 
 
 def reconstruction_error(outputs, targets, denorm_fn_dict, px_space=1, res=1):
@@ -65,9 +50,7 @@ def reconstruction_error(outputs, targets, denorm_fn_dict, px_space=1, res=1):
 
 def _make_dataset(datadir, database_name, seq_dict, articulators, clip_tails, synthetic, seed):
     if datadir == "synthetic":
-        cfg = dict(synthetic or {})
-        n = (seq_dict or {}).get("num_frames", cfg.pop("num_frames", 256))
-        cfg.pop("num_frames", None)
+        n, cfg = synthetic_size(seq_dict, synthetic, "num_frames", 256)
         return SyntheticPrincipalComponentsAutoencoderDataset(n, articulators, seed=seed, database_name=database_name, **cfg)
     return PrincipalComponentsAutoencoderDataset2(database_name=database_name, datadir=datadir,
                                                   sequences=sequences_from_dict(datadir, seq_dict), articulators=articulators,
@@ -79,13 +62,9 @@ def main(database_name, datadir, n_epochs, batch_size, patience, learning_rate, 
          seed=0, synthetic=None, results_dir=None):
     device = torch.device("cuda", torch.cuda.current_device())
     logging.info(f"Running on '{device}'")
-    results_dir = results_dir or RESULTS_DIR
-    os.makedirs(results_dir, exist_ok=True)
-    best_encoders_path = os.path.join(results_dir, "best_encoders.pt")
-    best_decoders_path = os.path.join(results_dir, "best_decoders.pt")
-    last_encoders_path = os.path.join(results_dir, "last_encoders.pt")
-    last_decoders_path = os.path.join(results_dir, "last_decoders.pt")
-    save_checkpoint_path = os.path.join(results_dir, "checkpoint.pt")
+    (results_dir, best_encoders_path, best_decoders_path, last_encoders_path, last_decoders_path,
+     save_checkpoint_path) = results_paths(results_dir, "artspeech_pc_ae_", ("best_encoders.pt", "best_decoders.pt", "last_encoders.pt",
+                                                                              "last_decoders.pt", "checkpoint.pt"))
 
     model_params = dict(model_params)
     indices_dict = model_params["indices_dict"]
@@ -100,7 +79,7 @@ def main(database_name, datadir, n_epochs, batch_size, patience, learning_rate, 
     autoencoder.to(device)
     print(f"\nMultiArticulatorAutoencoder -- {autoencoder.total_parameters} parameters\n")
     # the reference logs `model.total_parameters` here, an undefined name (NameError): the autoencoder's count is meant
-    _mlflow("log_param", "num_network_params", autoencoder.total_parameters)
+    mlflow_call("log_param", "num_network_params", autoencoder.total_parameters)
 
     gen = torch.Generator(device="cpu")
     gen.manual_seed(seed)
@@ -121,53 +100,22 @@ def main(database_name, datadir, n_epochs, batch_size, patience, learning_rate, 
     metrics = {"p2cp_mm": lambda outputs, targets: reconstruction_error(
         outputs, targets, denorm_fn_dict=denorm_fn_dict, px_space=dataset_config.PIXEL_SPACING, res=dataset_config.RES)}
 
-    best_metric = np.inf
-    epochs_since_best = 0
-    epochs = range(1, n_epochs + 1)
-    if checkpoint_filepath is not None:
-        checkpoint = torch.load(checkpoint_filepath, map_location=device)
-        autoencoder.load_state_dict(checkpoint["model"])
-        optimizer.load_state_dict(checkpoint["optimizer"])
-        scheduler.load_state_dict(checkpoint["scheduler"])
-        epoch = checkpoint["epoch"] + 1
-        epochs = range(epoch, n_epochs + 1)
-        best_metric = checkpoint["best_metric"]
-        epochs_since_best = checkpoint["epochs_since_best"]
-        logging.info(f"Loaded checkpoint -- training from epoch {epoch}, best metric {best_metric} "
-                     f"seen {epochs_since_best} epochs ago.")
-
-    history = []
-    for epoch in epochs:
-        info_train = run_autoencoder_epoch(phase=TRAIN, epoch=epoch, model=autoencoder, dataloader=train_dataloader,
-                                           optimizer=optimizer, criterion=loss_fn, device=device)
-        _mlflow("log_metrics", {f"train_{m}": v for m, v in info_train.items()}, step=epoch)
-        info_valid = run_autoencoder_epoch(phase=VALID, epoch=epoch, model=autoencoder, dataloader=valid_dataloader,
-                                           optimizer=optimizer, criterion=loss_fn, fn_metrics=metrics, device=device)
-        _mlflow("log_metrics", {f"valid_{m}": v for m, v in info_valid.items()}, step=epoch)
-        history.append({"epoch": epoch, "train": info_train, "valid": info_valid})
-
-        if info_valid["p2cp_mm"] < best_metric:
-            best_metric = info_valid["p2cp_mm"]
-            epochs_since_best = 0
-            torch.save(autoencoder.encoders.state_dict(), best_encoders_path)
-            torch.save(autoencoder.decoders.state_dict(), best_decoders_path)
-            _mlflow("log_artifact", best_encoders_path)
-            _mlflow("log_artifact", best_decoders_path)
-        else:
-            epochs_since_best += 1
-        torch.save(autoencoder.encoders.state_dict(), last_encoders_path)
-        torch.save(autoencoder.decoders.state_dict(), last_decoders_path)
-        _mlflow("log_artifact", last_encoders_path)
-        _mlflow("log_artifact", last_decoders_path)
-        checkpoint = {"epoch": epoch, "model": autoencoder.state_dict(), "optimizer": optimizer.state_dict(),
-                      "scheduler": scheduler.state_dict(), "best_metric": float(best_metric), "epochs_since_best": epochs_since_best,
-                      "best_encoders_path": best_encoders_path, "best_decoders_path": best_decoders_path,
-                      "last_encoders_path": last_encoders_path, "last_decoders_path": last_decoders_path}
-        torch.save(checkpoint, save_checkpoint_path)
-        _mlflow("log_artifact", save_checkpoint_path)
-        print(f"\nFinished training epoch {epoch}\nBest metric: {best_metric}, Epochs since best: {epochs_since_best}\n")
-        if epochs_since_best > patience:
-            break
+    # the scheduler is built and saved but never stepped, as in the reference
+    first_epoch, best_metric, epochs_since_best, _ = load_checkpoint(checkpoint_filepath, autoencoder, optimizer, scheduler,
+                                                                     map_location=device)
+    encoders, decoders = autoencoder.encoders.state_dict, autoencoder.decoders.state_dict
+    history = fit(range(first_epoch, n_epochs + 1),
+                  lambda epoch: run_autoencoder_epoch(phase=TRAIN, epoch=epoch, model=autoencoder, dataloader=train_dataloader,
+                                                      optimizer=optimizer, criterion=loss_fn, device=device),
+                  lambda epoch: run_autoencoder_epoch(phase=VALID, epoch=epoch, model=autoencoder, dataloader=valid_dataloader,
+                                                      optimizer=optimizer, criterion=loss_fn, fn_metrics=metrics, device=device),
+                  metric="p2cp_mm", patience=patience, best_files=[(best_encoders_path, encoders), (best_decoders_path, decoders)],
+                  last_files=[(last_encoders_path, encoders), (last_decoders_path, decoders)], checkpoint_path=save_checkpoint_path,
+                  checkpoint_state=lambda: {"model": autoencoder.state_dict(), "optimizer": optimizer.state_dict(),
+                                            "scheduler": scheduler.state_dict(), "best_encoders_path": best_encoders_path,
+                                            "best_decoders_path": best_decoders_path, "last_encoders_path": last_encoders_path,
+                                            "last_decoders_path": last_decoders_path},
+                  best_metric=best_metric, epochs_since_best=epochs_since_best)
 
     # test split: the best encoders / decoders through the test harness, as the reference does (:298): the
     # latent covariance per articulator goes to results_dir
@@ -179,32 +127,9 @@ def main(database_name, datadir, n_epochs, batch_size, patience, learning_rate, 
     info_test = run_multiart_autoencoder_test(epoch=0, model=best_autoencoder, dataloader=test_dataloader, criterion=loss_fn,
                                               dataset_config=dataset_config, plots_dir=results_dir, indices_dict=indices_dict,
                                               fn_metrics=metrics, device=device)
-    _mlflow("log_metrics", {f"test_{m}": v for m, v in info_test.items()}, step=0)
+    mlflow_call("log_metrics", {f"test_{m}": v for m, v in info_test.items()}, step=0)
     return {"history": history, "test": info_test, "results_dir": results_dir}
 
 
-TMP_DIR = tempfile.mkdtemp(prefix="artspeech_pc_ae_")
-RESULTS_DIR = os.path.join(TMP_DIR, "results")
-
 if __name__ == "__main__":
-    parser = argparse.ArgumentParser()
-    parser.add_argument("--config", dest="config_filepath")
-    parser.add_argument("--mlflow", dest="mlflow_tracking_uri", default=None)
-    parser.add_argument("--experiment", dest="experiment_name", default="multiarticulator_autoencoder")
-    parser.add_argument("--run_id", dest="run_id", default=None)
-    parser.add_argument("--run_name", dest="run_name", default=None)
-    parser.add_argument("--checkpoint", dest="checkpoint_filepath", default=None)
-    args = parser.parse_args()
-    seed = 0
-    random.seed(seed)
-    torch.manual_seed(seed)
-    np.random.seed(seed)
-    with open(args.config_filepath) as f:
-        cfg = yaml.safe_load(f)
-    if mlflow is not None and args.mlflow_tracking_uri is not None:
-        mlflow.set_tracking_uri(args.mlflow_tracking_uri)
-        mlflow.set_experiment(args.experiment_name)
-    try:
-        main(**cfg, checkpoint_filepath=args.checkpoint_filepath, seed=seed)
-    finally:
-        shutil.rmtree(TMP_DIR, ignore_errors=True)
+    run_cli(main, "multiarticulator_autoencoder")
