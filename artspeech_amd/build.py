@@ -14,7 +14,7 @@ ARCH = "gfx950"
 COMMON = ["-O3", "-fPIC", "-std=c++17", f"-I{os.path.join(ROOT, 'include')}", f"-I{CSRC}"]
 # per-file extra flags: metrics.hip keeps IEEE op-by-op arithmetic (arg-min pairs and the fp64 area
 # function must be bit-reproducible), so no fused multiply-add contraction there; pc_eval.hip likewise (its denormalisation
-# is torch's multiply, then add).
+# is torch's multiply, then add); p2cp_loss.hip finds its closest points with metrics.hip's arithmetic, so it is built alike.
 SOURCES = {
     "error.cpp": [],
     "prof.hip": [],
@@ -31,6 +31,7 @@ SOURCES = {
     "recog_eval.hip": [],
     "attention.hip": [],
     "metrics.hip": ["-ffp-contract=off"],
+    "p2cp_loss.hip": ["-ffp-contract=off"],
     "multi_mlp.hip": [],
     "pca.hip": [],
     "mean_contour.hip": [],

@@ -107,6 +107,27 @@ __device__ __forceinline__ float as_p2cp_scan(float px, float py, const float* _
     }
     return m;
 }
+// The arg-min sibling (p2cp_loss.hip): the same squared distances from the same expression, so *m_out is as_p2cp_scan's
+// value bit for bit, and the LOWEST index that attains it (strict < in ascending order: torch.min's tie rule).  A padding
+// point (+inf) or a NaN distance is never taken; n >= 1 real points, so the index is one of theirs.
+__device__ __forceinline__ int as_p2cp_scan_argmin(float px, float py, const float* __restrict__ qx, const float* __restrict__ qy, int n4,
+                                                   float* __restrict__ m_out) {
+    const f32x2 px2 = {px, px}, py2 = {py, py};
+    float m = INFINITY;
+    int at = 0;
+    for (int j = 0; j < n4; j += 4) {
+        const float4 x4 = *reinterpret_cast<const float4*>(qx + j), y4 = *reinterpret_cast<const float4*>(qy + j);
+        const f32x2 dxa = px2 - f32x2{x4.x, x4.y}, dxb = px2 - f32x2{x4.z, x4.w};
+        const f32x2 dya = py2 - f32x2{y4.x, y4.y}, dyb = py2 - f32x2{y4.z, y4.w};
+        const f32x2 sa = dxa * dxa + dya * dya, sb = dxb * dxb + dyb * dyb;
+        if (sa.x < m) { m = sa.x; at = j; }
+        if (sa.y < m) { m = sa.y; at = j + 1; }
+        if (sb.x < m) { m = sb.x; at = j + 2; }
+        if (sb.y < m) { m = sb.y; at = j + 3; }
+    }
+    *m_out = m;
+    return at;
+}
 
 // ---- exact (erf) GELU and d gelu / dx = Phi(x) + x phi(x)
 __device__ __forceinline__ float as_gelu(float x) { return 0.5f * x * (1.0f + erff(x * 0.70710678118654752440f)); }

@@ -330,6 +330,30 @@ int as_euclid_masked_fwd_bwd_presigmoid(const float* out, const float* tgt, int6
 int as_p2cp_fwd(const float* u, int64_t u_tile, int64_t u_pt, int64_t u_xy, int32_t n_u, const float* v,
                 int64_t v_tile, int64_t v_pt, int64_t v_xy, int32_t n_v, int64_t tiles, float* out, void* stream);
 
+/* Gradient of as_p2cp_fwd (MeanP2CPDistance, phoneme_to_articulation/metrics.py:27-46, which the reference differentiates
+ * through torch.cdist / min): dout [tiles] -> du, dv, addressed like u, v with their own tile / point / xy strides; either may
+ * be NULL (that side is not computed; the other side's bits do not change).  With j*(i) the closest v point to u_i, i*(j) the
+ * closest u point to v_j -- both from the forward's squared-distance arithmetic, the LOWEST index among equals (torch.min) --
+ * and e(a, b) = (a - b) / |a - b|, 0 where |a - b| = 0 (cdist's backward: a coincident pair contributes nothing, no NaN):
+ *   du_i = dout * ( e(u_i, v_j*(i)) / (2 n_u) + sum_{j : i*(j) = i} e(u_i, v_j) / (2 n_v) ),  dv_j the mirror image.
+ * No atomics, nothing saved by the forward; every sum runs in ascending index order: repeated runs are bit-identical.
+ * n_u, n_v in [1, 256], else AS_ERR_UNSUPPORTED before any launch. */
+int as_p2cp_bwd(const float* u, int64_t u_tile, int64_t u_pt, int64_t u_xy, int32_t n_u, const float* v, int64_t v_tile,
+                int64_t v_pt, int64_t v_xy, int32_t n_v, int64_t tiles, const float* dout, float* du, int64_t du_tile,
+                int64_t du_pt, int64_t du_xy, float* dv, int64_t dv_tile, int64_t dv_pt, int64_t dv_xy, void* stream);
+
+/* MeanP2CPDistance (metrics.py:27-46) as the training criterion: the criterion, padding mask and mean of
+ * train_phoneme_to_articulation.py:86-90 with the P2CP of every (frame, articulator) contour pair in place of the Euclidean
+ * distance, value and gradient from one pass over each tile (the twin of as_euclid_masked_fwd_bwd):
+ *   loss = scale * sum_{b, t < len_b, a} p2cp(out[b][t][a], tgt[b][t][a]),   dout [B][T][A][2][N] = d loss / d out.
+ * out [B][T][A][2][N], tgt [B][tgt_T][A][2][N] (the (.., 2, N) storage as it is); padded frames are never read (a NaN there
+ * does not leak) and their dout is exactly 0; dout may be NULL (evaluation).  scale = 1 / (N_valid * A) with N_valid the
+ * GLOBAL number of valid frames, so that data-parallel shards sum to the global mean.  loss: one float, overwritten;
+ * partial: workspace of as_p2cp_masked_partials() floats (workgroup sums, then one fixed-order final sum).  N in [1, 256]. */
+int32_t as_p2cp_masked_partials(void);
+int as_p2cp_masked_fwd_bwd(const float* out, const float* tgt, int64_t tgt_T, const int32_t* lengths, int32_t B, int32_t T,
+                           int32_t A, int32_t N, float scale, float* loss, float* dout, float* partial, void* stream);
+
 /* P2CPDistance.forward (encoder_decoder/metrics.py:18-26) reduction: p2cp [B][T][A], lengths ->
  * result[0] = mean_b( mean_{t < len_b, a} p2cp * to_mm ). */
 int as_p2cp_utterance_mean(const float* p2cp, const int32_t* lengths, int32_t B, int32_t T, int32_t A, float to_mm,

@@ -8,7 +8,9 @@
 # same YAML keys (= the keyword arguments of main()), same run_epoch() contract, same checkpoint dict.
 # Extras: `datadir: synthetic` trains on SyntheticArtSpeechDataset; launched under torchrun
 # (one process per GPU) every global batch is sharded by utterance and the flat gradient buffer is
-# all-reduced over RCCL before the optimizer step.
+# all-reduced over RCCL before the optimizer step; `loss: p2cp` trains on the mean point-to-closest-point distance (the
+# reference's MeanP2CPDistance, metrics.py:27-46, the figure the model is selected and reported by) instead of the
+# Euclidean distance.
 #
 ####################################################################################################
 import json
@@ -33,7 +35,8 @@ from artspeech_amd.phoneme_to_articulation.encoder_decoder.dataset import (
 from artspeech_amd.phoneme_to_articulation.encoder_decoder.evaluation import run_test
 from artspeech_amd.phoneme_to_articulation.encoder_decoder.metrics import P2CPDistance
 from artspeech_amd.phoneme_to_articulation.encoder_decoder.models import ArtSpeech
-from artspeech_amd.phoneme_to_articulation.metrics import EuclideanDistance, masked_euclidean_loss
+from artspeech_amd.phoneme_to_articulation.metrics import (EuclideanDistance, MeanP2CPDistance, masked_euclidean_loss,
+                                                            masked_p2cp_loss)
 from artspeech_amd.settings import DATASET_CONFIG, TRAIN, VALID
 from artspeech_amd.training import (build_vocabulary, fit, load_checkpoint, mlflow_call, results_paths, run_cli,
                                     synthetic_size)
@@ -55,7 +58,9 @@ def run_epoch(phase, epoch, model, dataloader, optimizer, criterion, fn_metrics=
     losses = []
     metrics_values = {name: [] for name in fn_metrics}
     # reduction "none" (the training configuration): criterion + mask + mean collapse into one kernel
-    fused = isinstance(criterion, EuclideanDistance) and getattr(torch, criterion.reduction_name, None) is None
+    fused = None
+    if isinstance(criterion, (EuclideanDistance, MeanP2CPDistance)) and getattr(torch, criterion.reduction_name, None) is None:
+        fused = masked_euclidean_loss if isinstance(criterion, EuclideanDistance) else masked_p2cp_loss
     deferred = hasattr(model, "check_tokens")   # token-id check next to the loop's own loss.item() instead of a sync per forward
     keep_defer = getattr(model, "defer_token_check", False)
     if deferred:
@@ -82,8 +87,8 @@ def _run_epoch_batches(phase, model, dataloader, optimizer, criterion, fn_metric
         optimizer.zero_grad()
         with torch.set_grad_enabled(training):
             outputs = model(sentence, lengths)
-            if fused:  # criterion + padding mask + mean in one kernel; shard losses sum to the global mean
-                loss = masked_euclidean_loss(outputs, targets, lengths, n_valid_global=n_valid_global)
+            if fused is not None:  # criterion + padding mask + mean in one kernel; shard losses sum to the global mean
+                loss = fused(outputs, targets, lengths, n_valid_global=n_valid_global)
             else:      # the reference's expression (:86-90)
                 loss = criterion(outputs, targets[:, :outputs.shape[1]])
                 padding_mask = make_padding_mask(lengths)
@@ -121,7 +126,11 @@ def _make_dataset(datadir, database_name, seq_dict, vocabulary, articulators, cl
 
 def main(datadir, database_name, num_epochs, batch_size, patience, learning_rate, weight_decay, train_seq_dict,
          valid_seq_dict, test_seq_dict, vocab_filepath, articulators, model_kwargs=None, num_workers=0, clip_tails=True,
-         state_dict_filepath=None, checkpoint_filepath=None, seed=0, synthetic=None, results_dir=None, hbm_resident=False):
+         state_dict_filepath=None, checkpoint_filepath=None, seed=0, synthetic=None, results_dir=None, hbm_resident=False,
+         loss="euclidean"):
+    criteria = {"euclidean": EuclideanDistance, "p2cp": MeanP2CPDistance}
+    if loss not in criteria:   # before the device is touched
+        raise ValueError(f"loss must be 'euclidean' or 'p2cp', got {loss!r}")
     if "RANK" in os.environ and int(os.environ.get("WORLD_SIZE", "1")) > 1 and not dist.is_initialized():
         backend = os.environ.get("ARTSPEECH_DIST_BACKEND", "nccl")  # "gloo": rehearsal with several ranks on one GPU
         torch.cuda.set_device(int(os.environ.get("LOCAL_RANK", "0")) if backend == "nccl" else 0)
@@ -142,7 +151,7 @@ def main(datadir, database_name, num_epochs, batch_size, patience, learning_rate
         print(f"\nArtSpeech -- {model.total_parameters} parameters\n")
     mlflow_call("log_param", "num_network_params", model.total_parameters)
 
-    loss_fn = EuclideanDistance(reduction="none")
+    loss_fn = criteria[loss](reduction="none")
     optimizer = Adam(model.parameters(), lr=learning_rate, weight_decay=weight_decay)
     scheduler = ReduceLROnPlateau(optimizer, factor=0.1, patience=10)
     gen = torch.Generator(device="cpu")
