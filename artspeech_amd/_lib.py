@@ -175,6 +175,7 @@ PROTOTYPES = {
     "as_mean_contour_weighted_fwd": (_I32, [_P, _P, _P, _P, _P, _P, _I32, _I32, _I32, _I32, _P, _P, _P]),
     "as_pc_shapes_eval": (_I32, [_P, _P, _P, _P, _P, _I32, _P, _I32, _I64, _I32, _I32, _F, _P, _P, _P, _P]),
     "as_pc_eval_accumulate": (_I32, [_P, _I32, _P, _P, _I32, _P, _I64, _P, _I32, _P]),
+    "as_segment_corr": (_I32, [_P, _P, _I64, _I32, _D, _P, _I32, _P, _P, _P]),
     "as_masked_mse_partials": (_I32, []),
     "as_masked_mse_fwd_bwd": (_I32, [_P, _P, _I64, _I64, _P, _I32, _P, _F, _P, _P, _P, _P]),
     "as_profile_enable": (None, [_I32]),

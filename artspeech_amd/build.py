@@ -14,7 +14,8 @@ ARCH = "gfx950"
 COMMON = ["-O3", "-fPIC", "-std=c++17", f"-I{os.path.join(ROOT, 'include')}", f"-I{CSRC}"]
 # per-file extra flags: metrics.hip keeps IEEE op-by-op arithmetic (arg-min pairs and the fp64 area
 # function must be bit-reproducible), so no fused multiply-add contraction there; pc_eval.hip likewise (its denormalisation
-# is torch's multiply, then add); p2cp_loss.hip finds its closest points with metrics.hip's arithmetic, so it is built alike.
+# is torch's multiply, then add); p2cp_loss.hip finds its closest points with metrics.hip's arithmetic, so it is built alike;
+# report.hip rounds x * scale before it centres it, like the reference's table in mm.
 SOURCES = {
     "error.cpp": [],
     "prof.hip": [],
@@ -36,6 +37,7 @@ SOURCES = {
     "pca.hip": [],
     "mean_contour.hip": [],
     "pc_eval.hip": ["-ffp-contract=off"],
+    "report.hip": ["-ffp-contract=off"],
     "artspeech.hip": [],
 }
 

@@ -64,6 +64,16 @@ __device__ __forceinline__ double as_wave_sum_d(double v) {
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
     return v;
 }
+__device__ __forceinline__ double as_wave_min_d(double v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = fmin(v, __shfl_xor(v, o, 64));
+    return v;
+}
+__device__ __forceinline__ double as_wave_max_d(double v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o, 64));
+    return v;
+}
 // ReLU that keeps a NaN a NaN, like torch.relu (fmaxf(NaN, 0) = 0 would hide an invalid activation: the transformer's test
 // loop finds utterances with NaN predictions by exactly that propagation, transformer/evaluation.py:69-86)
 __device__ __forceinline__ float as_relu(float v) { return v < 0.f ? 0.f : v; }

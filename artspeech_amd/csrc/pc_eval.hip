@@ -91,17 +91,6 @@ __global__ __launch_bounds__(256) void pc_shapes_eval_kernel(const float* __rest
     if (lane == 0) p2cp_mm[tile] = ((su / N + sv / N) * 0.5f) * to_mm;
 }
 
-__device__ __forceinline__ double pce_wave_min(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fmin(v, __shfl_xor(v, o, 64));
-    return v;
-}
-__device__ __forceinline__ double pce_wave_max(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o, 64));
-    return v;
-}
-
 // st [5][A]: count | mean | M2 | min | max.  Lane l takes the rows l, l + 64, ...; the butterfly adds the 64 partials in one order.
 __global__ __launch_bounds__(256) void pc_eval_errors_kernel(const float* __restrict__ e, int A, int64_t rows,
                                                              const int32_t* __restrict__ lengths, int T, double* __restrict__ st) {
@@ -124,8 +113,8 @@ __global__ __launch_bounds__(256) void pc_eval_errors_kernel(const float* __rest
             mx = fmax(mx, x);
         }
     q = as_wave_sum_d(q);
-    mn = pce_wave_min(mn);
-    mx = pce_wave_max(mx);
+    mn = as_wave_min_d(mn);
+    mx = as_wave_max_d(mx);
     if (lane != 0) return;
     const double n = st[a], nn = n + m, delta = bmean - st[A + a];
     st[2 * A + a] = st[2 * A + a] + q + delta * delta * (n * m / nn);

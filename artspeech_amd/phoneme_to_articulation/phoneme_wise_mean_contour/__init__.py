@@ -419,13 +419,15 @@ def train(dataset, save_to=None, weighted=False, frac=1.0, random_state=0, devic
     return model
 
 
-def test(dataset, df, save_to, weighted=False, frac=0.1, random_state=0, batch_size=32, regularize_out=False, device=None):
+def test(dataset, df, save_to, weighted=False, frac=0.1, random_state=0, batch_size=32, regularize_out=False, device=None,
+         report_dir=None):
     """The reference's ``test`` (:162-254): ``df`` is a model, a table file or a saved state_dict; a full table is first reduced to
     the reference's per-token sample (``frac``, ``random_state``; ``frac=None`` keeps the bank as it is).  Per sentence: the mean
     Euclidean distance, the Pearson correlations, tract variables and contour dumps under ``save_to/0`` with the upper incisor
     injected from the reference contour; sentences are evaluated ``batch_size`` at a time, one launch per batch.  Returns
     ``{"loss", articulator: {"x_corr", "y_corr"}}``, each the mean over sentences.  ``regularize_out`` (the reference passes True)
-    needs the external vt_tools package."""
+    needs the external vt_tools package.  ``report_dir``: also write the result tables of ..report there, from the frames of this
+    pass."""
     from ..encoder_decoder.evaluation import _Accumulator
     from ..metrics import EuclideanDistance
     model = _as_model(df, device)
@@ -437,7 +439,7 @@ def test(dataset, df, save_to, weighted=False, frac=0.1, random_state=0, batch_s
     save_to = os.path.join(save_to, "0")  # Keep compatibility with other methods
     os.makedirs(save_to, exist_ok=True)
     criterion = EuclideanDistance()
-    acc = _Accumulator(articulators, save_to, dev, regularize_out)
+    acc = _Accumulator(articulators, save_to, dev, regularize_out, report_dir, getattr(dataset, "dataset_config", None))
     for start in range(0, len(dataset), batch_size):
         items = [dataset[i] for i in range(start, min(start + batch_size, len(dataset)))]
         lengths = [len(item[3]) for item in items]
@@ -453,6 +455,7 @@ def test(dataset, df, save_to, weighted=False, frac=0.1, random_state=0, batch_s
             loss = criterion(sentence_outputs, sentence_targets)
             acc.add(loss.item(), sentence_outputs, sentence_targets, [length], [sentence_name], [frame_ids], [sentence_tokens],
                     reference_arrays.float().unsqueeze(dim=0))
+    acc.write_report()
     info = {"loss": float(np.mean(acc.losses))}
     info.update({
         art: {"x_corr": float(np.mean(acc.x_corrs[i])), "y_corr": float(np.mean(acc.y_corrs[i]))}

@@ -9,13 +9,14 @@ from ..encoder_decoder.evaluation import _Accumulator
 from ..metrics import masked_euclidean_loss
 
 
-def run_transformer_test(epoch, model, dataloader, criterion, outputs_dir, articulators, device=None, regularize_out=False):
+def run_transformer_test(epoch, model, dataloader, criterion, outputs_dir, articulators, device=None, regularize_out=False,
+                         report_dir=None):
     if device is None:
         device = torch.device("cuda")
     epoch_outputs_dir = os.path.join(outputs_dir, str(epoch))
     os.makedirs(epoch_outputs_dir, exist_ok=True)
     model.eval()
-    acc = _Accumulator(articulators, epoch_outputs_dir, device, regularize_out)
+    acc = _Accumulator(articulators, epoch_outputs_dir, device, regularize_out, report_dir, dataloader.dataset.dataset_config)
     for (sentences_ids, sentences, targets, lengths, phonemes, reference_arrays, sentence_frames, _, src_key_padding_mask, _, _,
          _) in dataloader:
         sentences, targets = sentences.to(device), targets.to(device)
@@ -40,4 +41,5 @@ def run_transformer_test(epoch, model, dataloader, criterion, outputs_dir, artic
         n = len(keep)
         acc.add(loss.item(), outputs, targets, lengths[:n], list(sentences_ids[:n]), list(sentence_frames[:n]), list(phonemes[:n]),
                 reference_arrays)
+    acc.write_report()
     return acc.info(dataloader.dataset.dataset_config)

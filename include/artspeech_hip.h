@@ -805,6 +805,20 @@ int as_pc_shapes_eval(const float* shapes, const float* targets, const float* me
 int as_pc_eval_accumulate(const float* p2cp_mm, int32_t A, double* err_state, const float* latents, int32_t L, double* lat_state,
                           int64_t rows, const int32_t* lengths, int32_t T, void* stream);
 
+/* Per-segment Pearson correlation of two tables with its summary (artspeech_amd/csrc/report.hip; reference
+ * report_phoneme_to_articulation.py:256-285: df.groupby("sentence")[[target, pred]].corr() per tract variable, then mean / std /
+ * min / max of the sentences' coefficients).  a, b [rows][K] float32; segment s owns the rows [seg_first[s], seg_first[s + 1])
+ * (seg_first int64 [S + 1] on the device, clipped to [0, rows]; segments need not cover all rows).  Every value is (double)x * scale;
+ *   corr [S][K]    = sum(ac bc) / sqrt(sum(ac^2) sum(bc^2)) of the centred values; NaN for a segment of fewer than 2 rows and
+ *                    whenever the values of either column inside the segment are all bit-identical (pandas answers NaN there; the
+ *                    centred sums would be rounding noise)
+ *   summary [5][K] = count | mean | std (n - 1) | min | max over the finite corr of each column: std is NaN below 2 finite
+ *                    coefficients; without one, count is 0 and the rest NaN.  min and max are elements of corr.
+ * One wave per (segment, column), two passes (means, then centred sums), fp64 after the fp32 load, every sum in a fixed order that
+ * does not depend on the launch geometry, no atomics: repeats are bit-identical.  S may be 0 (corr may then be NULL). */
+int as_segment_corr(const float* a, const float* b, int64_t rows, int32_t K, double scale, const int64_t* seg_first, int32_t S,
+                    double* corr, double* summary, void* stream);
+
 /* Optional per-kernel-phase timing with HIP events recorded on the launch stream (for bench.py's
  * roofline object).  as_profile_report writes "name count total_ms\n" lines (NUL terminated, truncated
  * to buflen) and returns the untruncated length; it waits for the recorded events to complete. */
