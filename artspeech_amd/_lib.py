@@ -178,10 +178,14 @@ PROTOTYPES = {
     "as_segment_corr": (_I32, [_P, _P, _I64, _I32, _D, _P, _I32, _P, _P, _P]),
     "as_masked_mse_partials": (_I32, []),
     "as_masked_mse_fwd_bwd": (_I32, [_P, _P, _I64, _I64, _P, _I32, _P, _F, _P, _P, _P, _P]),
+    "as_prepare_contours": (_I32, [_P, _P, _P, _I64, _I32, _I32, _F, _F, _F, _F, _P, _P, _I32, _P, _P, _P, _P]),
+    "as_column_mean_std": (_I32, [_P, _I64, _I32, _P, _P, _P, _I64, _P]),
     "as_profile_enable": (None, [_I32]),
     "as_profile_reset": (None, []),
     "as_profile_report": (_I32, [C.c_char_p, _I32]),
 }
+
+COLUMN_STATS_PART_ROWS = 512   # AS_COLUMN_STATS_PART_ROWS of the header: sizes as_column_mean_std's workspace
 
 _lib = None
 

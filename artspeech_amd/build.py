@@ -15,7 +15,8 @@ COMMON = ["-O3", "-fPIC", "-std=c++17", f"-I{os.path.join(ROOT, 'include')}", f"
 # per-file extra flags: metrics.hip keeps IEEE op-by-op arithmetic (arg-min pairs and the fp64 area
 # function must be bit-reproducible), so no fused multiply-add contraction there; pc_eval.hip likewise (its denormalisation
 # is torch's multiply, then add); p2cp_loss.hip finds its closest points with metrics.hip's arithmetic, so it is built alike;
-# report.hip rounds x * scale before it centres it, like the reference's table in mm.
+# report.hip rounds x * scale before it centres it, like the reference's table in mm; contours.hip's results are selections
+# and op-by-op float32 arithmetic ((p - u) + 0.3, (x - mean) / std), bit-equal to the reference's torch expressions.
 SOURCES = {
     "error.cpp": [],
     "prof.hip": [],
@@ -38,6 +39,7 @@ SOURCES = {
     "mean_contour.hip": [],
     "pc_eval.hip": ["-ffp-contract=off"],
     "report.hip": ["-ffp-contract=off"],
+    "contours.hip": ["-ffp-contract=off"],
     "artspeech.hip": [],
 }
 

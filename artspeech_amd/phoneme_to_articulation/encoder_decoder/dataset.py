@@ -4,8 +4,8 @@
 very same 8- / 12-tuples (same field order, dtypes, padding values).  ``SyntheticArtSpeechDataset``
 yields items in the 8-field layout of ``ArtSpeechDataset.__getitem__`` (:215-224) from a seeded
 generator (the private MRI corpora are not available; SURVEY 8d describes the synthetic distribution).
-``ArtSpeechDataset`` keeps the reference's constructor for real data and needs the same external
-packages the reference needs (database_collector / vt_shape_gen), which are outside this hot path.
+``ArtSpeechDataset`` keeps the reference's constructor for real data; it prepares its contours with this
+engine's own loader and clipper and needs only the reference's database_collector to walk a corpus.
 """
 import torch
 from torch.nn.utils.rnn import pad_sequence
@@ -90,22 +90,28 @@ class SyntheticArtSpeechDataset(Dataset):
 
 
 class ArtSpeechDataset(Dataset):
-    """Real-data dataset with the reference's constructor (dataset.py:131-156).  Walking the MRI
-    corpora needs the reference's own data stack (``database_collector.DATABASE_COLLECTORS`` and
-    ``phoneme_to_articulation.InputLoaderMixin`` with vt_shape_gen / vt_tools): real-data I/O is outside
-    the accelerated path, so this class only adapts those objects when they are importable."""
+    """Real-data dataset with the reference's constructor (dataset.py:131-156).  Walking the MRI corpora needs the
+    reference's ``database_collector.DATABASE_COLLECTORS``; the contours themselves are read and prepared by this engine
+    (``phoneme_to_articulation.InputLoaderMixin``, csrc/contours.hip).
+
+    Without ``device`` an item is prepared frame by frame and articulator by articulator through
+    ``InputLoaderMixin.prepare_articulator_array`` like the reference's (one launch each, in the calling process: use
+    num_workers=0).  With ``device`` (opt-in) a whole sentence is one ``load_raw_contours`` + ``prepare_contours`` call and the
+    item's targets and references stay on that device; main process only, like ``HBMResidentDataset``.  Both give the same
+    numbers bit for bit."""
 
     def __init__(self, datadir, database_name, sequences, vocabulary, articulators, n_samples=50, clip_tails=False,
-                 TVs=None, voiced_tokens=None):
+                 TVs=None, voiced_tokens=None, device=None):
         try:
             from database_collector import DATABASE_COLLECTORS  # the reference's collectors
-            from phoneme_to_articulation import InputLoaderMixin
         except ImportError as exc:
             raise ImportError(
-                "ArtSpeechDataset reads the real-time MRI corpora through the reference's database_collector / "
-                "vt_shape_gen stack, which is not part of artspeech_amd; use SyntheticArtSpeechDataset, or put the "
-                "reference repository and its dependencies on PYTHONPATH") from exc
+                "ArtSpeechDataset walks the real-time MRI corpora through the reference's database_collector, which is not "
+                "part of artspeech_amd; use SyntheticArtSpeechDataset, or put the reference repository and its dependencies "
+                "on PYTHONPATH") from exc
+        from .. import InputLoaderMixin
         self._loader = InputLoaderMixin
+        self.device = torch.device(device) if device is not None else None
         self.vocabulary = vocabulary
         self.datadir = datadir
         self.articulators = sorted(articulators)
@@ -121,22 +127,37 @@ class ArtSpeechDataset(Dataset):
     def __len__(self):
         return len(self.data)
 
+    def _prepare_sentence(self, item):
+        from torch.utils.data import get_worker_info
+        from .. import load_raw_contours, prepare_contours
+        if get_worker_info() is not None:
+            raise RuntimeError("ArtSpeechDataset(device=...) prepares its items on the GPU: use num_workers=0")
+        raw, refs = load_raw_contours(self.datadir, item["subject"], item["sequence"], item["frame_ids"], self.articulators,
+                                      norm_value=self.dataset_config.RES)
+        targets, references, _ = prepare_contours(raw.to(self.device), refs.to(self.device), self.articulators,
+                                                  self.dataset_config, clip_tails=self.clip_tails)
+        return targets, references
+
     def __getitem__(self, index):
         item = self.data[index]
-        frames, refs = [], []
-        for frame_id in item["frame_ids"]:
-            arts = []
-            for articulator in self.articulators:
-                arr, ref = self._loader.prepare_articulator_array(
-                    self.datadir, item["subject"], item["sequence"], frame_id, articulator, self.dataset_config,
-                    clip_tails=self.clip_tails)
-                arts.append(arr)
-            frames.append(torch.stack(arts))
-            refs.append(ref.unsqueeze(0))
+        if self.device is not None:
+            targets, references = self._prepare_sentence(item)
+        else:
+            frames, refs = [], []
+            for frame_id in item["frame_ids"]:
+                arts = []
+                for articulator in self.articulators:
+                    arr, ref = self._loader.prepare_articulator_array(
+                        self.datadir, item["subject"], item["sequence"], frame_id, articulator, self.dataset_config,
+                        clip_tails=self.clip_tails)
+                    arts.append(arr)
+                frames.append(torch.stack(arts))
+                refs.append(ref.unsqueeze(0))
+            targets, references = torch.stack(frames).float(), torch.stack(refs).float()
         tokens = item["phonemes"]
         numerized = torch.tensor([self.vocabulary.get(t, self.vocabulary[UNKNOWN]) for t in tokens], dtype=torch.long)
         voicing = torch.tensor([t in self.voiced_tokens for t in tokens], dtype=torch.float)
-        return (item["sentence_name"], numerized, torch.stack(frames).float(), tokens, torch.stack(refs).float(),
+        return (item["sentence_name"], numerized, targets, tokens, references,
                 torch.tensor([], dtype=torch.int), item["frame_ids"], voicing)
 
 

@@ -819,6 +819,42 @@ int as_pc_eval_accumulate(const float* p2cp_mm, int32_t A, double* err_state, co
 int as_segment_corr(const float* a, const float* b, int64_t rows, int32_t K, double scale, const int64_t* seg_first, int32_t S,
                     double* corr, double* summary, void* stream);
 
+/* Contour preparation (artspeech_amd/csrc/contours.hip; reference phoneme_to_articulation/__init__.py:57-118 and
+ * phoneme_to_articulation/tail_clipper.py:7-128): tail clipping, upper-incisor frame and optional normalisation of any number of
+ * frames in one launch, one wave per (frame, articulator).  All float arrays are float32 and contiguous.
+ *   raw  [F][A][N][2]   contour points as the loader yields them (point-major, divided by RES)
+ *   refs [F][3][N][2]   TailClipper.TAIL_CLIP_REFERENCES: lower incisor, upper incisor, epiglottis
+ *   kinds [A] int32     0 none, 1 tongue, 2 lower lip, 3 upper lip; NULL: no articulator is clipped.  With kinds, N must be 50
+ *                       (AS_ERR_UNSUPPORTED before any launch otherwise); without, any N >= 1
+ *   thr_*               10/PIXEL_SPACING/RES (tongue, back tail), 5/PIXEL_SPACING/RES (lower lip, front tail), 10/PIXEL_SPACING
+ *                       (upper lip, second half), 5/PIXEL_SPACING (upper lip, first half): each computed in double and rounded
+ *                       once to float by the caller, which is what torch does with a Python scalar next to a float32 tensor.  The
+ *                       upper lip's margins are NOT divided by RES in the reference: on RES-normalised contours they keep every
+ *                       point; reproduced as it is
+ *   mean, std [A][2][N] optional, together
+ *   out [F][A][2][N]    (p[i][c] - u[c]) + 0.3f, u = the last point of the frame's raw upper incisor (two rounded operations);
+ *                       with statistics then (. - mean) / std with IEEE division
+ *   ref_out [F][1][2][N] optional: the upper incisor in the same frame, never clipped, never normalised
+ *   counts [F][A]       optional: points kept before the last resampling; N for an articulator that is not clipped
+ *   point_major != 0    out is [F][A][N][2] and holds the clipped points as they are (what the reference's clip_*_tails
+ *                       methods return); mean, std and ref_out must be NULL
+ * Semantics are the reference's: halves are [:25] and [25:] of the current list, comparisons are strict and in float32 (a point on
+ * the threshold is dropped), resampling is F.interpolate(size=50) in nearest mode (output j = kept point floor(j n / 50)).
+ * A contour that keeps no point (the reference raises inside F.interpolate; possible for the tongue and the upper lip) gets
+ * counts = 0 and a NaN row; every other row is unaffected.  Inputs are finite: the NaN behaviour of argmax is not reproduced. */
+int as_prepare_contours(const float* raw, const float* refs, const int32_t* kinds, int64_t F, int32_t A, int32_t N, float thr_tongue,
+                        float thr_lower_lip, float thr_upper_lip_front, float thr_upper_lip_back, const float* mean, const float* std,
+                        int32_t point_major, float* out, float* ref_out, int32_t* counts, void* stream);
+/* Column mean and unbiased standard deviation of x [rows][cols] float32 (the reduction of the reference's
+ * scripts/calculate_normalization_statistics.py:73-75): mean [cols], std [cols] float32.  Two passes per partition of
+ * AS_COLUMN_STATS_PART_ROWS rows (mean, then centred squares), partitions merged by Chan's update, everything in fp64 after the
+ * fp32 load and rounded once at the end; the partition is a constant, the order of every sum is fixed, no atomics: repeats are
+ * bit-identical.  rows == 1 gives NaN std, like torch.std.  ws: caller's workspace of at least
+ * 2 * ceil(rows / AS_COLUMN_STATS_PART_ROWS) * cols doubles (AS_ERR_WORKSPACE below that). */
+#define AS_COLUMN_STATS_PART_ROWS 512
+int as_column_mean_std(const float* x, int64_t rows, int32_t cols, float* mean, float* std, double* ws, int64_t ws_doubles,
+                       void* stream);
+
 /* Optional per-kernel-phase timing with HIP events recorded on the launch stream (for bench.py's
  * roofline object).  as_profile_report writes "name count total_ms\n" lines (NUL terminated, truncated
  * to buflen) and returns the untruncated length; it waits for the recorded events to complete. */
