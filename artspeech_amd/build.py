@@ -1,6 +1,7 @@
 """Build recipe for libartspeech_hip.so (hipcc, gfx950 only).  Idempotent: sources newer than their
 object files are recompiled, then everything is linked in-tree next to this file."""
 import os
+import re
 import subprocess
 import sys
 
@@ -51,6 +52,42 @@ def _newer(src, dst, extra=()):
     return any(os.path.getmtime(s) > t for s in (src, *extra))
 
 
+def resources_path(name):
+    """Where the device compile of csrc/<name> leaves hipcc's per-kernel resource remarks (registers, scratch, occupancy)."""
+    return os.path.join(OBJ, name.rsplit(".", 1)[0] + ".resources.txt")
+
+
+def compile_one(name, extra, obj, hipcc, verbose=True):
+    """One source to its object.  Device compiles ask for the kernel-resource-usage remarks (free: the numbers exist anyway) and
+    keep them next to the object; whatever else the compiler says goes to stderr as usual."""
+    src = os.path.join(CSRC, name)
+    if name.endswith(".cpp"):
+        cmd = [hipcc, *COMMON, "-c", src, "-o", obj]
+        if verbose:
+            print("[build]", " ".join(cmd), flush=True)
+        subprocess.check_call(cmd)
+        return
+    cmd = [hipcc, f"--offload-arch={ARCH}", *COMMON, *extra, "-Rpass-analysis=kernel-resource-usage", "-c", src, "-o", obj]
+    if verbose:
+        print("[build]", " ".join(cmd), flush=True)
+    r = subprocess.run(cmd, stderr=subprocess.PIPE, text=True)
+    remarks, rest, quoted = [], [], False
+    for line in r.stderr.splitlines(keepends=True):
+        if "[-Rpass-analysis=kernel-resource-usage]" in line:
+            remarks.append(line)
+            quoted = True
+        elif quoted and re.match(r"\s+\d*\s*\|", line):
+            continue             # the source line and caret clang quotes under a remark
+        else:
+            rest.append(line)
+            quoted = False
+    sys.stderr.write("".join(rest))
+    if r.returncode:
+        raise subprocess.CalledProcessError(r.returncode, cmd)
+    with open(resources_path(name), "w") as f:
+        f.writelines(remarks)
+
+
 def build(force=False, verbose=True):
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
     os.makedirs(OBJ, exist_ok=True)
@@ -62,12 +99,7 @@ def build(force=False, verbose=True):
         obj = os.path.join(OBJ, name.rsplit(".", 1)[0] + ".o")
         objs.append(obj)
         if force or _newer(src, obj, headers):
-            cmd = [hipcc, f"--offload-arch={ARCH}", *COMMON, *extra, "-c", src, "-o", obj]
-            if name.endswith(".cpp"):
-                cmd = [hipcc, *COMMON, "-c", src, "-o", obj]
-            if verbose:
-                print("[build]", " ".join(cmd), flush=True)
-            subprocess.check_call(cmd)
+            compile_one(name, extra, obj, hipcc, verbose)
             relink = True
     if relink or not os.path.exists(LIB):
         cmd = [hipcc, f"--offload-arch={ARCH}", "-shared", "-fPIC", "-o", LIB, *objs]

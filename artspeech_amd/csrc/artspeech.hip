@@ -369,7 +369,7 @@ int head_bwd_dx(const as_dims& d, const as_layout& L, const float* P, const floa
         const int slabs = as_lin_plain_s6_slabs((int)AD, want);
         if ((int64_t)slabs * R * H <= SLAB_FLOATS) {
             AS_PROF("headb.dx1", st);
-            const int took1 = as_lin_plain_s6(&l, want, (long)R * H, st);
+            const int took1 = as_lin_plain_s6(&l, want, (long)R * H, st, 2);   // <= 512 workgroups (want): at most two per CU
             AS_REQUIRE(took1 >= 0, took1, "head dx1: launch failed");
             if (took1) dx1_slabs = slabs;
         }

@@ -81,7 +81,9 @@ int as_lin_try(const as_lin* a, hipStream_t st);
 // lin_f32.hip: epi 0 on the bf16 matrix instruction (a->Bp required; a->B unused): C = act(A . B^T + bias), N <= 256, K % 32 == 0.
 // ksplit > 1: the reduction is cut into that many chunks, chunk y writes its partial sums (no bias / activation allowed) to
 // C + y * c_split floats; the CONSUMER adds the slabs.  1 = launched, 0 = not a case (mode fp32, shapes), < 0 = error.
-int as_lin_plain_s6(const as_lin* a, int ksplit, long c_split, hipStream_t st);
+// waves_per_simd: 4, or 2 for a launch (N <= 128) that never has more than three workgroups of a CU resident: the instantiation
+// with registers for the whole 64-row loop (same instructions per accumulator: same result, bit for bit).
+int as_lin_plain_s6(const as_lin* a, int ksplit, long c_split, hipStream_t st, int waves_per_simd = 4);
 // the number of k-chunks (slabs) as_lin_plain_s6 really uses for a requested ksplit
 static inline int as_lin_plain_s6_slabs(int K, int ksplit) {
     if (ksplit < 1) ksplit = 1;

@@ -455,8 +455,9 @@ __device__ __forceinline__ void s6_main_loop(f32x16 (&acc)[2], unsigned char* sm
 #pragma unroll
         for (int p = 0; p < 3; ++p) dst[p] = *reinterpret_cast<gptr_u4>(as_uniform_ptr(bp + p * bp_plane + j * bp_step) + b_lane);
     };
-    const int sw = (l31 >> 2) & 3;        // rows i * 32 + l31 share it (32 = 0 mod 16)
+    int sw = (l31 >> 2) & 3;              // rows i * 32 + l31 share it (32 = 0 mod 16)
     const unsigned char* a_rd = sm + l31 * 64;
+    int lh_rd = lh;                       // (sw, a_rd, lh_rd: recomputed behind the loop for the tail tiles, see there)
 
     f32x4 aq[3][AL];
     u32x4 bq[3][3];
@@ -481,7 +482,7 @@ __device__ __forceinline__ void s6_main_loop(f32x16 (&acc)[2], unsigned char* sm
             for (int p = 0; p < 3; ++p)
 #pragma unroll
                 for (int i = 0; i < TME; ++i)
-                    fa[i][p] = *reinterpret_cast<const bf16x8*>(img + p * S6_PLANE + i * 32 * 64 + (((2 * s + lh) ^ sw) * 16));
+                    fa[i][p] = *reinterpret_cast<const bf16x8*>(img + p * S6_PLANE + i * 32 * 64 + (((2 * s + lh_rd) ^ sw) * 16));
             const u32x4(&bs)[3] = bq[(2 * U + s) % 3];
             bf16x8 fb[3];
 #pragma unroll
@@ -510,6 +511,17 @@ __device__ __forceinline__ void s6_main_loop(f32x16 (&acc)[2], unsigned char* sm
         tile(IC<1>{}, kt + 1);
         tile(IC<2>{}, kt + 2);
     }
+    // The tail tiles address their fragments from a lane index the compiler cannot trace back to the one in front of the loop.
+    // Otherwise it keeps the loop's lane-constant fragment offsets (precomputed per k-step) AND the values the tail tiles derive
+    // theirs from alive across the loop; in the kernels that are at their register limit those are spilled, and a reload from
+    // scratch is a vector-memory operation whose wait (vmcnt(0): operations retire in order) drains the look-ahead loads.
+    {
+        int ln = lane;
+        asm volatile("" : "+v"(ln));
+        lh_rd = ln >> 5;
+        sw = ((ln & 31) >> 2) & 3;
+        a_rd = sm + (ln & 31) * 64;
+    }
     if (kt < nk) tile(IC<0>{}, kt);
     if (kt + 1 < nk) tile(IC<1>{}, kt + 1);
 }
@@ -531,6 +543,10 @@ __global__ __launch_bounds__(NT, 4) void lin_s6_kernel(LinK g) {
         m0 = g.big_per_batch_rows + (j - bz * g.small_per_batch) * 32;
         tm_eff = 1;
     }
+    // the divisions above run on the vector unit: without this, head and first row (and their 64-bit forms) sit in vector
+    // registers from here to the epilogue, and the EPI_LNB kernel, at its register limit in the main loop, spills them
+    bz = __builtin_amdgcn_readfirstlane(bz);
+    m0 = __builtin_amdgcn_readfirstlane(m0);
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     f32x16 acc[2];
 #pragma unroll
@@ -563,8 +579,12 @@ __global__ __launch_bounds__(NT, 4) void lin_s6_kernel(LinK g) {
 // A plain Linear on the same main loop: C = act(A . B^T + bias), 64 (or 32) rows x 32 NW columns per workgroup (NW = 8:
 // N <= 256, NW = 4: N <= 128; four workgroups per CU at NW = 4), optionally split over K (gridDim.y chunks of kchunk, each
 // writing its partial sums -- no bias, no activation -- to its own slab C + y * c_split: the consumer adds them in a fixed order).
-template <int NW>
-__global__ __launch_bounds__(NW * 64, 4) void lin_s6_plain_kernel(LinK g) {
+// WPS = waves per SIMD the kernel is compiled for.  At 4 (128 VGPRs) the 64-row loop of NW = 4 does not fit (it needs 137: two
+// A loads per thread and k-tile), and what does not fit is reloaded from scratch INSIDE the loop -- a vector-memory operation,
+// whose wait (vmcnt(0), operations retire in order) drains every look-ahead load of s6_main_loop.  A launch that never has four
+// workgroups of a CU resident (the heads' dx1: two at most) takes WPS = 2, which compiles without scratch.
+template <int NW, int WPS>
+__global__ __launch_bounds__(NW * 64, WPS) void lin_s6_plain_kernel(LinK g) {
     __shared__ __attribute__((aligned(16))) unsigned char sm[2 * S6_BUF];
     int bz, m0, tm_eff;
     const int tile = blockIdx.x;   // (an XCD-contiguous map of the tile list, xcd_contiguous(), was measured: 5-10 % slower)
@@ -578,6 +598,8 @@ __global__ __launch_bounds__(NW * 64, 4) void lin_s6_plain_kernel(LinK g) {
         m0 = g.big_per_batch_rows + (j - bz * g.small_per_batch) * 32;
         tm_eff = 1;
     }
+    bz = __builtin_amdgcn_readfirstlane(bz);   // (scalar registers: see lin_s6_kernel)
+    m0 = __builtin_amdgcn_readfirstlane(m0);
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int l31 = lane & 31, lh = lane >> 5;
     const int ks = blockIdx.y, k0 = ks * g.kchunk;
@@ -845,8 +867,10 @@ __global__ __launch_bounds__(NT, 4) void lin_out_kernel(LinOutK g) {
 
 // The output layer on the bf16 matrix instruction (see lin_s6_kernel): 4 waves, wave w = columns 32 w .. 32 w + 31 of all 64
 // rows (two accumulators), A split once per workgroup into the plane image, W3' planes from L2 into registers.  32 KB of
-// LDS, <= 128 VGPRs: four workgroups per CU.  Epilogue as lin_out_kernel's, with 16 instead of 8 frames per wave.
-__global__ __launch_bounds__(256, 4) void lin_out_s6_kernel(LinOutK g) {
+// LDS, 139 VGPRs: THREE workgroups per CU (at four = 128 VGPRs the 64-row loop reloads from scratch behind vmcnt(0), see
+// lin_s6_plain_kernel).  Epilogue as lin_out_kernel's, with 16 instead of 8 frames per wave.
+constexpr int LOUT_WPS = 3;    // waves per SIMD = resident workgroups per CU of lin_out_s6_kernel
+__global__ __launch_bounds__(256, LOUT_WPS) void lin_out_s6_kernel(LinOutK g) {
     __shared__ __attribute__((aligned(16))) float smem[64 * ON];
     static_assert(64 * ON * 4 >= 2 * S6_BUF, "the epilogue's tile holds both plane images");
     int bz, m0, rows;
@@ -861,6 +885,8 @@ __global__ __launch_bounds__(256, 4) void lin_out_s6_kernel(LinOutK g) {
         m0 = g.big_per_batch_rows + (j - bz * g.small_per_batch) * 32;
         rows = 32;
     }
+    bz = __builtin_amdgcn_readfirstlane(bz);   // (scalar registers: see lin_s6_kernel)
+    m0 = __builtin_amdgcn_readfirstlane(m0);
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int l31 = lane & 31, lh = lane >> 5;
     f32x16 acc[2];
@@ -1060,7 +1086,7 @@ int as_lin_try(const as_lin* a, hipStream_t st) {
 }
 
 // see gemm_internal.h
-int as_lin_plain_s6(const as_lin* a, int ksplit, long c_split, hipStream_t st) {
+int as_lin_plain_s6(const as_lin* a, int ksplit, long c_split, hipStream_t st, int waves_per_simd) {
     if (as_matrix_arith() != AS_ARITH_BF16X6 || !a->Bp) return 0;
     if (a->epi != EPI_PLAIN || a->K % S6_BK || a->K < S6_BK || a->N > BN || a->N < 1 || a->M < 1 || a->batch < 1 || !a->C) return 0;
     if (!aligned16(a->A) || a->lda % 4 || a->a_batch % 4 || a->lda >= (1L << 23)) return 0;
@@ -1091,8 +1117,9 @@ int as_lin_plain_s6(const as_lin* a, int ksplit, long c_split, hipStream_t st) {
     const long total = (long)k.n_big + (long)k.small_per_batch * a->batch;
     if (k.small_per_batch == 0) k.small_per_batch = 1;
     if (total > (1L << 30) || ksplit > 65535) return 0;
-    if (nw == 4) hipLaunchKernelGGL((lin_s6_plain_kernel<4>), dim3((unsigned)total, ksplit), dim3(256), 0, st, k);
-    else hipLaunchKernelGGL((lin_s6_plain_kernel<8>), dim3((unsigned)total, ksplit), dim3(512), 0, st, k);
+    if (nw == 4 && waves_per_simd == 2) hipLaunchKernelGGL((lin_s6_plain_kernel<4, 2>), dim3((unsigned)total, ksplit), dim3(256), 0, st, k);
+    else if (nw == 4) hipLaunchKernelGGL((lin_s6_plain_kernel<4, 4>), dim3((unsigned)total, ksplit), dim3(256), 0, st, k);
+    else hipLaunchKernelGGL((lin_s6_plain_kernel<8, 4>), dim3((unsigned)total, ksplit), dim3(512), 0, st, k);
     AS_LAUNCH_CHECK("as_lin_plain_s6");
     return 1;
 }
@@ -1111,8 +1138,11 @@ int as_lin_out_try(const as_lin_out* a, int* n_partials, hipStream_t st) {
     k.M = a->M; k.N = a->N; k.K = a->K; k.batch = a->batch;
     k.tgt = a->tgt; k.tgt_T = a->tgt_T; k.lengths = a->lengths; k.T = a->T; k.scale = a->scale; k.dout = a->dout; k.partial = a->partial;
     if (k.tgt && (!k.lengths || !k.dout || !k.partial || k.T < 1 || k.ldo != (long)k.batch * k.N || k.o_batch != k.N)) return 0;
-    // tile list as for the 256-column kernel: 64-row tiles that fill whole rounds of the 4 x 256 resident slots, 32-row tiles
-    // over the rest
+    // tile list as for the 256-column kernel: 64-row tiles that fill whole rounds of 4 x 256 slots, 32-row tiles over the rest.
+    // The split-arithmetic kernel has LOUT_WPS = 3 workgroups of a CU resident, not 4, and keeps this list all the same: one
+    // of 3 x 256 slots (759 + 682 tiles at 6400 frames x 11 heads instead of 1023 + 154) was measured 4 us slower, as slow as
+    // the kernel with scratch -- a 32-row tile loads the same W3' planes for half the rows.  (Besides, the criterion's partial
+    // sums are per tile: with the list unchanged the loss is added in the order it always was.)
     constexpr int slots = 1024;
     const long units = (long)as_cdiv(k.M, 64) * k.batch;
     const long rounds = units / slots;
