@@ -15,17 +15,14 @@ from . import _lib
 def area_function_batched(air_column, alpha=np.pi, beta=2.0):
     """air_column (frames, 2, 2, Nw) float64 on the GPU: [:, 0] internal wall, [:, 1] external wall,
     coordinates (x, y) on dim 2.  Returns dists (frames, Nw), fx (frames, Nw)."""
-    _lib.require_gpu(air_column, "air_column")
-    L = _lib.lib()
     ac = air_column.to(torch.float64).contiguous()
     frames, walls, two, nw = ac.shape
     assert walls == 2 and two == 2
     dists = torch.empty((frames, nw), dtype=torch.float64, device=ac.device)
     fx = torch.empty_like(dists)
     internal, external = ac[:, 0], ac[:, 1]
-    _lib.check(L.as_area_function_fwd(_lib.ptr(internal), _lib.ptr(external), ac.stride(0), ac.stride(3), ac.stride(2),
-                                      frames, nw, float(alpha), float(beta), _lib.ptr(dists), _lib.ptr(fx),
-                                      _lib.stream_ptr()), "as_area_function_fwd")
+    _lib.call("as_area_function_fwd", internal, external, ac.stride(0), ac.stride(3), ac.stride(2), frames, nw, float(alpha), float(beta),
+              dists, fx)
     return dists, fx
 
 
@@ -43,12 +40,10 @@ def area_function(internal_wall, external_wall, alpha=np.pi, beta=2.):
 def evenly_spaced_fx_batched(x, fx, n_samples=200):
     """x, fx: (frames, Nw) float64 on the GPU with x increasing along dim 1 -> (frames, 2, n_samples) float32
     (abscissae, resampled values)."""
-    _lib.require_gpu(x, "x")
     x, fx = x.to(torch.float64).contiguous(), fx.to(torch.float64).contiguous()
     frames, nw = x.shape
     out = torch.empty((frames, 2, n_samples), dtype=torch.float32, device=x.device)
-    _lib.check(_lib.lib().as_evenly_spaced_fx(_lib.ptr(x), _lib.ptr(fx), frames, nw, n_samples, _lib.ptr(out), _lib.stream_ptr()),
-               "as_evenly_spaced_fx")
+    _lib.call("as_evenly_spaced_fx", x, fx, frames, nw, n_samples, out)
     return out
 
 
@@ -106,7 +101,6 @@ def intersect_semipolar_grid_batched(air_column, semipolar_grid):
     flags int32 (frames, n_lines) (bit 0 / 1: internal / external wall crossed; 0 = line skipped by the reference; bit 2:
     more than 16 crossings of one wall), internal / external points float64 (frames, n_lines, 2).  One wave per
     (frame, grid line); see ``intersect_semipolar_grid`` for the selection rule."""
-    _lib.require_gpu(air_column, "air_column")
     air = air_column.to(torch.float64).contiguous()
     grid = torch.as_tensor(np.asarray(semipolar_grid, dtype=np.float64)).to(air.device).contiguous()
     frames, _, _, n_pts = air.shape
@@ -114,8 +108,7 @@ def intersect_semipolar_grid_batched(air_column, semipolar_grid):
     flags = torch.empty((frames, n_lines), dtype=torch.int32, device=air.device)
     p_int = torch.empty((frames, n_lines, 2), dtype=torch.float64, device=air.device)
     p_ext = torch.empty_like(p_int)
-    _lib.check(_lib.lib().as_intersect_semipolar_grid(_lib.ptr(air), _lib.ptr(grid), frames, n_pts, n_lines, grid_res, _lib.ptr(flags),
-                                                      _lib.ptr(p_int), _lib.ptr(p_ext), _lib.stream_ptr()), "as_intersect_semipolar_grid")
+    _lib.call("as_intersect_semipolar_grid", air, grid, frames, n_pts, n_lines, grid_res, flags, p_int, p_ext)
     return flags, p_int, p_ext
 
 

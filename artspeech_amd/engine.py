@@ -16,7 +16,6 @@ update of the unpipelined loop -- same gradients, same step count, same order of
 parameters after ``flush()`` are bit-identical; only the schedule differs.  ``flush()`` applies the pending slice at once
 (call it before reading parameters, checkpointing, or evaluating).
 """
-import ctypes as C
 import os
 
 import torch
@@ -48,16 +47,15 @@ class TrainStep:
         self.late_off = int(lay.ln2_g)
         self.pending = None      # Adam step number of the slice that is still to be applied
         self.comm_stream = torch.cuda.Stream(device=model.flat.device) if self.ar_overlap else None
-        L = _lib.lib()
         dev = model.flat.device
         _lib.require_gpu(model.flat, "model parameters")
         d = self.dims
-        self.ws = torch.empty(L.as_artspeech_workspace_floats(C.byref(d), B, T), dtype=torch.float32, device=dev)
+        self.ws = torch.empty(_lib.call("as_artspeech_workspace_floats", d, B, T), dtype=torch.float32, device=dev)
         self.out = torch.empty((B, T, d.n_art, 2, d.n_samp), dtype=torch.float32, device=dev)
         self.dout = torch.empty_like(self.out)
         self.grads = torch.zeros_like(model.flat.data)
         self.loss = torch.zeros((), dtype=torch.float32, device=dev)
-        self.partial = torch.empty(L.as_euclid_masked_partials(), dtype=torch.float32, device=dev)
+        self.partial = torch.empty(_lib.call("as_euclid_masked_partials"), dtype=torch.float32, device=dev)
         self.exp_avg = torch.zeros_like(self.grads)
         self.exp_avg_sq = torch.zeros_like(self.grads)
         self.steps = 0
@@ -74,7 +72,7 @@ class TrainStep:
     def forward_backward(self, tokens, lengths_dev, targets, loss_scale):
         """tokens (B, >=T) int64, lengths_dev (B,) int32 on device, targets (B, >=T, A, 2, N).
         loss_scale = 1 / (N_valid_global * A * N).  Leaves loss in self.loss, gradients in self.grads."""
-        L, d, st = _lib.lib(), self.dims, _lib.stream_ptr()
+        d = self.dims
         P = self.model.flat.data
         B, T = self.B, self.T
         fo = self.fwd_opts
@@ -82,44 +80,37 @@ class TrainStep:
         if self.fuse_loss:
             fo.loss_targets, fo.loss_tgt_T, fo.loss_scale = targets.data_ptr(), targets.shape[1], float(loss_scale)
             fo.loss_out, fo.loss_dout = self.loss.data_ptr(), self.dout.data_ptr()
-        fwd_opts = C.byref(fo) if self.fuse_loss else None
+        fwd_opts = fo if self.fuse_loss else None
         if self.pipeline and self.pending is not None:
             # the previous step's late slice: weight gradient -> all-reduce -> Adam on the side stream, beside this step's
             # forward recurrences; the forward's fold of the head weights waits for late_event, the recurrences do not
             self._late_update(self.late_stream)
             self.late_event.record(self.late_stream)
             fo.fold_wait_event = self.late_event.cuda_event
-            fwd_opts = C.byref(fo)
-        _lib.check(L.as_artspeech_fwd(C.byref(d), _lib.ptr(P), _lib.ptr(tokens), tokens.stride(0), _lib.ptr(lengths_dev),
-                                      B, T, _lib.ptr(self.out), _lib.ptr(self.ws), 1, fwd_opts, st), "as_artspeech_fwd")
+            fwd_opts = fo
+        _lib.call("as_artspeech_fwd", d, P, tokens, tokens.stride(0), lengths_dev, B, T, self.out, self.ws, 1, fwd_opts)
         # criterion backward and the model's final sigmoid backward in one pass: dout holds d(loss)/d(pre-sigmoid)
         # (fused into the forward's output layer when the head is narrow enough: nothing to do here then)
         if not self.fuse_loss:
-            _lib.check(L.as_euclid_masked_fwd_bwd_presigmoid(_lib.ptr(self.out), _lib.ptr(targets), targets.shape[1],
-                                                         _lib.ptr(lengths_dev), B, T, d.n_art, d.n_samp, float(loss_scale),
-                                                         _lib.ptr(self.loss), _lib.ptr(self.dout), _lib.ptr(self.partial), st),
-                   "as_euclid_masked_fwd_bwd_presigmoid")
-        _lib.check(L.as_artspeech_bwd(C.byref(d), _lib.ptr(P), _lib.ptr(tokens), tokens.stride(0), _lib.ptr(lengths_dev),
-                                      B, T, _lib.ptr(self.out), _lib.ptr(self.dout), _lib.ptr(self.grads), _lib.ptr(self.ws),
-                                      C.byref(self.bwd_opts), st), "as_artspeech_bwd")
+            _lib.call("as_euclid_masked_fwd_bwd_presigmoid", self.out, targets, targets.shape[1], lengths_dev, B, T, d.n_art, d.n_samp,
+                      float(loss_scale), self.loss, self.dout, self.partial)
+        _lib.call("as_artspeech_bwd", d, P, tokens, tokens.stride(0), lengths_dev, B, T, self.out, self.dout, self.grads, self.ws,
+                  self.bwd_opts)
 
     def _late_update(self, stream):
         """Weight gradient of the heads' second Linear of the step recorded in ``pending`` + its all-reduce + its Adam update,
         enqueued on `stream` after everything the current stream holds (the backward that produced its operands)."""
-        L, d = _lib.lib(), self.dims
-        P, sp = self.model.flat.data, C.c_void_p(stream.cuda_stream)
+        d, P = self.dims, self.model.flat.data
         stream.wait_stream(torch.cuda.current_stream())
-        _lib.check(L.as_artspeech_dw2(C.byref(d), _lib.ptr(P), self.B, self.T, _lib.ptr(self.grads), _lib.ptr(self.ws), sp),
-                   "as_artspeech_dw2")
+        _lib.call("as_artspeech_dw2", d, P, self.B, self.T, self.grads, self.ws, stream=stream)
         lo, n = self.late_off, self.grads.numel() - self.late_off
         if self.use_dist:
             with torch.cuda.stream(stream):
                 ev = self._ar_mark("late", stream)
                 torch.distributed.all_reduce(self.grads[lo:], op=torch.distributed.ReduceOp.SUM, group=self.pg)
                 self._ar_mark_end(ev, stream)
-        _lib.check(L.as_adam_step(_lib.ptr(P[lo:]), _lib.ptr(self.grads[lo:]), _lib.ptr(self.exp_avg[lo:]),
-                                  _lib.ptr(self.exp_avg_sq[lo:]), n, self.lr, self.betas[0], self.betas[1], self.eps,
-                                  self.weight_decay, self.pending, 1.0, sp), "as_adam_step")
+        _lib.call("as_adam_step", P[lo:], self.grads[lo:], self.exp_avg[lo:], self.exp_avg_sq[lo:], n, self.lr, self.betas[0],
+                  self.betas[1], self.eps, self.weight_decay, self.pending, 1.0, stream=stream)
         self.pending = None
 
     def flush(self):
@@ -156,7 +147,7 @@ class TrainStep:
             dist.all_reduce(self.grads[:end], op=dist.ReduceOp.SUM, group=self.pg)
             self._ar_mark_end(ev, cur)
             return
-        _lib.check(_lib.lib().as_artspeech_wait_head_grads(_lib.stream_ptr(), self.comm_stream.cuda_stream), "as_artspeech_wait_head_grads")
+        _lib.call("as_artspeech_wait_head_grads", torch.cuda.current_stream().cuda_stream, self.comm_stream.cuda_stream)
         cur = torch.cuda.current_stream()
         with torch.cuda.stream(self.comm_stream):
             ev_t = self._ar_mark("tail", self.comm_stream)
@@ -200,12 +191,10 @@ class TrainStep:
         return {k: round(sum(v) / len(v), 4) for k, v in acc.items()}
 
     def adam(self):
-        L = _lib.lib()
         self.steps += 1
         n = self.late_off if self.pipeline else self.grads.numel()   # pipelined: the late slice is updated by _late_update
-        _lib.check(L.as_adam_step(_lib.ptr(self.model.flat.data), _lib.ptr(self.grads), _lib.ptr(self.exp_avg),
-                                  _lib.ptr(self.exp_avg_sq), n, self.lr, self.betas[0], self.betas[1],
-                                  self.eps, self.weight_decay, self.steps, 1.0, _lib.stream_ptr()), "as_adam_step")
+        _lib.call("as_adam_step", self.model.flat.data, self.grads, self.exp_avg, self.exp_avg_sq, n, self.lr, self.betas[0], self.betas[1],
+                  self.eps, self.weight_decay, self.steps, 1.0)
         if self.pipeline:
             self.pending = self.steps
 

@@ -26,9 +26,8 @@ def pearsons_correlation(outputs, targets):
     o, g = frames(outputs), frames(targets)
     x_corr = torch.empty((bs, n_art, n_samples), dtype=torch.float32, device=o.device)
     y_corr = torch.empty_like(x_corr)
-    _lib.check(_lib.lib().as_pearson_fwd(_lib.ptr(o), o.stride(0), o.stride(1), _lib.ptr(g), g.stride(0), g.stride(1), bs, seq_len,
-                                         n_art, n_samples, 1e-5, _lib.ptr(x_corr), _lib.ptr(y_corr), _lib.stream_ptr()),
-               "as_pearson_fwd")
+    _lib.call("as_pearson_fwd", o, o.stride(0), o.stride(1), g, g.stride(0), g.stride(1), bs, seq_len, n_art, n_samples, 1e-5, x_corr,
+              y_corr)
     return x_corr, y_corr
 
 

@@ -8,7 +8,6 @@ copied to the host.
 
 Token batches are (B, pitch) integer tensors with a count per row; ``class_map`` (one class per token id) is applied to both
 sides before comparing, which is how the reference aligns phonetic groups instead of phonemes."""
-import ctypes as C
 
 import torch
 
@@ -31,7 +30,7 @@ def _counts(v, B, dev, what):
 
 
 def _ptr(t):
-    return _lib.ptr(t) if t is not None and t.numel() else C.c_void_p(0)
+    return t if t is not None and t.numel() else None   # an empty tensor goes as NULL
 
 
 def _class_map(class_map, dev):
@@ -68,9 +67,8 @@ def decode_top1(emissions, lengths=None, blank=-1, return_argmax=False):
             raise ValueError(f"decode_top1: lengths must have one entry per utterance ({B}), got {lengths.numel()}")
         lengths = lengths.to(device=dev, dtype=torch.int64)
     if B and T and Cn:
-        _lib.check(_lib.lib().as_decode_top1(_lib.ptr(emissions), emissions.stride(0), emissions.stride(1), B, T, Cn, _lib.ptr(lengths),
-                                             -1 if blank is None else int(blank), _lib.ptr(tokens), _lib.ptr(counts), _lib.ptr(argmax),
-                                             _lib.stream_ptr()), "as_decode_top1")
+        _lib.call("as_decode_top1", emissions, emissions.stride(0), emissions.stride(1), B, T, Cn, lengths,
+                  -1 if blank is None else int(blank), tokens, counts, argmax)
     else:
         tokens.fill_(-1)
         counts.zero_()
@@ -102,8 +100,7 @@ def edit_distance(pred, pred_counts, target, target_counts, class_map=None):
     cm, n_map = _class_map(class_map, dev)
     dist = torch.empty(B, device=dev, dtype=torch.int32)
     if B:
-        _lib.check(_lib.lib().as_edit_distance(_ptr(pred), pred.shape[1], _lib.ptr(pc), _ptr(target), target.shape[1], _lib.ptr(tc), B,
-                                               _lib.ptr(cm), n_map, _lib.ptr(dist), _lib.stream_ptr()), "as_edit_distance")
+        _lib.call("as_edit_distance", _ptr(pred), pred.shape[1], pc, _ptr(target), target.shape[1], tc, B, cm, n_map, dist)
     return dist
 
 
@@ -124,12 +121,10 @@ def align_counts(pred, pred_counts, target, target_counts, n_classes, class_map=
             raise ValueError(f"align_counts: out must be a contiguous int32 ({n_classes + 1}, {n_classes + 1}) matrix")
     dist = torch.empty(B, device=dev, dtype=torch.int32)
     if B:
-        L = _lib.lib()
-        nbytes = int(L.as_align_workspace_bytes(B, pred.shape[1], target.shape[1]))
+        nbytes = int(_lib.call("as_align_workspace_bytes", B, pred.shape[1], target.shape[1]))
         ws = torch.empty(nbytes, device=dev, dtype=torch.uint8) if nbytes else None
-        _lib.check(L.as_align_counts(_ptr(pred), pred.shape[1], _lib.ptr(pc), _ptr(target), target.shape[1], _lib.ptr(tc), B, _lib.ptr(cm),
-                                     n_map, n_classes, _lib.ptr(out), _lib.ptr(dist), _lib.ptr(ws), nbytes, _lib.stream_ptr()),
-                   "as_align_counts")
+        _lib.call("as_align_counts", _ptr(pred), pred.shape[1], pc, _ptr(target), target.shape[1], tc, B, cm, n_map, n_classes, out, dist,
+                  ws, nbytes)
     return out, dist
 
 
@@ -161,6 +156,5 @@ def confusion_counts(argmax, targets, lengths, n, class_map=None, out=None):
         if out.shape != (n, n) or out.dtype != torch.int32 or not out.is_contiguous():
             raise ValueError(f"confusion_counts: out must be a contiguous int32 ({n}, {n}) matrix")
     if B and argmax.shape[1] and targets.shape[1]:
-        _lib.check(_lib.lib().as_confusion_counts(_lib.ptr(argmax), argmax.shape[1], _lib.ptr(targets), targets.shape[1], _lib.ptr(lengths),
-                                                  B, _lib.ptr(cm), n_map, n, _lib.ptr(out), _lib.stream_ptr()), "as_confusion_counts")
+        _lib.call("as_confusion_counts", argmax, argmax.shape[1], targets, targets.shape[1], lengths, B, cm, n_map, n, out)
     return out

@@ -8,8 +8,6 @@ costs no copy -- and targets either padded (B, S) (the reference's collate pads 
 itself, so a trainer can skip the log-softmax pass: the gradient is then taken with respect to the scores.  Reductions and
 ``zero_infinity`` follow torch: ``mean`` divides each utterance's loss by max(target_length, 1), then averages over the batch.
 """
-import ctypes as C
-
 import torch
 
 from .. import _lib
@@ -27,7 +25,6 @@ def _lengths(v, B, dev, what):
 class _CTC(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, targets, input_lengths, target_lengths, blank, reduction, zero_infinity, logits):
-        L, st = _lib.lib(), _lib.stream_ptr()
         T, B, Cn = x.shape
         dev = x.device
         if x.dtype != torch.float32:
@@ -59,12 +56,12 @@ class _CTC(torch.autograd.Function):
         if not 0 <= blank < Cn:
             raise ValueError(f"ctc_loss: blank {blank} outside [0, {Cn})")
         need_grad = ctx.needs_input_grad[0]
-        wsn = int(L.as_ctc_workspace_floats(T, B, max_l))
+        wsn = int(_lib.call("as_ctc_workspace_floats", T, B, max_l))
         ws = torch.empty(wsn, device=dev, dtype=torch.float32)
         nll = torch.empty(B, device=dev, dtype=torch.float32)
-        tptr = _lib.ptr(targets) if targets.numel() else C.c_void_p(0)
-        args = (_lib.ptr(x), x.stride(0), x.stride(1), T, B, Cn, int(logits), tptr, tstride, _lib.ptr(il), _lib.ptr(tl), max_l, blank)
-        _lib.check(L.as_ctc_loss(*args, int(need_grad), _lib.ptr(ws), wsn, _lib.ptr(nll), st), "as_ctc_loss")
+        tgt = targets if targets.numel() else None
+        _lib.call("as_ctc_loss", x, x.stride(0), x.stride(1), T, B, Cn, int(logits), tgt, tstride, il, tl, max_l, blank, int(need_grad),
+                  ws, wsn, nll)
         per = nll
         if zero_infinity:
             per = torch.where(torch.isinf(nll), torch.zeros_like(nll), nll)
@@ -76,14 +73,15 @@ class _CTC(torch.autograd.Function):
             out = (per / tl.clamp(min=1).to(per.dtype)).mean()
         if need_grad:
             ctx.save_for_backward(x, targets, il, tl, ws, nll)
-            ctx.meta = (args, tstride, max_l, blank, reduction, zero_infinity, wsn, B)
+            ctx.meta = (int(logits), tstride, max_l, blank, reduction, zero_infinity, wsn)
         return out
 
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, gout):
         x, targets, il, tl, ws, nll = ctx.saved_tensors
-        args, tstride, max_l, blank, reduction, zero_infinity, wsn, B = ctx.meta
+        logits, tstride, max_l, blank, reduction, zero_infinity, wsn = ctx.meta
+        T, B, Cn = x.shape
         gout = gout.float()
         if reduction == "none":
             scale = gout.reshape(B)
@@ -93,8 +91,9 @@ class _CTC(torch.autograd.Function):
             scale = gout.reshape(1) / (tl.clamp(min=1).to(torch.float32) * B)
         scale = scale.contiguous()
         grad = torch.empty(x.shape, device=x.device, dtype=torch.float32)
-        _lib.check(_lib.lib().as_ctc_grad(*args, _lib.ptr(ws), wsn, _lib.ptr(nll), _lib.ptr(scale), int(zero_infinity), _lib.ptr(grad),
-                                          grad.stride(0), grad.stride(1), _lib.stream_ptr()), "as_ctc_grad")
+        tgt = targets if targets.numel() else None
+        _lib.call("as_ctc_grad", x, x.stride(0), x.stride(1), T, B, Cn, logits, tgt, tstride, il, tl, max_l, blank, ws, wsn, nll, scale,
+                  int(zero_infinity), grad, grad.stride(0), grad.stride(1))
         return grad, None, None, None, None, None, None, None
 
 

@@ -23,8 +23,6 @@ backward walks the layers in reverse on the HIP library: as_gemm_f32 for every d
 as_layernorm_bwd, as_gru_unidir_bwd, as_conv3x3_c32 over flipped taps, as_ln_feat_gelu_bwd and as_conv3x3_stem_bwd.  The
 scorer's own parameters get no gradient: if any of them requires grad, that path raises instead.
 """
-import ctypes as C
-
 import torch
 import torch.nn as nn
 
@@ -67,31 +65,22 @@ class Adapter(_Params):
                                      nn.LayerNorm(out_features), nn.Linear(out_features, out_features))
 
 
-_SLAB = {}
-
-
 def _slab(dev):
-    if dev not in _SLAB:
-        _SLAB[dev] = torch.empty(4 << 20, dtype=torch.float32, device=dev)  # split-K partial tiles (16 MB)
-    return _SLAB[dev]
+    return _lib.slab(dev, 4 << 20)  # split-K partial tiles (16 MB); as_gemm_f32 derives its split-K factor from the size
 
 
 def _gemm(A, W, bias, out, act=0, split_k=False):
     """out[M][N] = act(A[M][K] . W[N][K]^T + bias) (bias None: none).  split_k (act == 0 only): few output tiles under a long reduction --
     the bias is laid down first and the GEMM accumulates onto it, its K range split over workgroups (deterministic slabs)."""
     assert A.is_contiguous() and W.is_contiguous() and out.is_contiguous(), "bare pointers below: dense row-major operands"
-    g = _lib.Gemm()
-    g.A, g.B, g.C = A.data_ptr(), W.data_ptr(), out.data_ptr()
-    g.M, g.N, g.K = A.shape[0], W.shape[0], W.shape[1]
-    g.a_i, g.a_k, g.b_j, g.b_k, g.ldc = g.K, 1, g.K, 1, g.N
-    g.batch, g.act = 1, act
+    N, K = W.shape
     if split_k and act == 0:
         out.copy_(bias.expand_as(out))
         slab = _slab(out.device)
-        g.accumulate, g.splitk_ws, g.splitk_ws_floats = 1, slab.data_ptr(), slab.numel()
-    elif bias is not None:
-        g.bias = bias.data_ptr()
-    _lib.check(_lib.lib().as_gemm_f32(C.byref(g), _lib.stream_ptr()), "as_gemm_f32")
+        how = dict(accumulate=1, splitk_ws=slab, splitk_ws_floats=slab.numel())
+    else:
+        how = dict(bias=bias)
+    _lib.gemm(A=A, B=W, C=out, M=A.shape[0], N=N, K=K, a_i=K, a_k=1, b_j=K, b_k=1, ldc=N, act=act, **how)
     return out
 
 
@@ -103,21 +92,18 @@ def _ln(x, ln, out, keep=None):
     if keep is not None:
         xhat, rstd = torch.empty_like(x), torch.empty(rows, device=x.device, dtype=torch.float32)
         keep += [xhat, rstd]
-    _lib.check(_lib.lib().as_layernorm_fwd(_lib.ptr(x), None, _lib.ptr(ln.weight), _lib.ptr(ln.bias), _lib.ptr(out), _lib.ptr(xhat),
-                                           _lib.ptr(rstd), rows, D, 0, _lib.stream_ptr()), "as_layernorm_fwd")
+    _lib.call("as_layernorm_fwd", x, None, ln.weight, ln.bias, out, xhat, rstd, rows, D, 0)
     return out
 
 
 def _ln_bwd(dxhat, xhat, rstd, out):
     rows, D = xhat.shape
-    _lib.check(_lib.lib().as_layernorm_bwd(_lib.ptr(dxhat), _lib.ptr(xhat), _lib.ptr(rstd), None, _lib.ptr(out), rows, D,
-                                           _lib.stream_ptr()), "as_layernorm_bwd")
+    _lib.call("as_layernorm_bwd", dxhat, xhat, rstd, None, out, rows, D)
     return out
 
 
 def _gelu_bwd(dy, x, scale, out):
-    _lib.check(_lib.lib().as_gelu_bwd(_lib.ptr(dy), _lib.ptr(x), _lib.ptr(scale), _lib.ptr(out), dy.numel(),
-                                      scale.numel() if scale is not None else 0, _lib.stream_ptr()), "as_gelu_bwd")
+    _lib.call("as_gelu_bwd", dy, x, scale, out, dy.numel(), scale.numel() if scale is not None else 0)
     return out
 
 
@@ -151,8 +137,7 @@ def _dropout(t, drop, k, out=None):
     """out (default: t, in place) = t * keep / (1 - p) with site k's mask; the backward applies the same call to the gradient."""
     p, seed = drop
     out = t if out is None else out
-    _lib.check(_lib.lib().as_dropout_fwd(_lib.ptr(t), _lib.ptr(out), t.numel(), p, _site_seed(seed, k), _lib.stream_ptr()),
-               "as_dropout_fwd")
+    _lib.call("as_dropout_fwd", t, out, t.numel(), p, _site_seed(seed, k))
     return out
 
 
@@ -254,7 +239,6 @@ class DeepSpeech2(nn.Module):
         what its parameter gradients need (without one those slots of the per-layer records are None).  drop: None, or (p, seed):
         training-mode dropout at the reference's sites, site k's mask being as_dropout_fwd's at _site_seed(seed, k)
         (TrainableDeepSpeech2)."""
-        L, st = _lib.lib(), _lib.stream_ptr()
         train = keep is not None and "train" in keep
         B, Cin, Din, T = x.shape
         assert Cin == self.in_channels
@@ -284,9 +268,8 @@ class DeepSpeech2(nn.Module):
             if voicing is not None:
                 voicing = voicing.to(device=dev, dtype=f32).contiguous()
             fmap = torch.empty(B, T, D, OUT_CHANNELS, device=dev, dtype=f32)
-            _lib.check(L.as_conv3x3_stem(_lib.ptr(planes), *strides, _lib.ptr(w["stem"]), _lib.ptr(self.cnn.bias),
-                                         _lib.ptr(voicing) if voicing is not None else None, _lib.ptr(fmap), B, T, D, Cin, st),
-                       "as_conv3x3_stem")
+            sb, sc, sd, st = strides
+            _lib.call("as_conv3x3_stem", planes, sb, sc, sd, st, w["stem"], self.cnn.bias, voicing, fmap, B, T, D, Cin)
             act, mid = torch.empty_like(fmap), torch.empty_like(fmap)
             kres = []
             act2 = act
@@ -296,19 +279,15 @@ class DeepSpeech2(nn.Module):
                     if train:
                         act, act2 = torch.empty_like(fmap), torch.empty_like(fmap)
                     kres.append((fmap, mid, act, act2) if train else (fmap, mid, None, None))
-                _lib.check(L.as_ln_feat_gelu(_lib.ptr(fmap), _lib.ptr(r.layer_norm1.weight), _lib.ptr(r.layer_norm1.bias), _lib.ptr(act),
-                                             B * T, D, OUT_CHANNELS, st), "as_ln_feat_gelu")
+                _lib.call("as_ln_feat_gelu", fmap, r.layer_norm1.weight, r.layer_norm1.bias, act, B * T, D, OUT_CHANNELS)
                 if drop:
                     _dropout(act, drop, 2 * i)
-                _lib.check(L.as_conv3x3_c32(_lib.ptr(act), _lib.ptr(w1), _lib.ptr(r.cnn1.bias), None, _lib.ptr(mid), B, T, D, st),
-                           "as_conv3x3_c32")
-                _lib.check(L.as_ln_feat_gelu(_lib.ptr(mid), _lib.ptr(r.layer_norm2.weight), _lib.ptr(r.layer_norm2.bias), _lib.ptr(act2),
-                                             B * T, D, OUT_CHANNELS, st), "as_ln_feat_gelu")
+                _lib.call("as_conv3x3_c32", act, w1, r.cnn1.bias, None, mid, B, T, D)
+                _lib.call("as_ln_feat_gelu", mid, r.layer_norm2.weight, r.layer_norm2.bias, act2, B * T, D, OUT_CHANNELS)
                 if drop:
                     _dropout(act2, drop, 2 * i + 1)
                 nxt = torch.empty_like(fmap)
-                _lib.check(L.as_conv3x3_c32(_lib.ptr(act2), _lib.ptr(w2), _lib.ptr(r.cnn2.bias), _lib.ptr(fmap), _lib.ptr(nxt), B, T, D, st),
-                           "as_conv3x3_c32")
+                _lib.call("as_conv3x3_c32", act2, w2, r.cnn2.bias, fmap, nxt, B, T, D)
                 fmap = nxt
             if train:
                 keep.update(planes_t=planes, lin_in=fmap)
@@ -323,19 +302,16 @@ class DeepSpeech2(nn.Module):
                 kln = [] if keep is not None else None
                 a = _ln(h, blk.layer_norm, torch.empty_like(h), kln)
                 ag = torch.empty_like(a) if keep is not None else a
-                _lib.check(L.as_gelu(_lib.ptr(a), _lib.ptr(ag), a.numel(), st), "as_gelu")
+                _lib.call("as_gelu", a, ag, a.numel())
                 _gemm(ag, blk.rnn.weight_ih_l0, blk.rnn.bias_ih_l0, gi)
                 h = torch.empty_like(h)
                 if keep is None:
-                    _lib.check(L.as_gru_unidir_fwd(_lib.ptr(gi), _lib.ptr(blk.rnn.weight_hh_l0), _lib.ptr(blk.rnn.bias_hh_l0),
-                                                   _lib.ptr(lengths), B, T, H, _lib.ptr(h), st), "as_gru_unidir_fwd")
+                    _lib.call("as_gru_unidir_fwd", gi, blk.rnn.weight_hh_l0, blk.rnn.bias_hh_l0, lengths, B, T, H, h)
                     if drop:
                         _dropout(h, drop, 2 * nres + j)
                 else:
                     gates = torch.empty(B * T, 4 * H, device=dev, dtype=f32)
-                    _lib.check(L.as_gru_unidir_fwd_gates(_lib.ptr(gi), _lib.ptr(blk.rnn.weight_hh_l0), _lib.ptr(blk.rnn.bias_hh_l0),
-                                                         _lib.ptr(lengths), B, T, H, _lib.ptr(h), _lib.ptr(gates), st),
-                               "as_gru_unidir_fwd_gates")
+                    _lib.call("as_gru_unidir_fwd_gates", gi, blk.rnn.weight_hh_l0, blk.rnn.bias_hh_l0, lengths, B, T, H, h, gates)
                     krnn.append((kln[0], kln[1], a, h, gates, ag if train else None))
                     if drop:   # the GRU's own output stays in krnn (its backward and dW_hh read it); the next block reads the copy
                         h = _dropout(h, drop, 2 * nres + j, torch.empty_like(h))
@@ -358,7 +334,6 @@ class DeepSpeech2(nn.Module):
         as_conv3x3_stem_wgrad for the convolutions, as_ln_feat_gelu_param_grad / as_layernorm_param_grad for the LayerNorms; it
         needs the "train" entries of saved.  The launches that lead to dx are the same either way, so dx is too, bit for bit.
         need_dx false (with grads only): the walk stops behind the first layer's parameter gradients and returns None."""
-        L, st = _lib.lib(), _lib.stream_ptr()
         wb = self._prepare_bwd()
         w = self._prepare()
         B, Cin, Din, T = saved["shape"]
@@ -379,7 +354,7 @@ class DeepSpeech2(nn.Module):
                     _dropout(df, drop, 2 * nres + nrnn)
                 if dfeatures is not None:
                     dfc = dfeatures.reshape(M, H).float().contiguous()
-                    _lib.check(L.as_add(_lib.ptr(df), _lib.ptr(dfc), _lib.ptr(df), df.numel(), st), "as_add")
+                    _lib.call("as_add", df, dfc, df, df.numel())
             else:
                 df = dfeatures.reshape(M, H).float().contiguous().clone()
             _gelu_bwd(df, saved["fe_pre"], None, df)
@@ -396,9 +371,7 @@ class DeepSpeech2(nn.Module):
                 pre = f"recurrent_layers.{j}."
                 if drop:
                     _dropout(dh, drop, 2 * nres + j)
-                _lib.check(L.as_gru_unidir_bwd(_lib.ptr(dh), _lib.ptr(h_out), _lib.ptr(gates), _lib.ptr(blk.rnn.weight_hh_l0),
-                                               _lib.ptr(saved["lengths"]), B, T, H, _lib.ptr(dgi), _lib.ptr(dgh), st),
-                           "as_gru_unidir_bwd")
+                _lib.call("as_gru_unidir_bwd", dh, h_out, gates, blk.rnn.weight_hh_l0, saved["lengths"], B, T, H, dgi, dgh)
                 if train:
                     g[pre + "rnn.weight_ih_l0"] = _wgrad(dgi, ag, empty(3 * H, H), g.setdefault(pre + "rnn.bias_ih_l0", empty(3 * H)))
                     g[pre + "rnn.weight_hh_l0"] = _wgrad(dgh, h_out, empty(3 * H, H), g.setdefault(pre + "rnn.bias_hh_l0", empty(3 * H)),
@@ -421,8 +394,7 @@ class DeepSpeech2(nn.Module):
 
             def c32_wgrad(x, dy, name):
                 dwk, dbk = empty(9, OUT_CHANNELS, OUT_CHANNELS), empty(OUT_CHANNELS)
-                _lib.check(L.as_conv3x3_c32_wgrad(_lib.ptr(x), _lib.ptr(dy), _lib.ptr(dwk), _lib.ptr(dbk), B, T, D, _lib.ptr(slab),
-                                                  slab.numel(), st), "as_conv3x3_c32_wgrad")
+                _lib.call("as_conv3x3_c32_wgrad", x, dy, dwk, dbk, B, T, D, slab, slab.numel())
                 g[name + ".weight"], g[name + ".bias"] = taps_grad(dwk, OUT_CHANNELS), dbk
 
             for i in reversed(range(nres)):
@@ -430,39 +402,32 @@ class DeepSpeech2(nn.Module):
                 pre = f"residual_layers.{i}."
                 if train:
                     c32_wgrad(act2, dmap, pre + "cnn2")
-                _lib.check(L.as_conv3x3_c32(_lib.ptr(dmap), _lib.ptr(f2), _lib.ptr(zb), None, _lib.ptr(dact), B, T, D, st),
-                           "as_conv3x3_c32")
+                _lib.call("as_conv3x3_c32", dmap, f2, zb, None, dact, B, T, D)
                 if drop:
                     _dropout(dact, drop, 2 * i + 1)
                 if train:
                     _ln_feat_param_grad(mid, r.layer_norm2, dact, g, pre + "layer_norm2")
-                _lib.check(L.as_ln_feat_gelu_bwd(_lib.ptr(mid), _lib.ptr(r.layer_norm2.weight), _lib.ptr(r.layer_norm2.bias),
-                                                 _lib.ptr(dact), None, _lib.ptr(dmid), M, D, OUT_CHANNELS, st), "as_ln_feat_gelu_bwd")
+                _lib.call("as_ln_feat_gelu_bwd", mid, r.layer_norm2.weight, r.layer_norm2.bias, dact, None, dmid, M, D, OUT_CHANNELS)
                 if train:
                     c32_wgrad(act1, dmid, pre + "cnn1")
-                _lib.check(L.as_conv3x3_c32(_lib.ptr(dmid), _lib.ptr(f1), _lib.ptr(zb), None, _lib.ptr(dact), B, T, D, st),
-                           "as_conv3x3_c32")
+                _lib.call("as_conv3x3_c32", dmid, f1, zb, None, dact, B, T, D)
                 if drop:
                     _dropout(dact, drop, 2 * i)
                 if train:
                     _ln_feat_param_grad(fin, r.layer_norm1, dact, g, pre + "layer_norm1")
                 nxt = torch.empty_like(dmap)
-                _lib.check(L.as_ln_feat_gelu_bwd(_lib.ptr(fin), _lib.ptr(r.layer_norm1.weight), _lib.ptr(r.layer_norm1.bias),
-                                                 _lib.ptr(dact), _lib.ptr(dmap), _lib.ptr(nxt), M, D, OUT_CHANNELS, st),
-                           "as_ln_feat_gelu_bwd")
+                _lib.call("as_ln_feat_gelu_bwd", fin, r.layer_norm1.weight, r.layer_norm1.bias, dact, dmap, nxt, M, D, OUT_CHANNELS)
                 dmap = nxt
             # stem: into the planes the forward read (voicing gets no gradient)
-            pshape, strides = saved["planes"]
+            pshape, (sb, sc, sd, st) = saved["planes"]
             if train:
                 dwk, dbk = empty(9, OUT_CHANNELS, Cin), empty(OUT_CHANNELS)
-                _lib.check(L.as_conv3x3_stem_wgrad(_lib.ptr(saved["planes_t"]), *strides, _lib.ptr(dmap), _lib.ptr(dwk), _lib.ptr(dbk), B, T, D,
-                                                   Cin, _lib.ptr(slab), slab.numel(), st), "as_conv3x3_stem_wgrad")
+                _lib.call("as_conv3x3_stem_wgrad", saved["planes_t"], sb, sc, sd, st, dmap, dwk, dbk, B, T, D, Cin, slab, slab.numel())
                 g["cnn.weight"], g["cnn.bias"] = taps_grad(dwk, Cin), dbk
                 if self.adapter is None and not need_dx:
                     return None
             dplanes = empty(*pshape)
-            _lib.check(L.as_conv3x3_stem_bwd(_lib.ptr(dmap), _lib.ptr(w["stem"]), _lib.ptr(dplanes), *strides, B, T, D, Cin, st),
-                       "as_conv3x3_stem_bwd")
+            _lib.call("as_conv3x3_stem_bwd", dmap, w["stem"], dplanes, sb, sc, sd, st, B, T, D, Cin)
             if self.adapter is None:
                 return dplanes
             # adapter: LN0 -> Linear1 -> LN2 -> Linear3 over (B, C, T, D) rows; for dx the gammas sit in the folded weights
@@ -490,18 +455,11 @@ class DeepSpeech2(nn.Module):
 def _wgrad(dy, x, dw, db=None, shift=None):
     """dw[n][k] = sum_m dy[m][n] x[m][k] (db[n] = sum_m dy[m][n]) on the exact fp32 instruction, deterministic split-K;
     shift = T: x is read one frame back within each utterance (h_{t-1} of dW_hh, zero at t = 0)."""
-    g = _lib.Gemm()
-    g.A, g.B, g.C = dy.data_ptr(), x.data_ptr(), dw.data_ptr()
-    g.M, g.N, g.K = dy.shape[1], x.shape[1], dy.shape[0]
-    g.a_i, g.a_k, g.b_j, g.b_k, g.ldc = 1, dy.shape[1], 1, x.shape[1], x.shape[1]
-    g.batch, g.precision = 1, 0
-    if db is not None:
-        g.colsum = db.data_ptr()
-    if shift is not None:
-        g.b_kshift, g.b_kT = -1, shift
+    R, N, K = dy.shape[0], dy.shape[1], x.shape[1]
     slab = _slab(dy.device)
-    g.splitk_ws, g.splitk_ws_floats = slab.data_ptr(), slab.numel()
-    _lib.check(_lib.lib().as_gemm_f32(C.byref(g), _lib.stream_ptr()), "as_gemm_f32")
+    back = dict(b_kshift=-1, b_kT=shift) if shift is not None else {}
+    _lib.gemm(A=dy, B=x, C=dw, M=N, N=K, K=R, a_i=1, a_k=N, b_j=1, b_k=K, ldc=K, precision=0, colsum=db, splitk_ws=slab,
+              splitk_ws_floats=slab.numel(), **back)
     return dw
 
 
@@ -509,8 +467,7 @@ def _ln_param_grad(dz, xhat, ln, grads, name):
     rows, D = xhat.shape
     dg, db = torch.empty(D, device=dz.device, dtype=torch.float32), torch.empty(D, device=dz.device, dtype=torch.float32)
     slab = _slab(dz.device)
-    _lib.check(_lib.lib().as_layernorm_param_grad(_lib.ptr(dz), _lib.ptr(xhat), rows, D, _lib.ptr(dg), _lib.ptr(db), _lib.ptr(slab),
-                                                  slab.numel(), _lib.stream_ptr()), "as_layernorm_param_grad")
+    _lib.call("as_layernorm_param_grad", dz, xhat, rows, D, dg, db, slab, slab.numel())
     grads[name + ".weight"], grads[name + ".bias"] = dg, db
 
 
@@ -518,9 +475,8 @@ def _ln_feat_param_grad(x, ln, dy, grads, name):
     D = ln.weight.numel()
     dg, db = torch.empty(D, device=x.device, dtype=torch.float32), torch.empty(D, device=x.device, dtype=torch.float32)
     slab = _slab(x.device)
-    _lib.check(_lib.lib().as_ln_feat_gelu_param_grad(_lib.ptr(x), _lib.ptr(ln.weight), _lib.ptr(ln.bias), _lib.ptr(dy), x.numel() // (D * OUT_CHANNELS),
-                                                     D, OUT_CHANNELS, _lib.ptr(dg), _lib.ptr(db), _lib.ptr(slab), slab.numel(),
-                                                     _lib.stream_ptr()), "as_ln_feat_gelu_param_grad")
+    _lib.call("as_ln_feat_gelu_param_grad", x, ln.weight, ln.bias, dy, x.numel() // (D * OUT_CHANNELS), D, OUT_CHANNELS, dg, db, slab,
+              slab.numel())
     grads[name + ".weight"], grads[name + ".bias"] = dg, db
 
 

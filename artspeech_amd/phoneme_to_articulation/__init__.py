@@ -129,8 +129,7 @@ def contour_statistics(x):
     mean = torch.empty(cols, dtype=torch.float32, device=x.device)
     std = torch.empty_like(mean)
     with torch.cuda.device(x.device):
-        _lib.check(_lib.lib().as_column_mean_std(_lib.ptr(x2), rows, cols, _lib.ptr(mean), _lib.ptr(std), _lib.ptr(ws), ws.numel(),
-                                                 _lib.stream_ptr()), "as_column_mean_std")
+        _lib.call("as_column_mean_std", x2, rows, cols, mean, std, ws, ws.numel())
     return mean.reshape(shape), std.reshape(shape)
 
 

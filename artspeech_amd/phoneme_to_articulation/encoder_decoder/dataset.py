@@ -205,12 +205,9 @@ class HBMResidentDataset(Dataset):
         return int(index)
 
     def _gather(self, src, first_dev, len_dev, B, T, pad):
-        L = self._lib.lib()
         row_elems = src[0].numel() if src.dim() > 1 else 1
         out = torch.empty((B, T) + tuple(src.shape[1:]), dtype=src.dtype, device=self.device)
-        self._lib.check(L.as_gather_pad_rows(self._lib.ptr(src), self._lib.ptr(first_dev), self._lib.ptr(len_dev), B, T, row_elems,
-                                             src.element_size(), float(pad), self._lib.ptr(out), self._lib.stream_ptr()),
-                        "as_gather_pad_rows")
+        self._lib.call("as_gather_pad_rows", src, first_dev, len_dev, B, T, row_elems, src.element_size(), float(pad), out)
         return out
 
     def collate(self, indices):

@@ -16,12 +16,10 @@ class P2CPDistance(nn.Module):
         self.to_mm = self.dataset_config.RES * self.dataset_config.PIXEL_SPACING
 
     def forward(self, outputs, targets, lengths):
-        L = _lib.lib()
         B, T, A = outputs.shape[:3]
         targets = targets[:, :T]
         p2cp = mean_p2cp(outputs.detach().transpose(-1, -2), targets.detach().transpose(-1, -2)).contiguous()  # (B, T, A)
         lengths_dev = torch.as_tensor(lengths, dtype=torch.int32, device="cpu").to(outputs.device)
         result = torch.empty(1, dtype=torch.float32, device=outputs.device)
-        _lib.check(L.as_p2cp_utterance_mean(_lib.ptr(p2cp), _lib.ptr(lengths_dev), B, T, A, float(self.to_mm),
-                                            _lib.ptr(result), _lib.stream_ptr()), "as_p2cp_utterance_mean")
+        _lib.call("as_p2cp_utterance_mean", p2cp, lengths_dev, B, T, A, float(self.to_mm), result)
         return result[0].cpu()

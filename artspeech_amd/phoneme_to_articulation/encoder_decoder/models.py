@@ -7,7 +7,6 @@ Mirrors reference ``phoneme_to_articulation/encoder_decoder/models.py``: ``ArtSp
 buffer, one RCCL all-reduce, one optimizer launch; all device math runs in libartspeech_hip.so.
 There is no CPU path: tensors must be on an MI355X.
 """
-import ctypes as C
 
 import torch
 import torch.nn as nn
@@ -95,19 +94,18 @@ class _ArtSpeechFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, flat, tokens, lengths_dev, dims, B, T, opts=None, defer=None):
-        L = _lib.lib()
         # `train` = keep what the backward needs.  Dropout (opts) is a property of the MODULE's mode, not of grad mode: the
         # reference's nn.Dropout / nn.GRU(dropout=p) also drop under torch.no_grad() while model.training is set, so the C
         # side is told to run in training mode whenever opts carry a dropout probability
         train = bool(ctx.needs_input_grad[0])  # (grad mode is always off inside Function.forward)
         out = torch.empty((B, T, dims.n_art, 2, dims.n_samp), dtype=torch.float32, device=flat.device)
-        n_ws = L.as_artspeech_workspace_floats(C.byref(dims), B, T)
+        n_ws = _lib.call("as_artspeech_workspace_floats", dims, B, T)
         if n_ws <= 0:
-            _lib.check(int(n_ws) or -1, "as_artspeech_workspace_floats")
+            raise RuntimeError(f"as_artspeech_workspace_floats failed (code {int(n_ws) or -1}): "
+                               f"{_lib.call('as_last_error').decode()}")
         ws = torch.empty(n_ws, dtype=torch.float32, device=flat.device)
-        _lib.check(L.as_artspeech_fwd(C.byref(dims), _lib.ptr(flat), _lib.ptr(tokens), tokens.stride(0),
-                                      _lib.ptr(lengths_dev), B, T, _lib.ptr(out), _lib.ptr(ws), int(train or opts is not None),
-                                      C.byref(opts) if opts is not None else None, _lib.stream_ptr()), "as_artspeech_fwd")
+        _lib.call("as_artspeech_fwd", dims, flat, tokens, tokens.stride(0), lengths_dev, B, T, out, ws, int(train or opts is not None),
+                  opts)
         # nn.Embedding raises for ids outside [0, V) (reference models.py:135); the kernels clamp them (memory safety) and
         # count them in the first word of the workspace -- read here, where the drop-in path may synchronise
         if defer is None:
@@ -125,13 +123,9 @@ class _ArtSpeechFn(torch.autograd.Function):
     def backward(ctx, dout):
         flat, tokens, lengths_dev, out, ws = ctx.saved_tensors
         dims, B, T, opts = ctx.meta
-        L = _lib.lib()
         dout = dout.contiguous()
         grads = torch.zeros_like(flat)  # padding words between parameter groups stay zero
-        _lib.check(L.as_artspeech_bwd(C.byref(dims), _lib.ptr(flat), _lib.ptr(tokens), tokens.stride(0),
-                                      _lib.ptr(lengths_dev), B, T, _lib.ptr(out), _lib.ptr(dout), _lib.ptr(grads),
-                                      _lib.ptr(ws), C.byref(opts) if opts is not None else None, _lib.stream_ptr()),
-                   "as_artspeech_bwd")
+        _lib.call("as_artspeech_bwd", dims, flat, tokens, tokens.stride(0), lengths_dev, B, T, out, dout, grads, ws, opts)
         return grads, None, None, None, None, None, None, None
 
 

@@ -15,12 +15,11 @@ from .. import _lib
 class _EuclidFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, outputs, targets):
-        L = _lib.lib()
         A, two, N = outputs.shape[-3:]
         frames = outputs.numel() // (A * 2 * N)
         o, t = outputs.contiguous(), targets.contiguous()
         dist = torch.empty((*outputs.shape[:-2], N), dtype=torch.float32, device=outputs.device)
-        _lib.check(L.as_euclid_fwd(_lib.ptr(o), _lib.ptr(t), frames, A, N, _lib.ptr(dist), _lib.stream_ptr()), "as_euclid_fwd")
+        _lib.call("as_euclid_fwd", o, t, frames, A, N, dist)
         ctx.save_for_backward(o, t)
         ctx.dims = (frames, A, N)
         return dist
@@ -29,11 +28,9 @@ class _EuclidFn(torch.autograd.Function):
     def backward(ctx, ddist):
         o, t = ctx.saved_tensors
         frames, A, N = ctx.dims
-        L = _lib.lib()
         dout = torch.empty_like(o)
         ddist = ddist.contiguous()  # named: must stay alive until the launch is enqueued
-        _lib.check(L.as_euclid_bwd(_lib.ptr(o), _lib.ptr(t), _lib.ptr(ddist), frames, A, N, _lib.ptr(dout),
-                                   _lib.stream_ptr()), "as_euclid_bwd")
+        _lib.call("as_euclid_bwd", o, t, ddist, frames, A, N, dout)
         return dout, (-dout if ctx.needs_input_grad[1] else None)
 
 
@@ -68,16 +65,16 @@ class _MaskedLossFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, outputs, targets, lengths_dev, scale, kind):
-        L = _lib.lib()
         B, T, A, _, N = outputs.shape
         o, t = outputs.contiguous(), targets.contiguous()
         loss = torch.empty((), dtype=torch.float32, device=o.device)
         need_grad = bool(ctx.needs_input_grad[0])
         dout = torch.empty_like(o) if need_grad else None
-        entry = f"as_{kind}_masked_fwd_bwd"
-        partial = torch.empty(getattr(L, f"as_{kind}_masked_partials")(), dtype=torch.float32, device=o.device)
-        _lib.check(getattr(L, entry)(_lib.ptr(o), _lib.ptr(t), t.shape[1], _lib.ptr(lengths_dev), B, T, A, N, float(scale),
-                                     _lib.ptr(loss), _lib.ptr(dout), _lib.ptr(partial), _lib.stream_ptr()), entry)
+        p2cp = kind == "p2cp"
+        n_partial = _lib.call("as_p2cp_masked_partials" if p2cp else "as_euclid_masked_partials")
+        partial = torch.empty(n_partial, dtype=torch.float32, device=o.device)
+        _lib.call("as_p2cp_masked_fwd_bwd" if p2cp else "as_euclid_masked_fwd_bwd", o, t, t.shape[1], lengths_dev, B, T, A, N, float(scale),
+                  loss, dout, partial)
         if need_grad:
             ctx.save_for_backward(dout)
         return loss
@@ -144,15 +141,13 @@ def _p2cp_operands(u_, v_):
 
 
 def _p2cp_fwd(u_, su, v_, sv):
-    L = _lib.lib()
     lead = u_.shape[:-2]
     tiles = 1
     for s in lead:
         tiles *= s
     out = torch.empty(lead, dtype=torch.float32, device=u_.device)
     with torch.no_grad():
-        _lib.check(L.as_p2cp_fwd(_lib.ptr(u_), su[0], su[1], su[2], u_.shape[-2], _lib.ptr(v_), sv[0], sv[1], sv[2],
-                                 v_.shape[-2], tiles, _lib.ptr(out), _lib.stream_ptr()), "as_p2cp_fwd")
+        _lib.call("as_p2cp_fwd", u_, su[0], su[1], su[2], u_.shape[-2], v_, sv[0], sv[1], sv[2], v_.shape[-2], tiles, out)
     return out
 
 
@@ -177,15 +172,13 @@ class _P2CPFn(torch.autograd.Function):
     def backward(ctx, dout):
         u_, v_ = ctx.saved_tensors
         su, sv = ctx.strides
-        L = _lib.lib()
         dout = dout.contiguous().float()  # named: must stay alive until the launch is enqueued
         du = _grad_like(u_, su) if ctx.needs_input_grad[0] else None   # only the sides that need a gradient
         dv = _grad_like(v_, sv) if ctx.needs_input_grad[1] else None
         sdu = _planar_strides(du) if du is not None else (0, 0, 0)
         sdv = _planar_strides(dv) if dv is not None else (0, 0, 0)
-        _lib.check(L.as_p2cp_bwd(_lib.ptr(u_), su[0], su[1], su[2], u_.shape[-2], _lib.ptr(v_), sv[0], sv[1], sv[2], v_.shape[-2],
-                                 dout.numel(), _lib.ptr(dout), _lib.ptr(du), sdu[0], sdu[1], sdu[2], _lib.ptr(dv), sdv[0], sdv[1],
-                                 sdv[2], _lib.stream_ptr()), "as_p2cp_bwd")
+        _lib.call("as_p2cp_bwd", u_, su[0], su[1], su[2], u_.shape[-2], v_, sv[0], sv[1], sv[2], v_.shape[-2], dout.numel(), dout, du,
+                  sdu[0], sdu[1], sdu[2], dv, sdv[0], sdv[1], sdv[2])
         return du, dv
 
 

@@ -145,10 +145,8 @@ def token_runs(tokens, first_row, lengths):
     abs_pos = torch.empty(frames, dtype=torch.int32, device=dev)
     seq_len = torch.empty_like(abs_pos)
     rel_pos = torch.empty(frames, dtype=torch.float32, device=dev)
-    L = _lib.lib()
-    ws = torch.empty(max(int(L.as_token_runs_workspace_ints(frames)), 1), dtype=torch.int32, device=dev)
-    _lib.check(L.as_token_runs(_lib.ptr(tokens), _lib.ptr(first), _lib.ptr(lens), first.numel(), frames, _lib.ptr(abs_pos),
-                               _lib.ptr(seq_len), _lib.ptr(rel_pos), _lib.ptr(ws), _lib.stream_ptr()), "as_token_runs")
+    ws = torch.empty(max(int(_lib.call("as_token_runs_workspace_ints", frames)), 1), dtype=torch.int32, device=dev)
+    _lib.call("as_token_runs", tokens, first, lens, first.numel(), frames, abs_pos, seq_len, rel_pos, ws)
     return abs_pos, seq_len, rel_pos
 
 
@@ -203,9 +201,7 @@ class PhonemeWiseMeanContour:
         has_pos = src_rel is not None
         src = src.contiguous()
         src_rel = src_rel.contiguous() if has_pos else torch.zeros(src.shape[0], dtype=torch.float32, device=dev)
-        _lib.check(_lib.lib().as_mean_contour_fit(_lib.ptr(src), _lib.ptr(src_rel), _lib.ptr(rows), _lib.ptr(self.offsets), vocab_size,
-                                                  D, _lib.ptr(bank), _lib.ptr(rel), _lib.ptr(table), _lib.stream_ptr()),
-                   "as_mean_contour_fit")
+        _lib.call("as_mean_contour_fit", src, src_rel, rows, self.offsets, vocab_size, D, bank, rel, table)
         self.bank, self.table = bank, table
         self.rel_pos = rel if has_pos else None
         self.positions = src_pos[rows] if has_pos else None
@@ -273,16 +269,13 @@ class PhonemeWiseMeanContour:
             lens = lengths.to(dtype=torch.int32).contiguous()
         out = torch.empty((B, T, len(self.articulators), 2, self.n_samples), dtype=torch.float32, device=dev)
         flag = torch.zeros(1, dtype=torch.int32, device=dev)
-        L, V, D = _lib.lib(), self.vocab_size, self.row_elems
+        V, D = self.vocab_size, self.row_elems
         if weighted:
             first = torch.arange(B, dtype=torch.int64) * T
             _, _, rel = token_runs(tokens.view(-1), first, lens_host if lens_host is not None else lens)
-            _lib.check(L.as_mean_contour_weighted_fwd(_lib.ptr(self.bank), _lib.ptr(self.rel_pos), _lib.ptr(self.offsets), _lib.ptr(tokens),
-                                                      _lib.ptr(rel), _lib.ptr(lens), B, T, V, D, _lib.ptr(out), _lib.ptr(flag),
-                                                      _lib.stream_ptr()), "as_mean_contour_weighted_fwd")
+            _lib.call("as_mean_contour_weighted_fwd", self.bank, self.rel_pos, self.offsets, tokens, rel, lens, B, T, V, D, out, flag)
         else:
-            _lib.check(L.as_mean_contour_fwd(_lib.ptr(self.table), _lib.ptr(self.offsets), _lib.ptr(tokens), _lib.ptr(lens), B, T, V, D,
-                                             _lib.ptr(out), _lib.ptr(flag), _lib.stream_ptr()), "as_mean_contour_fwd")
+            _lib.call("as_mean_contour_fwd", self.table, self.offsets, tokens, lens, B, T, V, D, out, flag)
         self._pending.append((flag, tokens, lens))
         if not self.defer_token_check:
             self.check_tokens()

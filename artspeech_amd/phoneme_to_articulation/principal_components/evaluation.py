@@ -59,9 +59,7 @@ def pc_shapes_eval(shapes, targets, mean, std, to_mm=1.0, lengths=None, referenc
     pred_out = torch.empty((*lead, C, 2, N), dtype=torch.float32, device=dev) if pred else None
     tgt_out = torch.empty((*lead, C, 2, N), dtype=torch.float32, device=dev) if tgt else None
     p2cp_mm = torch.empty((*lead, A), dtype=torch.float32, device=dev) if p2cp else None
-    _lib.check(_lib.lib().as_pc_shapes_eval(_lib.ptr(s), _lib.ptr(t), _lib.ptr(mean), _lib.ptr(std), _lib.ptr(len_dev), T,
-                                            _lib.ptr(ref), int(ref_idx), rows, A, N, float(to_mm), _lib.ptr(pred_out),
-                                            _lib.ptr(tgt_out), _lib.ptr(p2cp_mm), _lib.stream_ptr()), "as_pc_shapes_eval")
+    _lib.call("as_pc_shapes_eval", s, t, mean, std, len_dev, T, ref, int(ref_idx), rows, A, N, float(to_mm), pred_out, tgt_out, p2cp_mm)
     return pred_out, tgt_out, p2cp_mm
 
 
@@ -93,9 +91,7 @@ class PCEvalState:
             if len(lead) != 2 or len(lengths) != lead[0]:
                 raise ValueError("PCEvalState.update: lengths need (B, T, ...) inputs")
             T, len_dev = lead[1], _lengths_dev(lengths, first.device)
-        _lib.check(_lib.lib().as_pc_eval_accumulate(_lib.ptr(p2cp_mm), self.A, _lib.ptr(self.errors), _lib.ptr(latents), self.L,
-                                                    _lib.ptr(self.latents), rows, _lib.ptr(len_dev), T, _lib.stream_ptr()),
-                   "as_pc_eval_accumulate")
+        _lib.call("as_pc_eval_accumulate", p2cp_mm, self.A, self.errors, latents, self.L, self.latents, rows, len_dev, T)
 
     def covariance(self):
         """(L, L) fp64 on the device: M2 / (n - 1), torch.cov of the concatenated latents."""

@@ -35,9 +35,7 @@ class _MinPairDistance(torch.autograd.Function):
         values = torch.empty((frames, n_tv), dtype=torch.float32, device=dev)
         poc1, poc2 = torch.empty((frames, n_tv, 2), dtype=torch.float32, device=dev), torch.empty((frames, n_tv, 2), dtype=torch.float32, device=dev)
         idx = torch.empty((frames, n_tv, 2), dtype=torch.int32, device=dev)
-        _lib.check(_lib.lib().as_tract_variables_fwd(_lib.ptr(pairs), frames, channels, N, _lib.ptr(spec), n_tv, _lib.ptr(values),
-                                                     _lib.ptr(poc1), _lib.ptr(poc2), _lib.ptr(idx), _lib.stream_ptr()),
-                   "as_tract_variables_fwd")
+        _lib.call("as_tract_variables_fwd", pairs, frames, channels, N, spec, n_tv, values, poc1, poc2, idx)
         ctx.save_for_backward(values, poc1, poc2, idx)
         ctx.shape = pairs.shape
         return values
@@ -102,16 +100,13 @@ class _MaskedMSEFn(torch.autograd.Function):
         a, b = a.contiguous().float(), b.contiguous().float()
         if a.shape != b.shape:
             raise ValueError(f"shapes differ: {tuple(a.shape)} vs {tuple(b.shape)}")
-        L = _lib.lib()
         rows = a.shape[0] * a.shape[1] if lengths_dev is not None else a.shape[0]   # (B, T, ...) or (rows, ...)
         feat = a.numel() // rows
         loss = torch.empty((), dtype=torch.float32, device=a.device)
         grad = torch.empty_like(a) if ctx.needs_input_grad[0] else None
-        partial = torch.empty(L.as_masked_mse_partials(), dtype=torch.float32, device=a.device)
+        partial = torch.empty(_lib.call("as_masked_mse_partials"), dtype=torch.float32, device=a.device)
         w = None if row_weights is None else row_weights.contiguous().float()
-        _lib.check(L.as_masked_mse_fwd_bwd(_lib.ptr(a), _lib.ptr(b), rows, feat, _lib.ptr(lengths_dev), int(T), _lib.ptr(w),
-                                           float(scale), _lib.ptr(loss), _lib.ptr(grad), _lib.ptr(partial), _lib.stream_ptr()),
-                   "as_masked_mse_fwd_bwd")
+        _lib.call("as_masked_mse_fwd_bwd", a, b, rows, feat, lengths_dev, int(T), w, float(scale), loss, grad, partial)
         if grad is not None:
             ctx.save_for_backward(grad)
         return loss

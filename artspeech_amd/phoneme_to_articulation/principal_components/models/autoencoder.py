@@ -13,7 +13,6 @@ max over articulators torch glue.
 import os
 from enum import Enum
 
-import ctypes as C
 import torch
 import torch.nn as nn
 
@@ -197,8 +196,8 @@ class _Plan:
             own += [g * width + p for g, i in enumerate(idx) for p, v in enumerate(i) if v == j]
             own_ptr.append(len(own))
         self.own_ptr, self.own = own_ptr, own or [0]
-        self.supported = bool(_lib.lib().as_multi_mlp_supported(layers, self.k_max, self.h1, self.h2, self.n_max))
-        self.P = int(_lib.lib().as_multi_mlp_param_floats(layers, self.k_max, self.h1, self.h2, self.n_max))
+        self.supported = bool(_lib.call("as_multi_mlp_supported", layers, self.k_max, self.h1, self.h2, self.n_max))
+        self.P = int(_lib.call("as_multi_mlp_param_floats", layers, self.k_max, self.h1, self.h2, self.n_max))
         self._dev, self._ptr_tables = {}, {}
 
     def tables(self, dev):
@@ -260,7 +259,6 @@ class _MultiMlpFn(torch.autograd.Function):
         dev = x.device
         table, ptrs = plan.tables(dev), plan.ptr_table(dev, params)
         d = _descriptor(plan, x, scale, act, table, ptrs)
-        L = _lib.lib()
         lead = x.shape[:-2] if plan.encoder else x.shape[:-1]
         win = None
         if plan.encoder:
@@ -270,10 +268,10 @@ class _MultiMlpFn(torch.autograd.Function):
         else:
             y = torch.empty((d.rows, plan.G, plan.n_max), dtype=torch.float32, device=dev)
             d.y, d.y_r, d.y_g = y.data_ptr(), plan.G * plan.n_max, plan.n_max
-        n = L.as_multi_mlp_workspace_floats(C.byref(d), 0)
+        n = _lib.call("as_multi_mlp_workspace_floats", d, 0)
         ws = torch.empty(max(n, 1), dtype=torch.float32, device=dev)
         d.ws, d.ws_floats = ws.data_ptr(), n
-        _lib.check(L.as_multi_mlp_fwd(C.byref(d), _lib.stream_ptr()), "as_multi_mlp_fwd")
+        _lib.call("as_multi_mlp_fwd", d)
         ctx.plan, ctx.scale, ctx.act = plan, scale, act
         ctx.save_for_backward(x, y, win, ptrs, *params)
         return y.reshape(*lead, plan.latent) if plan.encoder else y.reshape(*lead, plan.G, plan.n_max)
@@ -302,11 +300,10 @@ class _MultiMlpFn(torch.autograd.Function):
         if need_dp:
             dparams = torch.empty((plan.G, plan.P), dtype=torch.float32, device=dev)
             d.dparams = dparams.data_ptr()
-        L = _lib.lib()
-        n = L.as_multi_mlp_workspace_floats(C.byref(d), 1)
+        n = _lib.call("as_multi_mlp_workspace_floats", d, 1)
         ws = torch.empty(max(n, 1), dtype=torch.float32, device=dev)
         d.ws, d.ws_floats = ws.data_ptr(), n
-        _lib.check(L.as_multi_mlp_bwd(C.byref(d), _lib.stream_ptr()), "as_multi_mlp_bwd")
+        _lib.call("as_multi_mlp_bwd", d)
         grads = [None] * len(params)
         if need_dp:
             per = 2 * plan.layers

@@ -6,7 +6,6 @@ articulator of a (rows, A, F) tensor in one ``as_pca_fit`` call (artspeech_amd/c
 The chain state is kept in float64 on the device, so ``fit`` and the loop of ``partial_fit`` calls over the same batches give the
 same bits.  There is no CPU path.
 """
-import ctypes as C
 from collections import OrderedDict
 
 import torch
@@ -50,7 +49,7 @@ class MultiArticulatorPCA:
         if x.shape[0] < 1:
             raise ValueError("inputs hold no rows")
         _lib.require_gpu(x, "inputs")
-        if not _lib.lib().as_pca_supported(F, self.k_max):
+        if not _lib.call("as_pca_supported", F, self.k_max):
             raise NotImplementedError(f"as_pca_fit: features={F}, n_components={self.k_max} outside the kernel's limits "
                                       "(features <= 256, n_components <= min(features, 64))")
 
@@ -78,13 +77,12 @@ class MultiArticulatorPCA:
         d.n_seen, d.state = self.n_samples_seen_, self._state.data_ptr()
         d.components, d.noise_variance = self._components.data_ptr(), self._noise.data_ptr()
         d.singular_values, d.explained_variance, d.explained_variance_ratio = (self._scalars[i].data_ptr() for i in range(3))
-        L = _lib.lib()
-        n = L.as_pca_workspace_floats(C.byref(d))
+        n = _lib.call("as_pca_workspace_floats", d)
         if n < 0:
             raise RuntimeError("as_pca_workspace_floats: bad descriptor")
         ws = torch.empty(max(n, 2), dtype=torch.float32, device=x.device)
         d.ws, d.ws_floats = ws.data_ptr(), n
-        _lib.check(L.as_pca_fit(C.byref(d), _lib.stream_ptr()), "as_pca_fit")
+        _lib.call("as_pca_fit", d)
         self.n_samples_seen_ += rows
         self._projections = None
         return self

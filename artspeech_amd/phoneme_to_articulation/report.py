@@ -47,8 +47,7 @@ def segment_correlation(a, b, seg_first, scale=1.0):
     S = seg_first.numel() - 1
     corr = torch.empty((S, K), dtype=torch.float64, device=a.device)
     summary = torch.empty((5, K), dtype=torch.float64, device=a.device)
-    _lib.check(_lib.lib().as_segment_corr(_lib.ptr(a), _lib.ptr(b), rows, K, float(scale), _lib.ptr(seg_first), S, _lib.ptr(corr),
-                                          _lib.ptr(summary), _lib.stream_ptr()), "as_segment_corr")
+    _lib.call("as_segment_corr", a, b, rows, K, float(scale), seg_first, S, corr, summary)
     return corr, summary
 
 
@@ -136,8 +135,7 @@ class ErrorReport:
         order_dev = torch.tensor(order, dtype=torch.int64).to(self.device, non_blocking=True)
         errors = torch.cat(self.errors).index_select(0, order_dev).contiguous()                  # (R, 2 A) float32
         state = torch.zeros(5, 2 * A, dtype=torch.float64, device=self.device)
-        _lib.check(_lib.lib().as_pc_eval_accumulate(_lib.ptr(errors), 2 * A, _lib.ptr(state), None, 0, None, R, None, 0,
-                                                    _lib.stream_ptr()), "as_pc_eval_accumulate")
+        _lib.call("as_pc_eval_accumulate", errors, 2 * A, state, None, 0, None, R, None, 0)
         parts = [errors.double().flatten(), state.flatten()]
         if self.tv_text:
             seg = torch.tensor(seg_first, dtype=torch.int64).to(self.device, non_blocking=True)

@@ -3,14 +3,17 @@ and backward are C-ABI launches: input-projection GEMM -> persistent recurrence 
 input-gradient GEMM + time-batched weight-gradient GEMMs (dW_hh through the time-shifted operand of ``as_gemm_f32``).
 Used by the models that choose the cell with the reference's ``RNNType`` switch (phoneme_to_articulation/__init__.py:47-49).
 """
-import ctypes as C
-
 import torch
 
 from .. import _lib
-from .transformer.ops import _c, _gemm, _slab
+from .transformer import ops
 
 GATES = {"gru": 3, "lstm": 4}
+_c = _lib.contiguous
+
+
+def _gemm(**fields):
+    _lib.gemm(precision=ops.GEMM_PRECISION, **fields)   # the recurrent layers follow the transformer's forward precision setting
 
 
 def check_lengths(lengths, batch_size, padded_len):
@@ -39,18 +42,16 @@ class BiRNNLayer(torch.autograd.Function):
         B, T, I = x.shape
         G = GATES[kind]
         H = w_hh.shape[2]
-        L, st, dev = _lib.lib(), _lib.stream_ptr(), x.device
+        dev = x.device
         gi = torch.empty((B * T, 2 * G * H), dtype=torch.float32, device=dev)
         _gemm(A=x, B=w_ih, C=gi, bias=b_ih, M=B * T, N=2 * G * H, K=I, a_i=I, a_k=1, b_j=I, b_k=1, ldc=2 * G * H)
         y = torch.empty((B, T, 2 * H), dtype=torch.float32, device=dev)
         train = any(ctx.needs_input_grad[:5])
         gates = torch.empty((B, T, 2, G + 1, H), dtype=torch.float32, device=dev) if train else None
         if kind == "gru":
-            _lib.check(L.as_gru_bidir_fwd(_lib.ptr(gi), None, 0, _lib.ptr(w_hh), _lib.ptr(b_hh), _lib.ptr(lengths_dev), B, T, H, _lib.ptr(y),
-                                          _lib.ptr(gates), st), "as_gru_bidir_fwd")
+            _lib.call("as_gru_bidir_fwd", gi, None, 0, w_hh, b_hh, lengths_dev, B, T, H, y, gates)
         else:
-            _lib.check(L.as_lstm_bidir_fwd(_lib.ptr(gi), None, 0, _lib.ptr(w_hh), _lib.ptr(b_hh), _lib.ptr(lengths_dev), B, T, H, _lib.ptr(y),
-                                           _lib.ptr(gates), st), "as_lstm_bidir_fwd")
+            _lib.call("as_lstm_bidir_fwd", gi, None, 0, w_hh, b_hh, lengths_dev, B, T, H, y, gates)
         if train:
             ctx.save_for_backward(x, w_ih, w_hh, y, gates, lengths_dev)
             ctx.kind = kind
@@ -64,18 +65,16 @@ class BiRNNLayer(torch.autograd.Function):
         G = GATES[kind]
         H = w_hh.shape[2]
         R, W = B * T, G * H
-        L, st, dev = _lib.lib(), _lib.stream_ptr(), x.device
+        dev = x.device
         dy = _c(dy)
         dgi = torch.empty((R, 2 * W), dtype=torch.float32, device=dev)
         if kind == "gru":
             dgh = torch.empty_like(dgi)
-            _lib.check(L.as_gru_bidir_bwd(_lib.ptr(dy), _lib.ptr(y), _lib.ptr(gates), _lib.ptr(w_hh), _lib.ptr(lengths_dev), B, T, H,
-                                          _lib.ptr(dgi), _lib.ptr(dgh), st), "as_gru_bidir_bwd")
+            _lib.call("as_gru_bidir_bwd", dy, y, gates, w_hh, lengths_dev, B, T, H, dgi, dgh)
         else:
-            _lib.check(L.as_lstm_bidir_bwd(_lib.ptr(dy), _lib.ptr(gates), _lib.ptr(w_hh), _lib.ptr(lengths_dev), B, T, H, _lib.ptr(dgi), st),
-                       "as_lstm_bidir_bwd")
+            _lib.call("as_lstm_bidir_bwd", dy, gates, w_hh, lengths_dev, B, T, H, dgi)
             dgh = dgi
-        slab = _slab(dev)
+        slab = _lib.slab(dev, ops.SLAB_FLOATS)   # the transformer ops' size: as_gemm_f32 derives its split-K factor from it
         dx = dw_ih = db_ih = dw_hh = db_hh = None
         if ctx.needs_input_grad[0]:
             dx = torch.empty_like(x)
@@ -100,7 +99,7 @@ class Dropout(torch.autograd.Function):
     def forward(ctx, x, p, seed):
         x = _c(x)
         y = torch.empty_like(x)
-        _lib.check(_lib.lib().as_dropout_fwd(_lib.ptr(x), _lib.ptr(y), x.numel(), p, seed, _lib.stream_ptr()), "as_dropout_fwd")
+        _lib.call("as_dropout_fwd", x, y, x.numel(), p, seed)
         ctx.meta = (p, seed)
         return y
 
@@ -109,7 +108,7 @@ class Dropout(torch.autograd.Function):
         p, seed = ctx.meta
         dy = _c(dy)
         dx = torch.empty_like(dy)
-        _lib.check(_lib.lib().as_dropout_fwd(_lib.ptr(dy), _lib.ptr(dx), dy.numel(), p, seed, _lib.stream_ptr()), "as_dropout_fwd")
+        _lib.call("as_dropout_fwd", dy, dx, dy.numel(), p, seed)
         return dx, None, None
 
 

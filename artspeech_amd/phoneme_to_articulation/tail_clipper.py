@@ -56,11 +56,10 @@ def launch_prepare_contours(raw, refs, kinds, dataset_config, mean=None, std=Non
     out = torch.empty((F, A, N, 2) if point_major else (F, A, 2, N), dtype=torch.float32, device=raw.device)
     ref_out = torch.empty((F, 1, 2, N), dtype=torch.float32, device=raw.device) if not point_major else None
     counts = torch.empty((F, A), dtype=torch.int32, device=raw.device)
-    thr = clip_thresholds(dataset_config)
+    tongue, lower_lip, upper_lip_front, upper_lip_back = clip_thresholds(dataset_config)
     with torch.cuda.device(raw.device):
-        _lib.check(_lib.lib().as_prepare_contours(_lib.ptr(raw), _lib.ptr(refs), _lib.ptr(kinds_dev), F, A, N, *thr, _lib.ptr(mean),
-                                                  _lib.ptr(std), int(point_major), _lib.ptr(out), _lib.ptr(ref_out), _lib.ptr(counts),
-                                                  _lib.stream_ptr()), "as_prepare_contours")
+        _lib.call("as_prepare_contours", raw, refs, kinds_dev, F, A, N, tongue, lower_lip, upper_lip_front, upper_lip_back, mean, std, int(point_major),
+                  out, ref_out, counts)
     return out, ref_out, counts
 
 

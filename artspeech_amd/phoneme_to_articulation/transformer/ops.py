@@ -5,7 +5,6 @@ wires them together (and adds gradients where a tensor has several consumers).
 Layout convention: per-block tensors are block-major ``[G][rows][features]`` (contiguous); a grouped linear reads
 channel ``src[g]`` of a channel-major input ``[C][rows][K]``.
 """
-import ctypes as C
 import math
 import os
 import weakref
@@ -15,7 +14,8 @@ import torch
 from ... import _lib
 
 _TABLES = {}
-_SLAB = {}
+SLAB_FLOATS = 20 << 20   # split-K slabs / stream-K pieces (80 MB); as_gemm_f32 derives its split-K factor from the size
+_c = _lib.contiguous
 
 # Precision of the forward linears of the modules built on these ops (as_gemm.precision): "f32" = exact fp32 MFMA,
 # "bf16x6" / "bf16x3" = fp32 operands split on the fly into 3 / 2 bf16 pieces on the bf16 MFMA, fp32 accumulation.
@@ -44,12 +44,8 @@ def set_gemm_precision(name, grad=None):
 
 
 def _gemm(**kw):
-    g = _lib.Gemm()
-    g.batch = 1
-    g.precision = GEMM_PRECISION
-    for k, v in kw.items():
-        setattr(g, k, v.data_ptr() if torch.is_tensor(v) else v)
-    _lib.check(_lib.lib().as_gemm_f32(C.byref(g), _lib.stream_ptr()), "as_gemm_f32")
+    kw.setdefault("precision", GEMM_PRECISION)
+    _lib.gemm(**kw)
 
 
 def _table(dev, key, build):
@@ -67,13 +63,7 @@ def _table32(dev, key, build):
 
 
 def _slab(dev):
-    if dev not in _SLAB:
-        _SLAB[dev] = torch.empty(20 << 20, dtype=torch.float32, device=dev)  # split-K slabs / stream-K pieces (80 MB)
-    return _SLAB[dev]
-
-
-def _c(t):
-    return t if t.is_contiguous() else t.contiguous()
+    return _lib.slab(dev, SLAB_FLOATS)
 
 
 class FoldLN(torch.autograd.Function):
@@ -84,8 +74,7 @@ class FoldLN(torch.autograd.Function):
         W, gamma, beta, b = _c(W), _c(gamma), _c(beta), _c(b)
         G, R, K = W.shape
         Wf, bf = torch.empty_like(W), torch.empty_like(b)
-        _lib.check(_lib.lib().as_fold_ln(_lib.ptr(W), _lib.ptr(gamma), _lib.ptr(beta), _lib.ptr(b), _lib.ptr(Wf), _lib.ptr(bf), G, R, K,
-                                         _lib.stream_ptr()), "as_fold_ln")
+        _lib.call("as_fold_ln", W, gamma, beta, b, Wf, bf, G, R, K)
         ctx.save_for_backward(W, gamma, beta)
         return Wf, bf
 
@@ -95,8 +84,7 @@ class FoldLN(torch.autograd.Function):
         G, R, K = W.shape
         dWf, dbf = _c(dWf), _c(dbf)
         dW, dgamma, dbeta = torch.empty_like(W), torch.empty_like(gamma), torch.empty_like(beta)
-        _lib.check(_lib.lib().as_unfold_ln(_lib.ptr(dWf), _lib.ptr(dbf), _lib.ptr(W), _lib.ptr(gamma), _lib.ptr(beta), _lib.ptr(dW),
-                                           _lib.ptr(dgamma), _lib.ptr(dbeta), G, R, K, _lib.stream_ptr()), "as_unfold_ln")
+        _lib.call("as_unfold_ln", dWf, dbf, W, gamma, beta, dW, dgamma, dbeta, G, R, K)
         return dW, dgamma, dbeta, dbf
 
 
@@ -110,8 +98,7 @@ class Normalize(torch.autograd.Function):
         rows = x.numel() // D
         xhat = torch.empty_like(x)
         rstd = torch.empty(rows, dtype=torch.float32, device=x.device)
-        _lib.check(_lib.lib().as_layernorm_fwd(_lib.ptr(x), None, None, None, None, _lib.ptr(xhat), _lib.ptr(rstd), rows, D, 0,
-                                               _lib.stream_ptr()), "as_layernorm_fwd")
+        _lib.call("as_layernorm_fwd", x, None, None, None, None, xhat, rstd, rows, D, 0)
         ctx.save_for_backward(xhat, rstd)
         return xhat
 
@@ -121,8 +108,7 @@ class Normalize(torch.autograd.Function):
         D = xhat.shape[-1]
         dxhat = _c(dxhat)
         dx = torch.empty_like(xhat)
-        _lib.check(_lib.lib().as_layernorm_bwd(_lib.ptr(dxhat), _lib.ptr(xhat), _lib.ptr(rstd), None, _lib.ptr(dx), xhat.numel() // D, D,
-                                               _lib.stream_ptr()), "as_layernorm_bwd")
+        _lib.call("as_layernorm_bwd", dxhat, xhat, rstd, None, dx, xhat.numel() // D, D)
         return dx
 
 
@@ -140,12 +126,10 @@ class NormalizeRes(torch.autograd.Function):
         xhat = torch.empty_like(x)
         rstd = torch.empty(rows, dtype=torch.float32, device=x.device)
         if cat is None:
-            _lib.check(_lib.lib().as_layernorm_fwd(_lib.ptr(x), _lib.ptr(res), None, None, None, _lib.ptr(xhat), _lib.ptr(rstd), rows, D, 0,
-                                                   _lib.stream_ptr()), "as_layernorm_fwd")
+            _lib.call("as_layernorm_fwd", x, res, None, None, None, xhat, rstd, rows, D, 0)
         else:
             A_, per = cat
-            _lib.check(_lib.lib().as_layernorm_fwd_blockres(_lib.ptr(x), _lib.ptr(res), _lib.ptr(xhat), _lib.ptr(rstd), A_, rows // A_, per,
-                                                            D // per, _lib.stream_ptr()), "as_layernorm_fwd_blockres")
+            _lib.call("as_layernorm_fwd_blockres", x, res, xhat, rstd, A_, rows // A_, per, D // per)
         ctx.save_for_backward(xhat, rstd)
         ctx.cat = cat
         return xhat
@@ -156,8 +140,7 @@ class NormalizeRes(torch.autograd.Function):
         D = xhat.shape[-1]
         dxhat = _c(dxhat)
         dx = torch.empty_like(xhat)
-        _lib.check(_lib.lib().as_layernorm_bwd(_lib.ptr(dxhat), _lib.ptr(xhat), _lib.ptr(rstd), None, _lib.ptr(dx), xhat.numel() // D, D,
-                                               _lib.stream_ptr()), "as_layernorm_bwd")
+        _lib.call("as_layernorm_bwd", dxhat, xhat, rstd, None, dx, xhat.numel() // D, D)
         if ctx.cat is None:
             return dx, dx, None
         # the residual's gradient is the same tensor seen block-major: a strided [A, per, R, d] view, no copy (ChannelBlocks
@@ -177,8 +160,7 @@ class LayerNormAffine(torch.autograd.Function):
         rows = x.numel() // D
         y, xhat = torch.empty_like(x), torch.empty_like(x)
         rstd = torch.empty(rows, dtype=torch.float32, device=x.device)
-        _lib.check(_lib.lib().as_layernorm_fwd(_lib.ptr(x), _lib.ptr(res), _lib.ptr(gamma), _lib.ptr(beta), _lib.ptr(y), _lib.ptr(xhat),
-                                               _lib.ptr(rstd), rows, D, 0, _lib.stream_ptr()), "as_layernorm_fwd")
+        _lib.call("as_layernorm_fwd", x, res, gamma, beta, y, xhat, rstd, rows, D, 0)
         ctx.save_for_backward(xhat, rstd, gamma)
         ctx.has_res = res is not None
         return y
@@ -192,8 +174,7 @@ class LayerNormAffine(torch.autograd.Function):
         dgamma, dbeta = (flat_dy * flat_xh).sum(0), flat_dy.sum(0)  # two small column reductions (glue)
         dxhat = dy * gamma
         dx = torch.empty_like(xhat)
-        _lib.check(_lib.lib().as_layernorm_bwd(_lib.ptr(dxhat), _lib.ptr(xhat), _lib.ptr(rstd), None, _lib.ptr(dx), xhat.numel() // D, D,
-                                               _lib.stream_ptr()), "as_layernorm_bwd")
+        _lib.call("as_layernorm_bwd", dxhat, xhat, rstd, None, dx, xhat.numel() // D, D)
         return dx, (dx if ctx.has_res else None), dgamma, dbeta
 
 
@@ -225,11 +206,10 @@ class GroupedLinear(torch.autograd.Function):
         src, identity, relu = ctx.meta
         Cc, R, K = x.shape
         G, N, _ = W.shape
-        L, st = _lib.lib(), _lib.stream_ptr()
         dz = _c(dout)
         if relu:
             dzr = torch.empty_like(dz)
-            _lib.check(L.as_relu_bwd(_lib.ptr(dz), _lib.ptr(out), _lib.ptr(dzr), dz.numel(), st), "as_relu_bwd")
+            _lib.call("as_relu_bwd", dz, out, dzr, dz.numel())
             dz = dzr
         dW = db = dx = None
         src_off = None if identity else _table(x.device, ("src", src, R * K), lambda: [s * R * K for s in src])
@@ -253,7 +233,7 @@ class GroupedLinear(torch.autograd.Function):
             else:
                 dx = torch.empty_like(x)
                 srct = torch.tensor(src, dtype=torch.int32, device=x.device)
-                _lib.check(L.as_group_reduce(_lib.ptr(part), _lib.ptr(srct), G, Cc, R * K, _lib.ptr(dx), st), "as_group_reduce")
+                _lib.call("as_group_reduce", part, srct, G, Cc, R * K, dx)
         return dx, dW, db, None, None
 
 
@@ -301,10 +281,9 @@ def attention_forward(Q, K, V, attn_mask, kpm, B, heads, training):
     T, Tk, dh = R // B, Rk // B, d // heads
     Z = G * B * heads
     dev = Q.device
-    L = _lib.lib()
     scale = 1.0 / math.sqrt(dh)
     km = _c(kpm) if kpm is not None else None
-    if FUSED_ATTENTION and L.as_attention_supported(T, Tk, d, heads):
+    if FUSED_ATTENTION and _lib.call("as_attention_supported", T, Tk, d, heads):
         # scores stay in registers (as_attention_fwd); training additionally keeps the probabilities, key-major
         out = torch.empty_like(Q)
         # key-major probabilities with rows padded to a multiple of 32 floats: a strip's 128-byte segment of a row is then one
@@ -314,15 +293,13 @@ def attention_forward(Q, K, V, attn_mask, kpm, B, heads, training):
         Pt = torch.empty((Z, Tk, Tp), dtype=torch.float32, device=dev) if training else None
         mt = _key_major_mask(attn_mask, Tk, T) if attn_mask is not None else None
         causal = mt is not None and bool(getattr(mt, "causal", False))
-        fwd = L.as_attention_fwd_causal if causal else L.as_attention_fwd
-        _lib.check(fwd(_lib.ptr(Q), _lib.ptr(K), _lib.ptr(V), _lib.ptr(mt), _lib.ptr(km), _lib.ptr(out), None, _lib.ptr(Pt), G, B, heads,
-                       T, Tk, d, scale, _lib.stream_ptr()), "as_attention_fwd")
+        _lib.call("as_attention_fwd_causal" if causal else "as_attention_fwd", Q, K, V, mt, km, out, None, Pt, G, B, heads, T, Tk, d, scale)
         return out, ((Q, K, V, Pt, out) if training else None), scale, causal
     zq, zk, zs = _z_tables(dev, G, B, T, Tk, d, heads)
     P = torch.empty((Z, T, Tk), dtype=torch.float32, device=dev)
     _gemm(A=Q, B=K, C=P, M=T, N=Tk, K=dh, a_i=d, a_k=1, b_j=d, b_k=1, ldc=Tk, batch=Z, a_off=zq, b_off=zk, c_off=zs)
     am = _c(attn_mask) if attn_mask is not None else None
-    _lib.check(L.as_attn_softmax(_lib.ptr(P), Z, T, Tk, heads, B, scale, _lib.ptr(am), _lib.ptr(km), _lib.stream_ptr()), "as_attn_softmax")
+    _lib.call("as_attn_softmax", P, Z, T, Tk, heads, B, scale, am, km)
     out = torch.empty_like(Q)
     _gemm(A=P, B=V, C=out, M=T, N=dh, K=Tk, a_i=Tk, a_k=1, b_j=1, b_k=d, ldc=d, batch=Z, a_off=zs, b_off=zk, c_off=zq)
     return out, ((Q, K, V, P) if training else None), scale, False
@@ -357,14 +334,11 @@ def attention_backward(saved, B, heads, scale, dctx, dQ=None, dK=None, dV=None, 
         _gemm(A=Pt, B=dctx, C=dV, M=Tk, N=dh, K=T, a_i=Tp, a_k=1, b_j=1, b_k=d, ldc=d, batch=Z, a_off=zp, b_off=zq, c_off=zk, **lower)
         if FUSED_DS:
             # dS^T = P^T o (V dctx^T - D) * scale in one kernel: dP is never formed
-            ds_fn = _lib.lib().as_attention_bwd_ds_causal if causal else _lib.lib().as_attention_bwd_ds
-            _lib.check(ds_fn(_lib.ptr(V), _lib.ptr(dctx), _lib.ptr(out), _lib.ptr(Pt), _lib.ptr(dPt), G, B, heads, T, Tk, d, scale,
-                             _lib.stream_ptr()), "as_attention_bwd_ds")
+            _lib.call("as_attention_bwd_ds_causal" if causal else "as_attention_bwd_ds", V, dctx, out, Pt, dPt, G, B, heads, T, Tk, d, scale)
         else:
             _gemm(A=V, B=dctx, C=dPt, M=Tk, N=T, K=dh, a_i=d, a_k=1, b_j=d, b_k=1, ldc=Tp, batch=Z, a_off=zk, b_off=zq, c_off=zp)
             dsum = torch.empty((Z, T), dtype=torch.float32, device=dev)
-            _lib.check(_lib.lib().as_attn_softmax_bwd_t(_lib.ptr(Pt), _lib.ptr(dPt), _lib.ptr(out), _lib.ptr(dctx), _lib.ptr(dsum), G, B,
-                                                        heads, T, Tk, d, scale, _lib.stream_ptr()), "as_attn_softmax_bwd_t")
+            _lib.call("as_attn_softmax_bwd_t", Pt, dPt, out, dctx, dsum, G, B, heads, T, Tk, d, scale)
         # dQ = dS K (dS read through its transpose) ; dK = dS^T Q
         _gemm(A=dPt, B=K, C=dQ, M=T, N=dh, K=Tk, a_i=1, a_k=Tp, b_j=1, b_k=d, ldc=d, batch=Z, a_off=zp, b_off=zk, c_off=zq, **upper)
         _gemm(A=dPt, B=Q, C=dK, M=Tk, N=dh, K=T, a_i=Tp, a_k=1, b_j=1, b_k=d, ldc=d, batch=Z, a_off=zp, b_off=zq, c_off=zk, **lower)
@@ -374,7 +348,7 @@ def attention_backward(saved, B, heads, scale, dctx, dQ=None, dK=None, dV=None, 
     # dP = dctx V^T ; dV = P^T dctx
     _gemm(A=dctx, B=V, C=dP, M=T, N=Tk, K=dh, a_i=d, a_k=1, b_j=d, b_k=1, ldc=Tk, batch=Z, a_off=zq, b_off=zk, c_off=zs)
     _gemm(A=P, B=dctx, C=dV, M=Tk, N=dh, K=T, a_i=1, a_k=Tk, b_j=1, b_k=d, ldc=d, batch=Z, a_off=zs, b_off=zq, c_off=zk)
-    _lib.check(_lib.lib().as_attn_softmax_bwd(_lib.ptr(P), _lib.ptr(dP), Z, T, Tk, scale, _lib.stream_ptr()), "as_attn_softmax_bwd")
+    _lib.call("as_attn_softmax_bwd", P, dP, Z, T, Tk, scale)
     # dQ = dS K ; dK = dS^T Q
     _gemm(A=dP, B=K, C=dQ, M=T, N=dh, K=Tk, a_i=Tk, a_k=1, b_j=1, b_k=d, ldc=d, batch=Z, a_off=zs, b_off=zk, c_off=zq)
     _gemm(A=dP, B=Q, C=dK, M=Tk, N=dh, K=T, a_i=1, a_k=Tk, b_j=1, b_k=d, ldc=d, batch=Z, a_off=zs, b_off=zq, c_off=zk)
@@ -416,7 +390,6 @@ def channel_blocks_forward(xt, xs, q_w, q_b, k_w, k_b, v_w, v_b, in_w, in_b, o_w
     G, d = q_w.shape[0], q_w.shape[-1]
     R = xt.shape[1]
     dev = xt.device
-    L, st = _lib.lib(), _lib.stream_ptr()
     new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)  # noqa: E731
     assert kv2 is None or not training
     if kv2 is None:
@@ -429,8 +402,7 @@ def channel_blocks_forward(xt, xs, q_w, q_b, k_w, k_b, v_w, v_b, in_w, in_b, o_w
     # LayerNorm affine folded into the three pre-projections
     W3, b3 = new(3, G, d, d), new(3, G, d)
     for j, (w, b) in enumerate(folds):
-        _lib.check(L.as_fold_ln(_lib.ptr(w), _lib.ptr(ln_w), _lib.ptr(ln_b), _lib.ptr(b), _ptr(W3, j * G * d * d), _ptr(b3, j * G * d), G,
-                                d, d, st), "as_fold_ln")
+        _lib.call("as_fold_ln", w, ln_w, ln_b, b, _ptr(W3, j * G * d * d), _ptr(b3, j * G * d), G, d, d)
     same = R == Rs and kv2 is None
     pre = new(3, G, R, d) if same else None          # q, k, v (after the ReLU), one buffer when the row counts agree
     q = pre[0] if same else new(G, R, d)
@@ -537,7 +509,6 @@ class ChannelBlocks(torch.autograd.Function):
         ncb = (d + 31) // 32
         (Ct, R, _), (Cs, Rs, _) = xt.shape, xs.shape
         dev = xt.device
-        L, st = _lib.lib(), _lib.stream_ptr()
         new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)  # noqa: E731
         slab = _slab(dev)
         ws = dict(splitk_ws=slab, splitk_ws_floats=slab.numel())
@@ -596,8 +567,8 @@ class ChannelBlocks(torch.autograd.Function):
               b_off=s_off2, c_batch=d * d, colsum=_ptr(dbf, G * d), colsum_batch=d, precision=GRAD_PRECISION, **ws)
         dW3, dg3, db3 = new(3, G, d, d), new(3, G, d), new(3, G, d)
         for j, w in enumerate((q_w, k_w, v_w)):
-            _lib.check(L.as_unfold_ln(_ptr(dWf, j * G * d * d), _ptr(dbf, j * G * d), _lib.ptr(w), _lib.ptr(ln_w), _lib.ptr(ln_b),
-                                      _ptr(dW3, j * G * d * d), _ptr(dg3, j * G * d), _ptr(db3, j * G * d), G, d, d, st), "as_unfold_ln")
+            _lib.call("as_unfold_ln", _ptr(dWf, j * G * d * d), _ptr(dbf, j * G * d), w, ln_w, ln_b, _ptr(dW3, j * G * d * d),
+                      _ptr(dg3, j * G * d), _ptr(db3, j * G * d), G, d, d)
         dln_w, dln_b = dg3.sum(0), db3.sum(0)   # the three projections share the block's LayerNorm
         # ---- input gradients per channel: sums over the blocks that read the channel
         dxt = _channel_sums(dq.view(G, R, d), W3[0], tgt, Ct, R, d) if ctx.needs_input_grad[0] else None
@@ -627,7 +598,7 @@ def _channel_sums(dz, W, idx, Cn, R, d):
     _gemm(A=dz, B=W, C=part, M=R, N=d, K=d, a_i=d, a_k=1, b_j=1, b_k=d, ldc=d, batch=N, a_batch=R * d, b_batch=d * d, c_batch=R * d,
           precision=GRAD_PRECISION)
     srct = _table32(dev, ("idx32", tuple(idx)), lambda: list(idx))
-    _lib.check(_lib.lib().as_group_reduce(_lib.ptr(part), _lib.ptr(srct), N, Cn, R * d, _lib.ptr(dx), _lib.stream_ptr()), "as_group_reduce")
+    _lib.call("as_group_reduce", part, srct, N, Cn, R * d, dx)
     return dx
 
 
@@ -636,13 +607,11 @@ class Heads(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, feat, head_flat, dims, lay):
-        L = _lib.lib()
         feat = _c(feat)
         R = feat.shape[0]
         out = torch.empty((R, dims.n_art, 2, dims.n_samp), dtype=torch.float32, device=feat.device)
-        ws = torch.empty(L.as_head_workspace_floats(C.byref(dims), R), dtype=torch.float32, device=feat.device)
-        _lib.check(L.as_head_fwd(C.byref(dims), C.byref(lay), _lib.ptr(head_flat), _lib.ptr(feat), R, _lib.ptr(out), _lib.ptr(ws), 1,
-                                 _lib.stream_ptr()), "as_head_fwd")
+        ws = torch.empty(_lib.call("as_head_workspace_floats", dims, R), dtype=torch.float32, device=feat.device)
+        _lib.call("as_head_fwd", dims, lay, head_flat, feat, R, out, ws, 1)
         ctx.save_for_backward(head_flat, out, ws)
         ctx.meta = (dims, lay, feat.shape)
         return out
@@ -651,10 +620,8 @@ class Heads(torch.autograd.Function):
     def backward(ctx, dout):
         head_flat, out, ws = ctx.saved_tensors
         dims, lay, shape = ctx.meta
-        L = _lib.lib()
         dout = _c(dout)
         dx = torch.empty(shape, dtype=torch.float32, device=out.device)
         grads = torch.zeros_like(head_flat)
-        _lib.check(L.as_head_bwd(C.byref(dims), C.byref(lay), _lib.ptr(head_flat), _lib.ptr(out), _lib.ptr(dout), shape[0], _lib.ptr(dx),
-                                 _lib.ptr(grads), _lib.ptr(ws), _lib.stream_ptr()), "as_head_bwd")
+        _lib.call("as_head_bwd", dims, lay, head_flat, out, dout, shape[0], dx, grads, ws)
         return dx, grads, None, None

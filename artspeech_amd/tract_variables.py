@@ -49,7 +49,6 @@ def tract_variables_batched(contours, articulators):
     Returns values (frames, 4), poc1 (frames, 4, 2), poc2 (frames, 4, 2), idx int32 (frames, 4, 2) with
     the variables ordered LA, TTCD, TBCD, VEL."""
     _lib.require_gpu(contours, "contours")
-    L = _lib.lib()
     frames, A, two, N = contours.shape
     if N < 50:
         raise IndexError(f"tract variables slice contours up to point 50, got n_samples={N}")
@@ -59,8 +58,7 @@ def tract_variables_batched(contours, articulators):
     poc1 = torch.empty((frames, 4, 2), dtype=torch.float32, device=c.device)
     poc2 = torch.empty_like(poc1)
     idx = torch.empty((frames, 4, 2), dtype=torch.int32, device=c.device)
-    _lib.check(L.as_tract_variables_fwd(_lib.ptr(c), frames, A, N, _lib.ptr(spec), 4, _lib.ptr(values), _lib.ptr(poc1),
-                                        _lib.ptr(poc2), _lib.ptr(idx), _lib.stream_ptr()), "as_tract_variables_fwd")
+    _lib.call("as_tract_variables_fwd", c, frames, A, N, spec, 4, values, poc1, poc2, idx)
     return values, poc1, poc2, idx
 
 

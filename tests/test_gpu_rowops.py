@@ -619,6 +619,39 @@ def test_add(dev, n):
     _same_bits(acc[:n], a + b, f"as_add in place n={n}")
 
 
+def test_call_passes_tensors_null_and_the_stream(dev):
+    """_lib.call, the way package code enters the library: tensors as their addresses, None as NULL, and the stream appended --
+    the current one, the one a torch.cuda.stream block makes current, or the one handed in -- at n = 5, an odd tail.  Then
+    _lib.gemm on a 4 x 4 x 4 product against float64."""
+    _lib, _ = _L()
+    n = 5
+    rng = np.random.RandomState(5)
+    a, b = rng.randn(n).astype(np.float32), rng.randn(n).astype(np.float32)
+    ta, tb = _dev(a, dev), _dev(b, dev)
+    dsts = [_nan(dev, n + 64) for _ in range(4)]
+    side = torch.cuda.Stream(device=dev)
+    side.wait_stream(torch.cuda.current_stream(dev))   # the operands and the NaN fills were enqueued on the current stream
+    _lib.call("as_add", ta, tb, dsts[0], n)
+    with torch.cuda.stream(side):
+        _lib.call("as_add", ta, tb, dsts[1], n)
+    _lib.call("as_add", ta, tb, dsts[2], n, stream=side)
+    _lib.call("as_add", ta, None, dsts[3], n, stream=side.cuda_stream)   # b == NULL: a copy; a raw stream handle
+    side.synchronize()
+    for dst, what in zip(dsts[:3], ("current stream", "torch.cuda.stream(side)", "stream=side")):
+        _guarded(dst, n, f"call as_add, {what}")
+        _same_bits(dst[:n], a + b, f"call as_add, {what}")
+    _guarded(dsts[3], n, "call as_add, b = None")
+    _same_bits(dsts[3][:n], a, "call as_add, b = None")
+    # C = A B^T in exact fp32 products, fp32 accumulation: |error| <= gamma_K sum_k |a b| with gamma_K ~ K 2^-24; twice that allowed
+    A, Bm = rng.randn(4, 4).astype(np.float32), rng.randn(4, 4).astype(np.float32)
+    tA, tB, out = _dev(A, dev), _dev(Bm, dev), _nan(dev, 16 + 64)
+    _lib.gemm(A=tA, B=tB, C=out, M=4, N=4, K=4, a_i=4, a_k=1, b_j=4, b_k=1, ldc=4)
+    _guarded(out, 16, "gemm 4 x 4 x 4")
+    ref = A.astype(np.float64) @ Bm.astype(np.float64).T
+    bound = 2 * 4 * 2.0 ** -24 * float((np.abs(A).astype(np.float64) @ np.abs(Bm).astype(np.float64).T).max())
+    _close(out[:16].cpu().numpy().reshape(4, 4), ref, 0.0, bound, "call gemm", "gemm 4 x 4 x 4")
+
+
 @pytest.mark.parametrize("row_len,rows", [(1, 3), (1, 600001), (50, 5), (50, 11003), (64, 1), (64, 9001), (2816, 3), (2816, 201)])
 def test_row_scale(dev, row_len, rows):
     _lib, L = _L()

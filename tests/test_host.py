@@ -356,35 +356,190 @@ def test_pc_autoencoder_keys_and_seeded_init_match_reference():
     assert abs(init - chk["init_abs_sum"]) < 1e-9 * chk["init_abs_sum"]
 
 
-def test_ctypes_structs_match_the_header_layout():
-    """The ctypes mirrors in _lib.py against a C compiler's view of include/artspeech_hip.h (sizes and the offsets of the
-    fields appended this round): a drifted struct would silently shift every later argument."""
+def test_ctypes_structs_match_the_header_layout(tmp_path):
+    """Every ctypes mirror in _lib.py against a C compiler's view of include/artspeech_hip.h: the size of each of the six
+    structs and the offset and size of every field (the C program is generated from the mirrors' _fields_, so a field the header does not
+    have fails to compile): a drifted struct would silently shift every later member."""
     import ctypes as C
     import subprocess
-    import tempfile
     from artspeech_amd import _lib
-    src = r"""
-#include <stddef.h>
-#include <stdio.h>
-#include "artspeech_hip.h"
-int main(void) {
-    printf("%zu %zu %zu %zu %zu %zu %zu %zu %zu %zu\n", sizeof(as_opts), offsetof(as_opts, dout_presigmoid), sizeof(as_gemm), offsetof(as_gemm, precision),
-           offsetof(as_gemm, b_kshift_batch), sizeof(as_dims), offsetof(as_gemm, cu_budget), offsetof(as_gemm, res_off),
-           offsetof(as_gemm, mask_batch), offsetof(as_gemm, k_tri));
-    return 0;
-}
-"""
-    inc = os.path.join(ROOT, "include")
-    with tempfile.TemporaryDirectory() as d:
-        c = os.path.join(d, "t.c")
-        open(c, "w").write(src)
-        exe = os.path.join(d, "t")
-        subprocess.check_call(["gcc", "-I", inc, c, "-o", exe])
-        got = [int(x) for x in subprocess.check_output([exe]).split()]
-    want = [C.sizeof(_lib.Opts), _lib.Opts.dout_presigmoid.offset, C.sizeof(_lib.Gemm), _lib.Gemm.precision.offset,
-            _lib.Gemm.b_kshift_batch.offset, C.sizeof(_lib.Dims), _lib.Gemm.cu_budget.offset, _lib.Gemm.res_off.offset,
-            _lib.Gemm.mask_batch.offset, _lib.Gemm.k_tri.offset]
-    assert got == want, (got, want)
+    assert set(_STRUCTS) == set(re.findall(r"typedef struct (as_\w+) \{", open(os.path.join(ROOT, "include", "artspeech_hip.h")).read()))
+    mirrors = [(name, getattr(_lib, cls)) for name, cls in _STRUCTS.items()]
+    lines = ['#include <stddef.h>', '#include <stdio.h>', '#include "artspeech_hip.h"', 'int main(void) {']
+    want = []
+    for name, cls in mirrors:
+        lines.append(f'    printf("%zu\\n", sizeof({name}));')
+        want.append(C.sizeof(cls))
+        for field, _ in cls._fields_:
+            lines.append(f'    printf("%zu %zu\\n", offsetof({name}, {field}), sizeof((({name}*)0)->{field}));')
+            want += [getattr(cls, field).offset, getattr(cls, field).size]
+    lines += ['    return 0;', '}', '']
+    c, exe = str(tmp_path / "t.c"), str(tmp_path / "t")
+    with open(c, "w") as f:
+        f.write("\n".join(lines))
+    subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), c, "-o", exe])
+    got = [int(x) for x in subprocess.check_output([exe]).split()]
+    assert len(want) == 6 + 2 * sum(len(cls._fields_) for _, cls in mirrors) and len(want) > 260
+    assert got == want, [(i, g, w) for i, (g, w) in enumerate(zip(got, want)) if g != w]
+
+
+_STRUCTS = {"as_dims": "Dims", "as_layout": "Layout", "as_opts": "Opts", "as_gemm": "Gemm", "as_multi_mlp": "MultiMlp", "as_pca": "Pca"}
+
+
+def _header_prototypes():
+    """name -> (return type, [(parameter type, parameter name)]) of every function include/artspeech_hip.h declares: one
+    declaration per `;` once the block comments, the preprocessor lines and the struct bodies are gone.  Types are spelt with
+    single spaces, `*` apart: "const float *"."""
+    text = open(os.path.join(ROOT, "include", "artspeech_hip.h")).read()
+    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
+    text = re.sub(r"^\s*#.*$", "", text, flags=re.M)
+    text = re.sub(r"typedef struct \w+ \{.*?\} \w+;", "", text, flags=re.S)
+    text = text.replace('extern "C" {', "").replace("}", "")
+    spell = lambda t: " ".join(t.replace("*", " * ").split())  # noqa: E731
+    out = {}
+    for decl in text.split(";"):
+        if not decl.strip():
+            continue
+        m = re.fullmatch(r"\s*([\w\s\*]+?)\s*\b(as_\w+)\s*\((.*)\)\s*", decl, flags=re.S)
+        assert m, f"declaration not understood: {decl.strip()!r}"
+        ret, name, params = m.groups()
+        assert name not in out, name
+        plist = []
+        if params.strip() not in ("", "void"):
+            for p in params.split(","):
+                pm = re.fullmatch(r"\s*(.*\S)\s*\b(\w+)\s*", p, flags=re.S)
+                assert pm, f"{name}: parameter not understood: {p!r}"
+                plist.append((spell(pm.group(1)), pm.group(2)))
+        out[name] = (spell(ret), plist)
+    return out
+
+
+def _ctype_of(c_type, _lib):
+    """The ctypes type PROTOTYPES must hold for a C type of the header; raises KeyError on a type it has no rule for."""
+    import ctypes as C
+    base = c_type.replace("const ", "")
+    if base == "char *":
+        return C.c_char_p
+    if base.endswith(" *"):
+        target = base[:-2]
+        return C.POINTER(getattr(_lib, _STRUCTS[target])) if target.startswith("as_") else C.c_void_p
+    return {"void": None, "int": C.c_int32, "int32_t": C.c_int32, "int64_t": C.c_int64, "uint64_t": C.c_uint64, "float": C.c_float,
+            "double": C.c_double}[base]
+
+
+def test_prototypes_match_the_header_type_by_type():
+    """PROTOTYPES against the declarations of include/artspeech_hip.h: every return type and every parameter type (a c_int32 bound
+    for an int64_t shifts every later argument silently), the stream mark exactly on the entry points whose last parameter is
+    `void* stream`, and call() checking the status of exactly the functions that return one."""
+    import ctypes as C
+    from artspeech_amd import _lib
+    header = _header_prototypes()
+    assert set(header) == set(_lib.PROTOTYPES), set(header) ^ set(_lib.PROTOTYPES)
+    plain = lambda t: C.c_void_p if t is _lib.Stream else t  # noqa: E731  (the mark is a void pointer to ctypes)
+    for name, (ret, params) in header.items():
+        res, args = _lib.PROTOTYPES[name]
+        assert res is _ctype_of(ret, _lib), f"{name}: returns {ret}, bound as {res}"
+        assert len(args) == len(params), f"{name}: {len(params)} parameters declared, {len(args)} bound"
+        for i, ((c_type, pname), bound) in enumerate(zip(params, args)):
+            assert plain(bound) is _ctype_of(c_type, _lib), f"{name}: parameter {i} `{c_type} {pname}` bound as {bound}"
+            assert (bound is _lib.Stream) == (i == len(params) - 1 and (c_type, pname) == ("void *", "stream")), \
+                f"{name}: parameter {i} `{c_type} {pname}` and the stream mark disagree"
+    streamed = {name for name, (_, args) in _lib.PROTOTYPES.items() if args and args[-1] is _lib.Stream}
+    assert streamed == {name for name, (_, params) in header.items() if params and params[-1] == ("void *", "stream")}
+    assert len(streamed) >= 78
+    _lib.lib()
+    assert {n: b[1] for n, b in _lib._bound.items()} == {n: n in streamed for n in header}
+    # a status code is an `int`; sizes, counts and answers are int32_t / int64_t -- but for one yes/no answer declared `int`
+    status = {name for name, (ret, _) in header.items() if ret == "int"} - {"as_attention_supported"}
+    assert {n for n, b in _lib._bound.items() if b[2]} == status
+
+
+def _library_calls(tree):
+    """The ast.Call nodes of a module that go through _lib.call: `_lib.call(...)`, `self._lib.call(...)` and, inside _lib.py, `call(...)`."""
+    import ast
+    for node in ast.walk(tree):
+        if isinstance(node, ast.Call):
+            f = node.func
+            if isinstance(f, ast.Name) and f.id == "call":
+                yield node
+            elif isinstance(f, ast.Attribute) and f.attr == "call":
+                owner = f.value
+                if (isinstance(owner, ast.Name) and owner.id == "_lib") or (isinstance(owner, ast.Attribute) and owner.attr == "_lib"):
+                    yield node
+
+
+def test_every_call_site_matches_its_prototype():
+    """Every `_lib.call(name, ...)` of the package, whether a GPU test reaches it or not: the name is a string literal (or a
+    conditional between two) that PROTOTYPES holds, and the positional arguments are as many as the prototype's parameters
+    without the stream.  No module but _lib.py spells a crossing out by hand."""
+    import ast
+    from artspeech_amd import _lib
+    allowed = {}   # (file, line) -> reason, for a site with a starred argument or a computed name: none
+    forbidden = ("_lib.check(", "_lib.ptr(", "stream_ptr()", "byref(")
+    sites = 0
+    pkg = os.path.join(ROOT, "artspeech_amd")
+    for base, _, files in os.walk(pkg):
+        for fname in sorted(files):
+            if not fname.endswith(".py"):
+                continue
+            path = os.path.join(base, fname)
+            rel = os.path.relpath(path, ROOT)
+            src = open(path).read()
+            tree = ast.parse(src)
+            if rel != os.path.join("artspeech_amd", "_lib.py"):
+                for text in forbidden:
+                    assert text not in src, f"{rel}: `{text}` -- library calls go through _lib.call"
+                for node in ast.walk(tree):   # a handle may read a helper; it never launches
+                    if isinstance(node, ast.Call) and isinstance(node.func, ast.Attribute) and node.func.attr in _lib.PROTOTYPES:
+                        args = _lib.PROTOTYPES[node.func.attr][1]
+                        assert not (args and args[-1] is _lib.Stream), f"{rel}:{node.lineno}: {node.func.attr} launched past _lib.call"
+            for node in _library_calls(tree):
+                where = f"{rel}:{node.lineno}"
+                if (rel, node.lineno) in allowed:
+                    continue
+                assert node.args, where
+                first = node.args[0]
+                names = [first] if isinstance(first, ast.Constant) else [first.body, first.orelse] if isinstance(first, ast.IfExp) else [None]
+                assert all(isinstance(n, ast.Constant) and isinstance(n.value, str) for n in names), f"{where}: computed entry point name"
+                assert not any(isinstance(a, ast.Starred) for a in node.args), f"{where}: starred argument"
+                assert all(k.arg == "stream" for k in node.keywords), f"{where}: keyword other than stream="
+                for n in names:
+                    assert n.value in _lib.PROTOTYPES, f"{where}: {n.value} is not bound"
+                    args = _lib.PROTOTYPES[n.value][1]
+                    takes_stream = bool(args) and args[-1] is _lib.Stream
+                    assert len(node.args) - 1 == len(args) - takes_stream, \
+                        f"{where}: {n.value} takes {len(args) - takes_stream} arguments (without the stream), {len(node.args) - 1} given"
+                    assert takes_stream or not node.keywords, f"{where}: {n.value} takes no stream"
+                sites += 1
+    assert sites >= 97, sites
+
+
+def test_call_without_a_device(monkeypatch):
+    """_lib.call where no GPU is needed: a refused argument raises with the function's name and the library's message, a CPU
+    tensor raises before the function is entered, a Structure goes by reference, a size helper hands its value back."""
+    from artspeech_amd import _lib
+    for name, args in (("as_group_reduce", (None, None, 1, 1, 2, None)), ("as_add", (None, None, None, 5))):
+        with pytest.raises(RuntimeError, match=rf"^{name} failed \(code -1\): .*bad argument"):
+            _lib.call(name, *args, stream=0)
+    fn, takes_stream, status = _lib._bound["as_add"]
+    entered = []
+    monkeypatch.setitem(_lib._bound, "as_add", (lambda *a: entered.append(a) or 0, takes_stream, status))
+    with pytest.raises(RuntimeError, match="as_add.*no CPU path"):
+        _lib.call("as_add", torch.zeros(5), None, torch.zeros(5), 5, stream=0)
+    assert not entered
+    _lib.call("as_add", None, None, None, 5, stream=7)
+    assert entered == [(None, None, None, 5, 7)]                        # the stream handle goes last, as given
+    with pytest.raises(RuntimeError, match=r"as_gemm\.B.*no CPU path"):
+        _lib.gemm_desc(A=None, B=torch.zeros(4), M=4)
+    g = _lib.gemm_desc(A=12345, M=3, bias=None)
+    assert (g.A, g.M, g.batch, g.bias, g.precision) == (12345, 3, 1, None, 0) and _lib.gemm_desc(batch=6).batch == 6
+    dims, lay = _lib.Dims(45, 3, 64, 128, 50, 0), _lib.Layout()
+    assert _lib.call("as_artspeech_layout", dims, lay) == 0
+    assert lay.total > lay.w3 > lay.lin_w > 0 and lay.total == _lib.layout(dims).total
+    assert _lib.call("as_linear_planes_floats", 256, 256) == 98304
+    assert _lib.call("as_version") == _lib.lib().as_version() and _lib.call("as_attention_supported", 200, 200, 256, 8) in (0, 1)
+    with pytest.raises(TypeError, match="takes no stream"):
+        _lib.call("as_linear_planes_floats", 256, 256, stream=0)
 
 
 def test_key_major_mask_is_transposed_padded_and_cached():
