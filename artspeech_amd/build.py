@@ -21,6 +21,7 @@ COMMON = ["-O3", "-fPIC", "-std=c++17", f"-I{os.path.join(ROOT, 'include')}", f"
 SOURCES = {
     "error.cpp": [],
     "prof.hip": [],
+    "gemm_plan.cpp": [],
     "gemm_f32.hip": [],
     "wgrad_f32.hip": [],
     "lin_f32.hip": [],

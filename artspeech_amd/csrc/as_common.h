@@ -1,6 +1,8 @@
 // Shared helpers for the gfx950 kernels of libartspeech_hip.so.
 #pragma once
+#ifndef AS_HOST_ONLY   // gemm_plan.cpp defines it: plain C++, no HIP header -- the integer helpers below and nothing else
 #include <hip/hip_runtime.h>
+#endif
 #include <stdint.h>
 #include <stdio.h>
 
@@ -34,6 +36,11 @@ void as_set_error(const char* fmt, ...);
         if (r__ != 0) return r__; \
     } while (0)
 
+static inline int64_t as_round_up(int64_t x, int64_t m) { return (x + m - 1) / m * m; }
+static inline int as_cdiv(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }
+static inline bool as_aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+
+#ifndef AS_HOST_ONLY
 // optional per-phase timing (prof.hip); a no-op unless as_profile_enable(1)
 struct AsProfScope {
     AsProfScope(const char* name, hipStream_t st);
@@ -50,9 +57,6 @@ bool as_profile_active();   // as_profile_enable(1) is in force
         AS_PROF(name, st);      \
         AS_TRY(expr);           \
     } while (0)
-
-static inline int64_t as_round_up(int64_t x, int64_t m) { return (x + m - 1) / m * m; }
-static inline int as_cdiv(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }
 
 __device__ __forceinline__ float as_wave_sum(float v) {
 #pragma unroll
@@ -85,3 +89,4 @@ __device__ __forceinline__ float as_sigmoid(float x) { return __builtin_amdgcn_r
 __device__ __forceinline__ float as_tanh(float x) {
     return 1.0f - 2.0f * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(x * 2.8853900817779268f));
 }
+#endif  // AS_HOST_ONLY

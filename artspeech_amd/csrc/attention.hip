@@ -648,8 +648,8 @@ static int attention_fwd(const float* Q, const float* K, const float* V, const f
     AS_REQUIRE(Q && K && V && out && G > 0 && B > 0 && heads > 0 && T > 0 && Tk > 0 && d > 0, AS_ERR_BAD_ARG, "as_attention_fwd: bad argument");
     AS_REQUIRE(as_attention_supported(T, Tk, d, heads), AS_ERR_UNSUPPORTED,
                "as_attention_fwd: head width %d / %d not in {16, 32, 64} or Tk=%d > 256 (use the unfused path)", d, heads, Tk);
-    AS_REQUIRE(((reinterpret_cast<uintptr_t>(Q) | reinterpret_cast<uintptr_t>(K) | reinterpret_cast<uintptr_t>(V) |
-                 reinterpret_cast<uintptr_t>(out)) & 15) == 0, AS_ERR_BAD_ARG, "as_attention_fwd: operands must be 16-byte aligned");
+    AS_REQUIRE(as_aligned16(Q) && as_aligned16(K) && as_aligned16(V) && as_aligned16(out), AS_ERR_BAD_ARG,
+               "as_attention_fwd: operands must be 16-byte aligned");
     AttnK k;
     k.Q = Q; k.K = K; k.V = V; k.O = out; k.mask_t = attn_mask_t; k.kpm = key_padding_mask; k.lse = lse; k.probs_t = probs_t;
     k.B = B; k.heads = heads; k.T = T; k.Tk = Tk; k.d = d; k.scale = scale;
@@ -683,8 +683,7 @@ extern "C" int as_attn_softmax_bwd_t(const float* probs_t, float* dprobs_t, cons
                AS_ERR_BAD_ARG, "as_attn_softmax_bwd_t: bad argument");
     const int dh = d / heads;
     AS_REQUIRE(dh == 16 || dh == 32 || dh == 64, AS_ERR_UNSUPPORTED, "as_attn_softmax_bwd_t: head width %d not in {16, 32, 64}", dh);
-    AS_REQUIRE(((reinterpret_cast<uintptr_t>(ctx) | reinterpret_cast<uintptr_t>(dctx)) & 15) == 0, AS_ERR_BAD_ARG,
-               "as_attn_softmax_bwd_t: ctx / dctx must be 16-byte aligned");
+    AS_REQUIRE(as_aligned16(ctx) && as_aligned16(dctx), AS_ERR_BAD_ARG, "as_attn_softmax_bwd_t: ctx / dctx must be 16-byte aligned");
     hipStream_t st = (hipStream_t)stream;
     const long rows = (long)G * B * T, Z = (long)G * B * heads;
     const long lanes = rows * heads * (dh / 4);
@@ -692,8 +691,7 @@ extern "C" int as_attn_softmax_bwd_t(const float* probs_t, float* dprobs_t, cons
     AS_LAUNCH_CHECK("as_attn_softmax_bwd_t(dsum)");
     const int Tp = (T + 31) / 32 * 32;   // row pitch of the key-major tensors (as_attention_fwd)
     const long plane = (long)Tk * Tp, total = Z * plane;
-    const bool vec = T % 4 == 0 && ((reinterpret_cast<uintptr_t>(probs_t) | reinterpret_cast<uintptr_t>(dprobs_t) |
-                                     reinterpret_cast<uintptr_t>(dsum)) & 15) == 0;
+    const bool vec = T % 4 == 0 && as_aligned16(probs_t) && as_aligned16(dprobs_t) && as_aligned16(dsum);
     if (vec) {
         long blocks = as_cdiv(total / 4, 4 * 256);
         if (blocks > 16384) blocks = 16384;
@@ -713,7 +711,7 @@ static int attention_bwd_ds(const float* V, const float* dctx, const float* ctx,
                "as_attention_bwd_ds: bad argument");
     AS_REQUIRE(as_attention_supported(T, Tk, d, heads), AS_ERR_UNSUPPORTED,
                "as_attention_bwd_ds: head width %d / %d not in {16, 32, 64} or Tk=%d > 256", d, heads, Tk);
-    AS_REQUIRE(((reinterpret_cast<uintptr_t>(V) | reinterpret_cast<uintptr_t>(dctx) | reinterpret_cast<uintptr_t>(ctx)) & 15) == 0,
+    AS_REQUIRE(as_aligned16(V) && as_aligned16(dctx) && as_aligned16(ctx),
                AS_ERR_BAD_ARG, "as_attention_bwd_ds: operands must be 16-byte aligned");
     AttnDsK k;
     k.V = V; k.dctx = dctx; k.ctx = ctx; k.probs_t = probs_t; k.ds_t = ds_t;

@@ -767,12 +767,13 @@ int* as_arrival_counter(hipStream_t st) {
 }
 namespace {
 
+static_assert(BK == AS_GEMM_BK, "gemm_plan.cpp plans for this k-tile");
+
 template <int BM, int BN>
-int launch(const GemmK& k, int batch, bool a_kc, bool b_kc, hipStream_t st) {
-    const long work = (long)as_cdiv(k.M, BM) * as_cdiv(k.N, BN) * k.splitk * batch;
+int launch(const GemmK& k, const as_gemm_plan& p, hipStream_t st) {
+    const bool a_kc = p.a_kc, b_kc = p.b_kc;
+    const long work = p.work;
     dim3 block(256);
-    // FAST needs whole float4s: aligned operands and contiguous extents that are multiples of 4
-    const bool fast = k.a_vec && k.b_vec && (a_kc ? k.K % 4 == 0 : k.M % 4 == 0) && (b_kc ? k.K % 4 == 0 : k.N % 4 == 0);
     // the call's last kernel (no reduce kernel behind it) may carry a fork event (gemm_internal.h, as_stop_event_set)
     hipEvent_t stop_ev = (k.splitk == 1 || k.counters != nullptr) ? as_stop_event_take() : nullptr;
 #define AS_GEMM_LAUNCH(AK, BK_, F)                                                                   \
@@ -782,23 +783,18 @@ int launch(const GemmK& k, int batch, bool a_kc, bool b_kc, hipStream_t st) {
         if (stop_ev) hipExtLaunchKernelGGL((gemm_f32_kernel<BM, BN, AK, BK_, F>), grid, block, 0, st, nullptr, stop_ev, 0, k); \
         else hipLaunchKernelGGL((gemm_f32_kernel<BM, BN, AK, BK_, F>), grid, block, 0, st, k);       \
     } while (0)
-    if (k.res || k.mask_bits || k.relu_bits || k.k_seg > 0 || k.k_tri != 0) {   // the extended instantiations (operands checked by as_gemm_f32)
+    if (p.ext) {   // the extended instantiations: a_kc, or (k_tri = 2: dQ = dS K reads dS^T through its transpose) both strided
 #define AS_GEMM_LAUNCH_EXT(AK, BK_)                                                                    \
     do {                                                                                               \
         static const int slots = resident_blocks(gemm_f32_kernel<BM, BN, AK, BK_, true, true>);        \
         const dim3 grid((unsigned)(work < slots ? work : slots));                                      \
         hipLaunchKernelGGL((gemm_f32_kernel<BM, BN, AK, BK_, true, true>), grid, block, 0, st, k);     \
     } while (0)
-        if constexpr (BM == BN) {   // 128 x 128 and 64 x 64 only
-            if (a_kc && b_kc) AS_GEMM_LAUNCH_EXT(true, true);
-            else if (a_kc) AS_GEMM_LAUNCH_EXT(true, false);
-            else if (!b_kc) AS_GEMM_LAUNCH_EXT(false, false);   // (k_tri = 2: dQ = dS K reads dS^T through its transpose)
-            else AS_REQUIRE(false, AS_ERR_BAD_ARG, "as_gemm_f32: the extended operands have no kernel for a strided A with a contiguous B");
-        } else {
-            AS_REQUIRE(false, AS_ERR_BAD_ARG, "as_gemm_f32: the extended operands need a square tile");
-        }
+        if (a_kc && b_kc) AS_GEMM_LAUNCH_EXT(true, true);
+        else if (a_kc) AS_GEMM_LAUNCH_EXT(true, false);
+        else AS_GEMM_LAUNCH_EXT(false, false);
 #undef AS_GEMM_LAUNCH_EXT
-    } else if (fast) {
+    } else if (p.fast) {
         if (a_kc && b_kc) AS_GEMM_LAUNCH(true, true, true);
         else if (a_kc && !b_kc) AS_GEMM_LAUNCH(true, false, true);
         else if (!a_kc && b_kc) AS_GEMM_LAUNCH(false, true, true);
@@ -814,174 +810,83 @@ int launch(const GemmK& k, int batch, bool a_kc, bool b_kc, hipStream_t st) {
     return 0;
 }
 
-inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
-}  // namespace
-
-extern "C" int as_gemm_f32(const as_gemm* g, void* stream) {
-    AS_REQUIRE(g && g->A && g->B && g->C, AS_ERR_BAD_ARG, "as_gemm_f32: null pointer");
-    AS_REQUIRE(g->M > 0 && g->N > 0 && g->K > 0 && g->batch > 0, AS_ERR_BAD_ARG,
-               "as_gemm_f32: non-positive size M=%d N=%d K=%d batch=%d", g->M, g->N, g->K, g->batch);
-    AS_REQUIRE((g->a_i == 1) != (g->a_k == 1) || (g->a_i == 1 && g->a_k == 1 && (g->M == 1 || g->K == 1)),
-               AS_ERR_BAD_ARG, "as_gemm_f32: exactly one of a_i/a_k must be 1 (a_i=%ld a_k=%ld)", (long)g->a_i, (long)g->a_k);
-    AS_REQUIRE((g->b_j == 1) != (g->b_k == 1) || (g->b_j == 1 && g->b_k == 1 && (g->N == 1 || g->K == 1)),
-               AS_ERR_BAD_ARG, "as_gemm_f32: exactly one of b_j/b_k must be 1 (b_j=%ld b_k=%ld)", (long)g->b_j, (long)g->b_k);
-    AS_REQUIRE(g->act >= 0 && g->act <= 3, AS_ERR_BAD_ARG, "as_gemm_f32: act=%d", g->act);
-    AS_REQUIRE(g->precision >= 0 && g->precision <= 3, AS_ERR_BAD_ARG, "as_gemm_f32: precision=%d", g->precision);
-    const int prec = g->precision == 3 ? 0 : g->precision;   // 3 = "the library's matrix arithmetic, at any size" (below)
-    // (M == 1 with both strides of A equal to 1 reads the same either way: output-contiguous then, the form the column sums take)
-    const bool a_kc = g->a_k == 1 && !(g->a_i == 1 && g->colsum), b_kc = g->b_k == 1;
-    AS_REQUIRE(!(g->b_kT > 0 && b_kc), AS_ERR_BAD_ARG, "as_gemm_f32: b_kshift needs a reduction-strided B operand");
-    if (!a_kc && !b_kc && g->k_tri == 0) {  // weight-gradient shapes: the kernel of wgrad_f32.hip (it does not know k_tri)
-        // precision == 3 in the split arithmetic: one workgroup per 128 x 128 output tile over the whole reduction, operand tiles
-        // staged once per workgroup (gemm_s6.hip; the transformer's grouped weight gradients, 110 x [256 x 256 x 6400]: 704 us
-        // with the stream-K kernel below, 597 - 659 us there; it declines launches of fewer than 256 tiles)
-        if (g->precision == 3 && g->a_i == 1 && g->b_j == 1) {
-            const int took = as_gemm_s6_nt_ext(g, (hipStream_t)stream);
-            if (took != 0) return took < 0 ? took : 0;
-        }
-        const int taken = as_wgrad_try(g, (hipStream_t)stream);
-        if (taken != 0) return taken < 0 ? taken : 0;
-    }
+// the descriptor and the plan as the kernels' argument block
+GemmK kernel_args(const as_gemm* g, const as_gemm_plan& p, hipStream_t st) {
     GemmK k;
     k.A = g->A; k.B = g->B; k.C = g->C; k.bias = g->bias;
     k.M = g->M; k.N = g->N; k.K = g->K;
     k.a_i = g->a_i; k.a_k = g->a_k; k.b_j = g->b_j; k.b_k = g->b_k; k.ldc = g->ldc;
     k.a_batch = g->a_batch; k.b_batch = g->b_batch; k.c_batch = g->c_batch; k.bias_batch = g->bias_batch;
     k.act = g->act; k.accumulate = g->accumulate; k.b_kshift = g->b_kshift; k.b_kT = g->b_kT; k.b_kshift_batch = g->b_kshift_batch;
-    const long a_ld = a_kc ? g->a_i : g->a_k, b_ld = b_kc ? g->b_j : g->b_k;
-    k.a_vec = aligned16(g->A) && a_ld % 4 == 0 && g->a_batch % 4 == 0;
-    k.b_vec = aligned16(g->B) && b_ld % 4 == 0 && g->b_batch % 4 == 0;
-    hipStream_t st = (hipStream_t)stream;
-    k.splitk = 1; k.kchunk = g->K; k.batch = g->batch; k.slab = nullptr; k.counters = nullptr; k.xcd_chunks = 0; k.xcd_panels = 0;
+    k.a_vec = p.a_vec; k.b_vec = p.b_vec;
+    k.splitk = p.splitk; k.kchunk = p.kchunk; k.batch = g->batch;
+    k.xcd_chunks = p.xcd_chunks; k.xcd_panels = p.xcd_panels;
+    k.slab = p.splitk > 1 ? g->splitk_ws : nullptr;
+    k.counters = p.reduce == AS_REDUCE_COUNTERS ? counters_for(st) : nullptr;
     k.colsum = g->colsum; k.colsum_batch = g->colsum_batch;
     k.a_off = (const long*)g->a_off; k.b_off = (const long*)g->b_off; k.c_off = (const long*)g->c_off;
     k.bias_off = (const long*)g->bias_off;
     k.res = g->res; k.res_ld = g->res_ld; k.res_batch = g->res_batch; k.res_off = (const long*)g->res_off;
     k.mask_bits = g->mask_bits; k.mask_batch = g->mask_batch; k.relu_bits = g->relu_bits; k.relu_bits_batch = g->relu_bits_batch;
     k.k_seg = g->k_seg; k.a_seg_off = (const long*)g->a_seg_off; k.b_seg_off = (const long*)g->b_seg_off;
-    k.k_tri = g->k_tri;
-    AS_REQUIRE(g->k_tri >= 0 && g->k_tri <= 2, AS_ERR_BAD_ARG, "as_gemm_f32: k_tri=%d", g->k_tri);
-    AS_REQUIRE(g->k_tri == 0 || (!g->colsum && !g->splitk_ws && prec == 0 && g->k_seg == 0 && !g->accumulate && g->act <= 1 &&
-                                 !g->bias_off && (long)g->M * g->ldc < (1L << 31)),
-               AS_ERR_BAD_ARG, "as_gemm_f32: k_tri goes with the extended general kernel only (no colsum, splitk_ws, split precision, "
-               "k_seg, accumulate, act > 1)");
-    // k_tri is a hint about zeros: operands the extended (float4) instantiation cannot take run the plain kernel over the full range
-    if (g->k_tri != 0 && !(aligned16(g->A) && aligned16(g->B) && a_ld % 4 == 0 && b_ld % 4 == 0 && (a_kc ? g->K % 4 == 0 : g->M % 4 == 0) &&
-                           (b_kc ? g->K % 4 == 0 : g->N % 4 == 0) && (g->a_off || g->a_batch % 4 == 0) && (g->b_off || g->b_batch % 4 == 0) &&
-                           (a_kc || !b_kc)))
-        k.k_tri = 0;
-    const bool epi_ops = g->res || g->mask_bits || g->relu_bits, segmented = g->k_seg > 0;
-    AS_REQUIRE(!(epi_ops || segmented) || (!g->colsum && !g->splitk_ws && !g->accumulate && prec == 0 && (a_kc || b_kc)),
-               AS_ERR_BAD_ARG, "as_gemm_f32: res / mask_bits / relu_bits / k_seg go with the general kernel only (no colsum, splitk_ws, "
-               "accumulate, split precision or weight-gradient shape)");
-    AS_REQUIRE(!g->relu_bits || g->act == 1, AS_ERR_BAD_ARG, "as_gemm_f32: relu_bits is the bit image of a ReLU epilogue (act == 1)");
-    AS_REQUIRE(!(epi_ops || segmented) || (a_kc && aligned16(g->A) && aligned16(g->B) && a_ld % 4 == 0 && b_ld % 4 == 0 && g->K % 4 == 0 &&
-                                           (b_kc || g->N % 4 == 0) && g->act <= 1 && (g->a_off || segmented || g->a_batch % 4 == 0) &&
-                                           (g->b_off || segmented || g->b_batch % 4 == 0)),
-               AS_ERR_BAD_ARG, "as_gemm_f32: res / mask_bits / relu_bits / k_seg need a reduction-contiguous A, float4-clean operands "
-               "and act <= 1");
-    AS_REQUIRE(!(epi_ops || segmented) || ((long)g->M * g->ldc < (1L << 31) && (long)g->M * g->res_ld < (1L << 31)),
-               AS_ERR_BAD_ARG, "as_gemm_f32: res / mask_bits / relu_bits / k_seg address one batch member's C and res with 32-bit offsets");
-    AS_REQUIRE(!segmented || (g->k_seg % BK == 0 && g->K % g->k_seg == 0 && g->a_seg_off && g->b_seg_off && g->b_kT == 0),
-               AS_ERR_BAD_ARG, "as_gemm_f32: k_seg=%d needs a multiple of %d that divides K=%d and both segment tables", g->k_seg, BK, g->K);
-    const bool grouped = g->a_off || g->b_off || g->c_off || g->bias_off;
-    if (grouped || segmented) {  // alignment of table offsets is the caller's contract (multiples of 4 floats) -- see header
-        k.a_vec = aligned16(g->A) && a_ld % 4 == 0;
-        k.b_vec = aligned16(g->B) && b_ld % 4 == 0;
+    k.k_tri = p.k_tri;
+    return k;
+}
+
+// the on-the-fly split kernel (as_gemm.precision 1 / 2)
+int launch_split(const as_gemm* g, const as_gemm_plan& p, hipStream_t st) {
+    const GemmK k = kernel_args(g, p, st);
+    if (p.planes == 3) {
+        static const int slots = resident_blocks(gemm_split_nt_kernel<128, 128, 3>);
+        hipLaunchKernelGGL((gemm_split_nt_kernel<128, 128, 3>), dim3((unsigned)(p.work < slots ? p.work : slots)), dim3(256), 0, st, k);
+    } else {
+        static const int slots = resident_blocks(gemm_split_nt_kernel<128, 128, 2>);
+        hipLaunchKernelGGL((gemm_split_nt_kernel<128, 128, 2>), dim3((unsigned)(p.work < slots ? p.work : slots)), dim3(256), 0, st, k);
     }
-    AS_REQUIRE(!(g->colsum && a_kc), AS_ERR_BAD_ARG, "as_gemm_f32: colsum needs an output-contiguous A operand (a_i == 1)");
-    // precision == 3: the library's split matrix arithmetic (as_set_matrix_arith(1)) for forward shapes -- both operands
-    // reduction-contiguous, plain or ReLU-bit epilogue, linear or grouped batches -- on the bf16 matrix instruction with both
-    // operands split inside the kernel (gemm_s6.hip: 1.36 x this kernel on the transformer's block groups, 110 x [6400 x 256 x
-    // 256]).  Opt-in per call and independent of the launch's size: a size threshold would make the last bits of a result
-    // depend on the batch it was computed in (measured: 7e-5 on the transformer's contours between batches of 4 and 32).
-    // The input-gradient orientation (B column-contiguous, with res / mask_bits / k_seg) goes the same way.
-    if (a_kc && (b_kc || g->b_j == 1) && g->precision == 3) {
-        const int took = as_gemm_s6_nt_ext(g, st);
-        if (took != 0) return took < 0 ? took : 0;
-    }
-    // split-precision request (forward linears only): both operands reduction-contiguous and float4-clean, else exact fp32
-    if (prec != 0 && a_kc && b_kc && k.a_vec && k.b_vec && g->K % 4 == 0 && !g->colsum) {
-        AS_REQUIRE(g->precision == 1 || g->precision == 2, AS_ERR_BAD_ARG, "as_gemm_f32: precision=%d", g->precision);
-        const long work = (long)as_cdiv(g->M, 128) * as_cdiv(g->N, 128) * g->batch;
-        if (prec == 2) {
-            static const int slots = resident_blocks(gemm_split_nt_kernel<128, 128, 3>);
-            hipLaunchKernelGGL((gemm_split_nt_kernel<128, 128, 3>), dim3((unsigned)(work < slots ? work : slots)), dim3(256), 0, st, k);
-        } else {
-            static const int slots = resident_blocks(gemm_split_nt_kernel<128, 128, 2>);
-            hipLaunchKernelGGL((gemm_split_nt_kernel<128, 128, 2>), dim3((unsigned)(work < slots ? work : slots)), dim3(256), 0, st, k);
-        }
-        AS_LAUNCH_CHECK("as_gemm_f32(split)");
-        return 0;
-    }
-    // 128x128 tiles once they fill the chip and N fills a tile (N = 100: 60 vs 72 us at 64x64), else 64x64 for more workgroups
-    const long big = (long)as_cdiv(g->M, 128) * as_cdiv(g->N, 128) * g->batch;
-    if (big >= 512 && g->N >= 128) {  // fewer 128x128 tiles leave most of the 768 resident slots empty: 64x64 then
-                                                 // (measured 6400 x 768 x 256: 300 tiles 39.9 us, as 1200 64x64 tiles 30.1 us)
-        // 128x128 tiles that do not fill the resident slots (3 per CU) with a long reduction: split K so that the persistent
-        // workgroups get equal shares (measured: 440 tiles, K = 6400 run at 75 TF/s, 768 tiles of the same shape at 100)
-        static const int slots = resident_blocks(gemm_f32_kernel<128, 128, true, true, true>);
-        if (g->splitk_ws && !grouped && big < slots && g->K >= 2048 && !g->bias && g->act == 0) {
-            const long per = (long)g->batch * g->M * (g->N + (g->colsum ? 1 : 0));
-            long best = 1;
-            double best_cost = 1.0;  // rounds of work per workgroup, in units of the unsplit tile time
-            for (long sk = 2; sk <= 8 && sk * per <= g->splitk_ws_floats; ++sk) {
-                const double cost = (double)((big * sk + slots - 1) / slots) / sk + 0.02 * sk;  // + slab traffic
-                if (cost < best_cost - 1e-9) best_cost = cost, best = sk;
-            }
-            if (best > 1) {
-                k.kchunk = (int)as_round_up(as_cdiv(g->K, best), BK);
-                k.splitk = as_cdiv(g->K, k.kchunk);
-                k.slab = g->splitk_ws;
-                AS_TRY((launch<128, 128>(k, g->batch, a_kc, b_kc, st)));
-                const long total = per;
-                long blocks = (total + 255) / 256;
-                if (blocks > 2048) blocks = 2048;
-                hipLaunchKernelGGL(splitk_reduce_kernel, dim3((int)blocks), dim3(256), 0, st, k);
-                AS_LAUNCH_CHECK("as_gemm_f32(splitk reduce)");
-                return 0;
-            }
-        }
-        k.xcd_panels = a_kc && g->N > 128 && g->k_tri == 0 && big >= 2048 && slots % 8 == 0;
-        return launch<128, 128>(k, g->batch, a_kc, b_kc, st);
-    }
-    // few output tiles and a long reduction (weight gradients): split K over workgroups
-    const long tiles = (long)as_cdiv(g->M, 64) * as_cdiv(g->N, 64) * g->batch;
-    if (g->splitk_ws && !grouped && tiles < 512 && g->K >= 512 && !g->bias && g->act == 0) {
-        long sk = (1024 + tiles - 1) / tiles;
-        const int min_chunk = tiles * (g->K / 128) < 128 ? 64 : 128;  // a handful of tiles: shorter chunks, still >= 2 k-steps
-        if (sk > g->K / min_chunk) sk = g->K / min_chunk;
-        if (sk > 64) sk = 64;
-        const long per = (long)g->batch * g->M * (g->N + (g->colsum ? 1 : 0));
-        if (sk * per > g->splitk_ws_floats) sk = g->splitk_ws_floats / per;
-        // weight-gradient shapes with many tiles per chunk: a multiple of 8 chunks, one XCD per chunk (GemmK::xcd_chunks)
-        const bool want_xcd = !a_kc && !b_kc && sk >= 12 && tiles >= 16;
-        if (want_xcd)   // the nearest multiple of 8 (downwards) whose BK-rounded chunks still number a multiple of 8
-            for (long c = (sk + 4) / 8 * 8; c >= 8; c -= 8)
-                if (as_cdiv(g->K, as_round_up(as_cdiv(g->K, c), BK)) % 8 == 0) { sk = c; break; }
-        if (sk > 1) {
-            k.kchunk = (int)as_round_up(as_cdiv(g->K, sk), BK);
-            k.splitk = as_cdiv(g->K, k.kchunk);
-            k.xcd_chunks = want_xcd && k.splitk % 8 == 0;
-            k.slab = g->splitk_ws;
-            // few slabs: the last workgroup to arrive at a tile sums them in the kernel (input gradient of GRU layer 1, 3 slabs:
-            // 52 us against 36 + 45 for a reduce kernel that has to squeeze in beside the side stream's persistent GEMM).
-            // Many slabs (a handful of tiles) would leave the sums to a handful of workgroups: the wide reduce kernel then.
-            if (k.splitk <= 16 && tiles < COUNTERS) k.counters = counters_for(st);
-        }
-    }
-    AS_TRY((launch<64, 64>(k, g->batch, a_kc, b_kc, st)));
-    if (k.splitk > 1 && !k.counters) {
-        const long total = (long)g->batch * g->M * (g->N + (g->colsum ? 1 : 0));
-        if (k.splitk >= 16 && total <= (1L << 20)) {
-            hipLaunchKernelGGL(splitk_reduce4_kernel, dim3((unsigned)((total + 63) / 64)), dim3(256), 0, st, k);
-        } else {
-            long blocks = (total + 255) / 256;
-            if (blocks > 2048) blocks = 2048;
-            hipLaunchKernelGGL(splitk_reduce_kernel, dim3((int)blocks), dim3(256), 0, st, k);
-        }
-        AS_LAUNCH_CHECK("as_gemm_f32(splitk reduce)");
-    }
+    AS_LAUNCH_CHECK("as_gemm_f32(split)");
     return 0;
+}
+
+// as_gemm_env.slots128
+int slots128() {
+    static const int slots = resident_blocks(gemm_f32_kernel<128, 128, true, true, true>);
+    return slots;
+}
+
+// the general kernel and the reduce kernel behind it
+int launch_general(const as_gemm* g, const as_gemm_plan& p, hipStream_t st) {
+    const GemmK k = kernel_args(g, p, st);
+    if (p.tile_m == 128) AS_TRY((launch<128, 128>(k, p, st)));
+    else AS_TRY((launch<64, 64>(k, p, st)));
+    const int reduce = p.reduce != AS_REDUCE_COUNTERS ? p.reduce : k.counters ? AS_REDUCE_NONE : p.reduce_fallback;
+    if (reduce == AS_REDUCE_NONE) return 0;
+    const long total = (long)g->batch * g->M * (g->N + (g->colsum ? 1 : 0));
+    if (reduce == AS_REDUCE_SPLITK4) {
+        hipLaunchKernelGGL(splitk_reduce4_kernel, dim3((unsigned)((total + 63) / 64)), dim3(256), 0, st, k);
+    } else {
+        long blocks = (total + 255) / 256;
+        if (blocks > 2048) blocks = 2048;
+        hipLaunchKernelGGL(splitk_reduce_kernel, dim3((int)blocks), dim3(256), 0, st, k);
+    }
+    AS_LAUNCH_CHECK("as_gemm_f32(splitk reduce)");
+    return 0;
+}
+
+}  // namespace
+
+// validate and plan (gemm_plan.cpp: nothing is launched before the whole descriptor has been checked), then the planned launcher
+extern "C" int as_gemm_f32(const as_gemm* g, void* stream) {
+    const as_gemm_env env{as_matrix_arith(), slots128(), COUNTERS};
+    as_gemm_plan p;
+    char err[512];
+    const int rc = as_gemm_plan_make(g, &env, &p, err, sizeof err);
+    AS_REQUIRE(rc == 0, rc, "%s", err);
+    hipStream_t st = (hipStream_t)stream;
+    switch (p.family) {
+        case AS_GEMM_S6: return as_gemm_s6_launch(g, p, st);
+        case AS_GEMM_WGRAD:
+        case AS_GEMM_WGRAD_STREAMK: return as_wgrad_launch(g, p, st);
+        case AS_GEMM_SPLIT: return launch_split(g, p, st);
+        default: return launch_general(g, p, st);
+    }
 }

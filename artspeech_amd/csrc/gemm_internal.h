@@ -1,30 +1,20 @@
 // Internal (non-ABI) hand-over between the GEMM translation units.
 #pragma once
 #include "as_common.h"
+#include "gemm_plan.h"
 
-// wgrad_f32.hip: weight-gradient shapes (both operands reduction-strided, long reduction).  1 = taken and launched,
-// 0 = not a shape for this kernel (the caller continues with the general kernel), < 0 = error.
-int as_wgrad_try(const as_gemm* g, hipStream_t st);
-// Several weight-gradient problems of the same reduction length (a_i == b_j == 1, linear batch strides, N > 128) as ONE
-// launch of 128 x 256 tiles + one reduce launch.  g.splitk_ws / cu_budget of the jobs are ignored (slab, cu_budget here).
-// colsum_b (optional): column sums of the B operand [batch][N] (the bias gradient when the problem is posed transposed);
-// c_trans: the result is stored transposed, C[batch][n * ldc + m].  1 = launched, 0 = not a case (caller falls back), < 0 = error.
-struct as_wgrad_job {
-    as_gemm g;
-    float* colsum_b; long colsum_b_batch;
-    int c_trans;
-};
+// The launchers as_gemm_f32 switches into once gemm_plan.cpp has validated the descriptor and chosen the kernel: each copies
+// descriptor fields into its kernel-argument struct and picks the instantiation from the plan.  0, or a launch error.
+int as_gemm_s6_launch(const as_gemm* g, const as_gemm_plan& p, hipStream_t st);   // gemm_s6.hip
+int as_wgrad_launch(const as_gemm* g, const as_gemm_plan& p, hipStream_t st);     // wgrad_f32.hip
+// wgrad_f32.hip: several weight-gradient problems as one launch (as_wgrad_job, gemm_plan.h).  1 = launched, 0 = not a case
+// (caller falls back), < 0 = error.
 // exact: the fp32 matrix instruction whatever as_matrix_arith() says -- for launches that run BESIDE a latency-bound kernel: the
 // bf16 instruction draws more power, the chip clocks ~10 % lower under it, and a recurrence on the other CUs pays that on
 // every dependent step (measured in the BiGRU step: weight gradients 161 -> 114 us, the recurrence beside them 115 -> 131 us).
 int as_wgrad_multi(const as_wgrad_job* jobs, int n, float* slab, long slab_floats, int cu_budget, hipStream_t st, bool exact = false);
 
-// How fp32 matrix products are formed (as_set_matrix_arith, include/artspeech_hip.h):
-//   AS_ARITH_FP32    v_mfma_f32_32x32x2_f32 on the fp32 operands (every kernel has this path)
-//   AS_ARITH_BF16X6  operands split exactly into three bfloat16 planes, six plane products on v_mfma_f32_32x32x16_bf16,
-//                    fp32 accumulation -- where a kernel has the path (the default)
-enum { AS_ARITH_FP32 = 0, AS_ARITH_BF16X6 = 1 };
-int as_matrix_arith();
+int as_matrix_arith();   // error.cpp: AS_ARITH_FP32 or AS_ARITH_BF16X6 (gemm_plan.h)
 
 // rowops.hip: B[batch][n][k] (element strides n_stride, k_stride, batch_stride) as three bfloat16 planes
 // out[plane][batch][Kpad / 16][rows_pad][16] (x = hi + mid + lo exactly; n >= N or k >= K: zeros).  Up to 8 jobs, one launch.
@@ -37,14 +27,6 @@ int as_emit_planes(const as_planes_job* jobs, int n, hipStream_t st);
 static inline long as_planes_batch_stride(int rows_pad, int Kpad) { return (long)(Kpad / 16) * rows_pad * 16; }
 static inline long as_planes_floats(int batch, int rows_pad, int Kpad) { return 3 * batch * as_planes_batch_stride(rows_pad, Kpad) / 2; }
 
-// gemm_s6.hip: C[g] = act(A[g][M][K] . B[g][N][K]^T + bias[g]) with both operands fp32 and reduction-contiguous, in the split
-// arithmetic (both split inside the kernel: no plane copies).  K % 16 == 0, lda / ldb / batch strides % 4 == 0, 16-byte aligned
-// operands.  1 = launched, 0 = not a case (mode fp32, shape, alignment: take as_gemm_f32), < 0 = error.
-int as_gemm_s6_nt(const float* A, long lda, long a_batch, const float* B, long ldb, long b_batch, const float* bias, long bias_batch, float* C,
-                  long ldc, long c_batch, int M, int N, int K, int batch, int act, hipStream_t st);
-// the same from an as_gemm descriptor: forward shapes (a_k == b_k == 1) incl. grouped offsets (a_off ...) and relu_bits; everything
-// else the descriptor may ask for (res, mask_bits, k_seg, k_tri, colsum, split K, accumulate, shifts) -> 0
-int as_gemm_s6_nt_ext(const as_gemm* g, hipStream_t st);
 template <int N> struct IC2 { static constexpr int value = N; };
 
 // A cross-stream fork without a barrier packet on the producing stream: the event is bound to the completion of the NEXT kernel

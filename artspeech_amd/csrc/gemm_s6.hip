@@ -418,29 +418,13 @@ __global__ __launch_bounds__(NTH, 3) void gemm_s6_kernel(S6K g) {
 
 }  // namespace
 
+static_assert(TB == AS_S6_TILE && BK == AS_S6_BK, "gemm_plan.cpp plans for this tile");
+
 // see gemm_internal.h
-int as_gemm_s6_nt_ext(const as_gemm* g, hipStream_t st) {
-    if (as_matrix_arith() != AS_ARITH_BF16X6) return 0;
-    const bool anc = g->a_k != 1;     // A[k][m], m contiguous (weight-gradient orientation)
-    const bool bnc = g->b_k != 1;     // B[k][n], n contiguous (input- and weight-gradient orientation)
-    if ((anc && (g->a_i != 1 || !bnc)) || (bnc && g->b_j != 1) || g->K < BK || g->K % BK || g->act < 0 || g->act > 2) return 0;
-    if (g->k_tri || g->accumulate || g->b_kT || g->b_kshift || (g->precision != 0 && g->precision != 3)) return 0;
-    if (g->colsum && !anc) return 0;
-    const bool ext = g->res || g->mask_bits || g->k_seg;
-    if (anc && (ext || g->relu_bits || g->bias)) return 0;
-    if (g->relu_bits && (g->act != 1 || ext)) return 0;
-    if (!anc && (g->a_i % 4 || (reinterpret_cast<uintptr_t>(g->A) & 15) || (!g->a_off && !g->k_seg && g->a_batch % 4))) return 0;
-    if (!bnc && (g->b_j % 4 || (reinterpret_cast<uintptr_t>(g->B) & 15) || (!g->b_off && !g->k_seg && g->b_batch % 4))) return 0;
-    // row-contiguous operands are loaded as float4s along the rows
-    if (anc && (g->a_k % 4 || g->M % 4 || (reinterpret_cast<uintptr_t>(g->A) & 15) || (!g->a_off && g->a_batch % 4))) return 0;
-    if (bnc && (g->b_k % 4 || g->N % 4 || (reinterpret_cast<uintptr_t>(g->B) & 15) || (!g->b_off && !g->k_seg && g->b_batch % 4))) return 0;
-    if (g->k_seg && (g->k_seg % BK || g->K % g->k_seg || !g->a_seg_off || !g->b_seg_off)) return 0;
-    const long kspan = g->k_seg ? g->k_seg : g->K;
-    // 32-bit byte offsets inside one batch member / segment
-    if ((anc ? kspan * g->a_k + g->M : (long)g->M * g->a_i) >= (1L << 30) || (bnc ? kspan * g->b_k + g->N : (long)g->N * g->b_j) >= (1L << 30)) return 0;
+int as_gemm_s6_launch(const as_gemm* g, const as_gemm_plan& p, hipStream_t st) {
     S6K k{};
-    k.A = g->A; k.lda = anc ? g->a_k : g->a_i; k.a_batch = g->a_batch;
-    k.B = g->B; k.ldb = bnc ? g->b_k : g->b_j; k.b_batch = g->b_batch;
+    k.A = g->A; k.lda = p.anc ? g->a_k : g->a_i; k.a_batch = g->a_batch;
+    k.B = g->B; k.ldb = p.bnc ? g->b_k : g->b_j; k.b_batch = g->b_batch;
     k.C = g->C; k.ldc = g->ldc; k.c_batch = g->c_batch;
     k.bias = g->bias; k.bias_batch = g->bias_batch;
     k.M = g->M; k.N = g->N; k.K = g->K; k.act = g->act; k.tiles_m = as_cdiv(g->M, TB); k.tiles_n = as_cdiv(g->N, TB);
@@ -451,42 +435,18 @@ int as_gemm_s6_nt_ext(const as_gemm* g, hipStream_t st) {
     k.k_seg = g->k_seg; k.nseg = g->k_seg ? g->K / g->k_seg : 1;
     k.a_seg_off = (const long*)g->a_seg_off; k.b_seg_off = (const long*)g->b_seg_off;
     k.colsum = g->colsum; k.colsum_batch = g->colsum_batch;
-    {
-        auto al16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
-        k.vec_epi = g->N % 4 == 0 && g->ldc % 4 == 0 && al16(g->C) && (g->c_off || g->c_batch % 4 == 0) &&
-                    (!g->bias || (al16(g->bias) && (g->bias_off || g->bias_batch % 4 == 0))) &&
-                    (!g->res || (al16(g->res) && g->res_ld % 4 == 0 && (g->res_off || g->res_batch % 4 == 0)));
-    }
-    long blocks = (long)k.tiles_m * k.tiles_n * g->batch;
-    if (blocks > (1L << 30)) return 0;
+    k.vec_epi = p.vec_epi;
     k.batch = g->batch;
-    if (anc) {
-        // one workgroup walks the whole reduction of its tile: worth it once the tiles fill the chip (else wgrad_f32.hip's stream-K)
-        if (blocks < 256) return 0;
-        k.xcd_group = k.tiles_m * k.tiles_n;
-        blocks = (long)as_round_up(g->batch, 8) * k.xcd_group;
-    } else if (k.tiles_n > 1) {
-        blocks = (long)as_round_up((long)g->batch * k.tiles_m, 8) * k.tiles_n;
-    }
-    const dim3 grid((unsigned)blocks), blk(NTH);
-    if (anc) hipLaunchKernelGGL((gemm_s6_kernel<true, true, false>), grid, blk, 0, st, k);
-    else if (ext) {
-        if (bnc) hipLaunchKernelGGL((gemm_s6_kernel<false, true, true>), grid, blk, 0, st, k);
+    k.xcd_group = p.xcd_group;
+    const dim3 grid((unsigned)p.work), blk(NTH);
+    if (p.anc) hipLaunchKernelGGL((gemm_s6_kernel<true, true, false>), grid, blk, 0, st, k);
+    else if (p.ext) {
+        if (p.bnc) hipLaunchKernelGGL((gemm_s6_kernel<false, true, true>), grid, blk, 0, st, k);
         else hipLaunchKernelGGL((gemm_s6_kernel<false, false, true>), grid, blk, 0, st, k);
     } else {
-        if (bnc) hipLaunchKernelGGL((gemm_s6_kernel<false, true, false>), grid, blk, 0, st, k);
+        if (p.bnc) hipLaunchKernelGGL((gemm_s6_kernel<false, true, false>), grid, blk, 0, st, k);
         else hipLaunchKernelGGL((gemm_s6_kernel<false, false, false>), grid, blk, 0, st, k);
     }
     AS_LAUNCH_CHECK("as_gemm_s6");
-    return 1;
-}
-
-int as_gemm_s6_nt(const float* A, long lda, long a_batch, const float* B, long ldb, long b_batch, const float* bias, long bias_batch, float* C,
-                  long ldc, long c_batch, int M, int N, int K, int batch, int act, hipStream_t st) {
-    if (!A || !B || !C || M < 1 || N < 1 || batch < 1) return 0;
-    as_gemm g{};
-    g.A = A; g.B = B; g.C = C; g.bias = bias; g.M = M; g.N = N; g.K = K;
-    g.a_i = lda; g.a_k = 1; g.b_j = ldb; g.b_k = 1; g.ldc = ldc;
-    g.batch = batch; g.a_batch = a_batch; g.b_batch = b_batch; g.c_batch = c_batch; g.bias_batch = bias_batch; g.act = act;
-    return as_gemm_s6_nt_ext(&g, st);
+    return 0;
 }

@@ -1005,7 +1005,19 @@ __global__ __launch_bounds__(256, LOUT_WPS) void lin_out_s6_kernel(LinOutK g) {
     criterion_tail(g, tile, wg_sum, tid, red, 4);
 }
 
-inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+// The kernels' tile list from x, the number of 64-row tiles per batch member: those are dispatched first, then the remaining
+// rows as 32-row tiles.  Returns the number of tiles (workgroups).
+template <typename K>
+long tile_list(K& k, int x) {
+    const int rest = k.M - x * 64;
+    k.big_per_batch = x > 0 ? x : 1;
+    k.big_per_batch_rows = x * 64;
+    k.n_big = x * k.batch;
+    k.small_per_batch = as_cdiv(rest, 32);
+    const long total = (long)k.n_big + (long)k.small_per_batch * k.batch;
+    if (k.small_per_batch == 0) k.small_per_batch = 1;
+    return total;
+}
 
 // Tile list.  Two workgroups per CU = 512 slots; a launch of T equal tiles takes ceil(T / 512) rounds, and the head
 // layers' 1100 tiles of 64 rows were 3 rounds of which the last held 76 tiles (measured: 31 us of a 118 us launch with
@@ -1020,13 +1032,7 @@ int launch(const LinK& k, hipStream_t st) {
     int x = (int)(rounds * slots / k.batch);                    // 64-row tiles per head that fill whole rounds
     if (x > k.M / 64 || k.tile_rows == 64) x = k.M / 64;
     if (k.tile_rows == 32) x = 0;
-    const int rest = k.M - x * 64;
-    kk.big_per_batch = x > 0 ? x : 1;
-    kk.big_per_batch_rows = x * 64;
-    kk.n_big = x * k.batch;
-    kk.small_per_batch = as_cdiv(rest, 32);
-    const long total = (long)kk.n_big + (long)kk.small_per_batch * k.batch;
-    if (kk.small_per_batch == 0) kk.small_per_batch = 1;
+    const long total = tile_list(kk, x);
     if (kk.Bp) {   // the products on the bf16 matrix instruction, B as planes (lin_s6_kernel)
         hipLaunchKernelGGL((lin_s6_kernel<EPI>), dim3((unsigned)total), dim3(NT), 0, st, kk);
         AS_LAUNCH_CHECK("as_lin_s6");
@@ -1051,7 +1057,7 @@ extern "C" void as_lin_debug_stamps(uint64_t* buf, int64_t max_workgroups) {
 // then takes the general GEMM + row kernels), < 0 on a launch error.
 int as_lin_try(const as_lin* a, hipStream_t st) {
     if (a->K % BK || a->K < BK || a->N > BN || a->N < 4 || a->M < 1 || a->batch < 1) return 0;
-    if (!aligned16(a->A) || !aligned16(a->B) || a->lda % 4 || a->ldb % 4 || a->a_batch % 4 || a->b_batch % 4) return 0;
+    if (!as_aligned16(a->A) || !as_aligned16(a->B) || a->lda % 4 || a->ldb % 4 || a->a_batch % 4 || a->b_batch % 4) return 0;
     if (!a->b_kc && a->N % 4) return 0;
     if (a->epi != EPI_PLAIN && (a->N != BN || !a->C)) return 0;
     if (a->epi == EPI_PLAIN && a->N <= BN / 2) return 0;  // half of the 8 feature-side waves would multiply padding
@@ -1069,7 +1075,7 @@ int as_lin_try(const as_lin* a, hipStream_t st) {
     k.xhat = a->xhat; k.ldx = a->ldx; k.x_batch = a->x_batch; k.rstd_in = a->rstd_in; k.bits_in = a->bits_in;
     if (k.ka_valid % 4) return 0;
     // B as bfloat16 planes (as_emit_planes) and the split arithmetic on: the bf16-MFMA kernel; else the exact fp32 one
-    if (a->Bp && as_matrix_arith() == AS_ARITH_BF16X6 && a->K % S6_BK == 0 && a->bp_rows >= BN && (reinterpret_cast<uintptr_t>(a->Bp) & 15) == 0 &&
+    if (a->Bp && as_matrix_arith() == AS_ARITH_BF16X6 && a->K % S6_BK == 0 && a->bp_rows >= BN && as_aligned16(a->Bp) &&
         a->bp_plane % 8 == 0 && a->bp_batch % 8 == 0 && a->lda < (1L << 23)) {
         k.Bp = a->Bp; k.bp_plane = a->bp_plane; k.bp_batch = a->bp_batch; k.bp_rows = a->bp_rows;
     }
@@ -1089,8 +1095,8 @@ int as_lin_try(const as_lin* a, hipStream_t st) {
 int as_lin_plain_s6(const as_lin* a, int ksplit, long c_split, hipStream_t st, int waves_per_simd) {
     if (as_matrix_arith() != AS_ARITH_BF16X6 || !a->Bp) return 0;
     if (a->epi != EPI_PLAIN || a->K % S6_BK || a->K < S6_BK || a->N > BN || a->N < 1 || a->M < 1 || a->batch < 1 || !a->C) return 0;
-    if (!aligned16(a->A) || a->lda % 4 || a->a_batch % 4 || a->lda >= (1L << 23)) return 0;
-    if ((reinterpret_cast<uintptr_t>(a->Bp) & 15) || a->bp_plane % 8 || a->bp_batch % 8) return 0;
+    if (!as_aligned16(a->A) || a->lda % 4 || a->a_batch % 4 || a->lda >= (1L << 23)) return 0;
+    if (!as_aligned16(a->Bp) || a->bp_plane % 8 || a->bp_batch % 8) return 0;
     const int nw = a->N <= 128 ? 4 : 8;
     if (a->bp_rows < nw * 32) return 0;
     if (ksplit < 1) ksplit = 1;
@@ -1109,13 +1115,7 @@ int as_lin_plain_s6(const as_lin* a, int ksplit, long c_split, hipStream_t st, i
     int tile = a->tile_rows;
     if (tile != 32 && tile != 64) tile = (long)as_cdiv(a->M, 64) * a->batch * ksplit >= 384 ? 64 : 32;
     const int x = tile == 64 ? a->M / 64 : 0;
-    const int rest = a->M - x * 64;
-    k.big_per_batch = x > 0 ? x : 1;
-    k.big_per_batch_rows = x * 64;
-    k.n_big = x * a->batch;
-    k.small_per_batch = as_cdiv(rest, 32);
-    const long total = (long)k.n_big + (long)k.small_per_batch * a->batch;
-    if (k.small_per_batch == 0) k.small_per_batch = 1;
+    const long total = tile_list(k, x);
     if (total > (1L << 30) || ksplit > 65535) return 0;
     if (nw == 4 && waves_per_simd == 2) hipLaunchKernelGGL((lin_s6_plain_kernel<4, 2>), dim3((unsigned)total, ksplit), dim3(256), 0, st, k);
     else if (nw == 4) hipLaunchKernelGGL((lin_s6_plain_kernel<4, 4>), dim3((unsigned)total, ksplit), dim3(256), 0, st, k);
@@ -1128,7 +1128,7 @@ int as_lin_plain_s6(const as_lin* a, int ksplit, long c_split, hipStream_t st, i
 // 1 = launched (fused: *n_partials workgroup sums were written to `partial`), 0 = not a case, < 0 = error.
 int as_lin_out_try(const as_lin_out* a, int* n_partials, hipStream_t st) {
     if (a->K % BK || a->K < BK || a->N > ON || a->N < 4 || a->N % 2 || a->M < 1 || a->batch < 1) return 0;
-    if (!aligned16(a->A) || !aligned16(a->B) || a->lda % 4 || a->ldb % 4 || a->a_batch % 4 || a->b_batch % 4) return 0;
+    if (!as_aligned16(a->A) || !as_aligned16(a->B) || a->lda % 4 || a->ldb % 4 || a->a_batch % 4 || a->b_batch % 4) return 0;
     if (a->b_rows < a->N) return 0;
     LinOutK k{};
     k.A = a->A; k.lda = a->lda; k.a_batch = a->a_batch;
@@ -1149,20 +1149,14 @@ int as_lin_out_try(const as_lin_out* a, int* n_partials, hipStream_t st) {
     int x = (int)(rounds * slots / k.batch);
     if (x > k.M / 64) x = k.M / 64;
     if (rounds == 0) x = k.M / 64;                       // less than one round: plain 64-row tiles (+ a ragged end)
-    const int rest = k.M - x * 64;
-    k.big_per_batch = x > 0 ? x : 1;
-    k.big_per_batch_rows = x * 64;
-    k.n_big = x * k.batch;
-    k.small_per_batch = as_cdiv(rest, 32);
-    const long total = (long)k.n_big + (long)k.small_per_batch * k.batch;
-    if (k.small_per_batch == 0) k.small_per_batch = 1;
+    const long total = tile_list(k, x);
     if (k.tgt && total > a->partial_capacity) return 0;
     if (k.tgt && a->loss) {
         k.counter = as_arrival_counter(st);
         k.loss = k.counter ? a->loss : nullptr;
     }
     const int left = k.counter ? 0 : (int)total;   // partials that still await as_loss_final
-    if (a->Bp && as_matrix_arith() == AS_ARITH_BF16X6 && a->K % S6_BK == 0 && a->bp_rows >= ON && (reinterpret_cast<uintptr_t>(a->Bp) & 15) == 0 &&
+    if (a->Bp && as_matrix_arith() == AS_ARITH_BF16X6 && a->K % S6_BK == 0 && a->bp_rows >= ON && as_aligned16(a->Bp) &&
         a->bp_plane % 8 == 0 && a->bp_batch % 8 == 0 && a->lda < (1L << 23)) {
         k.Bp = a->Bp; k.bp_plane = a->bp_plane; k.bp_batch = a->bp_batch; k.bp_rows = a->bp_rows;
         hipLaunchKernelGGL(lin_out_s6_kernel, dim3((unsigned)total), dim3(256), 0, st, k);
@@ -1198,13 +1192,8 @@ extern "C" int as_linear_fwd(const float* A, int64_t lda, const float* W, int64_
                "as_linear_fwd: bad argument");
     hipStream_t st = (hipStream_t)stream;
     int bn, nb;
-    if (!planes_ws) {   // both operands split inside the kernel (gemm_s6.hip): no scratch needed
-        const int took = as_gemm_s6_nt(A, lda, 0, W, ldw, 0, bias, 0, out, ldo, 0, M, N, K, 1, act, st);
-        AS_REQUIRE(took >= 0, took, "as_linear_fwd: launch failed");
-        if (took) return 0;
-    }
     if (as_matrix_arith() == AS_ARITH_BF16X6 && planes_ws && K % S6_BK == 0 && lda % 4 == 0 && linear_blocks(N, &bn, &nb) &&
-        (reinterpret_cast<uintptr_t>(planes_ws) & 15) == 0) {
+        as_aligned16(planes_ws)) {
         const int rows_last = N - (nb - 1) * bn;   // (nb > 1: whole blocks)
         as_planes_job j{W, ldw, 1, (long)bn * ldw, nb, nb > 1 ? bn : rows_last, K, bn, K, reinterpret_cast<uint16_t*>(planes_ws)};
         AS_TRY(as_emit_planes(&j, 1, st));
@@ -1221,5 +1210,8 @@ extern "C" int as_linear_fwd(const float* A, int64_t lda, const float* W, int64_
     as_gemm g{};
     g.A = A; g.B = W; g.C = out; g.bias = bias; g.M = M; g.N = N; g.K = K;
     g.a_i = lda; g.a_k = 1; g.b_j = ldw; g.b_k = 1; g.ldc = ldo; g.batch = 1; g.act = act;
+    // no scratch for planes: both operands split inside the kernel where gemm_s6.hip takes the shape; a plane kernel that declined
+    // stays on the exact general kernel
+    g.precision = planes_ws ? 0 : 3;
     return as_gemm_f32(&g, st);
 }

@@ -711,8 +711,7 @@ __global__ __launch_bounds__(256) void normalize_bwd_wide_kernel(const float* dy
 }
 
 inline bool wide_ok(int D, const void* a, const void* b, const void* c) {
-    return D % 256 == 0 && D > 1024 && D <= 256 * WIDE_NV &&
-           ((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b) | reinterpret_cast<uintptr_t>(c)) & 15) == 0;
+    return D % 256 == 0 && D > 1024 && D <= 256 * WIDE_NV && as_aligned16(a) && as_aligned16(b) && as_aligned16(c);
 }
 
 // ---- masked softmax over the last dim of [Z][Tq][Tk], one wave per row ------------------------------
@@ -903,7 +902,7 @@ int as_emit_planes(const as_planes_job* jobs, int n, hipStream_t st) {
     for (int i = 0; i < n; ++i) {
         const as_planes_job& J = jobs[i];
         AS_REQUIRE(J.B && J.out && J.batch > 0 && J.N > 0 && J.K > 0 && J.rows_pad >= J.N && J.Kpad >= J.K && J.Kpad % 16 == 0 &&
-                   (reinterpret_cast<uintptr_t>(J.out) & 15) == 0, AS_ERR_BAD_ARG, "as_emit_planes: bad job %d", i);
+                   as_aligned16(J.out), AS_ERR_BAD_ARG, "as_emit_planes: bad job %d", i);
         pj.j[i] = J;
         pj.first[i] = total;
         total += (long)J.batch * (J.Kpad / 16) * J.rows_pad * 8;
@@ -1106,7 +1105,7 @@ extern "C" int as_attn_softmax_bwd(const float* probs, float* dprobs, int64_t Z,
 
 extern "C" int as_group_reduce(const float* part, const int32_t* src, int32_t G, int32_t C, int64_t len, float* dst, void* stream) {
     AS_REQUIRE(part && src && dst && G > 0 && C > 0 && len > 0, AS_ERR_BAD_ARG, "as_group_reduce: bad argument");
-    AS_REQUIRE((reinterpret_cast<uintptr_t>(part) & 15) == 0 && (reinterpret_cast<uintptr_t>(dst) & 15) == 0 && len % 4 == 0,
+    AS_REQUIRE(as_aligned16(part) && as_aligned16(dst) && len % 4 == 0,
                AS_ERR_BAD_ARG, "as_group_reduce: buffers must be 16-byte aligned and len a multiple of 4");
     long bx = (len / 4 + 255) / 256;
     if (bx > 1024) bx = 1024;
@@ -1209,7 +1208,7 @@ __global__ __launch_bounds__(256) void copy_f32x4_kernel(const float4* __restric
 }
 }  // namespace
 extern "C" int as_copy_f32(const float* src, float* dst, int64_t n, void* stream) {
-    AS_REQUIRE(src && dst && n > 0 && n % 4 == 0 && (reinterpret_cast<uintptr_t>(src) & 15) == 0 && (reinterpret_cast<uintptr_t>(dst) & 15) == 0,
+    AS_REQUIRE(src && dst && n > 0 && n % 4 == 0 && as_aligned16(src) && as_aligned16(dst),
                AS_ERR_BAD_ARG, "as_copy_f32: n %% 4 == 0, 16-byte aligned buffers");
     const long n4 = n / 4;
     const long blocks = std::min<long>((n4 + 255) / 256, 256L * 16);   // 16 workgroups per CU

@@ -524,16 +524,11 @@ __global__ __launch_bounds__(256) void wgrad_reduce_kernel(WgradMulti mm) {
     g.colsum_b[bz * g.colsum_b_batch + (e - bz * g.N)] = s;
 }
 
-inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+static_assert(BM == AS_WGRAD_BM && BK == AS_WGRAD_BK && PIECE_FLOATS == AS_WGRAD_PIECE_FLOATS && MAXP == AS_WGRAD_MAXP,
+              "gemm_plan.cpp plans for these tiles");
 
-// shape / alignment contract of one problem; fills the descriptor's operand fields.  false = not a case for this kernel.
-bool describe(const as_gemm* g, WgradK& k) {
-    if (!(g->a_i == 1 && g->b_j == 1) || g->K < 256 || g->K % KALIGN || g->act != 0 || g->bias) return false;
-    if (g->b_kT > 0 && (g->a_off || g->b_off || g->c_off)) return false;   // shifted operand: linear batch strides only
-    if (g->M % 4 || g->N % 4 || g->a_k % 4 || g->b_k % 4 || !aligned16(g->A) || !aligned16(g->B)) return false;
-    const bool grouped = g->a_off || g->b_off || g->c_off;
-    if (!grouped && (g->a_batch % 4 || g->b_batch % 4)) return false;
-    if ((long)g->M * g->N % 4) return false;
+// the descriptor's operand fields of one problem
+void fill(const as_gemm* g, bool c_vec, WgradK& k) {
     k = WgradK{};
     k.A = g->A; k.B = g->B; k.C = g->C;
     k.M = g->M; k.N = g->N; k.K = g->K;
@@ -543,15 +538,13 @@ bool describe(const as_gemm* g, WgradK& k) {
     k.batch = g->batch;
     k.b_kshift = g->b_kshift; k.b_kT = g->b_kT; k.b_kshift_batch = g->b_kshift_batch;
     k.accumulate = g->accumulate;
-    k.c_vec = aligned16(g->C) && g->ldc % 4 == 0 && (g->c_off ? 1 : g->c_batch % 4 == 0);
+    k.c_vec = c_vec;
     k.colsum = g->colsum; k.colsum_batch = g->colsum_batch;
-    return true;
 }
 
 template <int BNT>
-int launch_multi(WgradMulti& mm, hipStream_t st, bool exact = false) {
+int launch_multi(WgradMulti& mm, hipStream_t st, bool s6) {
     const dim3 grid((unsigned)(8 * mm.per_xcd));
-    const bool s6 = !exact && as_matrix_arith() == AS_ARITH_BF16X6;
     if (mm.streamk && s6) hipLaunchKernelGGL((wgrad_f32_kernel<BNT, true, true>), grid, dim3(NT), 0, st, mm);
     else if (mm.streamk) hipLaunchKernelGGL((wgrad_f32_kernel<BNT, true>), grid, dim3(NT), 0, st, mm);
     else if (s6) hipLaunchKernelGGL((wgrad_f32_kernel<BNT, false, true>), grid, dim3(NT), 0, st, mm);
@@ -575,126 +568,65 @@ int launch_multi(WgradMulti& mm, hipStream_t st, bool exact = false) {
 
 }  // namespace
 
-// Takes the GEMM if it is a weight-gradient shape this kernel is built for (returns 1 and launches), else returns 0;
-// negative = error.  Called by as_gemm_f32 ahead of its general tile selection.
-int as_wgrad_try(const as_gemm* g, hipStream_t st) {
+// see gemm_internal.h: one weight-gradient problem, whole tiles per workgroup (split over K) or stream-K, as planned
+int as_wgrad_launch(const as_gemm* g, const as_gemm_plan& p, hipStream_t st) {
     WgradMulti mm{};
     WgradK& k = mm.p[0];
-    if (!describe(g, k)) return 0;
-    const int bn = g->N > 128 ? 256 : 128;
+    fill(g, p.c_vec, k);
     k.tiles_m = as_cdiv(g->M, BM);
-    k.tiles_n = as_cdiv(g->N, bn);
-    const long tiles = (long)k.tiles_m * k.tiles_n * g->batch;
-    // too little work to give every CU a 128-row tile over >= 256 frames: the general kernel's 64 x 64 tiles spread it better
-    if (tiles * (g->K / 256) < 256) return 0;
-    // split K so that the launch has about `target` workgroups (one per CU and round); cost model in DESIGN.md 5
-    const int cus = g->cu_budget > 0 ? g->cu_budget : 256;
-    long S = 1;
+    k.tiles_n = as_cdiv(g->N, p.tile_n);
+    k.kchunk = p.kchunk; k.splitk = p.splitk;
     const long per = (long)g->batch * g->M * g->N, per_cs = g->colsum ? (long)g->batch * g->M : 0;
-    if (g->splitk_ws && tiles < cus) {
-        // time ~ rounds * k-steps per workgroup * c1 + slab traffic; c1 = us per k of one 128 x bn tile on one CU
-        const double c1 = (bn == 256 ? 256.0 : 128.0) / 2400.0, c2 = 8.0 / 4.0e6;  // write + read of a float at ~4 TB/s
-        double best = 1e30;
-        for (long s = 1; s <= 64 && s * 128 <= g->K; ++s) {
-            const long chunk = as_round_up(as_cdiv(g->K, s), KALIGN);
-            const long rounds = (tiles * s + cus - 1) / cus;
-            const double cost = rounds * chunk * c1 + (s > 1 ? s * (per + per_cs) * c2 : 0.0);
-            if (cost < best - 1e-9) best = cost, S = s;
-        }
-        if (S > g->K / 128) S = g->K / 128;
-        if (S * (per + per_cs) > g->splitk_ws_floats) S = g->splitk_ws_floats / (per + per_cs);
-        if (S < 1) S = 1;
-    }
-    // Many tiles that do not fill whole rounds of the CUs: stream-K (see WgradMulti) instead of whole tiles per workgroup
-    const long rounds = (tiles + cus - 1) / cus;
-    if (g->splitk_ws && tiles * 2 >= cus && tiles * 100 < rounds * cus * 95 && g->K / 32 >= 16 &&
-        (long)cus * 2 * PIECE_FLOATS <= g->splitk_ws_floats) {
-        k.kchunk = g->K; k.splitk = 1; k.tile0 = 0;
-        k.ncombos = (long)g->batch * k.tiles_n;
-        mm.n = 1;
-        mm.streamk = 1;
-        mm.nkt = g->K / 32;
-        mm.total_tiles = tiles;
-        mm.total_units = tiles * mm.nkt;
-        mm.unit_per_wg = (mm.total_units + cus - 1) / cus;
-        mm.total_items = (mm.total_units + mm.unit_per_wg - 1) / mm.unit_per_wg;   // workgroups
-        mm.per_xcd = (int)((mm.total_items + 7) / 8);
-        mm.pieces = g->splitk_ws;
-        const int rc = bn == 256 ? launch_multi<256>(mm, st) : launch_multi<128>(mm, st);
-        return rc == 0 ? 1 : rc;
-    }
-    k.kchunk = (int)as_round_up(as_cdiv(g->K, S), KALIGN);
-    k.splitk = as_cdiv(g->K, k.kchunk);
-    if (k.splitk > 1) {
-        k.slab = g->splitk_ws;
-        k.cs_slab = g->splitk_ws + (long)k.splitk * per;
-    }
-    k.ncombos = (long)g->batch * k.splitk * k.tiles_n;
     mm.n = 1;
-    mm.total_items = k.ncombos * k.tiles_m;
-    mm.per_xcd = (int)((mm.total_items + 7) / 8);
-    mm.total_red = per / 4 + per_cs;
-    const int rc = bn == 256 ? launch_multi<256>(mm, st) : launch_multi<128>(mm, st);
-    return rc == 0 ? 1 : rc;
+    mm.total_items = p.work;
+    mm.per_xcd = p.per_xcd;
+    if (p.family == AS_GEMM_WGRAD_STREAMK) {
+        k.tile0 = 0;
+        k.ncombos = (long)g->batch * k.tiles_n;
+        mm.streamk = 1;
+        mm.nkt = p.nkt;
+        mm.total_tiles = k.ncombos * k.tiles_m;
+        mm.total_units = mm.total_tiles * mm.nkt;
+        mm.unit_per_wg = p.unit_per_wg;
+        mm.pieces = g->splitk_ws;
+    } else {
+        if (k.splitk > 1) {
+            k.slab = g->splitk_ws;
+            k.cs_slab = g->splitk_ws + (long)k.splitk * per;
+        }
+        k.ncombos = (long)g->batch * k.splitk * k.tiles_n;
+        mm.total_red = per / 4 + per_cs;
+    }
+    return p.tile_n == 256 ? launch_multi<256>(mm, st, p.split_arith) : launch_multi<128>(mm, st, p.split_arith);
 }
 
-// Several weight-gradient problems of one reduction length as ONE launch + one reduce launch (gemm_internal.h).  Every
-// problem runs on 128 x 256 tiles (N > 128 expected) and is split over K in chunks of the same length, chosen so that the
-// grid is a few rounds of the CUs the caller expects (cu_budget, 0 = chip): many short workgroups instead of one long one
-// per CU, so the dispatcher fills every free CU and other streams' kernels get CUs as workgroups retire.
-// 1 = launched, 0 = not a case (nothing launched: the caller issues the problems one by one), < 0 = error.
+// Several weight-gradient problems of one reduction length as ONE launch + one reduce launch (gemm_plan.h: the contract and the
+// chunk length).  1 = launched, 0 = not a case (nothing launched: the caller issues the problems one by one), < 0 = error.
 int as_wgrad_multi(const as_wgrad_job* jobs, int n, float* slab, long slab_floats, int cu_budget, hipStream_t st, bool exact) {
-    if (n < 1 || n > MAXP || !slab) return 0;
+    as_wgrad_multi_plan p;
+    if (!slab || !as_wgrad_multi_plan_make(jobs, n, slab_floats, cu_budget, &p)) return 0;
     WgradMulti mm{};
-    long tiles = 0;
-    const int K = jobs[0].g.K;
     for (int i = 0; i < n; ++i) {
         const as_gemm* g = &jobs[i].g;
         WgradK& k = mm.p[i];
-        if (g->K != K || g->a_off || g->b_off || g->c_off || !describe(g, k)) return 0;
-        if (jobs[i].colsum_b && g->b_kT > 0) return 0;
+        fill(g, p.c_vec[i], k);
         k.tiles_m = as_cdiv(g->M, BM);
         k.tiles_n = as_cdiv(g->N, 256);
         k.colsum_b = jobs[i].colsum_b; k.colsum_b_batch = jobs[i].colsum_b_batch; k.c_trans = jobs[i].c_trans;
-        tiles += (long)k.tiles_m * k.tiles_n * g->batch;
-    }
-    // chunk length: a multiple of 32 frames, at least 256; cost = rounds of `cus` workgroups x (chunk + fixed cost per
-    // workgroup) + slab traffic, all in units of one k-tile of 32 frames (~4 us for a 128 x 256 tile)
-    const int cus = cu_budget > 0 ? cu_budget : 256;
-    const int nkt = K / 32;
-    int best_chunk = nkt;
-    double best = 1e30;
-    for (int chunk = 8; chunk <= nkt; ++chunk) {
-        const long S = as_cdiv(nkt, chunk);
-        const long W = tiles * S;
-        const double rounds = (double)((W + cus - 1) / cus);
-        const double cost = rounds * (chunk + 1.0) + 0.016 * W;   // 128 KB of slab written + read per workgroup at ~4 TB/s
-        if (cost < best - 1e-9) best = cost, best_chunk = chunk;
-    }
-    long off_f = 0, item0 = 0, red0 = 0;
-    for (int i = 0; i < n; ++i) {
-        WgradK& k = mm.p[i];
-        k.kchunk = best_chunk * 32;
-        k.splitk = as_cdiv(K, k.kchunk);
-        const long per = (long)k.batch * k.M * k.N;
-        const long per_cs = k.colsum ? (long)k.batch * k.M : 0, per_csb = k.colsum_b ? (long)k.batch * k.N : 0;
+        k.kchunk = p.kchunk; k.splitk = p.splitk;
         if (k.splitk > 1) {
-            k.slab = slab + off_f;
-            k.cs_slab = k.slab + (long)k.splitk * per;
-            k.csb_slab = k.cs_slab + (long)k.splitk * per_cs;
-            off_f += as_round_up((long)k.splitk * (per + per_cs + per_csb), 64);
+            k.slab = slab + p.slab_off[i];
+            k.cs_slab = k.slab + (long)k.splitk * k.batch * k.M * k.N;
+            k.csb_slab = k.cs_slab + (k.colsum ? (long)k.splitk * k.batch * k.M : 0);
         }
         k.ncombos = (long)k.batch * k.splitk * k.tiles_n;
-        k.item0 = item0;
-        k.red0 = red0;
-        item0 += k.ncombos * k.tiles_m;
-        red0 += per / 4 + per_cs + per_csb;
+        k.item0 = p.item0[i];
+        k.red0 = p.red0[i];
     }
-    if (off_f > slab_floats) return 0;
     mm.n = n;
-    mm.total_items = item0;
-    mm.total_red = red0;
-    mm.per_xcd = (int)((item0 + 7) / 8);
-    const int rc = launch_multi<256>(mm, st, exact);
+    mm.total_items = p.total_items;
+    mm.total_red = p.total_red;
+    mm.per_xcd = p.per_xcd;
+    const int rc = launch_multi<256>(mm, st, !exact && as_matrix_arith() == AS_ARITH_BF16X6);
     return rc == 0 ? 1 : rc;
 }

@@ -539,6 +539,34 @@ def test_weight_gradient_stream_k(dev, M, N, K, batch, grouped):
     assert (acc - (c0 + outs[0][0])).abs().max().item() <= 2e-6 * scale
 
 
+@pytest.mark.parametrize("batch", [8, 256])
+def test_weight_gradient_shape_refuses_extended_operands(dev, batch):
+    """A weight-gradient descriptor (a_i == b_j == 1) that carries `res` is refused with AS_ERR_BAD_ARG and C untouched, whether
+    the general kernel (batch 8) or the weight-gradient kernel (batch 256: 256 tiles) would run it; without `res` it runs and
+    matches float64 at the bound of test_weight_gradient_stream_k."""
+    from artspeech_amd import _lib
+    L = _lib.lib()
+    M, N, K = 128, 128, 256
+    rng = np.random.RandomState(M + K + batch)
+    a = rng.randn(batch, K, M).astype(np.float32)
+    b = rng.randn(batch, K, N).astype(np.float32)
+    ad, bd = T_(a, dev), T_(b, dev)
+    ws = torch.empty(4 << 20, device=dev)
+    res = torch.zeros(batch, M, N, device=dev)
+    out = torch.full((batch, M, N), float("nan"), device=dev)
+    g = _lib.gemm_desc(A=ad, B=bd, C=out, M=M, N=N, K=K, batch=batch, a_i=1, a_k=M, b_j=1, b_k=N, ldc=N, a_batch=K * M, b_batch=K * N,
+                       c_batch=M * N, splitk_ws=ws, splitk_ws_floats=ws.numel(), res=res, res_ld=N, res_batch=M * N)
+    assert L.as_gemm_f32(C.byref(g), _lib.stream_ptr()) == -1     # AS_ERR_BAD_ARG
+    assert b"res / mask_bits / relu_bits / k_seg go with the general kernel only" in L.as_last_error()
+    torch.cuda.synchronize()
+    assert torch.isnan(out).all()
+    g.res = None
+    _lib.check(L.as_gemm_f32(C.byref(g), _lib.stream_ptr()), "as_gemm_f32")
+    torch.cuda.synchronize()
+    ref = np.matmul(a.astype(np.float64).transpose(0, 2, 1), b.astype(np.float64))
+    assert np.abs(out.cpu().numpy() - ref).max() <= 2e-6 * np.abs(ref).max() * np.sqrt(K)
+
+
 @pytest.mark.parametrize("M,N,K,batch,grouped", [(256, 256, 6400, 110, False), (200, 132, 2048, 7, True), (128, 384, 160, 3, False),
                                                     (256, 256, 6400, 110, True)])
 def test_weight_gradient_split_arithmetic_tiles(dev, M, N, K, batch, grouped):
