@@ -40,6 +40,9 @@ static inline int64_t as_round_up(int64_t x, int64_t m) { return (x + m - 1) / m
 static inline int as_cdiv(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }
 static inline bool as_aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
+// an integer as a type: hands a compile-time constant to a generic lambda (decltype(arg)::value)
+template <int N> struct IC { static constexpr int value = N; };
+
 #ifndef AS_HOST_ONLY
 // optional per-phase timing (prof.hip); a no-op unless as_profile_enable(1)
 struct AsProfScope {

@@ -27,8 +27,6 @@ int as_emit_planes(const as_planes_job* jobs, int n, hipStream_t st);
 static inline long as_planes_batch_stride(int rows_pad, int Kpad) { return (long)(Kpad / 16) * rows_pad * 16; }
 static inline long as_planes_floats(int batch, int rows_pad, int Kpad) { return 3 * batch * as_planes_batch_stride(rows_pad, Kpad) / 2; }
 
-template <int N> struct IC2 { static constexpr int value = N; };
-
 // A cross-stream fork without a barrier packet on the producing stream: the event is bound to the completion of the NEXT kernel
 // this thread launches through a launch site that knows the mechanism (hipExtLaunchKernelGGL's stopEvent: the dispatch packet's
 // own completion signal), instead of hipEventRecord's marker packet behind it (~7 us on the stream that records it, measured on

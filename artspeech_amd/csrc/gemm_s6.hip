@@ -154,8 +154,8 @@ __global__ __launch_bounds__(NTH, 3) void gemm_s6_kernel(S6K g) {
         }
     };
     auto load = [&](Regs& x) {
-        load_op(IC2<ANC>{}, x.a, Au, la);
-        load_op(IC2<BNC>{}, x.b, Bu, lb);
+        load_op(IC<ANC>{}, x.a, Au, la);
+        load_op(IC<BNC>{}, x.b, Bu, lb);
         // advance (behind the last tile the loads repeat it: unconditional loads keep hipcc's vmcnt counts exact)
         if constexpr (!EXT) {
             ld_t = min(ld_t + 1, nk - 1);
@@ -281,10 +281,10 @@ __global__ __launch_bounds__(NTH, 3) void gemm_s6_kernel(S6K g) {
     };
     int kt = 0;
     for (; kt + 2 <= nk; kt += 2) {
-        tile(IC2<0>{});
-        tile(IC2<1>{});
+        tile(IC<0>{});
+        tile(IC<1>{});
     }
-    if (kt < nk) tile(IC2<0>{});
+    if (kt < nk) tile(IC<0>{});
 
     if constexpr (ANC) {   // column sums of A (a bias gradient): the two k halves of a column meet in LDS, in a fixed order
         if (g.colsum && tn == 0) {

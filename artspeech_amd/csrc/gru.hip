@@ -35,12 +35,19 @@
 #include "as_device.h"
 #include "as_launch.h"
 #include "gemm_internal.h"
+#include "rnn_plain.h"
 
 namespace {
 
 constexpr int AHEAD = 2;   // steps of look-ahead of the operand loads (see the header)
 
-template <int H, int LPU, bool TRAIN, bool TOK>
+// Lanes per hidden unit: 512 threads at H = 128, two waves per SIMD.  LPU = 2 (256 threads, one wave per SIMD, 252 VGPRs) was
+// measured at H = 128, B = 32, T = 200 (tools/bench_gru.py) at 0.56 us per step forward and 0.77 backward against 0.55 / 0.70
+// -- the second wave hides the first one's LDS / DPP / transcendental latencies about as well as halving the redundant gate
+// math helps -- and is no longer built.
+constexpr int LPU = 4;
+
+template <int H, bool TRAIN, bool TOK>
 __global__ __launch_bounds__(LPU * H) void gru_fwd_kernel(const float* __restrict__ gi, const int64_t* __restrict__ tokens,
                                                           long tok_stride, const float* __restrict__ w_hh,
                                                           const float* __restrict__ b_hh, const int* __restrict__ lengths,
@@ -92,13 +99,13 @@ __global__ __launch_bounds__(LPU * H) void gru_fwd_kernel(const float* __restric
     // 64-bit vector shifts and adds.  (Every array here is far below 4 GB: checked by the launcher.)
     const unsigned ys = (unsigned)nd * H * 4u, gs = (unsigned)nd * 4u * H * 4u, is = (unsigned)nd * 3u * H * 4u;   // bytes per frame
     const unsigned yo = (unsigned)(dir * H + j) * 4u;                       // + frame * ys
-    const unsigned go = (unsigned)(dir * 4 * H + j + (LPU == 4 ? q * H : q * H)) * 4u;   // + frame * gs: this lane's plane
+    const unsigned go = (unsigned)(dir * 4 * H + j + q * H) * 4u;   // + frame * gs: this lane's plane
     const unsigned io = (unsigned)(dir * 3 * H + j) * 4u;                   // + row offset (bytes)
     const char* gi_c = reinterpret_cast<const char*>(gi);
     char* y_c = reinterpret_cast<char*>(y);
     char* g_c = reinterpret_cast<char*>(gates);
-    // the LPU lanes of a unit hold identical gate values: lane q stores planes q, q + LPU, ... (branch-free selects)
-    const int m0 = q == 0 ? -1 : 0, m1 = q == 1 ? -1 : 0, m2 = q == 2 ? -1 : 0, m3 = q == 3 ? -1 : 0;
+    // the LPU lanes of a unit hold identical gate values: lane q stores plane q (branch-free selects)
+    const int m0 = q == 0 ? -1 : 0, m1 = q == 1 ? -1 : 0, m2 = q == 2 ? -1 : 0;
 
     float h = 0.f;
     struct Gi { float r, z, n; };
@@ -140,19 +147,13 @@ __global__ __launch_bounds__(LPU * H) void gru_fwd_kernel(const float* __restric
                 }
         }
         const float sr = as_quad_sum<LPU>(ar.x + ar.y), sz = as_quad_sum<LPU>(az.x + az.y), sn = as_quad_sum<LPU>(an.x + an.y);
-        float r, z;
-        if constexpr (LPU == 4) {
-            // the four lanes of a unit hold the same sums: lane 0 takes r's sigmoid, lanes 1..3 z's -- ONE exp + rcp sequence per
-            // lane instead of two (quarter-rate instructions: 32 of the step's ~410 issue cycles per wave) -- and two quad
-            // broadcasts hand both to every lane.  Same operations on the same values: bit-identical.
-            const float pre = __int_as_float((__float_as_int(ci.r + sr) & m0) | (__float_as_int(ci.z + sz) & ~m0));
-            const float sg = as_sigmoid(pre);
-            r = __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(sg), 0x00, 0xF, 0xF, true));   // quad_perm [0,0,0,0]
-            z = __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(sg), 0x55, 0xF, 0xF, true));   // quad_perm [1,1,1,1]
-        } else {
-            r = as_sigmoid(ci.r + sr);
-            z = as_sigmoid(ci.z + sz);
-        }
+        // the four lanes of a unit hold the same sums: lane 0 takes r's sigmoid, lanes 1..3 z's -- ONE exp + rcp sequence per
+        // lane instead of two (quarter-rate instructions: 32 of the step's ~410 issue cycles per wave) -- and two quad
+        // broadcasts hand both to every lane.  Same operations on the same values: bit-identical.
+        const float pre = __int_as_float((__float_as_int(ci.r + sr) & m0) | (__float_as_int(ci.z + sz) & ~m0));
+        const float sg = as_sigmoid(pre);
+        const float r = __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(sg), 0x00, 0xF, 0xF, true));   // quad_perm [0,0,0,0]
+        const float z = __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(sg), 0x55, 0xF, 0xF, true));   // quad_perm [1,1,1,1]
         const float hn = sn;
         const float n = as_tanh(ci.n + r * hn);
         const float hnew = (1.f - z) * n + z * h;
@@ -162,18 +163,11 @@ __global__ __launch_bounds__(LPU * H) void gru_fwd_kernel(const float* __restric
         *reinterpret_cast<float*>(y_c + (fr * ys + yo)) = hnew;
         if (TRAIN) {
             float* gp = reinterpret_cast<float*>(g_c + (fr * gs + go));
-            if (LPU == 4) {
-                // lane q stores plane q: three bitfield inserts ((a & m) | (b & ~m) is v_bfi_b32) on loop-invariant lane masks
-                const int m01 = m0 | m1;
-                const int t1 = (__float_as_int(r) & m0) | (__float_as_int(z) & ~m0);
-                const int t2 = (__float_as_int(n) & m2) | (__float_as_int(hn) & ~m2);
-                gp[0] = __int_as_float((t1 & m01) | (t2 & ~m01));
-            } else {  // two lanes per unit: lane 0 stores r and n, lane 1 stores z and hn
-                const int ga = (__float_as_int(r) & m0) | (__float_as_int(z) & m1);
-                const int gc = (__float_as_int(n) & m0) | (__float_as_int(hn) & m1);
-                gp[0] = __int_as_float(ga);
-                gp[2 * H] = __int_as_float(gc);
-            }
+            // lane q stores plane q: three bitfield inserts ((a & m) | (b & ~m) is v_bfi_b32) on loop-invariant lane masks
+            const int m01 = m0 | m1;
+            const int t1 = (__float_as_int(r) & m0) | (__float_as_int(z) & ~m0);
+            const int t2 = (__float_as_int(n) & m2) | (__float_as_int(hn) & ~m2);
+            gp[0] = __int_as_float((t1 & m01) | (t2 & ~m01));
         }
         __syncthreads();
     };
@@ -445,25 +439,21 @@ __global__ __launch_bounds__(4 * H) void gru_bwd_row_kernel(const float* __restr
     }
 }
 
-
-// ---- any hidden size (nn.GRU takes any, encoder_decoder/models.py:100-111): plain kernels for the sizes the register-
-// resident ones above are not built for (they hold W_hh in 96 VGPRs per lane at H = 128; at H = 256 it would be 192).  One
-// workgroup of 1024 threads per (utterance, direction) as above, h in LDS, W_hh streamed from L2 every step (768 KB per step
-// and workgroup at H = 256).  Same gates / y / dgi / dgh layouts and the same packed-sequence semantics; the reduction order
-// over k differs from the kernels above in the last bits.  Several times slower per step -- a correct fallback, not a tuned
-// path (measured: DESIGN.md 8).
-constexpr int GEN_THREADS = 1024;
+// ---- any hidden size (nn.GRU takes any, encoder_decoder/models.py:100-111): the plain kernels, rnn_plain.h.
 
 // Forward: four adjacent lanes share a hidden unit (j = tid / 4); lane q takes the 16-byte chunks q, q + 4, ... of the unit's
 // three W_hh rows -- the four lanes read 64 consecutive bytes of a row -- four chunks (12 global loads) in flight per pass,
 // and the three dot products are finished with the quad DPP sum of the kernels above.  H % 4 == 0.
+// (lstm.hip has this loop for four gates.  It stays written out in both: hipcc packs the gates' sums into v_pk instructions in
+// the order it meets them and packs a shared function's inlined body another way; a variant with such a function, not kept,
+// moved the last bits of y against the written-out loops: profiles/recurrence_plain_equivalence.log, attempt 1.)
 template <bool TRAIN, bool TOK>
 __global__ __launch_bounds__(GEN_THREADS) void gru_fwd_generic_kernel(const float* __restrict__ gi, const int64_t* __restrict__ tokens,
-                                                                     long tok_stride, const float* __restrict__ w_hh,
-                                                                     const float* __restrict__ b_hh, const int* __restrict__ lengths,
-                                                                     int T, int H, float* __restrict__ y, float* __restrict__ gates,
-                                                                     int nd, int V) {
-    extern __shared__ __attribute__((aligned(16))) float gsm[];   // h double buffer [2][H]
+                                                                   long tok_stride, const float* __restrict__ w_hh,
+                                                                   const float* __restrict__ b_hh, const int* __restrict__ lengths,
+                                                                   int T, int H, float* __restrict__ y, float* __restrict__ gates,
+                                                                   int nd, int V) {
+    extern __shared__ __attribute__((aligned(16))) float gsm[];   // GRU_FWD_LDS_PER_UNIT
     const int b = blockIdx.x, dir = blockIdx.y, tid = threadIdx.x;
     const int q = tid & 3;
     const int len = lengths[b];
@@ -531,33 +521,25 @@ __global__ __launch_bounds__(GEN_THREADS) void gru_fwd_generic_kernel(const floa
     }
 }
 
-// Backward: the gate gradients of a step by one thread per hidden unit; then dh = dht * z + W_hh^T g with the 3H gate rows
-// dealt over four thread groups (lanes = consecutive hidden columns: a wave reads 256 consecutive bytes of a row, eight rows
-// in flight), the four partial sums meeting in LDS in a fixed order.
+// Backward: the gate gradients of a step by one thread per hidden unit; then dh = dht * z + W_hh^T g (rnn_plain_matvec_bwd).
 __global__ __launch_bounds__(GEN_THREADS) void gru_bwd_generic_kernel(const float* __restrict__ dy, const float* __restrict__ y,
-                                                                     const float* __restrict__ gates, const float* __restrict__ w_hh,
-                                                                     const int* __restrict__ lengths, int T, int H,
-                                                                     float* __restrict__ dgi, float* __restrict__ dgh, int nd) {
-    extern __shared__ __attribute__((aligned(16))) float gsm[];   // g [3H], dh carried [H], dht * z [H], partial sums [4][H]
+                                                                   const float* __restrict__ gates, const float* __restrict__ w_hh,
+                                                                   const int* __restrict__ lengths, int T, int H,
+                                                                   float* __restrict__ dgi, float* __restrict__ dgh, int nd) {
+    extern __shared__ __attribute__((aligned(16))) float gsm[];   // GRU_BWD_LDS_PER_UNIT
     float* gb = gsm;
     float* dhb = gsm + 3 * H;
     float* dhz = gsm + 4 * H;
     float* part = gsm + 5 * H;
     const int b = blockIdx.x, dir = blockIdx.y, tid = threadIdx.x;
     const int len = lengths[b];
-    for (long i = (long)len * 3 * H + tid; i < (long)T * 3 * H; i += GEN_THREADS) {   // padded frames feed time-batched GEMMs
-        const long t = i / (3 * H), c = i % (3 * H);
-        const long o = (((long)b * T + t) * nd + dir) * 3 * H + c;
-        dgi[o] = 0.f;
-        dgh[o] = 0.f;
-    }
+    rnn_plain_zero_padded(dgi, dgh, b, T, len, 3 * H, (long)nd * 3 * H, (long)dir * 3 * H, tid);
     for (int j = tid; j < H; j += GEN_THREADS) dhb[j] = 0.f;
     __syncthreads();
     if (len <= 0) return;
     const float* wd = w_hh + (long)dir * 3 * H * H;
     // opposite to the forward walk; h_prev of frame t is the output of the frame visited NEXT (zero beyond the sequence)
     const int dt = dir ? 1 : -1;
-    const int kq = tid >> 8, kl = tid & 255;   // row group (0..3), column within a block of 256
     for (int s = 0; s < len; ++s) {
         const int t = dir ? s : len - 1 - s;
         const long frame = (long)b * T + t;
@@ -581,35 +563,12 @@ __global__ __launch_bounds__(GEN_THREADS) void gru_bwd_generic_kernel(const floa
             dhz[j] = dht * z;
         }
         __syncthreads();
-        for (int k0 = 0; k0 < H; k0 += 256) {
-            const int k = k0 + kl;
-            const int kc = k < H ? k : H - 1;
-            float acc = 0.f;
-            for (int i0 = kq; i0 < 3 * H; i0 += 32) {   // rows kq, kq + 4, ...: eight of them in flight
-                float wv[8], gv[8];
-#pragma unroll
-                for (int u = 0; u < 8; ++u) {
-                    const int i = i0 + 4 * u;
-                    const int ic = i < 3 * H ? i : 3 * H - 1;
-                    wv[u] = wd[(long)ic * H + kc];
-                    gv[u] = i < 3 * H ? gb[ic] : 0.f;
-                }
-#pragma unroll
-                for (int u = 0; u < 8; ++u) acc += gv[u] * wv[u];
-            }
-            if (k < H) part[kq * H + k] = acc;
-        }
+        rnn_plain_matvec_bwd<3>(wd, gb, H, tid, part);
         __syncthreads();
         for (int k = tid; k < H; k += GEN_THREADS) dhb[k] = dhz[k] + ((part[k] + part[H + k]) + (part[2 * H + k] + part[3 * H + k]));
         __syncthreads();
     }
 }
-
-// Lanes per hidden unit.  Both layouts are built; measured at H = 128, B = 32, T = 200 (tools/bench_gru.py):
-// LPU = 4 (512 threads, two waves per SIMD): forward 0.55 us/step, backward 0.70; LPU = 2 (256 threads, one
-// wave per SIMD, 252 VGPRs): 0.56 / 0.77 -- the second wave hides the first one's LDS / DPP / transcendental
-// latencies about as well as halving the redundant gate math helps, so the 4-lane layout stays.
-constexpr int lpu_of(int) { return 4; }
 
 }  // namespace
 
@@ -636,45 +595,32 @@ extern "C" void as_gru_debug_stamps(uint64_t* buf) { g_gru_dbg = (unsigned long 
 static int gru_fwd_launch(const float* gi, const int64_t* tokens, int64_t tok_stride, const float* w_hh, const float* b_hh,
                           const int32_t* lengths, int32_t B, int32_t T, int32_t H, float* y, float* gates, int nd, void* stream,
                           int V = 0) {
-    AS_REQUIRE(gi && w_hh && b_hh && lengths && y, AS_ERR_BAD_ARG, "as_gru_fwd: null pointer");
-    AS_REQUIRE(B > 0 && T > 0, AS_ERR_BAD_ARG, "as_gru_fwd: B=%d T=%d", B, T);
+    AS_TRY(rnn_check_args("as_gru_fwd", gi && w_hh && b_hh && lengths && y, B, T));
     AS_REQUIRE(!tokens || T <= 32768, AS_ERR_UNSUPPORTED, "as_gru_fwd: T=%d > 32768 with a token table", T);
     AS_REQUIRE((long)B * T * nd * 4 * H * 4 < (1L << 32), AS_ERR_UNSUPPORTED, "as_gru_fwd: B*T=%ld frames exceed the 32-bit offsets", (long)B * T);
     hipStream_t st = (hipStream_t)stream;
-    dim3 grid(B, nd);
-    const size_t pad = gru_lds_pad(B * nd);
-    const size_t need = tokens ? (size_t)T * sizeof(int) : 0;
-#define AS_GRU_LAUNCH(HH, TR, TK)                                                                                      \
-    do {                                                                                                               \
-        /* not granted: the kernel keeps the 64 KB limit of dynamic LDS (no padding then) */                           \
-        const bool big = pad > need && as_allow_dynamic_lds(gru_fwd_kernel<HH, lpu_of(HH), TR, TK>, GRU_LDS_ATTR) == hipSuccess; \
-        const size_t shm = big ? pad : need;                                                                           \
-        hipLaunchKernelGGL((gru_fwd_kernel<HH, lpu_of(HH), TR, TK>), grid, dim3(lpu_of(HH) * HH), shm, st, gi, tokens, \
-                           (long)tok_stride, w_hh, b_hh, lengths, T, y, gates, nd, V);                                 \
-    } while (0)
-#define AS_GRU_FWD(HH)                                      \
-    if (gates && tokens) AS_GRU_LAUNCH(HH, true, true);     \
-    else if (gates) AS_GRU_LAUNCH(HH, true, false);         \
-    else if (tokens) AS_GRU_LAUNCH(HH, false, true);        \
-    else AS_GRU_LAUNCH(HH, false, false)
-    switch (H) {
-        case 32: AS_GRU_FWD(32); break;
-        case 64: AS_GRU_FWD(64); break;
-        case 128: AS_GRU_FWD(128); break;
-        default: {   // any other hidden size: the plain kernels
-            const size_t gshm = (size_t)2 * H * sizeof(float);
-            AS_REQUIRE(H > 0 && H % 4 == 0 && gshm <= 64 * 1024, AS_ERR_UNSUPPORTED, "as_gru_fwd: hidden size %d (a multiple of 4 up to 8192)", H);
-#define AS_GRU_GEN(TR, TK) \
-    hipLaunchKernelGGL((gru_fwd_generic_kernel<TR, TK>), grid, dim3(GEN_THREADS), gshm, st, gi, tokens, (long)tok_stride, w_hh, b_hh, lengths, T, H, y, gates, nd, V)
-            if (gates && tokens) AS_GRU_GEN(true, true);
-            else if (gates) AS_GRU_GEN(true, false);
-            else if (tokens) AS_GRU_GEN(false, true);
-            else AS_GRU_GEN(false, false);
-#undef AS_GRU_GEN
-        }
+    const dim3 grid(B, nd);
+    int rc = 0;
+    const bool resident = rnn_resident(H, gates != nullptr, tokens != nullptr, &rc, [&](auto h, auto train, auto tok) {
+        constexpr int HH = decltype(h)::value;
+        const auto kernel = gru_fwd_kernel<HH, decltype(train)::value, decltype(tok)::value>;
+        const size_t pad = gru_lds_pad(B * nd), need = tokens ? (size_t)T * sizeof(int) : 0;
+        // not granted: the kernel keeps the 64 KB limit of dynamic LDS (no padding then)
+        const bool big = pad > need && as_allow_dynamic_lds(kernel, GRU_LDS_ATTR) == hipSuccess;
+        hipLaunchKernelGGL(kernel, grid, dim3(LPU * HH), big ? pad : need, st, gi, tokens, (long)tok_stride, w_hh, b_hh, lengths, T, y,
+                           gates, nd, V);
+        return 0;
+    });
+    if (!resident) {   // any other hidden size: the plain kernels
+        size_t gshm;
+        AS_TRY(rnn_plain_lds("as_gru_fwd", H, GRU_FWD_LDS_PER_UNIT, &gshm));
+        rnn_with_flags(gates != nullptr, tokens != nullptr, [&](auto train, auto tok) {
+            hipLaunchKernelGGL((gru_fwd_generic_kernel<decltype(train)::value, decltype(tok)::value>), grid, dim3(GEN_THREADS), gshm, st, gi,
+                               tokens, (long)tok_stride, w_hh, b_hh, lengths, T, H, y, gates, nd, V);
+            return 0;
+        });
     }
-#undef AS_GRU_FWD
-#undef AS_GRU_LAUNCH
+    AS_TRY(rc);
     AS_LAUNCH_CHECK("as_gru_fwd");
     return 0;
 }
@@ -706,49 +652,44 @@ extern "C" int as_gru_unidir_fwd_gates(const float* gi, const float* w_hh, const
 static int gru_bwd_launch(const float* dy, const float* y, const float* gates, const float* w_hh, const int32_t* lengths,
                           int32_t B, int32_t T, int32_t H, float* dgi, float* dgh, const int64_t* tokens, int64_t tok_stride,
                           int32_t V, float* part, void* stream, int nd = 2) {
-    AS_REQUIRE(dy && y && gates && w_hh && lengths && (dgi || tokens) && dgh, AS_ERR_BAD_ARG, "as_gru_bidir_bwd: null pointer");
-    AS_REQUIRE(B > 0 && T > 0, AS_ERR_BAD_ARG, "as_gru_bidir_bwd: B=%d T=%d", B, T);
+    AS_TRY(rnn_check_args("as_gru_bidir_bwd", dy && y && gates && w_hh && lengths && (dgi || tokens) && dgh, B, T));
     AS_REQUIRE(!tokens || (part && V > 0 && tok_stride >= T && nd == 2), AS_ERR_BAD_ARG, "as_gru_bidir_bwd: token table arguments");
     AS_REQUIRE((long)B * T * nd * 4 * H * 4 < (1L << 32), AS_ERR_UNSUPPORTED, "as_gru_bidir_bwd: B*T=%ld frames exceed the 32-bit offsets", (long)B * T);
     hipStream_t st = (hipStream_t)stream;
-    dim3 grid(B, nd);
+    const dim3 grid(B, nd);
     // diagnostic stamps (as_gru_debug_stamps): 2 x (2 B workgroups x 4 words); launch k writes half k % 2, so that the two
     // backward recurrences of one training step (layer 1, then layer 0) can both be read afterwards
     unsigned long long* dbg_now = g_gru_dbg ? g_gru_dbg + (size_t)(g_gru_dbg_launch++ & 1u) * 8u * (size_t)B : nullptr;
-    hipEvent_t stop_ev = (H == 32 || H == 64 || H == 128) ? as_stop_event_take() : nullptr;
-    const size_t pad = gru_lds_pad(B * nd);
-    const size_t need = tokens ? ((size_t)V * 3 * H + 4 * H + T) * sizeof(float) : 0;   // + one dummy word per lane + T offsets
-#define AS_GRU_BWD_ROW(HH, TK, ND)                                                                                     \
-    do {                                                                                                                      \
-        const bool big = as_allow_dynamic_lds(gru_bwd_row_kernel<HH, TK, ND>, GRU_LDS_ATTR) == hipSuccess;                    \
-        AS_REQUIRE(big || need <= 64 * 1024, AS_ERR_UNSUPPORTED, "as_gru_bidir_bwd: cannot reserve %zu bytes of LDS", need);   \
-        const size_t shm = big && pad > need ? pad : need;                                                                    \
-        if (stop_ev)   /* a fork event rides on this dispatch (gemm_internal.h, as_stop_event_set) */                         \
-            hipExtLaunchKernelGGL((gru_bwd_row_kernel<HH, TK, ND>), grid, dim3(4 * HH), (unsigned)shm, st, nullptr, stop_ev, 0, dy, \
-                                  y, gates, w_hh, lengths, T, dgi, dgh, dbg_now, tokens, (long)tok_stride, V, part);          \
-        else                                                                                                                  \
-            hipLaunchKernelGGL((gru_bwd_row_kernel<HH, TK, ND>), grid, dim3(4 * HH), shm, st, dy, y, gates, w_hh,         \
-                               lengths, T, dgi, dgh, dbg_now, tokens, (long)tok_stride, V, part);                             \
-    } while (0)
-#define AS_GRU_BWD(HH) \
-    if (tokens) AS_GRU_BWD_ROW(HH, true, 2); else AS_GRU_BWD_ROW(HH, false, 2)
-    if (nd == 1 && (H == 32 || H == 64 || H == 128)) {   // unidirectional: no token table
-        if (H == 32) AS_GRU_BWD_ROW(32, false, 1);
-        else if (H == 64) AS_GRU_BWD_ROW(64, false, 1);
-        else AS_GRU_BWD_ROW(128, false, 1);
-    } else switch (H) {
-        case 32: AS_GRU_BWD(32); break;
-        case 64: AS_GRU_BWD(64); break;
-        case 128: AS_GRU_BWD(128); break;
-        default: {   // any other hidden size: the plain kernel (never with a token table: as_gru_bwd_tokens_fits)
-            AS_REQUIRE(!tokens && dgi, AS_ERR_UNSUPPORTED, "as_gru_bidir_bwd: token sums need a hidden size in {32, 64, 128}");
-            const size_t gshm = (size_t)9 * H * sizeof(float);
-            AS_REQUIRE(H > 0 && H % 4 == 0 && gshm <= 64 * 1024, AS_ERR_UNSUPPORTED, "as_gru_bidir_bwd: hidden size %d (a multiple of 4 up to 1820)", H);
-            hipLaunchKernelGGL(gru_bwd_generic_kernel, grid, dim3(GEN_THREADS), gshm, st, dy, y, gates, w_hh, lengths, T, H, dgi, dgh, nd);
+    // flags: token sums instead of dgi (layer 0 under a token table), unidirectional (never both: checked above)
+    int rc = 0;
+    const bool resident = rnn_resident(H, tokens != nullptr, nd == 1, &rc, [&](auto h, auto tok, auto uni) {
+        constexpr int HH = decltype(h)::value, ND = decltype(uni)::value ? 1 : 2;
+        constexpr bool TK = decltype(tok)::value;
+        if constexpr (TK && ND == 1) return (int)AS_ERR_BAD_ARG;
+        else {
+            const auto kernel = gru_bwd_row_kernel<HH, TK, ND>;
+            hipEvent_t stop_ev = as_stop_event_take();
+            const size_t pad = gru_lds_pad(B * nd);
+            const size_t need = tokens ? ((size_t)V * 3 * H + 4 * H + T) * sizeof(float) : 0;   // + one dummy word per lane + T offsets
+            const bool big = as_allow_dynamic_lds(kernel, GRU_LDS_ATTR) == hipSuccess;
+            AS_REQUIRE(big || need <= 64 * 1024, AS_ERR_UNSUPPORTED, "as_gru_bidir_bwd: cannot reserve %zu bytes of LDS", need);
+            const size_t shm = big && pad > need ? pad : need;
+            if (stop_ev)   // a fork event rides on this dispatch (gemm_internal.h, as_stop_event_set)
+                hipExtLaunchKernelGGL(kernel, grid, dim3(4 * HH), (unsigned)shm, st, nullptr, stop_ev, 0, dy, y, gates, w_hh, lengths, T,
+                                      dgi, dgh, dbg_now, tokens, (long)tok_stride, V, part);
+            else
+                hipLaunchKernelGGL(kernel, grid, dim3(4 * HH), shm, st, dy, y, gates, w_hh, lengths, T, dgi, dgh, dbg_now, tokens,
+                                   (long)tok_stride, V, part);
+            return 0;
         }
+    });
+    if (!resident) {   // any other hidden size: the plain kernel (never with a token table: as_gru_bwd_tokens_fits)
+        AS_REQUIRE(!tokens && dgi, AS_ERR_UNSUPPORTED, "as_gru_bidir_bwd: token sums need a hidden size in {32, 64, 128}");
+        size_t gshm;
+        AS_TRY(rnn_plain_lds("as_gru_bidir_bwd", H, GRU_BWD_LDS_PER_UNIT, &gshm));
+        hipLaunchKernelGGL(gru_bwd_generic_kernel, grid, dim3(GEN_THREADS), gshm, st, dy, y, gates, w_hh, lengths, T, H, dgi, dgh, nd);
     }
-#undef AS_GRU_BWD
-#undef AS_GRU_BWD_ROW
+    AS_TRY(rc);
     AS_LAUNCH_CHECK("as_gru_bidir_bwd");
     return 0;
 }

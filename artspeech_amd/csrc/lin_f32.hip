@@ -399,8 +399,6 @@ constexpr int S6_BK = 32;                 // k-tile of the A image (two MFMA k-s
 constexpr int S6_PLANE = 64 * S6_BK * 2;  // bytes of one plane of one k-tile: 64 rows x 32 bf16
 constexpr int S6_BUF = 3 * S6_PLANE;
 
-template <int N> struct IC { static constexpr int value = N; };
-
 // The main loop shared by the 256-column kernel (NW = 8 waves) and the output layer's (NW = 4): 64 rows x 32 NW columns,
 // wave w = columns 32 w .. 32 w + 31 of all 64 rows (two accumulators).  `sm`: 2 x S6_BUF bytes.
 //   A / lda: first row of the tile's operand rows (row index clamped to rows_valid - 1), k >= ka_valid reads as zero

@@ -11,6 +11,7 @@
 
 #include "as_common.h"
 #include "as_device.h"
+#include "rnn_plain.h"
 
 namespace {
 
@@ -243,20 +244,17 @@ __global__ __launch_bounds__(4 * H) void lstm_bwd_row_kernel(const float* __rest
     if (s + 1 < len) step(s + 1, bq, a);
 }
 
-// ---- any hidden size (nn.LSTM takes any, principal_components/models/rnn.py:58-68): plain kernels for the sizes the
-// register-resident ones above are not built for (gru.hip has the same pair for the GRU).  One workgroup of 1024 threads per
-// (utterance, direction), h and c in LDS, W_hh streamed from L2 every step.  Same gates / y / dg layouts and packed-sequence
-// semantics; the reduction order over k differs from the kernels above in the last bits.  A correct fallback, not a tuned path.
-constexpr int GEN_THREADS = 1024;
+// ---- any hidden size (nn.LSTM takes any, principal_components/models/rnn.py:58-68): the plain kernels, rnn_plain.h.
 
 // Forward: four adjacent lanes share a hidden unit; lane q takes the 16-byte chunks q, q + 4, ... of the unit's four W_hh rows
-// (the quad reads 64 consecutive bytes of a row), four chunks = 16 global loads in flight per pass.  H % 4 == 0.
+// (the quad reads 64 consecutive bytes of a row), four chunks = 16 global loads in flight per pass.  H % 4 == 0.  (The loop
+// is gru.hip's for four gates, written out here too: see there.)
 template <bool TRAIN, bool TOK>
 __global__ __launch_bounds__(GEN_THREADS) void lstm_fwd_generic_kernel(const float* __restrict__ gi, const int64_t* __restrict__ tokens,
                                                                       long tok_stride, const float* __restrict__ w_hh,
                                                                       const float* __restrict__ b_hh, const int* __restrict__ lengths,
                                                                       int T, int H, float* __restrict__ y, float* __restrict__ gates) {
-    extern __shared__ __attribute__((aligned(16))) float gsm[];   // h double buffer [2][H], c [H]
+    extern __shared__ __attribute__((aligned(16))) float gsm[];   // LSTM_FWD_LDS_PER_UNIT
     float* cb = gsm + 2 * H;
     const int b = blockIdx.x, dir = blockIdx.y, tid = threadIdx.x;
     const int q = tid & 3;
@@ -315,29 +313,23 @@ __global__ __launch_bounds__(GEN_THREADS) void lstm_fwd_generic_kernel(const flo
     }
 }
 
-// Backward: the four gate gradients of a step by one thread per hidden unit; then dh = W_hh^T p with the 4H gate rows dealt
-// over four thread groups (lanes = consecutive hidden columns: a wave reads 256 consecutive bytes of a row, eight rows in
-// flight), the four partial sums meeting in LDS in a fixed order.
+// Backward: the four gate gradients of a step by one thread per hidden unit; then dh = W_hh^T p (rnn_plain_matvec_bwd).
 __global__ __launch_bounds__(GEN_THREADS) void lstm_bwd_generic_kernel(const float* __restrict__ dy, const float* __restrict__ gates,
                                                                       const float* __restrict__ w_hh, const int* __restrict__ lengths,
                                                                       int T, int H, float* __restrict__ dg) {
-    extern __shared__ __attribute__((aligned(16))) float gsm[];   // p [4H], dh carried [H], dc carried [H], partial sums [4][H]
+    extern __shared__ __attribute__((aligned(16))) float gsm[];   // LSTM_BWD_LDS_PER_UNIT
     float* gb = gsm;
     float* dhb = gsm + 4 * H;
     float* dcb = gsm + 5 * H;
     float* part = gsm + 6 * H;
     const int b = blockIdx.x, dir = blockIdx.y, tid = threadIdx.x;
     const int len = lengths[b];
-    for (long i = (long)len * 4 * H + tid; i < (long)T * 4 * H; i += GEN_THREADS) {   // padded frames feed the time-batched GEMMs as zeros
-        const long t = i / (4 * H), c = i % (4 * H);
-        dg[(((long)b * T + t) * 2 + dir) * 4 * H + c] = 0.f;
-    }
+    rnn_plain_zero_padded(dg, nullptr, b, T, len, 4 * H, 8L * H, (long)dir * 4 * H, tid);
     for (int j = tid; j < 2 * H; j += GEN_THREADS) dhb[j] = 0.f;   // dh and dc
     __syncthreads();
     if (len <= 0) return;
     const float* wd = w_hh + (long)dir * 4 * H * H;
     const int dt = dir ? 1 : -1;   // opposite to the forward walk; c_prev of frame t is the cell state of the frame visited NEXT
-    const int kq = tid >> 8, kl = tid & 255;   // row group (0..3), column within a block of 256
     for (int s = 0; s < len; ++s) {
         const int t = dir ? s : len - 1 - s;
         const long frame = (long)b * T + t;
@@ -359,24 +351,7 @@ __global__ __launch_bounds__(GEN_THREADS) void lstm_bwd_generic_kernel(const flo
             gb[j] = p_i; gb[H + j] = p_f; gb[2 * H + j] = p_g; gb[3 * H + j] = p_o;
         }
         __syncthreads();
-        for (int k0 = 0; k0 < H; k0 += 256) {
-            const int k = k0 + kl;
-            const int kc = k < H ? k : H - 1;
-            float acc = 0.f;
-            for (int i0 = kq; i0 < 4 * H; i0 += 32) {   // rows kq, kq + 4, ...: eight of them in flight
-                float wv[8], gv[8];
-#pragma unroll
-                for (int u = 0; u < 8; ++u) {
-                    const int i = i0 + 4 * u;
-                    const int ic = i < 4 * H ? i : 4 * H - 1;
-                    wv[u] = wd[(long)ic * H + kc];
-                    gv[u] = i < 4 * H ? gb[ic] : 0.f;
-                }
-#pragma unroll
-                for (int u = 0; u < 8; ++u) acc += gv[u] * wv[u];
-            }
-            if (k < H) part[kq * H + k] = acc;
-        }
+        rnn_plain_matvec_bwd<4>(wd, gb, H, tid, part);
         __syncthreads();
         for (int k = tid; k < H; k += GEN_THREADS) dhb[k] = (part[k] + part[H + k]) + (part[2 * H + k] + part[3 * H + k]);
         __syncthreads();
@@ -387,59 +362,46 @@ __global__ __launch_bounds__(GEN_THREADS) void lstm_bwd_generic_kernel(const flo
 
 extern "C" int as_lstm_bidir_fwd(const float* gi, const int64_t* tokens, int64_t tok_stride, const float* w_hh, const float* b_hh,
                                  const int32_t* lengths, int32_t B, int32_t T, int32_t H, float* y, float* gates, void* stream) {
-    AS_REQUIRE(gi && w_hh && b_hh && lengths && y, AS_ERR_BAD_ARG, "as_lstm_bidir_fwd: null pointer");
-    AS_REQUIRE(B > 0 && T > 0, AS_ERR_BAD_ARG, "as_lstm_bidir_fwd: B=%d T=%d", B, T);
+    AS_TRY(rnn_check_args("as_lstm_bidir_fwd", gi && w_hh && b_hh && lengths && y, B, T));
     AS_REQUIRE(!tokens || T <= 32768, AS_ERR_UNSUPPORTED, "as_lstm_bidir_fwd: T=%d > 32768 with a token table", T);
     hipStream_t st = (hipStream_t)stream;
     const dim3 grid(B, 2);
-    const size_t shm = tokens ? (size_t)T * sizeof(int) : 0;
-#define AS_LSTM_LAUNCH(HH, TR, TK) \
-    hipLaunchKernelGGL((lstm_fwd_kernel<HH, TR, TK>), grid, dim3(LPU * HH), shm, st, gi, tokens, (long)tok_stride, w_hh, b_hh, lengths, T, y, gates)
-#define AS_LSTM_FWD(HH)                                  \
-    if (gates && tokens) AS_LSTM_LAUNCH(HH, true, true); \
-    else if (gates) AS_LSTM_LAUNCH(HH, true, false);     \
-    else if (tokens) AS_LSTM_LAUNCH(HH, false, true);    \
-    else AS_LSTM_LAUNCH(HH, false, false);
-    switch (H) {
-        case 32: AS_LSTM_FWD(32) break;
-        case 64: AS_LSTM_FWD(64) break;
-        case 128: AS_LSTM_FWD(128) break;
-        default: {   // any other hidden size: the plain kernels
-            const size_t gshm = (size_t)3 * H * sizeof(float);
-            AS_REQUIRE(H > 0 && H % 4 == 0 && gshm <= 64 * 1024, AS_ERR_UNSUPPORTED, "as_lstm_bidir_fwd: hidden size %d (a multiple of 4 up to 5460)", H);
-#define AS_LSTM_GEN(TR, TK) \
-    hipLaunchKernelGGL((lstm_fwd_generic_kernel<TR, TK>), grid, dim3(GEN_THREADS), gshm, st, gi, tokens, (long)tok_stride, w_hh, b_hh, lengths, T, H, y, gates)
-            if (gates && tokens) AS_LSTM_GEN(true, true);
-            else if (gates) AS_LSTM_GEN(true, false);
-            else if (tokens) AS_LSTM_GEN(false, true);
-            else AS_LSTM_GEN(false, false);
-#undef AS_LSTM_GEN
-        }
+    int rc = 0;
+    if (!rnn_resident(H, gates != nullptr, tokens != nullptr, &rc, [&](auto h, auto train, auto tok) {
+        constexpr int HH = decltype(h)::value;
+        hipLaunchKernelGGL((lstm_fwd_kernel<HH, decltype(train)::value, decltype(tok)::value>), grid, dim3(LPU * HH),
+                           tokens ? (size_t)T * sizeof(int) : 0, st, gi, tokens, (long)tok_stride, w_hh, b_hh, lengths, T, y, gates);
+        return 0;
+    })) {   // any other hidden size: the plain kernels
+        size_t gshm;
+        AS_TRY(rnn_plain_lds("as_lstm_bidir_fwd", H, LSTM_FWD_LDS_PER_UNIT, &gshm));
+        rnn_with_flags(gates != nullptr, tokens != nullptr, [&](auto train, auto tok) {
+            hipLaunchKernelGGL((lstm_fwd_generic_kernel<decltype(train)::value, decltype(tok)::value>), grid, dim3(GEN_THREADS), gshm, st,
+                               gi, tokens, (long)tok_stride, w_hh, b_hh, lengths, T, H, y, gates);
+            return 0;
+        });
     }
-#undef AS_LSTM_FWD
-#undef AS_LSTM_LAUNCH
+    AS_TRY(rc);
     AS_LAUNCH_CHECK("as_lstm_bidir_fwd");
     return 0;
 }
 
 extern "C" int as_lstm_bidir_bwd(const float* dy, const float* gates, const float* w_hh, const int32_t* lengths, int32_t B, int32_t T,
                                  int32_t H, float* dg, void* stream) {
-    AS_REQUIRE(dy && gates && w_hh && lengths && dg, AS_ERR_BAD_ARG, "as_lstm_bidir_bwd: null pointer");
-    AS_REQUIRE(B > 0 && T > 0, AS_ERR_BAD_ARG, "as_lstm_bidir_bwd: B=%d T=%d", B, T);
+    AS_TRY(rnn_check_args("as_lstm_bidir_bwd", dy && gates && w_hh && lengths && dg, B, T));
     hipStream_t st = (hipStream_t)stream;
     const dim3 grid(B, 2);
-#define AS_LSTM_BWD(HH) hipLaunchKernelGGL((lstm_bwd_row_kernel<HH>), grid, dim3(4 * HH), 0, st, dy, gates, w_hh, lengths, T, dg)
-    switch (H) {
-        case 32: AS_LSTM_BWD(32); break;
-        case 64: AS_LSTM_BWD(64); break;
-        case 128: AS_LSTM_BWD(128); break;
-        default: {   // any other hidden size: the plain kernel
-            const size_t gshm = (size_t)10 * H * sizeof(float);
-            AS_REQUIRE(H > 0 && H % 4 == 0 && gshm <= 64 * 1024, AS_ERR_UNSUPPORTED, "as_lstm_bidir_bwd: hidden size %d (a multiple of 4 up to 1636)", H);
-            hipLaunchKernelGGL(lstm_bwd_generic_kernel, grid, dim3(GEN_THREADS), gshm, st, dy, gates, w_hh, lengths, T, H, dg);
-        }
+    int rc = 0;
+    if (!rnn_resident(H, &rc, [&](auto h) {
+        constexpr int HH = decltype(h)::value;
+        hipLaunchKernelGGL((lstm_bwd_row_kernel<HH>), grid, dim3(4 * HH), 0, st, dy, gates, w_hh, lengths, T, dg);
+        return 0;
+    })) {   // any other hidden size: the plain kernel
+        size_t gshm;
+        AS_TRY(rnn_plain_lds("as_lstm_bidir_bwd", H, LSTM_BWD_LDS_PER_UNIT, &gshm));
+        hipLaunchKernelGGL(lstm_bwd_generic_kernel, grid, dim3(GEN_THREADS), gshm, st, dy, gates, w_hh, lengths, T, H, dg);
     }
-#undef AS_LSTM_BWD
+    AS_TRY(rc);
     AS_LAUNCH_CHECK("as_lstm_bidir_bwd");
     return 0;
 }

@@ -73,8 +73,9 @@ def test_random_configurations_vs_oracle(seed, dev):
 @pytest.mark.parametrize("lstm", [True, False], ids=["lstm", "gru"])
 @pytest.mark.parametrize("H", [20, 100, 260])
 def test_any_hidden_size_vs_oracle(lstm, H, dev):
-    """Hidden sizes outside {32, 64, 128} (nn.LSTM / nn.GRU take any): the plain recurrence kernels (lstm.hip / gru.hip,
-    `*_generic_kernel`), forward and backward, against the same oracle and the same bounds."""
+    """Hidden sizes outside {32, 64, 128} (nn.LSTM / nn.GRU take any): the plain recurrence kernels (`lstm_*_generic_kernel`
+    in lstm.hip, `gru_*_generic_kernel` in gru.hip, their shared backward mat-vec in rnn_plain.h), forward and backward, against
+    the same oracle and the same bounds."""
     r = np.random.RandomState(900 + H + int(lstm))
     _check_configuration(r, H, lstm, H, int(r.choice([8, 64])), int(r.randint(2, 60)), dev)
 
@@ -111,37 +112,157 @@ def _check_configuration(r, seed, lstm, H, E, V, dev):
     assert abs(analytic - numeric) <= 1e-3 * max(abs(numeric), 1.0), (what, analytic, numeric)
 
 
-def test_raw_lstm_kernels_ragged_and_padded(dev):
-    """as_lstm_bidir_fwd/bwd on their own: zeros at padded frames (outputs and gate gradients), batch independence."""
+def _raw_inputs(cell, B, T, H, dev, seed):
+    """Seeded inputs of the raw recurrence entry points: input projections gi [B*T][2][G H], W_hh [2][G H][H], b_hh [2][G H]."""
+    G = 4 if cell == "lstm" else 3
+    g = torch.Generator().manual_seed(seed)
+    gi = torch.randn(B * T, 2, G * H, generator=g).to(dev)
+    w_hh = (torch.randn(2, G * H, H, generator=g) * 0.2).to(dev)
+    b_hh = (torch.randn(2, G * H, generator=g) * 0.1).to(dev)
+    return G, gi, w_hh, b_hh
+
+
+def _raw_fwd(cell, gi, tokens, w_hh, b_hh, lengths, B, T, H, gates):
     from artspeech_amd import _lib
+    y = torch.empty(B, T, 2 * H, device=gi.device)
+    _lib.call(f"as_{cell}_bidir_fwd", gi, tokens, T if tokens is not None else 0, w_hh, b_hh, lengths, B, T, H, y, gates)
+    return y
+
+
+def _raw_bwd(cell, dy, y, gates, w_hh, lengths, B, T, H):
+    """The gate gradients [B][T][2][G H]: (dgi, dgh) of the GRU, (dg,) of the LSTM."""
+    from artspeech_amd import _lib
+    G = 4 if cell == "lstm" else 3
+    out = [torch.empty(B, T, 2, G * H, device=dy.device) for _ in range(1 if cell == "lstm" else 2)]
+    if cell == "lstm":
+        _lib.call("as_lstm_bidir_bwd", dy, gates, w_hh, lengths, B, T, H, out[0])
+    else:
+        _lib.call("as_gru_bidir_bwd", dy, y, gates, w_hh, lengths, B, T, H, out[0], out[1])
+    return out
+
+
+@pytest.mark.parametrize("H", [4, 20, 32, 260])
+@pytest.mark.parametrize("cell", ["gru", "lstm"])
+def test_raw_kernels_ragged_and_padded(cell, H, dev):
+    """as_{gru,lstm}_bidir_fwd/bwd on their own, register-resident (H = 32) and plain (H = 4: one chunk per row; 20: the clamped
+    tail; 260: the second pass of every loop): zeros at padded frames (outputs and gate gradients), batch independence, the
+    token-table form and the forward without saved gates.  Every comparison is exact."""
     from artspeech_amd.phoneme_to_articulation.rnn_ops import BiRNNLayer
     torch.manual_seed(3)
-    B, T, I, H = 4, 11, 20, 32
-    lengths = torch.tensor([11, 8, 3, 1], dtype=torch.int32, device=dev)
+    B, T, I = 4, 11, 20
+    lens = [11, 8, 3, 1]
+    lengths = torch.tensor(lens, dtype=torch.int32, device=dev)
+    G = 4 if cell == "lstm" else 3
     x = torch.randn(B, T, I, device=dev, requires_grad=True)
-    w_ih, w_hh = torch.randn(2, 4 * H, I, device=dev) * 0.2, torch.randn(2, 4 * H, H, device=dev) * 0.2
-    b_ih, b_hh = torch.randn(2, 4 * H, device=dev) * 0.1, torch.randn(2, 4 * H, device=dev) * 0.1
-    y = BiRNNLayer.apply(x, w_ih, w_hh, b_ih, b_hh, lengths, "lstm")
-    for b, l in enumerate(lengths.tolist()):
+    w_ih, w_hh = torch.randn(2, G * H, I, device=dev) * 0.2, torch.randn(2, G * H, H, device=dev) * 0.2
+    b_ih, b_hh = torch.randn(2, G * H, device=dev) * 0.1, torch.randn(2, G * H, device=dev) * 0.1
+    y = BiRNNLayer.apply(x, w_ih, w_hh, b_ih, b_hh, lengths, cell)
+    for b, l in enumerate(lens):
         assert torch.all(y[b, l:] == 0)
     y.sum().backward()
-    for b, l in enumerate(lengths.tolist()):
+    for b, l in enumerate(lens):
         assert torch.all(x.grad[b, l:] == 0)
     # utterance 1 alone gives the same rows (workgroups are independent)
-    y1 = BiRNNLayer.apply(x[1:2].detach(), w_ih, w_hh, b_ih, b_hh, lengths[1:2].contiguous(), "lstm")
+    y1 = BiRNNLayer.apply(x[1:2].detach(), w_ih, w_hh, b_ih, b_hh, lengths[1:2].contiguous(), cell)
     assert torch.equal(y1[0], y[1].detach())
-    # token-table form of the input projection (embedding folded into W_ih): same rows gathered inside the kernel
+    # the entry points themselves: token-table form of the input projection (embedding folded into W_ih: same rows gathered
+    # inside the kernel), forward with and without saved gates, gate gradients
     V = 7
-    table = torch.randn(V, 2, 4 * H, device=dev)
+    table = torch.randn(V, 2, G * H, device=dev)
     tokens = torch.randint(0, V, (B, T), device=dev)
-    y_tab, y_ref = torch.empty(B, T, 2 * H, device=dev), torch.empty(B, T, 2 * H, device=dev)
-    gi = table[tokens].reshape(B * T, 2, 4 * H).contiguous()
-    L = _lib.lib()
-    _lib.check(L.as_lstm_bidir_fwd(_lib.ptr(table), _lib.ptr(tokens), T, _lib.ptr(w_hh), _lib.ptr(b_hh), _lib.ptr(lengths), B, T, H,
-                                   _lib.ptr(y_tab), None, _lib.stream_ptr()), "as_lstm_bidir_fwd")
-    _lib.check(L.as_lstm_bidir_fwd(_lib.ptr(gi), None, 0, _lib.ptr(w_hh), _lib.ptr(b_hh), _lib.ptr(lengths), B, T, H, _lib.ptr(y_ref), None,
-                                   _lib.stream_ptr()), "as_lstm_bidir_fwd")
-    assert torch.equal(y_tab, y_ref)
+    gi = table[tokens].reshape(B * T, 2, G * H).contiguous()
+    gates = torch.zeros(B, T, 2, G + 1, H, device=dev)
+    y_ref = _raw_fwd(cell, gi, None, w_hh, b_hh, lengths, B, T, H, gates)
+    assert torch.equal(_raw_fwd(cell, table, tokens, w_hh, b_hh, lengths, B, T, H, None), y_ref)
+    assert torch.equal(_raw_fwd(cell, gi, None, w_hh, b_hh, lengths, B, T, H, None), y_ref)
+    assert torch.equal(_raw_fwd(cell, table, tokens, w_hh, b_hh, lengths, B, T, H, torch.empty_like(gates)), y_ref)
+    assert torch.equal(_raw_fwd(cell, gi[T:2 * T].contiguous(), None, w_hh, b_hh, lengths[1:2].contiguous(), 1, T, H, None)[0], y_ref[1])
+    grads = _raw_bwd(cell, torch.randn(B, T, 2 * H, device=dev), y_ref, gates, w_hh, lengths, B, T, H)
+    for b, l in enumerate(lens):
+        assert torch.all(y_ref[b, l:] == 0)
+        for dg in grads:
+            assert torch.all(dg[b, l:] == 0) and torch.any(dg[b, :l] != 0)
+
+
+@pytest.mark.parametrize("cell", ["gru", "lstm"])
+def test_raw_kernels_hidden_size_4_vs_oracle(cell, dev):
+    """H = 4 (one 16-byte chunk per row: three lanes of every quad have none), which the model-level oracle tests do not
+    reach: y against the oracle's float64 cell recurrence fed the input projections directly (W_ih = identity, b_ih = 0), to
+    the 2e-5 of test_matches_oracle; the gate gradients against central differences of that recurrence along every input
+    projection (smooth in float64: step 1e-5, error ~1e-10), to assert_grad_close.  The GRU's hidden-side gradients are its
+    input-side ones with the n plane times r (artspeech_oracle.gru_dir_bwd)."""
+    B, T, H = 3, 6, 4
+    lens = np.array([6, 4, 1])
+    G, gi, w_hh, b_hh = _raw_inputs(cell, B, T, H, dev, 40)
+    lengths = torch.tensor(lens, dtype=torch.int32, device=dev)
+    dy = torch.randn(B, T, 2 * H, generator=torch.Generator().manual_seed(41)).to(dev)
+    gates = torch.zeros(B, T, 2, G + 1, H, device=dev)
+    y = _raw_fwd(cell, gi, None, w_hh, b_hh, lengths, B, T, H, gates)
+    got = [g.cpu().numpy() for g in _raw_bwd(cell, dy, y, gates, w_hh, lengths, B, T, H)]
+
+    gi64, w64, b64 = (a.cpu().numpy().astype(np.float64) for a in (gi.view(B, T, 2, G * H), w_hh, b_hh))
+    dy64 = dy.cpu().numpy().astype(np.float64).reshape(B, T, 2, H)
+    eye, zero = np.eye(G * H), np.zeros(G * H)
+    want_y, want = np.zeros((B, T, 2, H)), [np.zeros((B, T, 2, G * H)) for _ in got]
+    for d in range(2):
+        def fwd(g):
+            if cell == "lstm":
+                return PO.lstm_dir_fwd(g, lens, eye, w64[d], zero, b64[d], bool(d)), None
+            return PO.gru_dir_fwd(g, lens, eye, w64[d], zero, b64[d], bool(d))
+        want_y[:, :, d], cache = fwd(gi64[:, :, d])
+        eps = 1e-5
+        for b in range(B):
+            for t in range(lens[b]):
+                for c in range(G * H):
+                    g = gi64[:, :, d].copy()
+                    g[b, t, c] += eps
+                    up = (fwd(g)[0] * dy64[:, :, d]).sum()
+                    g[b, t, c] -= 2 * eps
+                    want[0][b, t, d, c] = (up - (fwd(g)[0] * dy64[:, :, d]).sum()) / (2 * eps)
+        if cell == "gru":
+            want[1][:, :, d] = want[0][:, :, d]
+            want[1][:, :, d, 2 * H:] *= cache[0]
+    err = np.abs(y.cpu().numpy().reshape(B, T, 2, H) - want_y).max()
+    print(f"{cell} H=4: max|y - oracle| = {err:.2e}")
+    assert err < 2e-5
+    for name, a, w in zip(("dgi", "dgh") if cell == "gru" else ("dg",), got, want):
+        print(f"{cell} H=4: {name} max rel err {assert_grad_close(a, w, f'{cell} H=4 {name}'):.2e}")
+
+
+# (entry point, gate rows, directions, largest hidden size whose state fits the plain kernel's 64 KB of LDS)
+_LIMITS = [("as_gru_bidir_fwd", 3, 2, 8192), ("as_gru_unidir_fwd_gates", 3, 1, 8192), ("as_gru_bidir_bwd", 3, 2, 1820),
+           ("as_gru_unidir_bwd", 3, 1, 1820), ("as_lstm_bidir_fwd", 4, 2, 5460), ("as_lstm_bidir_bwd", 4, 2, 1636)]
+
+
+@pytest.mark.parametrize("entry,G,nd,limit", _LIMITS, ids=[e[0] for e in _LIMITS])
+def test_plain_kernels_refuse_beyond_their_lds_limit(entry, G, nd, limit, dev):
+    """Every recurrence entry point refuses the first multiple of 4 beyond its limit with AS_ERR_UNSUPPORTED and a message that
+    names the limit, and accepts the limit itself: the launch at B = T = 1 goes through and completes (all-zero inputs, so
+    the outputs stay zero; this is an acceptance check, not a numeric one).  The buffers are sized for the refused width."""
+    from artspeech_amd import _lib
+    B = T = 1
+    Hb = limit + 4
+    z = lambda *shape: torch.zeros(*shape, device=dev)   # noqa: E731
+    w_hh, b_hh, gi = z(nd, G * Hb, Hb), z(nd, G * Hb), z(B * T, nd, G * Hb)
+    y, gates, dy = z(B, T, nd * Hb), z(B, T, nd, G + 1, Hb), z(B, T, nd * Hb)
+    dg, dg2 = z(B, T, nd, G * Hb), z(B, T, nd, G * Hb)
+    lengths = torch.ones(B, dtype=torch.int32, device=dev)
+
+    def run(H):
+        if entry.endswith("bidir_fwd"):
+            _lib.call(entry, gi, None, 0, w_hh, b_hh, lengths, B, T, H, y, gates)
+        elif entry == "as_gru_unidir_fwd_gates":
+            _lib.call(entry, gi, w_hh, b_hh, lengths, B, T, H, y, gates)
+        elif entry == "as_lstm_bidir_bwd":
+            _lib.call(entry, dy, gates, w_hh, lengths, B, T, H, dg)
+        else:
+            _lib.call(entry, dy, y, gates, w_hh, lengths, B, T, H, dg, dg2)
+
+    with pytest.raises(RuntimeError, match=rf"\(code -2\).*hidden size {Hb} \(a multiple of 4 up to {limit}\)"):
+        run(Hb)
+    run(limit)
+    torch.cuda.synchronize()
+    assert not y.any() and not dg.any() and not dg2.any()
 
 
 @pytest.mark.parametrize("lstm", [True, False])
