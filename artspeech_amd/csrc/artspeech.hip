@@ -13,6 +13,16 @@
 //    N = A*256 columns.  The backward unfolds dW', db' into dW, dgamma, dbeta, db exactly.
 //  * heads are batched over A with strided-batched GEMMs on [rows][A][256] activations; the last GEMM
 //    writes sigmoid(.) straight into the (B, T, A, 2, N) output (:141-145).
+//
+// Where to look in the head stack:
+//  * head_ws carves the workspace, head_plane_jobs states the geometry of every bfloat16 plane image, and head_stack
+//    turns both into one HeadLayer per Linear: where its input, folded weight, planes, gradients and parameters live.
+//    head_fold, the forward, the input-gradient chain and the weight gradients all read a layer's operands from there.
+//  * lin_fwd / lin_bwd pose a layer as an as_lin; lin_or_general launches the fused kernel for it or, when that declines,
+//    the general GEMM + row kernel that lin_general derives from the same as_lin.
+//  * wgrad / wgrad1 (and the model's backward for the trunk) pose each weight-gradient problem once: as_wgrad_multi takes
+//    them as jobs, and the single-problem route hands the same as_gemm to as_gemm_f32 with slab and CU budget filled in.
+//  * gemm_nt / gemm_nn / gemm_tn only set an orientation's strides; everything else is set by field name at the call site.
 #include <stdlib.h>
 
 #include <algorithm>
@@ -38,59 +48,111 @@ struct Carve {
     }
 };
 
-struct HeadWs {  // offsets in floats relative to the head workspace base
-    int64_t xhat, rstd0, w1f, b1f, w2f, b2f, w3f, b3f, r1, r1hat, rstd1, r2, r2hat, rstd2;
-    int64_t dpre3, dz2, dz1, dxhat, dw1f, dw2f, dw3f, slab, slab2, slab3, bits1, bits2, lpart, lpart_n, total;
-    // the folded weights as bfloat16 planes (as_emit_planes): forward orientation [rows = out features][k = in features] and,
-    // for the input-gradient chain, transposed [rows = in features][k = out features]
-    int64_t w1p, w2p, w3p, w2tp, w3tp, w1tp;
-};
 constexpr int OUT_BN = 128;   // column tile of the output layer's kernel (lin_out): rows of the W3' planes per head
+enum { W1P, W2P, W3P, W2TP, W3TP, W1TP, N_PLANES };   // the plane images of the folded weights, in carve and emission order
+
+// in / out features per head of head layer i (0..2), and the rows per head of its folded weight (rows N .. Npad-1 are zeros)
+struct LayerDims { int K, N, Npad; };
+LayerDims layer_dims(const as_dims& d, int i) {
+    const int O = 2 * d.n_samp;
+    if (i < 2) return {i == 0 ? d.hidden : D, D, D};
+    return {D, O, (int)as_round_up(O, 32)};
+}
+
+struct HeadWs {  // offsets in floats relative to the head workspace base; [i]: head layer i
+    int64_t x[3], rstd[3], bits[3], wf[3], bf[3], dz[3], dwf[3], planes[N_PLANES];   // see HeadLayer
+    int64_t dxhat, slab, slab2, slab3, lpart, lpart_n, total;
+};
+
+// The folded weights as bfloat16 planes (as_emit_planes) for the split-arithmetic kernels: the source view and the padded
+// geometry of each image, stated here and nowhere else (B and out are filled in by head_stack).  Forward orientation
+// [rows = out features][k = in features] and, for the input-gradient chain (d(x_hat) = dz . W': the reduction runs over W'
+// rows), transposed [rows = in features][k = out features].
+void head_plane_jobs(const as_dims& d, as_planes_job j[N_PLANES]) {
+    const int A = d.n_art, H = d.hidden, O = 2 * d.n_samp, Opad = (int)as_round_up(O, 32);
+    //         B, n_stride, k_stride, batch_stride, batch, N, K, rows_pad, Kpad, out
+    j[W1P] = {nullptr, H, 1, (long)D * H, A, D, H, D, (int)as_round_up(H, 32), nullptr};
+    j[W2P] = {nullptr, D, 1, (long)D * D, A, D, D, D, D, nullptr};
+    j[W3P] = {nullptr, D, 1, (long)Opad * D, A, O, D, (int)as_round_up(O, OUT_BN), D, nullptr};
+    j[W2TP] = {nullptr, 1, D, (long)D * D, A, D, D, D, D, nullptr};
+    j[W3TP] = {nullptr, 1, D, (long)Opad * D, A, D, O, D, Opad, nullptr};
+    // d(x_hat) = dz1 . W1' summed over the heads: ONE image, rows = the H inputs, k = (head, feature)
+    j[W1TP] = {nullptr, 1, H, 0, 1, H, A * D, (int)as_round_up(H, 128), A * D, nullptr};
+}
 
 HeadWs head_ws(const as_dims& d, int64_t rows) {
-    const int64_t A = d.n_art, H = d.hidden, O = 2 * d.n_samp;
+    const int64_t A = d.n_art;
+    const LayerDims n[3] = {layer_dims(d, 0), layer_dims(d, 1), layer_dims(d, 2)};
     Carve c;
-    HeadWs w;
-    w.xhat = c.take(rows * H);
-    w.rstd0 = c.take(rows);
-    w.w1f = c.take(A * D * H);
-    w.b1f = c.take(A * D);
-    w.w2f = c.take(A * D * D);
-    w.b2f = c.take(A * D);
-    w.w3f = c.take(A * as_round_up(O, 32) * D);  // rows O .. Opad-1 of every head are zeros (head_fold)
-    w.b3f = c.take(A * O);
-    w.r1hat = c.take(rows * A * D);
-    w.rstd1 = c.take(rows * A);
-    w.r2hat = c.take(rows * A * D);
-    w.rstd2 = c.take(rows * A);
-    w.dpre3 = c.take(rows * A * O);
-    w.dz2 = c.take(rows * A * D);
-    w.dz1 = c.take(rows * A * D);
-    // pre-normalisation activations of the UNFUSED forward path only (as_lin_try declined): they live where the backward's
-    // dz1 / dz2 will go, which nothing touches before the backward (the fused path never materialises them)
-    w.r1 = w.dz1;
-    w.r2 = w.dz2;
-    w.dxhat = c.take(rows * H);
-    w.dw1f = c.take(A * D * H);
-    w.dw2f = c.take(A * D * D);
-    w.dw3f = c.take(A * O * D);
+    HeadWs w{};
+    w.x[0] = c.take(rows * n[0].K);
+    w.rstd[0] = c.take(rows);
+    for (int i = 0; i < 3; ++i) {
+        w.wf[i] = c.take(A * n[i].Npad * n[i].K);
+        w.bf[i] = c.take(A * n[i].N);
+    }
+    for (int i = 1; i < 3; ++i) {
+        w.x[i] = c.take(rows * A * n[i].K);
+        w.rstd[i] = c.take(rows * A);
+    }
+    for (int i = 2; i >= 0; --i) w.dz[i] = c.take(rows * A * n[i].N);
+    w.dxhat = c.take(rows * n[0].K);
+    for (int i = 0; i < 3; ++i) w.dwf[i] = c.take(A * n[i].N * n[i].K);
     w.slab = c.take(SLAB_FLOATS);   // split-K partial tiles of the weight-gradient GEMMs (main stream)
     w.slab2 = c.take(SLAB2_FLOATS); // same, for GEMMs issued on the side stream
     w.slab3 = c.take(SLAB_FLOATS);  // same, second side stream
-    w.bits1 = c.take(rows * A * (D / 64) * 2);  // ReLU masks of r1 / r2: one bit per element (64-bit words, 16-byte aligned)
-    w.bits2 = c.take(rows * A * (D / 64) * 2);
+    for (int i = 1; i < 3; ++i) w.bits[i] = c.take(rows * A * (n[i].K / 64) * 2);   // 64-bit words, 16-byte aligned
     // workgroup partial sums of the fused criterion (one per output-layer tile), or of the separate criterion kernel
     w.lpart_n = std::max<int64_t>((rows / 32 + 2) * A, as_euclid_masked_partials());
     w.lpart = c.take(w.lpart_n);
-    const int Opad = (int)as_round_up(O, 32);
-    w.w1p = c.take(as_planes_floats((int)A, D, (int)as_round_up(H, 32)));
-    w.w2p = c.take(as_planes_floats((int)A, D, D));
-    w.w3p = c.take(as_planes_floats((int)A, (int)as_round_up(O, OUT_BN), D));
-    w.w2tp = c.take(as_planes_floats((int)A, D, D));
-    w.w3tp = c.take(as_planes_floats((int)A, D, Opad));
-    w.w1tp = c.take(as_planes_floats(1, (int)as_round_up(H, 128), (int)(A * D)));   // d(x_hat) = dz1 . W1': rows = the H inputs, k = (head, feature)
+    as_planes_job pj[N_PLANES];
+    head_plane_jobs(d, pj);
+    for (int i = 0; i < N_PLANES; ++i) w.planes[i] = c.take(as_planes_floats(pj[i].batch, pj[i].rows_pad, pj[i].Kpad));
     w.total = c.off;
     return w;
+}
+
+// One Linear of the heads with the LayerNorm in front of it folded in: where its operands live.  What layer i produces
+// (x_hat, 1 / std, ReLU bits) is the input of layer i + 1; the output layer writes the caller's `out`.
+struct HeadLayer : LayerDims {
+    float* x; long ldx, x_batch;   // normalised input [rows][A][K] (layer 1: [rows][K] shared by all heads, batch stride 0),
+    float* rstd;                   // its 1 / std per row and head,
+    unsigned long long* bits;      // and the ReLU mask of what was normalised: one bit per element (layer 1: none)
+    float* wf; float* bf;          // folded weight [A][Npad][K] and bias [A][N]
+    as_planes_job fwd, tr;         // wf as bfloat16 planes, forward and transposed (head_plane_jobs)
+    // d loss / d(pre-activation) [rows][A][N].  Layers 1, 2: the forward's general route (lin_general) leaves the
+    // pre-normalisation activations here -- nothing touches it before the backward; the fused route never stores them.
+    float* dz; long ldz;
+    float* dwf;                    // gradient of wf [A][N][K]
+    int64_t w, b, ln_g, ln_b;      // the unfolded layer in the flat parameter / gradient buffers (as_layout)
+    long w_batch() const { return (long)Npad * K; }
+};
+struct HeadStack {
+    int A, H, O, R, n_samp;        // heads, input width, outputs per head (2 n_samp), rows
+    float* ws; HeadWs w;           // the carve: dxhat, the slabs and the criterion's partials belong to no layer
+    HeadLayer l[3];
+};
+
+HeadStack head_stack(const as_dims& d, const as_layout& L, int64_t rows, float* ws) {
+    HeadStack s{};
+    s.A = d.n_art; s.H = d.hidden; s.n_samp = d.n_samp; s.O = 2 * d.n_samp; s.R = (int)rows; s.ws = ws; s.w = head_ws(d, rows);
+    const HeadWs& w = s.w;
+    as_planes_job pj[N_PLANES];
+    head_plane_jobs(d, pj);
+    for (int i = 0; i < N_PLANES; ++i) pj[i].out = reinterpret_cast<uint16_t*>(ws + w.planes[i]);
+    const int tr[3] = {W1TP, W2TP, W3TP};   // (forward images: W1P + i)
+    const int64_t pw[3] = {L.w1, L.w2, L.w3}, pb[3] = {L.b1, L.b2, L.b3}, pg[3] = {L.ln1_g, L.ln2_g, L.ln3_g}, pbt[3] = {L.ln1_b, L.ln2_b, L.ln3_b};
+    for (int i = 0; i < 3; ++i) {
+        HeadLayer& l = s.l[i];
+        static_cast<LayerDims&>(l) = layer_dims(d, i);
+        l.x = ws + w.x[i]; l.ldx = i ? (long)s.A * l.K : l.K; l.x_batch = i ? l.K : 0;
+        l.rstd = ws + w.rstd[i]; l.bits = i ? reinterpret_cast<unsigned long long*>(ws + w.bits[i]) : nullptr;
+        l.wf = ws + w.wf[i]; l.bf = ws + w.bf[i];
+        l.fwd = pj[W1P + i]; l.tr = pj[tr[i]]; l.fwd.B = l.tr.B = l.wf;
+        l.dz = ws + w.dz[i]; l.ldz = (long)s.A * l.N; l.dwf = ws + w.dwf[i];
+        l.w = pw[i]; l.b = pb[i]; l.ln_g = pg[i]; l.ln_b = pbt[i];
+    }
+    return s;
 }
 
 struct ModelWs {
@@ -141,163 +203,162 @@ int check_dims(const as_dims* d, const char* who) {
     return 0;
 }
 
-// C = act(A . B^T + bias): both operands reduction-contiguous
-int gemm_nt(const float* A, long lda, const float* Bw, long ldb, float* C, long ldc, const float* bias, int M, int N, int K,
-            int act, hipStream_t st, int batch = 1, long ab = 0, long bb = 0, long cb = 0, long biasb = 0) {
+// as_gemm builders: one problem (batch 1) with the orientation's strides set (x_kc: the operand is reduction-contiguous).
+// Everything else -- bias, act, batch and its strides, the time shift of B, colsum, the split-K slab, cu_budget -- is set by
+// field name where the GEMM is posed.
+as_gemm gemm_of(const float* A, long lda, bool a_kc, const float* B, long ldb, bool b_kc, float* C, long ldc, int M, int N, int K) {
     as_gemm g{};
-    g.A = A; g.B = Bw; g.C = C; g.bias = bias; g.M = M; g.N = N; g.K = K;
-    g.a_i = lda; g.a_k = 1; g.b_j = ldb; g.b_k = 1; g.ldc = ldc;
-    g.batch = batch; g.a_batch = ab; g.b_batch = bb; g.c_batch = cb; g.bias_batch = biasb; g.act = act;
-    return as_gemm_f32(&g, st);
+    g.A = A; g.B = B; g.C = C; g.ldc = ldc; g.M = M; g.N = N; g.K = K; g.batch = 1;
+    g.a_i = a_kc ? lda : 1; g.a_k = a_kc ? 1 : lda; g.b_j = b_kc ? ldb : 1; g.b_k = b_kc ? 1 : ldb;
+    return g;
+}
+// C = act(A . B^T + bias): both operands reduction-contiguous
+as_gemm gemm_nt(const float* A, long lda, const float* B, long ldb, float* C, long ldc, int M, int N, int K) {
+    return gemm_of(A, lda, true, B, ldb, true, C, ldc, M, N, K);
 }
 // C[M][N] = A[M][K] . B[K][N]   (input gradient: reduction over the rows of B)
-int gemm_nn(const float* A, long lda, const float* Bm, long ldb, float* C, long ldc, int M, int N, int K, hipStream_t st,
-            int batch = 1, long ab = 0, long bb = 0, long cb = 0, float* slab = nullptr) {
-    as_gemm g{};
-    g.A = A; g.B = Bm; g.C = C; g.M = M; g.N = N; g.K = K;
-    g.a_i = lda; g.a_k = 1; g.b_j = 1; g.b_k = ldb; g.ldc = ldc;
-    g.batch = batch; g.a_batch = ab; g.b_batch = bb; g.c_batch = cb;
-    g.splitk_ws = slab; g.splitk_ws_floats = slab ? SLAB_FLOATS : 0;  // few output tiles + long reduction: split K
-    return as_gemm_f32(&g, st);
+as_gemm gemm_nn(const float* A, long lda, const float* B, long ldb, float* C, long ldc, int M, int N, int K) {
+    return gemm_of(A, lda, true, B, ldb, false, C, ldc, M, N, K);
 }
-// C[M][N] = A[K][M]^T . B[K][N]   (weight gradient: reduction over the rows of both)
-// colsum (optional): column sums of A, i.e. the bias gradient that goes with this weight gradient, [batch][M]
-// cu_budget: CUs the launch can count on (0 = all): 192 for the side stream's launches beside a 64-workgroup recurrence
-int gemm_tn(const float* A, long lda, const float* Bm, long ldb, float* C, long ldc, int M, int N, int K, hipStream_t st,
-            float* slab, float* colsum = nullptr, long csb = 0, int batch = 1, long ab = 0, long bb = 0, long cb = 0,
-            int kshift = 0, int kT = 0, int kshift_batch = 0, int cu_budget = 0) {
-    as_gemm g{};
-    g.A = A; g.B = Bm; g.C = C; g.M = M; g.N = N; g.K = K;
-    g.a_i = 1; g.a_k = lda; g.b_j = 1; g.b_k = ldb; g.ldc = ldc;
-    g.batch = batch; g.a_batch = ab; g.b_batch = bb; g.c_batch = cb; g.b_kshift = kshift; g.b_kT = kT; g.b_kshift_batch = kshift_batch;
-    g.splitk_ws = slab; g.splitk_ws_floats = SLAB_FLOATS; g.colsum = colsum; g.colsum_batch = csb; g.cu_budget = cu_budget;
+// C[M][N] = A[K][M]^T . B[K][N]   (weight gradient: reduction over the rows of both; g.colsum: the column sums of A, i.e. the
+// bias gradient that goes with it, [batch][M])
+as_gemm gemm_tn(const float* A, long lda, const float* B, long ldb, float* C, long ldc, int M, int N, int K) {
+    return gemm_of(A, lda, false, B, ldb, false, C, ldc, M, N, K);
+}
+// few output tiles under a long reduction: split K over `slab` (every slab of the carve holds SLAB_FLOATS or more; the split
+// factor depends on the size stated).  cu_budget: CUs the launch can count on (0 = all): 192 beside a 64-workgroup recurrence
+int run_split_k(as_gemm g, float* slab, hipStream_t st, int cu_budget = 0) {
+    g.splitk_ws = slab; g.splitk_ws_floats = SLAB_FLOATS; g.cu_budget = cu_budget;
     return as_gemm_f32(&g, st);
 }
 
+// hand a plane image to the kernel that reads it (as_lin.Bp / as_lin_out.Bp)
+template <typename Lin>
+void use_planes(Lin& a, const as_planes_job& p) {
+    a.Bp = p.out; a.bp_rows = p.rows_pad; a.bp_batch = as_planes_batch_stride(p.rows_pad, p.Kpad); a.bp_plane = p.batch * a.bp_batch;
+}
+
 // fold the LayerNorm affines into the head weights (depends on the parameters only: can run early / elsewhere)
-int head_fold(const as_dims& d, const as_layout& L, const float* P, int64_t rows, float* ws, hipStream_t st) {
-    const int A = d.n_art, H = d.hidden, O = 2 * d.n_samp;
-    const HeadWs w = head_ws(d, rows);
-    AS_STEP("head.fold", st, as_fold(P + L.w1, P + L.ln1_g, P + L.ln1_b, P + L.b1, ws + w.w1f, ws + w.b1f, A, D, H, st));
-    AS_STEP("head.fold", st, as_fold(P + L.w2, P + L.ln2_g, P + L.ln2_b, P + L.b2, ws + w.w2f, ws + w.b2f, A, D, D, st));
-    AS_STEP("head.fold", st, as_fold(P + L.w3, P + L.ln3_g, P + L.ln3_b, P + L.b3, ws + w.w3f, ws + w.b3f, A, O, D, st, (int)as_round_up(O, 32)));
-    {
-        // the folded weights as bfloat16 planes for the split-arithmetic kernels: forward orientation, and transposed for
-        // the input-gradient chain (d(x_hat) = dz . W': the reduction runs over W' rows).  Emitted for every hidden size and
-        // in both arithmetics: the head layers hand them to the split kernels whatever H is, and the arithmetic is read at
-        // each launch, so a backward may run in the split arithmetic after a forward in the exact one.
-        const int Opad = (int)as_round_up(O, 32), Hp = (int)as_round_up(H, 32);
-        auto up = [&](int64_t off) { return reinterpret_cast<uint16_t*>(ws + off); };
-        as_planes_job j[6] = {
-            {ws + w.w1f, H, 1, (long)D * H, A, D, H, D, Hp, up(w.w1p)},
-            {ws + w.w2f, D, 1, (long)D * D, A, D, D, D, D, up(w.w2p)},
-            {ws + w.w3f, D, 1, (long)Opad * D, A, O, D, (int)as_round_up(O, OUT_BN), D, up(w.w3p)},
-            {ws + w.w2f, 1, D, (long)D * D, A, D, D, D, D, up(w.w2tp)},
-            {ws + w.w3f, 1, D, (long)Opad * D, A, D, O, D, Opad, up(w.w3tp)},
-            {ws + w.w1f, 1, H, 0, 1, H, A * D, (int)as_round_up(H, 128), A * D, up(w.w1tp)},
-        };
-        AS_STEP("head.planes", st, as_emit_planes(j, 6, st));
-    }
+int head_fold(const HeadStack& s, const float* P, hipStream_t st) {
+    for (const HeadLayer& l : s.l)
+        AS_STEP("head.fold", st, as_fold(P + l.w, P + l.ln_g, P + l.ln_b, P + l.b, l.wf, l.bf, s.A, l.N, l.K, st, l.Npad));
+    // the folded weights as bfloat16 planes.  Emitted for every hidden size and in both arithmetics: the head layers hand them
+    // to the split kernels whatever H is, and the arithmetic is read at each launch, so a backward may run in the split
+    // arithmetic after a forward in the exact one.
+    const as_planes_job j[N_PLANES] = {s.l[0].fwd, s.l[1].fwd, s.l[2].fwd, s.l[1].tr, s.l[2].tr, s.l[0].tr};
+    AS_STEP("head.planes", st, as_emit_planes(j, N_PLANES, st));
     return 0;
+}
+
+// Layer i forward as the fused kernels see it.  i < 2: Linear + ReLU + the next LayerNorm in one kernel per (64 frames,
+// head), which writes layer i + 1's input (lin_f32.hip); i == 2: Linear (x_coords | y_coords) + sigmoid into out[rows][A][2][N].
+as_lin lin_fwd(const HeadStack& s, int i, float* out = nullptr) {
+    const HeadLayer& l = s.l[i];
+    as_lin a{};
+    a.A = l.x; a.lda = l.ldx; a.a_batch = l.x_batch;
+    a.B = l.wf; a.ldb = l.K; a.b_batch = l.w_batch(); a.b_kc = 1;
+    a.bias = l.bf; a.bias_batch = l.N;
+    a.M = s.R; a.N = l.N; a.K = l.K; a.batch = s.A;
+    if (i == 2) {
+        a.C = out; a.ldc = (long)s.A * l.N; a.c_batch = l.N; a.act = 2; a.epi = 0;
+        return a;
+    }
+    const HeadLayer& y = s.l[i + 1];
+    a.C = y.x; a.ldc = y.ldx; a.c_batch = y.x_batch; a.epi = 1; a.rstd = y.rstd; a.bits = y.bits;
+    if (l.K % 32 == 0) use_planes(a, l.fwd);
+    return a;
+}
+// Input gradient of layer i (2, 1): d(x_hat) = dz . W' through the LayerNorm and the ReLU behind layer i - 1 in one kernel,
+// which writes layer i - 1's dz.  The reduction runs over Npad (the folded weights' rows N .. Npad-1 are zeros; dz is read
+// up to N); the ReLU masks come as bit words (32 B per row).
+as_lin lin_bwd(const HeadStack& s, int i, const float* dz) {
+    const HeadLayer &l = s.l[i], &to = s.l[i - 1];
+    as_lin a{};
+    a.A = dz; a.lda = l.ldz; a.a_batch = l.N;
+    a.B = l.wf; a.ldb = l.K; a.b_batch = l.w_batch(); a.b_kc = 0;
+    a.C = to.dz; a.ldc = to.ldz; a.c_batch = to.N;
+    a.M = s.R; a.N = l.K; a.K = l.Npad; a.ka_valid = l.N; a.batch = s.A; a.epi = 2;
+    a.xhat = l.x; a.ldx = l.ldx; a.x_batch = l.x_batch; a.rstd_in = l.rstd; a.bits_in = l.bits;
+    use_planes(a, l.tr);
+    return a;
+}
+
+// What runs when the fused kernel declines, derived from the SAME as_lin: the general GEMM, then the epilogue's row kernel
+// (which takes C as [M * batch][N], the heads' layout).  epi 0: C = act(A . B^T + bias).  epi 1: pre = relu(A . B^T + bias),
+// then as_normalize_fwd: pre -> C, rstd, bits.  epi 2: C = A . B over the ka_valid rows of B, then as_normalize_bwd in place.
+// A batch that is one problem is posed as one: when every member reads the same A (a_batch == 0) and B, C and the bias are
+// contiguous across the batch (b_batch == N * ldb, c_batch == N, bias_batch == N), it is ONE GEMM over batch * N columns
+// (layer 1: A * 256), not `batch` GEMMs of N.
+int lin_general(const as_lin& a, float* pre, const char* gemm_phase, const char* norm_phase, hipStream_t st) {
+    as_gemm g = a.b_kc ? gemm_nt(a.A, a.lda, a.B, a.ldb, a.epi == 1 ? pre : a.C, a.ldc, a.M, a.N, a.K)
+                       : gemm_nn(a.A, a.lda, a.B, a.ldb, a.C, a.ldc, a.M, a.N, a.ka_valid > 0 ? a.ka_valid : a.K);
+    g.bias = a.bias;
+    g.act = a.epi == 1 ? 1 : a.act;
+    if (a.b_kc && a.a_batch == 0 && a.b_batch == a.N * a.ldb && a.c_batch == a.N && a.bias_batch == a.N) {
+        g.N = a.batch * a.N;
+    } else {
+        g.batch = a.batch; g.a_batch = a.a_batch; g.b_batch = a.b_batch; g.c_batch = a.c_batch; g.bias_batch = a.bias_batch;
+    }
+    AS_STEP(gemm_phase, st, as_gemm_f32(&g, st));
+    const long rows = (long)a.M * a.batch;
+    if (a.epi == 1) AS_STEP(norm_phase, st, as_normalize_fwd(pre, a.C, a.rstd, rows, a.N, st, a.bits));
+    if (a.epi == 2) AS_STEP(norm_phase, st, as_normalize_bwd(a.C, a.xhat, a.rstd_in, nullptr, a.C, rows, a.N, st, a.bits_in));
+    return 0;
+}
+// One head layer: the fused kernel, else lin_general.  pre (epi 1): scratch for the general route's pre-normalisation values.
+int lin_or_general(const as_lin& a, float* pre, const char* gemm_phase, const char* norm_phase, const char* what, hipStream_t st) {
+    int took;
+    {
+        AS_PROF(gemm_phase, st);
+        took = as_lin_try(&a, st);
+        AS_REQUIRE(took >= 0, took, "%s: launch failed", what);
+    }
+    return took ? 0 : lin_general(a, pre, gemm_phase, norm_phase, st);
 }
 
 // crit (optional): the training criterion fused into the output layer (as_opts.loss_*; lengths / T of the batch)
 struct Criterion { const float* tgt; long tgt_T; const int* lengths; int T; float scale; float* loss; float* dout; };
 
-int head_fwd_impl(const as_dims& d, const as_layout& L, const float* P, const float* x, int64_t rows, float* out, float* ws,
-                  hipStream_t st, const Criterion* crit = nullptr) {
-    (void)P;
-    const int A = d.n_art, H = d.hidden, O = 2 * d.n_samp;
-    const HeadWs w = head_ws(d, rows);
-    const int R = (int)rows;
-    AS_STEP("head.norm0", st, as_normalize_fwd(x, ws + w.xhat, ws + w.rstd0, rows, H, st));
-    const long AD = (long)A * D;
-    const int Opad = (int)as_round_up(O, 32);
-    unsigned long long* bits1 = reinterpret_cast<unsigned long long*>(ws + w.bits1);
-    unsigned long long* bits2 = reinterpret_cast<unsigned long long*>(ws + w.bits2);
-    // Linear 1 + ReLU + LayerNorm 2 in one kernel per (96 frames, head): r1hat, rstd1, ReLU bits (lin_f32.hip); else the
-    // general GEMM (all heads at once: shared x_hat, N = A*256 columns) followed by the row kernel
-    as_lin l1{};
-    l1.A = ws + w.xhat; l1.lda = H; l1.a_batch = 0;
-    l1.B = ws + w.w1f; l1.ldb = H; l1.b_batch = (long)D * H; l1.b_kc = 1;
-    l1.C = ws + w.r1hat; l1.ldc = AD; l1.c_batch = D;
-    l1.bias = ws + w.b1f; l1.bias_batch = D;
-    l1.M = R; l1.N = D; l1.K = H; l1.batch = A; l1.epi = 1;
-    l1.rstd = ws + w.rstd1; l1.bits = bits1;
-    const uint16_t* w1p = reinterpret_cast<const uint16_t*>(ws + w.w1p);
-    const uint16_t* w2p = reinterpret_cast<const uint16_t*>(ws + w.w2p);
-    if (H % 32 == 0) {
-        l1.Bp = w1p; l1.bp_rows = D; l1.bp_batch = as_planes_batch_stride(D, H); l1.bp_plane = A * l1.bp_batch;
-    }
+int head_fwd_impl(const HeadStack& s, const float* x, float* out, hipStream_t st, const Criterion* crit = nullptr) {
+    AS_STEP("head.norm0", st, as_normalize_fwd(x, s.l[0].x, s.l[0].rstd, s.R, s.H, st));
+    // Linear 1 (all heads read the shared x_hat) and Linear 2, each with its ReLU and the LayerNorm behind it
+    AS_TRY(lin_or_general(lin_fwd(s, 0), s.l[0].dz, "head.gemm1", "head.norm1", "head gemm1", st));
+    AS_TRY(lin_or_general(lin_fwd(s, 1), s.l[1].dz, "head.gemm2", "head.norm2", "head gemm2", st));
+    // The output layer's chain: lin_out (64 x 128-column tiles of one head each, four workgroups per CU; with `crit` the masked
+    // Euclidean criterion and its gradient ride in the epilogue), else the 256-column kernel, else the general GEMM
+    const as_lin l3 = lin_fwd(s, 2, out);
+    float* lpart = s.ws + s.w.lpart;
     int took;
     bool crit_done = false;
     {
-        AS_PROF("head.gemm1", st);
-        took = as_lin_try(&l1, st);
-        AS_REQUIRE(took >= 0, took, "head gemm1: launch failed");
-    }
-    if (!took) {
-        AS_STEP("head.gemm1", st, gemm_nt(ws + w.xhat, H, ws + w.w1f, H, ws + w.r1, AD, ws + w.b1f, R, A * D, H, 1, st));
-        AS_STEP("head.norm1", st, as_normalize_fwd(ws + w.r1, ws + w.r1hat, ws + w.rstd1, rows * A, D, st, bits1));
-    }
-    // Linear 2 + ReLU + LayerNorm 3, batched over heads on [rows][A][D]
-    as_lin l2 = l1;
-    l2.A = ws + w.r1hat; l2.lda = AD; l2.a_batch = D;
-    l2.B = ws + w.w2f; l2.ldb = D; l2.b_batch = (long)D * D;
-    l2.C = ws + w.r2hat; l2.bias = ws + w.b2f;
-    l2.K = D; l2.rstd = ws + w.rstd2; l2.bits = bits2;
-    l2.Bp = w2p; l2.bp_rows = D; l2.bp_batch = as_planes_batch_stride(D, D); l2.bp_plane = A * l2.bp_batch;
-    {
-        AS_PROF("head.gemm2", st);
-        took = as_lin_try(&l2, st);
-        AS_REQUIRE(took >= 0, took, "head gemm2: launch failed");
-    }
-    if (!took) {
-        AS_STEP("head.gemm2", st, gemm_nt(ws + w.r1hat, AD, ws + w.w2f, D, ws + w.r2, AD, ws + w.b2f, R, D, D, 1, st, A, D,
-                       (long)D * D, D, D));
-        AS_STEP("head.norm2", st, as_normalize_fwd(ws + w.r2, ws + w.r2hat, ws + w.rstd2, rows * A, D, st, bits2));
-    }
-    // Linear 3 (x_coords | y_coords) with the sigmoid epilogue writes out[rows][A][2][N]
-    as_lin l3{};
-    l3.A = ws + w.r2hat; l3.lda = AD; l3.a_batch = D;
-    l3.B = ws + w.w3f; l3.ldb = D; l3.b_batch = (long)Opad * D; l3.b_kc = 1;
-    l3.C = out; l3.ldc = (long)A * O; l3.c_batch = O;
-    l3.bias = ws + w.b3f; l3.bias_batch = O;
-    l3.M = R; l3.N = O; l3.K = D; l3.batch = A; l3.act = 2; l3.epi = 0;
-    {
         AS_PROF("head.gemm3", st);
-        // 64 x 128-column tiles of one head each, four workgroups per CU (lin_out_kernel); with `crit` the masked Euclidean
-        // criterion and its gradient ride in the epilogue
         as_lin_out lo{};
-        lo.A = ws + w.r2hat; lo.lda = AD; lo.a_batch = D;
-        lo.B = ws + w.w3f; lo.ldb = D; lo.b_batch = (long)Opad * D; lo.b_rows = Opad;
-        lo.bias = ws + w.b3f; lo.bias_batch = O;
-        lo.out = out; lo.ldo = (long)A * O; lo.o_batch = O;
-        lo.M = R; lo.N = O; lo.K = D; lo.batch = A;
-        lo.Bp = reinterpret_cast<const uint16_t*>(ws + w.w3p); lo.bp_rows = (int)as_round_up(O, OUT_BN);
-        lo.bp_batch = as_planes_batch_stride(lo.bp_rows, D); lo.bp_plane = A * lo.bp_batch;
+        lo.A = l3.A; lo.lda = l3.lda; lo.a_batch = l3.a_batch;
+        lo.B = l3.B; lo.ldb = l3.ldb; lo.b_batch = l3.b_batch; lo.b_rows = s.l[2].Npad;
+        lo.bias = l3.bias; lo.bias_batch = l3.bias_batch;
+        lo.out = l3.C; lo.ldo = l3.ldc; lo.o_batch = l3.c_batch;
+        lo.M = l3.M; lo.N = l3.N; lo.K = l3.K; lo.batch = l3.batch;
+        use_planes(lo, s.l[2].fwd);
         int n_part = 0;
         if (crit) {
             lo.tgt = crit->tgt; lo.tgt_T = crit->tgt_T; lo.lengths = crit->lengths; lo.T = crit->T; lo.scale = crit->scale;
-            lo.dout = crit->dout; lo.partial = ws + w.lpart; lo.partial_capacity = w.lpart_n; lo.loss = crit->loss;
+            lo.dout = crit->dout; lo.partial = lpart; lo.partial_capacity = s.w.lpart_n; lo.loss = crit->loss;
         }
         took = as_lin_out_try(&lo, &n_part, st);
         AS_REQUIRE(took >= 0, took, "head gemm3: launch failed");
-        if (took && crit && n_part > 0) AS_TRY(as_loss_final(ws + w.lpart, n_part, crit->scale, crit->loss, st));   // (0: summed in the kernel)
+        if (took && crit && n_part > 0) AS_TRY(as_loss_final(lpart, n_part, crit->scale, crit->loss, st));   // (0: summed in the kernel)
         crit_done = took && crit;
         if (!took) {
             took = as_lin_try(&l3, st);
             AS_REQUIRE(took >= 0, took, "head gemm3: launch failed");
         }
     }
-    if (!took)
-        AS_STEP("head.gemm3", st, gemm_nt(ws + w.r2hat, AD, ws + w.w3f, D, out, (long)A * O, ws + w.b3f, R, O, D, 2, st, A, D,
-                       (long)Opad * D, O, O));
+    if (!took) AS_TRY(lin_general(l3, nullptr, "head.gemm3", nullptr, st));
     if (crit && !crit_done) {
         // the output-layer kernel declined (more than 128 outputs per head, fewer than 4, odd strides): the criterion as its own
         // kernel on the stored contours -- same loss, same d loss / d(pre-sigmoid), one pass more
-        AS_STEP("loss", st, as_euclid_masked_fwd_bwd_presigmoid(out, crit->tgt, crit->tgt_T, crit->lengths, (int32_t)(rows / crit->T), crit->T, A,
-                                                               d.n_samp, crit->scale, crit->loss, crit->dout, ws + w.lpart, st));
+        AS_STEP("loss", st, as_euclid_masked_fwd_bwd_presigmoid(out, crit->tgt, crit->tgt_T, crit->lengths, (int32_t)(s.R / crit->T), crit->T, s.A,
+                                                               s.n_samp, crit->scale, crit->loss, crit->dout, lpart, st));
     }
     return 0;
 }
@@ -307,66 +368,27 @@ int head_fwd_impl(const as_dims& d, const as_layout& L, const float* P, const fl
 //  head_bwd_dw : weight/bias gradients + LayerNorm-affine unfold (only consumes what the chain left in ws)
 // relu_src: optional [rows][H] activation whose ReLU produced x (its mask is fused into the last step)
 // presig: dout already is the gradient w.r.t. the pre-sigmoid activations (as_opts.dout_presigmoid): read in place
-int head_bwd_dx(const as_dims& d, const as_layout& L, const float* P, const float* out, const float* dout, int64_t rows,
-                float* dx, const float* relu_src, float* ws, hipStream_t st, bool presig = false) {
-    (void)L; (void)P;
-    const int A = d.n_art, H = d.hidden, O = 2 * d.n_samp;
-    const HeadWs w = head_ws(d, rows);
-    const int R = (int)rows;
-    const long AD = (long)A * D, AO = (long)A * O;
-    const float* dpre3 = presig ? dout : ws + w.dpre3;
-    if (!presig) AS_STEP("headb.sigmoid", st, as_sigmoid_bwd(out, dout, ws + w.dpre3, rows * AO, st));
-    const int Opad = (int)as_round_up(O, 32);
-    const unsigned long long* bits1 = reinterpret_cast<const unsigned long long*>(ws + w.bits1);
-    const unsigned long long* bits2 = reinterpret_cast<const unsigned long long*>(ws + w.bits2);
-    // d(r2hat) = dpre3 . W3' through LayerNorm 3 and ReLU 2 in one kernel (the reduction runs over Opad: the folded
-    // weights' rows O .. Opad-1 are zeros); else GEMM + the row kernel.  The ReLU masks come as bit words (32 B per row).
-    as_lin b3{};
-    b3.A = dpre3; b3.lda = AO; b3.a_batch = O;
-    b3.B = ws + w.w3f; b3.ldb = D; b3.b_batch = (long)Opad * D; b3.b_kc = 0;
-    b3.C = ws + w.dz2; b3.ldc = AD; b3.c_batch = D;
-    b3.M = R; b3.N = D; b3.K = Opad; b3.ka_valid = O; b3.batch = A; b3.epi = 2;
-    b3.xhat = ws + w.r2hat; b3.ldx = AD; b3.x_batch = D; b3.rstd_in = ws + w.rstd2; b3.bits_in = bits2;
-    b3.Bp = reinterpret_cast<const uint16_t*>(ws + w.w3tp); b3.bp_rows = D; b3.bp_batch = as_planes_batch_stride(D, Opad);
-    b3.bp_plane = A * b3.bp_batch;
-    int took;
-    {
-        AS_PROF("headb.dx3", st);
-        took = as_lin_try(&b3, st);
-        AS_REQUIRE(took >= 0, took, "head dx3: launch failed");
-    }
-    if (!took) {
-        AS_STEP("headb.dx3", st, gemm_nn(dpre3, AO, ws + w.w3f, D, ws + w.dz2, AD, R, D, O, st, A, O, (long)Opad * D, D));
-        AS_STEP("headb.norm2", st, as_normalize_bwd(ws + w.dz2, ws + w.r2hat, ws + w.rstd2, nullptr, ws + w.dz2, rows * A, D, st, bits2));
-    }
-    as_lin b2 = b3;
-    b2.A = ws + w.dz2; b2.lda = AD; b2.a_batch = D;
-    b2.B = ws + w.w2f; b2.b_batch = (long)D * D;
-    b2.C = ws + w.dz1; b2.K = D; b2.ka_valid = D;
-    b2.xhat = ws + w.r1hat; b2.rstd_in = ws + w.rstd1; b2.bits_in = bits1;
-    b2.Bp = reinterpret_cast<const uint16_t*>(ws + w.w2tp); b2.bp_batch = as_planes_batch_stride(D, D); b2.bp_plane = A * b2.bp_batch;
-    {
-        AS_PROF("headb.dx2", st);
-        took = as_lin_try(&b2, st);
-        AS_REQUIRE(took >= 0, took, "head dx2: launch failed");
-    }
-    if (!took) {
-        AS_STEP("headb.dx2", st, gemm_nn(ws + w.dz2, AD, ws + w.w2f, D, ws + w.dz1, AD, R, D, D, st, A, D, (long)D * D, D));
-        AS_STEP("headb.norm1", st, as_normalize_bwd(ws + w.dz1, ws + w.r1hat, ws + w.rstd1, nullptr, ws + w.dz1, rows * A, D, st, bits1));
-    }
+int head_bwd_dx(const HeadStack& s, const float* out, const float* dout, float* dx, const float* relu_src, hipStream_t st,
+                bool presig = false) {
+    const int H = s.H, R = s.R;
+    const HeadLayer& l1 = s.l[0];
+    float* slab = s.ws + s.w.slab;
+    float* dxhat = s.ws + s.w.dxhat;
+    if (!presig) AS_STEP("headb.sigmoid", st, as_sigmoid_bwd(out, dout, s.l[2].dz, (long)R * s.l[2].ldz, st));
+    AS_TRY(lin_or_general(lin_bwd(s, 2, presig ? dout : s.l[2].dz), nullptr, "headb.dx3", "headb.norm2", "head dx3", st));
+    AS_TRY(lin_or_general(lin_bwd(s, 1, s.l[1].dz), nullptr, "headb.dx2", "headb.norm1", "head dx2", st));
     // d(x_hat) = dz1 . W1' summed over the heads: N = H columns under an A * 256-long reduction.  Split arithmetic: 64 x 128
     // tiles, the reduction cut into chunks whose partial sums the LayerNorm backward below adds (as_lin_plain_s6); else the
     // general kernel (100 x 2 tiles of 64 x 64, split K over the main-stream slab)
     int dx1_slabs = 0;
     if (H <= 256 && H % 4 == 0) {
         as_lin l{};
-        l.A = ws + w.dz1; l.lda = AD;
-        l.Bp = reinterpret_cast<const uint16_t*>(ws + w.w1tp); l.bp_rows = (int)as_round_up(H, 128);
-        l.bp_batch = as_planes_batch_stride(l.bp_rows, (int)AD); l.bp_plane = l.bp_batch;
-        l.C = ws + w.slab; l.ldc = H;
-        l.M = R; l.N = H; l.K = (int)AD; l.batch = 1;
+        l.A = l1.dz; l.lda = l1.ldz;
+        use_planes(l, l1.tr);
+        l.C = slab; l.ldc = H;
+        l.M = R; l.N = H; l.K = (int)l1.ldz; l.batch = 1;
         const int want = (int)std::max<int64_t>(1, std::min<int64_t>(8, 512 / std::max(1, as_cdiv(R, 64))));
-        const int slabs = as_lin_plain_s6_slabs((int)AD, want);
+        const int slabs = as_lin_plain_s6_slabs(l.K, want);
         if ((int64_t)slabs * R * H <= SLAB_FLOATS) {
             AS_PROF("headb.dx1", st);
             const int took1 = as_lin_plain_s6(&l, want, (long)R * H, st, 2);   // <= 512 workgroups (want): at most two per CU
@@ -375,87 +397,75 @@ int head_bwd_dx(const as_dims& d, const as_layout& L, const float* P, const floa
         }
     }
     if (!dx1_slabs)
-        AS_STEP("headb.dx1", st, gemm_nn(ws + w.dz1, AD, ws + w.w1f, H, ws + w.dxhat, H, R, H, (int)AD, st, 1, 0, 0, 0, ws + w.slab));
-    AS_STEP("headb.norm0", st, as_normalize_bwd(dx1_slabs ? ws + w.slab : ws + w.dxhat, ws + w.xhat, ws + w.rstd0, relu_src, dx, rows, H, st, nullptr,
+        AS_STEP("headb.dx1", st, run_split_k(gemm_nn(l1.dz, l1.ldz, l1.wf, H, dxhat, H, R, H, (int)l1.ldz), slab, st));
+    AS_STEP("headb.norm0", st, as_normalize_bwd(dx1_slabs ? slab : dxhat, l1.x, l1.rstd, relu_src, dx, R, H, st, nullptr,
                                                  dx1_slabs ? dx1_slabs : 1, (long)R * H));
     return 0;
 }
 
-// trunk (optional): the trunk Linear's weight gradient dzlin^T . y1 rides in the same launch (ArtSpeech: N = 2H = 256)
-struct TrunkJob { const float* dz; const float* y; float* dW; float* db; int H; };
+// The weight gradient of layer i (1, 2) with its bias gradient: dW'[A][N][K] = dz^T . x_hat, db' = column sums of dz
+as_wgrad_job wgrad(const HeadStack& s, int i, const float* dz, float* G) {
+    const HeadLayer& l = s.l[i];
+    as_wgrad_job j{};
+    j.g = gemm_tn(dz, l.ldz, l.x, l.ldx, l.dwf, l.K, l.N, l.K, s.R);
+    j.g.batch = s.A; j.g.a_batch = l.N; j.g.b_batch = l.x_batch; j.g.c_batch = (long)l.N * l.K;
+    j.g.colsum = G + l.b; j.g.colsum_batch = l.N;
+    return j;
+}
+// Layer 1's, whose x_hat all heads share, in its two poses.  transposed (the multi launch): dW1'^T = x_hat^T . dz1 per head
+// -- 11 tiles of 128 x 256 like the other layers instead of 22 of 128 x 128 -- stored transposed, the bias gradient being the
+// column sums of the B operand.  Plain (the single-problem route): all heads as ONE problem with M = A * 256.
+as_wgrad_job wgrad1(const HeadStack& s, float* G, bool transposed) {
+    const HeadLayer& l = s.l[0];
+    as_wgrad_job j{};
+    if (transposed) {
+        j.g = gemm_tn(l.x, l.ldx, l.dz, l.ldz, l.dwf, l.K, l.K, l.N, s.R);
+        j.g.batch = s.A; j.g.a_batch = l.x_batch; j.g.b_batch = l.N; j.g.c_batch = (long)l.N * l.K;
+        j.colsum_b = G + l.b; j.colsum_b_batch = l.N; j.c_trans = 1;
+    } else {
+        j.g = gemm_tn(l.dz, l.ldz, l.x, l.ldx, l.dwf, l.K, s.A * l.N, l.K, s.R);
+        j.g.colsum = G + l.b;
+    }
+    return j;
+}
 
 // part: 0 = everything; 1 = layers 3 and 1 (+ the trunk's); 2 = layer 2 + the LayerNorm-affine unfold of all three.  The
 // model's backward issues part 1 beside the layer-1 recurrence and part 2 beside the layer-0 recurrence: each is one round
 // of <= 192 long-lived workgroups, so that the GRU input-gradient GEMM between the two recurrences finds the chip free
 // (a single launch of all four problems kept 184 CUs for ~240 us and that GEMM waited for CUs: 113 us instead of 52).
-int head_bwd_dw(const as_dims& d, const as_layout& L, const float* P, int64_t rows, float* G, float* ws, float* slab,
-                hipStream_t st, const float* dpre3_in = nullptr, int cu_budget = 0, long slab_floats = SLAB_FLOATS,
-                const TrunkJob* trunk = nullptr, int part = 0, int unfold_layers = -1) {
-    const int A = d.n_art, H = d.hidden, O = 2 * d.n_samp;
-    const HeadWs w = head_ws(d, rows);
-    const int R = (int)rows;
-    const long AD = (long)A * D, AO = (long)A * O;
-    // each weight-gradient GEMM also emits the bias gradient = column sums of its A operand
-    const float* dpre3 = dpre3_in ? dpre3_in : ws + w.dpre3;
-    // ---- several of them as ONE launch of 128 x 256 tiles + one reduce (wgrad_f32.hip, as_wgrad_multi).  Layer 1 is posed
-    // transposed (dW1'^T = xhat^T . dz1: 11 tiles of 128 x 256 like the others instead of 22 of 128 x 128): its result is
-    // stored transposed and its bias gradient is the column sum of the B operand.
-    as_wgrad_job jobs[4] = {};
-    as_gemm& g3 = jobs[0].g;
-    g3.A = dpre3; g3.a_i = 1; g3.a_k = AO; g3.a_batch = O; g3.M = O;
-    g3.B = ws + w.r2hat; g3.b_j = 1; g3.b_k = AD; g3.b_batch = D; g3.N = D;
-    g3.C = ws + w.dw3f; g3.ldc = D; g3.c_batch = (long)O * D; g3.K = R; g3.batch = A;
-    g3.colsum = G + L.b3; g3.colsum_batch = O;
-    as_gemm& g1 = jobs[1].g;
-    g1 = g3;
-    g1.A = ws + w.xhat; g1.a_k = H; g1.a_batch = 0; g1.M = H;
-    g1.B = ws + w.dz1;
-    g1.C = ws + w.dw1f; g1.ldc = H; g1.c_batch = (long)D * H;
-    g1.colsum = nullptr; g1.colsum_batch = 0;
-    jobs[1].colsum_b = G + L.b1; jobs[1].colsum_b_batch = D; jobs[1].c_trans = 1;
-    as_wgrad_job job2{};
-    as_gemm& g2 = job2.g;
-    g2 = g3;
-    g2.A = ws + w.dz2; g2.a_k = AD; g2.a_batch = D; g2.M = D;
-    g2.B = ws + w.r1hat;
-    g2.C = ws + w.dw2f; g2.c_batch = (long)D * D;
-    g2.colsum = G + L.b2; g2.colsum_batch = D;
-    const bool multi_ok = R % 32 == 0 && R >= 512;
+// trunk (optional): the trunk Linear's weight gradient dzlin^T . y1, which rides in the same launch at N = 2H = 256 (ArtSpeech).
+// From 512 rows on several problems go as ONE launch of 128 x 256 tiles + one reduce (as_wgrad_multi); what it declines goes
+// to as_gemm_f32 as the same as_gemm plus the two fields the multi launch ignores, slab and CU budget (run_split_k).
+int head_bwd_dw(const HeadStack& s, const float* P, float* G, float* slab, hipStream_t st, const float* dpre3_in = nullptr,
+                int cu_budget = 0, long slab_floats = SLAB_FLOATS, const as_gemm* trunk = nullptr, int part = 0,
+                int unfold_layers = -1) {
+    const bool multi_ok = s.R % 32 == 0 && s.R >= 512;
+    const as_wgrad_job job3 = wgrad(s, 2, dpre3_in ? dpre3_in : s.l[2].dz, G), job2 = wgrad(s, 1, s.l[1].dz, G);
+    auto multi = [&](const as_wgrad_job* jobs, int n, const char* phase, int* took) {
+        *took = 0;
+        if (!multi_ok) return 0;
+        AS_PROF(phase, st);
+        *took = as_wgrad_multi(jobs, n, slab, slab_floats, cu_budget, st, cu_budget > 0);   // (beside a recurrence: exact, see gemm_internal.h)
+        AS_REQUIRE(*took >= 0, *took, "head weight gradients: launch failed");
+        return 0;
+    };
+    int took;
     if (part == 0 || part == 1) {
+        as_wgrad_job jobs[4] = {job3, wgrad1(s, G, true)};
         int n = 2;
-        const bool trunk_rides = trunk && 2 * trunk->H == 256;
-        if (trunk_rides) {
-            as_gemm& gt = jobs[n].g;
-            gt.A = trunk->dz; gt.a_i = 1; gt.a_k = trunk->H; gt.M = trunk->H;
-            gt.B = trunk->y; gt.b_j = 1; gt.b_k = 2 * trunk->H; gt.N = 2 * trunk->H;
-            gt.C = trunk->dW; gt.ldc = 2 * trunk->H; gt.K = R; gt.batch = 1;
-            gt.colsum = trunk->db; gt.colsum_batch = 0;
-            ++n;
-        }
+        const bool trunk_rides = trunk && trunk->N == 256;
+        if (trunk_rides) jobs[n++].g = *trunk;
         if (part == 0) jobs[n++] = job2;
-        int took = 0;
-        if (multi_ok) {
-            AS_PROF(part == 0 ? "headb.dw_fused" : "headb.dw31", st);
-            took = as_wgrad_multi(jobs, n, slab, slab_floats, cu_budget, st, cu_budget > 0);   // (beside a recurrence: exact, see gemm_internal.h)
-            AS_REQUIRE(took >= 0, took, "head weight gradients: launch failed");
-        }
+        AS_TRY(multi(jobs, n, part == 0 ? "headb.dw_fused" : "headb.dw31", &took));
         if (!took) {
-            AS_STEP("headb.dw3", st, gemm_tn(dpre3, AO, ws + w.r2hat, AD, ws + w.dw3f, D, O, D, R, st, slab, G + L.b3, O, A, O, D, (long)O * D, 0, 0, 0, cu_budget));
-            AS_STEP("headb.dw1", st, gemm_tn(ws + w.dz1, AD, ws + w.xhat, H, ws + w.dw1f, H, (int)AD, H, R, st, slab, G + L.b1, 0, 1, 0, 0, 0, 0, 0, 0, cu_budget));
-            if (part == 0)
-                AS_STEP("headb.dw2", st, gemm_tn(ws + w.dz2, AD, ws + w.r1hat, AD, ws + w.dw2f, D, D, D, R, st, slab, G + L.b2, D, A, D, D, (long)D * D, 0, 0, 0, cu_budget));
+            AS_STEP("headb.dw3", st, run_split_k(job3.g, slab, st, cu_budget));
+            AS_STEP("headb.dw1", st, run_split_k(wgrad1(s, G, false).g, slab, st, cu_budget));
+            if (part == 0) AS_STEP("headb.dw2", st, run_split_k(job2.g, slab, st, cu_budget));
         }
-        if (trunk && !(took && trunk_rides))
-            AS_STEP("trunkb.dw", st, gemm_tn(trunk->dz, trunk->H, trunk->y, 2 * trunk->H, trunk->dW, 2 * trunk->H, trunk->H, 2 * trunk->H, R, st, slab, trunk->db, 0));
+        if (trunk && !(took && trunk_rides)) AS_STEP("trunkb.dw", st, run_split_k(*trunk, slab, st));
     } else {
-        int took = 0;
-        if (multi_ok) {
-            AS_PROF("headb.dw2", st);
-            took = as_wgrad_multi(&job2, 1, slab, slab_floats, cu_budget, st, cu_budget > 0);
-            AS_REQUIRE(took >= 0, took, "head weight gradients: launch failed");
-        }
-        if (!took)
-            AS_STEP("headb.dw2", st, gemm_tn(ws + w.dz2, AD, ws + w.r1hat, AD, ws + w.dw2f, D, D, D, R, st, slab, G + L.b2, D, A, D, D, (long)D * D, 0, 0, 0, cu_budget));
+        AS_TRY(multi(&job2, 1, "headb.dw2", &took));
+        if (!took) AS_STEP("headb.dw2", st, run_split_k(job2.g, slab, st, cu_budget));
     }
     // unfold the LayerNorm affines (bit 0: layer 3, bit 1: layer 2, bit 2: layer 1; default: all three once everything is
     // there, i.e. with part 0 or 2): one launch
@@ -464,14 +474,13 @@ int head_bwd_dw(const as_dims& d, const as_layout& L, const float* P, int64_t ro
     const float* dWf[3]; const float* dbf[3]; const float* Wp[3]; const float* gm[3]; const float* bt[3];
     float* dWo[3]; float* dgm[3]; float* dbt[3];
     int Rs[3], Ks[3], cnt = 0;
-    auto add = [&](int64_t dwf, int64_t b, int64_t wgt, int64_t g_, int64_t b_, int r, int k) {
-        dWf[cnt] = ws + dwf; dbf[cnt] = G + b; Wp[cnt] = P + wgt; gm[cnt] = P + g_; bt[cnt] = P + b_;
-        dWo[cnt] = G + wgt; dgm[cnt] = G + g_; dbt[cnt] = G + b_; Rs[cnt] = r; Ks[cnt] = k; ++cnt;
-    };
-    if (unfold_layers & 1) add(w.dw3f, L.b3, L.w3, L.ln3_g, L.ln3_b, O, D);
-    if (unfold_layers & 2) add(w.dw2f, L.b2, L.w2, L.ln2_g, L.ln2_b, D, D);
-    if (unfold_layers & 4) add(w.dw1f, L.b1, L.w1, L.ln1_g, L.ln1_b, D, H);
-    AS_STEP("headb.unfold", st, as_unfold3(dWf, dbf, Wp, gm, bt, dWo, dgm, dbt, Rs, Ks, A, st, cnt));
+    for (int i = 2; i >= 0; --i) {
+        if (!(unfold_layers & (1 << (2 - i)))) continue;
+        const HeadLayer& l = s.l[i];
+        dWf[cnt] = l.dwf; dbf[cnt] = G + l.b; Wp[cnt] = P + l.w; gm[cnt] = P + l.ln_g; bt[cnt] = P + l.ln_b;
+        dWo[cnt] = G + l.w; dgm[cnt] = G + l.ln_g; dbt[cnt] = G + l.ln_b; Rs[cnt] = l.N; Ks[cnt] = l.K; ++cnt;
+    }
+    AS_STEP("headb.unfold", st, as_unfold3(dWf, dbf, Wp, gm, bt, dWo, dgm, dbt, Rs, Ks, s.A, st, cnt));
     return 0;
 }
 
@@ -576,6 +585,21 @@ int fork_to(hipStream_t from, hipStream_t to, hipEvent_t ev) {
     return 0;
 }
 
+// C = act(A . B^T + bias) on dense operands (an nn.Linear forward: ld = row length)
+int linear_fwd(as_gemm g, const float* bias, int act, hipStream_t st) {
+    g.bias = bias; g.act = act;
+    return as_gemm_f32(&g, st);
+}
+// the GRU's dW_hh = dgh^T . h_prev with db_hh: B = y shifted by -1 (forward direction) / +1 (reverse) frame inside each
+// utterance of T frames; both directions as one batch of two
+as_gemm gru_dw_hh(const float* dgh, const float* y, float* dW, float* db, int H, int R, int T) {
+    as_gemm g = gemm_tn(dgh, 6 * H, y, 2 * H, dW, H, 3 * H, H, R);
+    g.batch = 2; g.a_batch = 3 * H; g.b_batch = H; g.c_batch = 3L * H * H;
+    g.b_kshift = -1; g.b_kT = T; g.b_kshift_batch = 2;
+    g.colsum = db; g.colsum_batch = 3 * H;
+    return g;
+}
+
 }  // namespace
 
 extern "C" void as_set_overlap(int32_t on) {
@@ -646,8 +670,9 @@ extern "C" int as_head_fwd(const as_dims* d, const as_layout* lay, const float* 
     (void)train;  // the forward keeps its activations in ws either way
     AS_TRY(check_dims(d, "as_head_fwd"));
     AS_REQUIRE(lay && params && x && out && ws && rows > 0 && rows < (1LL << 31), AS_ERR_BAD_ARG, "as_head_fwd: bad argument");
-    AS_TRY(head_fold(*d, *lay, params, rows, ws, (hipStream_t)stream));
-    return head_fwd_impl(*d, *lay, params, x, rows, out, ws, (hipStream_t)stream);
+    const HeadStack hs = head_stack(*d, *lay, rows, ws);
+    AS_TRY(head_fold(hs, params, (hipStream_t)stream));
+    return head_fwd_impl(hs, x, out, (hipStream_t)stream);
 }
 
 extern "C" int as_head_bwd(const as_dims* d, const as_layout* lay, const float* params, const float* out, const float* dout,
@@ -655,9 +680,9 @@ extern "C" int as_head_bwd(const as_dims* d, const as_layout* lay, const float* 
     AS_TRY(check_dims(d, "as_head_bwd"));
     AS_REQUIRE(lay && params && out && dout && dx && grads && ws && rows > 0 && rows < (1LL << 31), AS_ERR_BAD_ARG,
                "as_head_bwd: bad argument");
-    const HeadWs hw = head_ws(*d, rows);
-    AS_TRY(head_bwd_dx(*d, *lay, params, out, dout, rows, dx, nullptr, ws, (hipStream_t)stream));
-    return head_bwd_dw(*d, *lay, params, rows, grads, ws, ws + hw.slab, (hipStream_t)stream);
+    const HeadStack hs = head_stack(*d, *lay, rows, ws);
+    AS_TRY(head_bwd_dx(hs, out, dout, dx, nullptr, (hipStream_t)stream));
+    return head_bwd_dw(hs, params, grads, ws + hs.w.slab, (hipStream_t)stream);
 }
 
 extern "C" int as_artspeech_fwd(const as_dims* d, const float* P, const int64_t* tokens, int64_t tok_stride,
@@ -674,6 +699,7 @@ extern "C" int as_artspeech_fwd(const as_dims* d, const float* P, const int64_t*
     AS_TRY(as_artspeech_layout(d, &L));
     const ModelWs w = model_ws(*d, B, T);
     const int V = d->vocab, E = d->embed, H = d->hidden, R = B * T;
+    const HeadStack hs = head_stack(*d, L, R, ws + w.head);
     // the weight folds depend on the parameters only: run them on the side stream beside the recurrences
     StreamState* sd = d->simple ? nullptr : side_for(st);
     const bool late = opts && opts->fold_wait_event;
@@ -686,14 +712,14 @@ extern "C" int as_artspeech_fwd(const as_dims* d, const float* P, const int64_t*
         // the event above already stands behind that (the update was enqueued after it), and an event record on `st` is a
         // barrier packet in front of the step's first kernel: skipped then
         if (!late) AS_TRY(fork_to(st, sd->side, sd->fork[0]));
-        AS_TRY(head_fold(*d, L, P, R, ws + w.head, sd->side));
+        AS_TRY(head_fold(hs, P, sd->side));
         AS_TRY(as_count_bad_tokens(tokens, tok_stride, T, R, V, reinterpret_cast<int*>(ws + w.tokflag), sd->side));
         if (hipEventRecord(sd->join, sd->side) != hipSuccess) {
             as_set_error("as_artspeech_fwd: event record failed");
             return AS_ERR_BAD_ARG;
         }
     } else {
-        AS_TRY(head_fold(*d, L, P, R, ws + w.head, st));
+        AS_TRY(head_fold(hs, P, st));
         AS_TRY(as_count_bad_tokens(tokens, tok_stride, T, R, V, reinterpret_cast<int*>(ws + w.tokflag), st));
     }
     if (!d->simple) {
@@ -703,7 +729,7 @@ extern "C" int as_artspeech_fwd(const as_dims* d, const float* P, const int64_t*
         if ((long)V * E <= 16384 && ((size_t)4 * E + 64 * ((size_t)E + 1)) * sizeof(float) <= 65536)
             AS_STEP("gru.table0", st, as_token_table(P + L.embedding, P + L.w_ih[0], P + L.b_ih[0], V, 6 * H, E, ws + w.tab0, st));
         else
-            AS_STEP("gru.table0", st, gemm_nt(P + L.embedding, E, P + L.w_ih[0], E, ws + w.tab0, 6 * H, P + L.b_ih[0], V, 6 * H, E, 0, st));
+            AS_STEP("gru.table0", st, linear_fwd(gemm_nt(P + L.embedding, E, P + L.w_ih[0], E, ws + w.tab0, 6 * H, V, 6 * H, E), P + L.b_ih[0], 0, st));
         AS_STEP("gru.fwd_l0", st, as_gru_bidir_fwd_tokens(ws + w.tab0, tokens, tok_stride, V, P + L.w_hh[0], P + L.b_hh[0], lengths, B, T, H, ws + w.y0,
                                 train ? ws + w.g0 : nullptr, st));
         const float* l1_in = ws + w.y0;
@@ -715,19 +741,19 @@ extern "C" int as_artspeech_fwd(const as_dims* d, const float* P, const int64_t*
         // (split arithmetic measured here twice and not kept: the plane-fed kernel of the heads 39.5 vs 43 us + a 10-us plane
         // launch in front of the step's first kernel; both operands split in the kernel, gemm_s6.hip, 35.3 vs 33.1 us alone,
         // tools/bench_linear.py -- at 2.5 GFLOP the launch is bound by its prologue and fill, not by the matrix pipe)
-        AS_STEP("gru.xproj1", st, gemm_nt(l1_in, 2 * H, P + L.w_ih[1], 2 * H, ws + w.xp1, 6 * H, P + L.b_ih[1], R, 6 * H, 2 * H, 0, st));
+        AS_STEP("gru.xproj1", st, linear_fwd(gemm_nt(l1_in, 2 * H, P + L.w_ih[1], 2 * H, ws + w.xp1, 6 * H, R, 6 * H, 2 * H), P + L.b_ih[1], 0, st));
         AS_STEP("gru.fwd_l1", st, as_gru_bidir_fwd(ws + w.xp1, nullptr, 0, P + L.w_hh[1], P + L.b_hh[1], lengths, B, T, H, ws + w.y1,
                                 train ? ws + w.g1 : nullptr, st));
         // (trunk Linear: 10.5 us on the fp32 instruction, 14 - 23 us on either split kernel: 50 - 200 short workgroups)
-        AS_STEP("trunk.linear", st, gemm_nt(ws + w.y1, 2 * H, P + L.lin_w, 2 * H, ws + w.lin, H, P + L.lin_b, R, H, 2 * H, 1, st));
+        AS_STEP("trunk.linear", st, linear_fwd(gemm_nt(ws + w.y1, 2 * H, P + L.lin_w, 2 * H, ws + w.lin, H, R, H, 2 * H), P + L.lin_b, 1, st));
     } else if (pdrop > 0.f) {
         // SimpleArtSpeech in training mode (models.py:64,85): Dropout acts on the embedded frame, so every position has its
         // own mask and the token-table fold below does not apply: gather -> counter mask -> Linear + ReLU on all frames
         AS_TRY(as_gather_rows(P + L.embedding, tokens, tok_stride, T, R, E, ws + w.y0, st, V));
         AS_TRY(as_dropout(ws + w.y0, ws + w.y0, (long)R * E, pdrop, opts->dropout_seed, st));
-        AS_TRY(gemm_nt(ws + w.y0, E, P + L.lin_w, E, ws + w.lin, H, P + L.lin_b, R, H, E, 1, st));
+        AS_TRY(linear_fwd(gemm_nt(ws + w.y0, E, P + L.lin_w, E, ws + w.lin, H, R, H, E), P + L.lin_b, 1, st));
     } else {
-        AS_TRY(gemm_nt(P + L.embedding, E, P + L.lin_w, E, ws + w.tab0, H, P + L.lin_b, V, H, E, 1, st));
+        AS_TRY(linear_fwd(gemm_nt(P + L.embedding, E, P + L.lin_w, E, ws + w.tab0, H, V, H, E), P + L.lin_b, 1, st));
         AS_TRY(as_gather_rows(ws + w.tab0, tokens, tok_stride, T, R, H, ws + w.lin, st, V));
     }
     if (sd && hipStreamWaitEvent(st, sd->join, 0) != hipSuccess) {  // folded weights ready before head GEMM 1
@@ -738,9 +764,9 @@ extern "C" int as_artspeech_fwd(const as_dims* d, const float* P, const int64_t*
         AS_REQUIRE(train && lengths && opts->loss_out && opts->loss_dout && opts->loss_tgt_T >= T, AS_ERR_BAD_ARG,
                    "as_artspeech_fwd: fused criterion needs train, lengths, loss_out, loss_dout and loss_tgt_T >= T");
         const Criterion crit{opts->loss_targets, (long)opts->loss_tgt_T, lengths, T, opts->loss_scale, opts->loss_out, opts->loss_dout};
-        return head_fwd_impl(*d, L, P, ws + w.lin, R, out, ws + w.head, st, &crit);
+        return head_fwd_impl(hs, ws + w.lin, out, st, &crit);
     }
-    return head_fwd_impl(*d, L, P, ws + w.lin, R, out, ws + w.head, st);
+    return head_fwd_impl(hs, ws + w.lin, out, st);
 }
 
 extern "C" int as_artspeech_dw2(const as_dims* d, const float* P, int32_t B, int32_t T, float* G, float* ws, void* stream) {
@@ -749,10 +775,9 @@ extern "C" int as_artspeech_dw2(const as_dims* d, const float* P, int32_t B, int
     as_layout L;
     AS_TRY(as_artspeech_layout(d, &L));
     const ModelWs w = model_ws(*d, B, T);
-    const HeadWs hw = head_ws(*d, (int64_t)B * T);
-    float* hws = ws + w.head;
+    const HeadStack hs = head_stack(*d, L, (int64_t)B * T, ws + w.head);
     // beside a forward recurrence (2 B workgroups): 192 CUs to count on
-    return head_bwd_dw(*d, L, P, (int64_t)B * T, G, hws, hws + hw.slab2, (hipStream_t)stream, nullptr, 192, SLAB2_FLOATS, nullptr, 2, 2);
+    return head_bwd_dw(hs, P, G, hs.ws + hs.w.slab2, (hipStream_t)stream, nullptr, 192, SLAB2_FLOATS, nullptr, 2, 2);
 }
 
 extern "C" int as_artspeech_bwd(const as_dims* d, const float* P, const int64_t* tokens, int64_t tok_stride,
@@ -768,31 +793,36 @@ extern "C" int as_artspeech_bwd(const as_dims* d, const float* P, const int64_t*
     as_layout L;
     AS_TRY(as_artspeech_layout(d, &L));
     const ModelWs w = model_ws(*d, B, T);
-    const HeadWs hw = head_ws(*d, (int64_t)B * T);
     const int V = d->vocab, E = d->embed, H = d->hidden, R = B * T;
-    float* slab = ws + w.head + hw.slab;
-    float* slab2 = ws + w.head + hw.slab2;
-    float* dzlin = ws + w.head + hw.dxhat;  // reused: d(trunk pre-activation) [R][H]
-    float* hws = ws + w.head;
+    const HeadStack hs = head_stack(*d, L, R, ws + w.head);
+    float* slab = hs.ws + hs.w.slab;
+    float* slab2 = hs.ws + hs.w.slab2;
+    float* dzlin = hs.ws + hs.w.dxhat;  // reused: d(trunk pre-activation) [R][H]
     // heads: input-gradient chain (+ the trunk ReLU mask fused into the last normalize-backward)
     const bool presig = opts && opts->dout_presigmoid;
     const float* dpre3 = presig ? dout : nullptr;
-    AS_TRY(head_bwd_dx(*d, L, P, out, dout, R, dzlin, ws + w.lin, hws, st, presig));
+    AS_TRY(head_bwd_dx(hs, out, dout, dzlin, ws + w.lin, st, presig));
     AS_REQUIRE(!(d->simple && opts && opts->defer_dw2), AS_ERR_UNSUPPORTED, "as_artspeech_bwd: defer_dw2 is for the GRU model");
     if (d->simple) {
-        AS_TRY(head_bwd_dw(*d, L, P, R, G, hws, slab, st, dpre3));
+        AS_TRY(head_bwd_dw(hs, P, G, slab, st, dpre3));
         AS_TRY(record_heads_done(st, st));
         if (pdrop > 0.f) {  // per-frame path of the forward: Linear backward on all frames, mask regenerated from the seed
-            AS_TRY(gemm_tn(dzlin, H, ws + w.y0, E, G + L.lin_w, E, H, E, R, st, slab, G + L.lin_b, 0));
-            AS_TRY(gemm_nn(dzlin, H, P + L.lin_w, E, ws + w.dy0, E, R, E, H, st));
+            as_gemm dw = gemm_tn(dzlin, H, ws + w.y0, E, G + L.lin_w, E, H, E, R);
+            dw.colsum = G + L.lin_b;
+            AS_TRY(run_split_k(dw, slab, st));
+            const as_gemm gdx = gemm_nn(dzlin, H, P + L.lin_w, E, ws + w.dy0, E, R, E, H);
+            AS_TRY(as_gemm_f32(&gdx, st));
             AS_TRY(as_dropout(ws + w.dy0, ws + w.dy0, (long)R * E, pdrop, opts->dropout_seed, st));
             AS_TRY(as_token_segsum(ws + w.dy0, tokens, tok_stride, T, R, E, V, G + L.embedding, st, slab, SLAB_FLOATS));
             return 0;
         }
         // lin = gather(relu(Emb Wl^T + bl)); dzlin already carries the ReLU mask of the gathered rows
         AS_TRY(as_token_segsum(dzlin, tokens, tok_stride, T, R, H, V, ws + w.dtab0, st, slab, SLAB_FLOATS));
-        AS_TRY(gemm_tn(ws + w.dtab0, H, P + L.embedding, E, G + L.lin_w, E, H, E, V, st, slab, G + L.lin_b, 0));
-        AS_TRY(gemm_nn(ws + w.dtab0, H, P + L.lin_w, E, G + L.embedding, E, V, E, H, st));
+        as_gemm dw = gemm_tn(ws + w.dtab0, H, P + L.embedding, E, G + L.lin_w, E, H, E, V);
+        dw.colsum = G + L.lin_b;
+        AS_TRY(run_split_k(dw, slab, st));
+        const as_gemm demb = gemm_nn(ws + w.dtab0, H, P + L.lin_w, E, G + L.embedding, E, V, E, H);
+        AS_TRY(as_gemm_f32(&demb, st));
         return 0;
     }
     StreamState* sd = side_for(st);
@@ -801,7 +831,7 @@ extern "C" int as_artspeech_bwd(const as_dims* d, const float* P, const int64_t*
     // second side stream: the small hidden-to-hidden weight gradients (few workgroups, latency bound), so that they run
     // beside the head / input-projection ones instead of queueing behind them: -9 us per step
     hipStream_t s3 = (sd && sd->side2) ? sd->side2 : s2;
-    float* sl3 = (sd && sd->side2) ? ws + w.head + hw.slab3 : sl2;
+    float* sl3 = (sd && sd->side2) ? hs.ws + hs.w.slab3 : sl2;
     // every fork an event record on `st` while the per-phase timers are on (as_profile_enable): a timing event recorded
     // right behind an event-carrying dispatch reads ~20 us late, which would inflate the phase.
     hipStreamCaptureStatus cap_ = hipStreamCaptureStatusNone;   // inside a stream capture: ordinary event records (graph edges)
@@ -811,17 +841,18 @@ extern "C" int as_artspeech_bwd(const as_dims* d, const float* P, const int64_t*
     // dispatch (AsStopEventScope): no marker packet on `st` between it and the recurrence
     {
         AsStopEventScope fork0(sd && !plain_forks ? sd->fork[0] : nullptr);
-        AS_STEP("trunkb.dx", st, gemm_nn(dzlin, H, P + L.lin_w, 2 * H, ws + w.dy1, 2 * H, R, 2 * H, H, st));
+        const as_gemm gdx = gemm_nn(dzlin, H, P + L.lin_w, 2 * H, ws + w.dy1, 2 * H, R, 2 * H, H);
+        AS_STEP("trunkb.dx", st, as_gemm_f32(&gdx, st));
         if (sd) AS_TRY(fork_after(st, s2, sd->fork[0], plain_forks ? sd->fork[0] : fork0.take()));
     }
     AS_STEP("gru.bwd_l1", st, as_gru_bidir_bwd(ws + w.dy1, ws + w.y1, ws + w.g1, P + L.w_hh[1], lengths, B, T, H, ws + w.dgi1, ws + w.dgh1, st));
     const int side_cus = sd ? 192 : 0;  // the recurrence's 2 * B workgroups hold 64 CUs while the side stream works
-    const TrunkJob trunk{dzlin, ws + w.y1, G + L.lin_w, G + L.lin_b, H};
+    as_gemm trunk = gemm_tn(dzlin, H, ws + w.y1, 2 * H, G + L.lin_w, 2 * H, H, 2 * H, R);
+    trunk.colsum = G + L.lin_b;
     // with a side stream: layers 3, 1 and the trunk now, layer 2 + unfold beside the layer-0 recurrence (see head_bwd_dw)
     const bool defer = opts && opts->defer_dw2;   // layer 2's is computed later by as_artspeech_dw2()
     const bool two_parts = sd != nullptr || defer;
-    AS_TRY(head_bwd_dw(*d, L, P, R, G, hws, sl2, s2, dpre3, side_cus, sd ? SLAB2_FLOATS : SLAB_FLOATS, &trunk, two_parts ? 1 : 0,
-                       defer ? 5 : -1));
+    AS_TRY(head_bwd_dw(hs, P, G, sl2, s2, dpre3, side_cus, sd ? SLAB2_FLOATS : SLAB_FLOATS, &trunk, two_parts ? 1 : 0, defer ? 5 : -1));
     // [lin_w, total) of the flat gradient buffer is final from here on ([lin_w, ln2_g) with defer_dw2)
     if (!two_parts || defer) AS_TRY(record_heads_done(st, s2));
     // input gradient of GRU layer 1: [R][6H] . [6H][2H]
@@ -830,7 +861,7 @@ extern "C" int as_artspeech_bwd(const as_dims* d, const float* P, const int64_t*
     hipEvent_t fork1_left = nullptr;
     {
         AsStopEventScope fork1(fork1_armed ? sd->fork[1] : nullptr);   // fork 1 rides on this GEMM (see fork 0)
-        AS_STEP("grub.dx1", st, gemm_nn(ws + w.dgi1, 6 * H, P + L.w_ih[1], 2 * H, ws + w.dy0, 2 * H, R, 2 * H, 6 * H, st, 1, 0, 0, 0, slab));
+        AS_STEP("grub.dx1", st, run_split_k(gemm_nn(ws + w.dgi1, 6 * H, P + L.w_ih[1], 2 * H, ws + w.dy0, 2 * H, R, 2 * H, 6 * H), slab, st));
         fork1_left = fork1.take();
     }
     if (pdrop > 0.f)  // back through the inter-layer dropout: same mask, regenerated from the seed
@@ -861,13 +892,13 @@ extern "C" int as_artspeech_bwd(const as_dims* d, const float* P, const int64_t*
         if (sd && !plain_forks) fork2_left = fork2.take();
     }
     if (two_parts && !defer) {
-        AS_TRY(head_bwd_dw(*d, L, P, R, G, hws, sl2, s2, dpre3, side_cus, sd ? SLAB2_FLOATS : SLAB_FLOATS, nullptr, 2));
+        AS_TRY(head_bwd_dw(hs, P, G, sl2, s2, dpre3, side_cus, sd ? SLAB2_FLOATS : SLAB_FLOATS, nullptr, 2));
         AS_TRY(record_heads_done(st, s2));  // [lin_w, total) of the flat gradient buffer is final from here on
     }
-    AS_STEP("grub.dw_ih1", s2, gemm_tn(ws + w.dgi1, 6 * H, pdrop > 0.f ? ws + w.y0d : ws + w.y0, 2 * H, G + L.w_ih[1], 2 * H, 6 * H, 2 * H, R, s2, sl2, G + L.b_ih[1], 0));
-    // dW_hh = dgh^T . h_{prev}: y shifted by -1 (forward) / +1 (reverse) frame; both directions as one batch of two
-    AS_STEP("grub.dw_hh", s3, gemm_tn(ws + w.dgh1, 6 * H, ws + w.y1, 2 * H, G + L.w_hh[1], H, 3 * H, H, R, s3, sl3, G + L.b_hh[1], 3 * H, 2,
-                   3 * H, H, 3L * H * H, -1, T, 2));
+    as_gemm dw_ih1 = gemm_tn(ws + w.dgi1, 6 * H, pdrop > 0.f ? ws + w.y0d : ws + w.y0, 2 * H, G + L.w_ih[1], 2 * H, 6 * H, 2 * H, R);
+    dw_ih1.colsum = G + L.b_ih[1];
+    AS_STEP("grub.dw_ih1", s2, run_split_k(dw_ih1, sl2, s2));
+    AS_STEP("grub.dw_hh", s3, run_split_k(gru_dw_hh(ws + w.dgh1, ws + w.y1, G + L.w_hh[1], G + L.b_hh[1], H, R, T), sl3, s3));
     // ---- layer-0 gradients.  What follows the last recurrence is the step's tail, and a cross-stream wait costs ~10 us
     // each way on top of the work it guards (measured on the timeline): the LONGER of the two remaining jobs therefore
     // stays on the caller's stream, back to back with the recurrence, and the shorter one forks off.
@@ -880,8 +911,7 @@ extern "C" int as_artspeech_bwd(const as_dims* d, const float* P, const int64_t*
     hipStream_t s_hh = tok_sums ? st : s3, s_emb = tok_sums ? s3 : st;
     float* sl_hh = tok_sums ? slab : sl3;
     if (sd) AS_TRY(fork_after(st, s3, fork2_ev, fork2_left));
-    AS_STEP("grub.dw_hh", s_hh, gemm_tn(ws + w.dgh0, 6 * H, ws + w.y0, 2 * H, G + L.w_hh[0], H, 3 * H, H, R, s_hh, sl_hh, G + L.b_hh[0], 3 * H, 2,
-                   3 * H, H, 3L * H * H, -1, T, 2));
+    AS_STEP("grub.dw_hh", s_hh, run_split_k(gru_dw_hh(ws + w.dgh0, ws + w.y0, G + L.w_hh[0], G + L.b_hh[0], H, R, T), sl_hh, s_hh));
     // embedding + layer-0 input projection through the token table
     if (tok_sums)
         AS_STEP("grub.segsum", s_emb, as_sum_partials(ws + w.dgi0, (long)V * 6 * H, B, ws + w.dtab0, s_emb));
@@ -893,8 +923,10 @@ extern "C" int as_artspeech_bwd(const as_dims* d, const float* P, const int64_t*
     } else {
         // (only reached with s_emb == st or with the main slab free: token sums need V <= T, these need V > 128)
         float* sl_e = tok_sums ? sl3 : slab;
-        AS_STEP("grub.dw_ih0", s_emb, gemm_tn(ws + w.dtab0, 6 * H, P + L.embedding, E, G + L.w_ih[0], E, 6 * H, E, V, s_emb, sl_e, G + L.b_ih[0], 0));
-        AS_STEP("grub.demb", s_emb, gemm_nn(ws + w.dtab0, 6 * H, P + L.w_ih[0], E, G + L.embedding, E, V, E, 6 * H, s_emb, 1, 0, 0, 0, sl_e));
+        as_gemm dw_ih0 = gemm_tn(ws + w.dtab0, 6 * H, P + L.embedding, E, G + L.w_ih[0], E, 6 * H, E, V);
+        dw_ih0.colsum = G + L.b_ih[0];
+        AS_STEP("grub.dw_ih0", s_emb, run_split_k(dw_ih0, sl_e, s_emb));
+        AS_STEP("grub.demb", s_emb, run_split_k(gemm_nn(ws + w.dtab0, 6 * H, P + L.w_ih[0], E, G + L.embedding, E, V, E, 6 * H), sl_e, s_emb));
     }
     // join: `st` continues only after the side streams' work.  One wait on `st` (each costs the tail a few microseconds):
     // the second side stream first waits for the first one, then `st` waits for it alone.

@@ -1017,32 +1017,65 @@ long tile_list(K& k, int x) {
     return total;
 }
 
-// Tile list.  Two workgroups per CU = 512 slots; a launch of T equal tiles takes ceil(T / 512) rounds, and the head
-// layers' 1100 tiles of 64 rows were 3 rounds of which the last held 76 tiles (measured: 31 us of a 118 us launch with
-// 180 CUs idle).  So: as many 64-row tiles as fill whole rounds, dispatched first, then the remaining rows as 32-row
-// tiles (half the matrix work each), which pack the last round about half as high.
-template <bool B_KC, int EPI>
-int launch(const LinK& k, hipStream_t st) {
-    LinK kk = k;
-    constexpr int slots = 512;
-    const long units = (long)as_cdiv(k.M, 64) * k.batch;      // work in 64-row tiles
+// How many 64-row tiles per batch member fill whole rounds of `slots` resident workgroups.  A launch of T equal tiles takes
+// ceil(T / slots) rounds, and the head layers' 1100 tiles of 64 rows were 3 rounds of 512 of which the last held 76 tiles
+// (measured: 31 us of a 118 us launch with 180 CUs idle).  So: as many 64-row tiles as fill whole rounds, dispatched first,
+// then the remaining rows as 32-row tiles (half the matrix work each), which pack the last round about half as high.
+// short_64: what a launch of LESS than one round gets -- false: 32-row tiles only (they spread over more CUs), true: plain
+// 64-row tiles + a ragged end (the output layer: a 32-row tile loads the same W3' planes for half the rows).
+int whole_round_tiles(int M, int batch, int slots, bool short_64) {
+    const long units = (long)as_cdiv(M, 64) * batch;      // work in 64-row tiles
     const long rounds = units / slots;
-    int x = (int)(rounds * slots / k.batch);                    // 64-row tiles per head that fill whole rounds
-    if (x > k.M / 64 || k.tile_rows == 64) x = k.M / 64;
-    if (k.tile_rows == 32) x = 0;
-    const long total = tile_list(kk, x);
-    if (kk.Bp) {   // the products on the bf16 matrix instruction, B as planes (lin_s6_kernel)
-        hipLaunchKernelGGL((lin_s6_kernel<EPI>), dim3((unsigned)total), dim3(NT), 0, st, kk);
-        AS_LAUNCH_CHECK("as_lin_s6");
-        return 0;
-    }
-    hipLaunchKernelGGL((lin_f32_kernel<64, B_KC, EPI>), dim3((unsigned)total), dim3(NT), 0, st, kk);
-    AS_LAUNCH_CHECK("as_lin_f32");
-    return 0;
+    if (rounds == 0 && short_64) return M / 64;
+    const long x = rounds * slots / batch;
+    return x > M / 64 ? M / 64 : (int)x;
+}
+
+// B as bfloat16 planes (as_emit_planes) can feed a split-arithmetic kernel whose column tile is min_rows wide: the arithmetic
+// is on, K is whole 32-deep k-tiles, the image has the tile's rows, planes and batch members start 16-byte aligned, and a row
+// offset of A fits the kernels' 32-bit byte offsets.  Then the kernel argument gets them; else the exact fp32 kernel
+// (as_lin_try, as_lin_out_try) or no launch (as_lin_plain_s6).
+template <typename K, typename L>
+bool take_planes(K& k, const L* a, int min_rows) {
+    if (!a->Bp || as_matrix_arith() != AS_ARITH_BF16X6 || a->K % S6_BK || a->bp_rows < min_rows || !as_aligned16(a->Bp) ||
+        a->bp_plane % 8 || a->bp_batch % 8 || a->lda >= (1L << 23)) return false;
+    k.Bp = a->Bp; k.bp_plane = a->bp_plane; k.bp_batch = a->bp_batch; k.bp_rows = a->bp_rows;
+    return true;
 }
 
 unsigned long long* g_dbg = nullptr;
 long g_dbg_max = 0;
+
+// as_lin as the kernels' argument: every field but the planes (take_planes), the k-split and the tile list
+LinK lin_args(const as_lin* a) {
+    LinK k{};
+    k.A = a->A; k.lda = a->lda; k.a_batch = a->a_batch;
+    k.B = a->B; k.ldb = a->ldb; k.b_batch = a->b_batch;
+    k.C = a->C; k.ldc = a->ldc; k.c_batch = a->c_batch;
+    k.bias = a->bias; k.bias_batch = a->bias_batch;
+    k.M = a->M; k.N = a->N; k.K = a->K; k.ka_valid = a->ka_valid > 0 ? a->ka_valid : a->K; k.batch = a->batch; k.act = a->act;
+    k.tile_rows = a->tile_rows;
+    k.eps = 1e-5f;
+    k.dbg = g_dbg; k.dbg_max = g_dbg_max;
+    k.rstd = a->rstd; k.bits = a->bits;
+    k.xhat = a->xhat; k.ldx = a->ldx; k.x_batch = a->x_batch; k.rstd_in = a->rstd_in; k.bits_in = a->bits_in;
+    return k;
+}
+
+// Tile list for two workgroups per CU = 512 slots (whole_round_tiles), or what as_lin.tile_rows asks for
+template <bool B_KC, int EPI>
+int launch(const LinK& k, hipStream_t st) {
+    LinK kk = k;
+    int x = whole_round_tiles(k.M, k.batch, 512, false);
+    if (k.tile_rows == 64) x = k.M / 64;
+    if (k.tile_rows == 32) x = 0;
+    const long total = tile_list(kk, x);
+    // with B as planes the products run on the bf16 matrix instruction (lin_s6_kernel)
+    if (kk.Bp) hipLaunchKernelGGL((lin_s6_kernel<EPI>), dim3((unsigned)total), dim3(NT), 0, st, kk);
+    else hipLaunchKernelGGL((lin_f32_kernel<64, B_KC, EPI>), dim3((unsigned)total), dim3(NT), 0, st, kk);
+    AS_LAUNCH_CHECK(kk.Bp ? "as_lin_s6" : "as_lin_f32");
+    return 0;
+}
 
 }  // namespace
 
@@ -1060,23 +1093,9 @@ int as_lin_try(const as_lin* a, hipStream_t st) {
     if (a->epi != EPI_PLAIN && (a->N != BN || !a->C)) return 0;
     if (a->epi == EPI_PLAIN && a->N <= BN / 2) return 0;  // half of the 8 feature-side waves would multiply padding
     if ((long)as_cdiv(a->M, 64) * a->batch > (1L << 30)) return 0;
-    LinK k{};
-    k.A = a->A; k.lda = a->lda; k.a_batch = a->a_batch;
-    k.B = a->B; k.ldb = a->ldb; k.b_batch = a->b_batch;
-    k.C = a->C; k.ldc = a->ldc; k.c_batch = a->c_batch;
-    k.bias = a->bias; k.bias_batch = a->bias_batch;
-    k.M = a->M; k.N = a->N; k.K = a->K; k.ka_valid = a->ka_valid > 0 ? a->ka_valid : a->K; k.batch = a->batch; k.act = a->act;
-    k.tile_rows = a->tile_rows;
-    k.eps = 1e-5f;
-    k.dbg = g_dbg; k.dbg_max = g_dbg_max;
-    k.rstd = a->rstd; k.bits = a->bits;
-    k.xhat = a->xhat; k.ldx = a->ldx; k.x_batch = a->x_batch; k.rstd_in = a->rstd_in; k.bits_in = a->bits_in;
+    LinK k = lin_args(a);
     if (k.ka_valid % 4) return 0;
-    // B as bfloat16 planes (as_emit_planes) and the split arithmetic on: the bf16-MFMA kernel; else the exact fp32 one
-    if (a->Bp && as_matrix_arith() == AS_ARITH_BF16X6 && a->K % S6_BK == 0 && a->bp_rows >= BN && as_aligned16(a->Bp) &&
-        a->bp_plane % 8 == 0 && a->bp_batch % 8 == 0 && a->lda < (1L << 23)) {
-        k.Bp = a->Bp; k.bp_plane = a->bp_plane; k.bp_batch = a->bp_batch; k.bp_rows = a->bp_rows;
-    }
+    take_planes(k, a, BN);   // taken: the bf16-MFMA kernel; else the exact fp32 one
     if (a->epi == EPI_LNF) {
         if (!a->rstd || !a->bits || !a->b_kc) return 0;
         return launch<true, EPI_LNF>(k, st) == 0 ? 1 : -1;
@@ -1091,20 +1110,13 @@ int as_lin_try(const as_lin* a, hipStream_t st) {
 
 // see gemm_internal.h
 int as_lin_plain_s6(const as_lin* a, int ksplit, long c_split, hipStream_t st, int waves_per_simd) {
-    if (as_matrix_arith() != AS_ARITH_BF16X6 || !a->Bp) return 0;
-    if (a->epi != EPI_PLAIN || a->K % S6_BK || a->K < S6_BK || a->N > BN || a->N < 1 || a->M < 1 || a->batch < 1 || !a->C) return 0;
-    if (!as_aligned16(a->A) || a->lda % 4 || a->a_batch % 4 || a->lda >= (1L << 23)) return 0;
-    if (!as_aligned16(a->Bp) || a->bp_plane % 8 || a->bp_batch % 8) return 0;
     const int nw = a->N <= 128 ? 4 : 8;
-    if (a->bp_rows < nw * 32) return 0;
+    LinK k = lin_args(a);
+    if (!take_planes(k, a, nw * 32)) return 0;
+    if (a->epi != EPI_PLAIN || a->K < S6_BK || a->N > BN || a->N < 1 || a->M < 1 || a->batch < 1 || !a->C) return 0;
+    if (!as_aligned16(a->A) || a->lda % 4 || a->a_batch % 4) return 0;
     if (ksplit < 1) ksplit = 1;
     if (ksplit > 1 && (a->bias || a->act)) return 0;
-    LinK k{};
-    k.A = a->A; k.lda = a->lda; k.a_batch = a->a_batch;
-    k.Bp = a->Bp; k.bp_plane = a->bp_plane; k.bp_batch = a->bp_batch; k.bp_rows = a->bp_rows;
-    k.C = a->C; k.ldc = a->ldc; k.c_batch = a->c_batch;
-    k.bias = a->bias; k.bias_batch = a->bias_batch;
-    k.M = a->M; k.N = a->N; k.K = a->K; k.ka_valid = a->ka_valid > 0 ? a->ka_valid : a->K; k.batch = a->batch; k.act = a->act;
     if (k.ka_valid % 4) return 0;
     k.kchunk = (int)as_round_up(as_cdiv(a->K, ksplit), S6_BK);
     ksplit = as_cdiv(a->K, k.kchunk);
@@ -1136,35 +1148,21 @@ int as_lin_out_try(const as_lin_out* a, int* n_partials, hipStream_t st) {
     k.M = a->M; k.N = a->N; k.K = a->K; k.batch = a->batch;
     k.tgt = a->tgt; k.tgt_T = a->tgt_T; k.lengths = a->lengths; k.T = a->T; k.scale = a->scale; k.dout = a->dout; k.partial = a->partial;
     if (k.tgt && (!k.lengths || !k.dout || !k.partial || k.T < 1 || k.ldo != (long)k.batch * k.N || k.o_batch != k.N)) return 0;
-    // tile list as for the 256-column kernel: 64-row tiles that fill whole rounds of 4 x 256 slots, 32-row tiles over the rest.
+    // tile list as for the 256-column kernel, over rounds of 4 x 256 slots; less than one round: plain 64-row tiles.
     // The split-arithmetic kernel has LOUT_WPS = 3 workgroups of a CU resident, not 4, and keeps this list all the same: one
     // of 3 x 256 slots (759 + 682 tiles at 6400 frames x 11 heads instead of 1023 + 154) was measured 4 us slower, as slow as
     // the kernel with scratch -- a 32-row tile loads the same W3' planes for half the rows.  (Besides, the criterion's partial
     // sums are per tile: with the list unchanged the loss is added in the order it always was.)
-    constexpr int slots = 1024;
-    const long units = (long)as_cdiv(k.M, 64) * k.batch;
-    const long rounds = units / slots;
-    int x = (int)(rounds * slots / k.batch);
-    if (x > k.M / 64) x = k.M / 64;
-    if (rounds == 0) x = k.M / 64;                       // less than one round: plain 64-row tiles (+ a ragged end)
-    const long total = tile_list(k, x);
+    const long total = tile_list(k, whole_round_tiles(k.M, k.batch, 1024, true));
     if (k.tgt && total > a->partial_capacity) return 0;
     if (k.tgt && a->loss) {
         k.counter = as_arrival_counter(st);
         k.loss = k.counter ? a->loss : nullptr;
     }
-    const int left = k.counter ? 0 : (int)total;   // partials that still await as_loss_final
-    if (a->Bp && as_matrix_arith() == AS_ARITH_BF16X6 && a->K % S6_BK == 0 && a->bp_rows >= ON && as_aligned16(a->Bp) &&
-        a->bp_plane % 8 == 0 && a->bp_batch % 8 == 0 && a->lda < (1L << 23)) {
-        k.Bp = a->Bp; k.bp_plane = a->bp_plane; k.bp_batch = a->bp_batch; k.bp_rows = a->bp_rows;
-        hipLaunchKernelGGL(lin_out_s6_kernel, dim3((unsigned)total), dim3(256), 0, st, k);
-        AS_LAUNCH_CHECK("as_lin_out_s6");
-        if (n_partials) *n_partials = left;
-        return 1;
-    }
-    hipLaunchKernelGGL(lin_out_kernel, dim3((unsigned)total), dim3(NT), 0, st, k);
-    AS_LAUNCH_CHECK("as_lin_out");
-    if (n_partials) *n_partials = left;
+    if (n_partials) *n_partials = k.counter ? 0 : (int)total;   // partials that still await as_loss_final
+    if (take_planes(k, a, ON)) hipLaunchKernelGGL(lin_out_s6_kernel, dim3((unsigned)total), dim3(256), 0, st, k);
+    else hipLaunchKernelGGL(lin_out_kernel, dim3((unsigned)total), dim3(NT), 0, st, k);
+    AS_LAUNCH_CHECK(k.Bp ? "as_lin_out_s6" : "as_lin_out");
     return 1;
 }
 

@@ -840,6 +840,17 @@ def test_head_stack_any_input_width_vs_oracle(dev, matrix_arith, H, rows, mode):
     _head_stack_vs_oracle(dev, H, rows, matrix_arith, mode, mode)
 
 
+@pytest.mark.parametrize("mode", [1, 0])
+@pytest.mark.parametrize("rows", [512, 37])
+@pytest.mark.parametrize("N", [1, 3, 33, 64, 70])
+def test_head_stack_any_output_width_vs_oracle(dev, matrix_arith, N, rows, mode):
+    """The head stack at output widths 2N that leave the output layer's own kernel (4 <= 2N <= 128: N = 3, 33, 64) for the
+    256-column kernel (N = 70) or the general GEMM (N = 1), and whose input-gradient kernel (2N % 4 == 0: N = 64, 70) gives
+    way to the general GEMM + row kernel (N = 1, 3, 33); 512 rows are the fewest that take the multi-problem weight
+    gradient, 37 take the single ones.  Bounds as in the other head-stack tests."""
+    _head_stack_vs_oracle(dev, 128, rows, matrix_arith, mode, mode, N=N)
+
+
 @pytest.mark.parametrize("fwd_mode,bwd_mode", [(0, 1), (1, 0)])
 @pytest.mark.parametrize("H", [128, 50])
 def test_head_stack_arithmetic_switched_between_forward_and_backward(dev, matrix_arith, H, fwd_mode, bwd_mode):
