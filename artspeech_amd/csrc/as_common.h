@@ -43,6 +43,39 @@ static inline bool as_aligned16(const void* p) { return (reinterpret_cast<uintpt
 // an integer as a type: hands a compile-time constant to a generic lambda (decltype(arg)::value)
 template <int N> struct IC { static constexpr int value = N; };
 
+// A run-time number as a template argument: each helper calls the generic lambda f with the IC<N> it picked, once, and f
+// launches the kernel instantiated for decltype(arg)::value.  A dispatch must not instantiate a kernel that is never
+// launched: f is instantiated for every N of a list, so a choice with three outcomes is ONE list of three, not two nested flags.
+// (The lists are walked by recursion, not by a fold expression: hipcc emitted the kernels of a folded list in reverse order, and
+// the code objects are compared with those of the ladders these helpers replaced.)
+// First fit over an ascending list: f(IC<N>) for the first N >= v, for the last N otherwise (the caller has checked the
+// range); f's result, void included
+template <int N, int... Rest, typename F>
+auto as_up_to(int v, F&& f) {
+    if constexpr (sizeof...(Rest) == 0) return f(IC<N>{});
+    else if (v <= N) return f(IC<N>{});
+    else return as_up_to<Rest...>(v, f);
+}
+// Exact match: v in the list: *rc = f(IC<v>), true; otherwise f is not called, false
+template <int N, int... Rest, typename F>
+auto as_exactly(int v, int* rc, F&& f) {
+    if (v == N) return *rc = f(IC<N>{}), true;
+    if constexpr (sizeof...(Rest) > 0) return as_exactly<Rest...>(v, rc, f);
+    else return false;
+}
+// A flag: f(IC<1>) or f(IC<0>); f's result
+template <typename F>
+auto as_flag(bool on, F&& f) {
+    if (on) return f(IC<1>{});
+    return f(IC<0>{});
+}
+
+// grid of a grid-stride element-wise kernel with 256 threads: a workgroup per 256 elements, at least one, at most 2048
+static inline int as_ew_grid(long n) {
+    const long b = (n + 255) / 256;
+    return (int)(b < 1 ? 1 : (b > 2048 ? 2048 : b));
+}
+
 #ifndef AS_HOST_ONLY
 // optional per-phase timing (prof.hip); a no-op unless as_profile_enable(1)
 struct AsProfScope {

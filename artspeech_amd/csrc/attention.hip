@@ -532,17 +532,6 @@ int launch_attn_ds_causal(const AttnDsK& k, long Z, hipStream_t st) {
     return 0;
 }
 
-template <int DH>
-int launch_attn_ds_nb(const AttnDsK& k, long Z, hipStream_t st) {
-    const int nb = (k.Tk + 31) / 32;
-    if (nb <= 1) return launch_attn_ds<DH, 1>(k, Z, st);
-    if (nb <= 2) return launch_attn_ds<DH, 2>(k, Z, st);
-    if (nb <= 4) return launch_attn_ds<DH, 4>(k, Z, st);
-    if (nb <= 6) return launch_attn_ds<DH, 6>(k, Z, st);
-    if (nb <= 7) return launch_attn_ds<DH, 7>(k, Z, st);
-    return launch_attn_ds<DH, 8>(k, Z, st);
-}
-
 // softmax backward on key-major tensors, two launches:
 //  (1) D[z][q] = sum_c dctx[q][c] ctx[q][c] over the head's columns: a quarter-wave per query row (16 lanes x float4 = 64
 //      floats), consecutive quarter-waves on consecutive heads of the same row -> a wave reads one contiguous 1 KB row;
@@ -623,15 +612,17 @@ int launch_attn(const AttnK& k, long Z, hipStream_t st) {
     return 0;
 }
 
-template <int DH>
-int launch_attn_nb(const AttnK& k, long Z, hipStream_t st) {
-    const int nb = (k.Tk + 31) / 32;
-    if (nb <= 1) return launch_attn<DH, 1>(k, Z, st);
-    if (nb <= 2) return launch_attn<DH, 2>(k, Z, st);
-    if (nb <= 4) return launch_attn<DH, 4>(k, Z, st);
-    if (nb <= 6) return launch_attn<DH, 6>(k, Z, st);
-    if (nb <= 7) return launch_attn<DH, 7>(k, Z, st);
-    return launch_attn<DH, 8>(k, Z, st);
+// The kernels' template arguments from the run-time shape: f(IC<head width>) over 64 / 32 / 16 (as_attention_supported admits
+// no other), and f(IC<head width>, IC<NB>) with the smallest NB of 1, 2, 4, 6, 7, 8 blocks of 32 keys that holds Tk <= 256
+template <typename F>
+int attn_with_width(int dh, F&& f) {
+    int rc = AS_ERR_UNSUPPORTED;
+    as_exactly<64, 32, 16>(dh, &rc, f);
+    return rc;
+}
+template <typename F>
+int attn_with_shape(int dh, int Tk, F&& f) {
+    return attn_with_width(dh, [&](auto w) { return as_up_to<1, 2, 4, 6, 7, 8>(as_cdiv(Tk, 32), [&](auto nb) { return f(w, nb); }); });
 }
 
 }  // namespace
@@ -657,10 +648,7 @@ static int attention_fwd(const float* Q, const float* K, const float* V, const f
     k.causal = causal && attn_mask_t != nullptr;
     const long Z = (long)G * B * heads;
     hipStream_t st = (hipStream_t)stream;
-    const int dh = d / heads;
-    if (dh == 64) AS_TRY(launch_attn_nb<64>(k, Z, st));
-    else if (dh == 32) AS_TRY(launch_attn_nb<32>(k, Z, st));
-    else AS_TRY(launch_attn_nb<16>(k, Z, st));
+    AS_TRY(attn_with_shape(d / heads, Tk, [&](auto w, auto nb) { return launch_attn<decltype(w)::value, decltype(nb)::value>(k, Z, st); }));
     AS_LAUNCH_CHECK("as_attention_fwd");
     return 0;
 }
@@ -719,14 +707,10 @@ static int attention_bwd_ds(const float* V, const float* dctx, const float* ctx,
     k.tp = (T + 31) / 32 * 32;
     const long Z = (long)G * B * heads;
     hipStream_t st = (hipStream_t)stream;
-    const int dh = d / heads;
-    if (causal && T <= 256 && Tk <= 256) {
-        if (dh == 64) AS_TRY(launch_attn_ds_causal<64>(k, Z, st));
-        else if (dh == 32) AS_TRY(launch_attn_ds_causal<32>(k, Z, st));
-        else AS_TRY(launch_attn_ds_causal<16>(k, Z, st));
-    } else if (dh == 64) AS_TRY(launch_attn_ds_nb<64>(k, Z, st));
-    else if (dh == 32) AS_TRY(launch_attn_ds_nb<32>(k, Z, st));
-    else AS_TRY(launch_attn_ds_nb<16>(k, Z, st));
+    if (causal && T <= 256 && Tk <= 256)
+        AS_TRY(attn_with_width(d / heads, [&](auto w) { return launch_attn_ds_causal<decltype(w)::value>(k, Z, st); }));
+    else
+        AS_TRY(attn_with_shape(d / heads, Tk, [&](auto w, auto nb) { return launch_attn_ds<decltype(w)::value, decltype(nb)::value>(k, Z, st); }));
     AS_LAUNCH_CHECK("as_attention_bwd_ds");
     return 0;
 }

@@ -495,18 +495,14 @@ extern "C" int as_conv3x3_stem(const float* x, int64_t sb, int64_t sc, int64_t s
     AS_REQUIRE(x && w && bias && y && B > 0 && D > 0 && T > 0 && Cin > 0, AS_ERR_BAD_ARG, "as_conv3x3_stem: bad argument");
     const long P = (long)B * D * T;
     hipStream_t s = (hipStream_t)stream;
-#define AS_STEM(CIN)                                                                                                              \
-    hipLaunchKernelGGL(conv3x3_stem_kernel<CIN>, dim3(as_cdiv(P, 256)), dim3(256), 0, s, x, w, bias, voicing, y, B, D, T, (long)sb, \
-                       (long)sc, (long)sd, (long)st)
-    switch (Cin) {
-        case 1: AS_STEM(1); break;
-        case 2: AS_STEM(2); break;
-        case 3: AS_STEM(3); break;
-        default:
-            hipLaunchKernelGGL(conv3x3_small_kernel, dim3(as_cdiv(P * CO, 256)), dim3(256), 0, s, x, w, bias, voicing, y, B, D, T, Cin,
+    int rc = 0;
+    if (!as_exactly<1, 2, 3>(Cin, &rc, [&](auto cin) {
+            hipLaunchKernelGGL(conv3x3_stem_kernel<decltype(cin)::value>, dim3(as_cdiv(P, 256)), dim3(256), 0, s, x, w, bias, voicing, y, B, D, T,
                                (long)sb, (long)sc, (long)sd, (long)st);
-    }
-#undef AS_STEM
+            return 0;
+        }))
+        hipLaunchKernelGGL(conv3x3_small_kernel, dim3(as_cdiv(P * CO, 256)), dim3(256), 0, s, x, w, bias, voicing, y, B, D, T, Cin, (long)sb,
+                           (long)sc, (long)sd, (long)st);
     AS_LAUNCH_CHECK("as_conv3x3_stem");
     return 0;
 }
@@ -528,9 +524,7 @@ extern "C" int as_ln_feat_gelu(const float* x, const float* gamma, const float* 
 
 extern "C" int as_gelu(const float* x, float* y, int64_t n, void* stream) {
     AS_REQUIRE(x && y && n > 0, AS_ERR_BAD_ARG, "as_gelu: bad argument");
-    long blocks = (n + 255) / 256;
-    if (blocks > 2048) blocks = 2048;
-    hipLaunchKernelGGL(gelu_kernel, dim3((int)blocks), dim3(256), 0, (hipStream_t)stream, x, y, (long)n);
+    hipLaunchKernelGGL(gelu_kernel, dim3(as_ew_grid(n)), dim3(256), 0, (hipStream_t)stream, x, y, (long)n);
     AS_LAUNCH_CHECK("as_gelu");
     return 0;
 }
@@ -556,24 +550,17 @@ extern "C" int as_conv3x3_stem_bwd(const float* dy, const float* w, float* dx, i
     const long blocks = as_cdiv(P, 8);
     const dim3 grid((unsigned)(blocks < 16384 ? blocks : 16384));
     hipStream_t s = (hipStream_t)stream;
-#define AS_STEM_BWD(CIN) \
-    hipLaunchKernelGGL(conv3x3_stem_bwd_kernel<CIN>, grid, dim3(256), 0, s, dy, w, dx, B, D, T, (long)sb, (long)sc, (long)sd, (long)st)
-    switch (Cin) {
-        case 1: AS_STEM_BWD(1); break;
-        case 2: AS_STEM_BWD(2); break;
-        case 3: AS_STEM_BWD(3); break;
-        default: AS_STEM_BWD(4);
-    }
-#undef AS_STEM_BWD
+    as_up_to<1, 2, 3, 4>(Cin, [&](auto cin) {
+        hipLaunchKernelGGL(conv3x3_stem_bwd_kernel<decltype(cin)::value>, grid, dim3(256), 0, s, dy, w, dx, B, D, T, (long)sb, (long)sc, (long)sd,
+                           (long)st);
+    });
     AS_LAUNCH_CHECK("as_conv3x3_stem_bwd");
     return 0;
 }
 
 extern "C" int as_gelu_bwd(const float* dy, const float* x, const float* scale, float* dx, int64_t n, int32_t row_len, void* stream) {
     AS_REQUIRE(dy && x && dx && n > 0 && (!scale || row_len > 0), AS_ERR_BAD_ARG, "as_gelu_bwd: bad argument");
-    long blocks = (n + 255) / 256;
-    if (blocks > 2048) blocks = 2048;
-    hipLaunchKernelGGL(gelu_bwd_kernel, dim3((int)blocks), dim3(256), 0, (hipStream_t)stream, dy, x, scale, dx, (long)n, row_len);
+    hipLaunchKernelGGL(gelu_bwd_kernel, dim3(as_ew_grid(n)), dim3(256), 0, (hipStream_t)stream, dy, x, scale, dx, (long)n, row_len);
     AS_LAUNCH_CHECK("as_gelu_bwd");
     return 0;
 }

@@ -460,11 +460,6 @@ __global__ __launch_bounds__(256) void grid_intersect_kernel(const double* __res
     p_ext[2 * item] = oe[0]; p_ext[2 * item + 1] = oe[1];
 }
 
-inline int ew_grid(long n) {
-    long b = (n + 255) / 256;
-    return (int)(b < 1 ? 1 : (b > 2048 ? 2048 : b));
-}
-
 
 // ---------------------------------------------------------------- Pearson correlation over time (root metrics.py:9-35)
 // One thread per (utterance, articulator, plane, point) column; consecutive threads read consecutive floats of a frame's
@@ -506,7 +501,7 @@ extern "C" int as_euclid_fwd(const float* out, const float* tgt, int64_t frames,
                              void* stream) {
     AS_REQUIRE(out && tgt && dist && frames > 0 && A > 0 && N > 0, AS_ERR_BAD_ARG, "as_euclid_fwd: bad argument");
     const long points = (long)frames * A * N;
-    hipLaunchKernelGGL(euclid_fwd_kernel, dim3(ew_grid(points)), dim3(256), 0, (hipStream_t)stream, out, tgt, points, N, dist);
+    hipLaunchKernelGGL(euclid_fwd_kernel, dim3(as_ew_grid(points)), dim3(256), 0, (hipStream_t)stream, out, tgt, points, N, dist);
     AS_LAUNCH_CHECK("as_euclid_fwd");
     return 0;
 }
@@ -515,7 +510,7 @@ extern "C" int as_euclid_bwd(const float* out, const float* tgt, const float* dd
                              float* dout, void* stream) {
     AS_REQUIRE(out && tgt && ddist && dout && frames > 0 && A > 0 && N > 0, AS_ERR_BAD_ARG, "as_euclid_bwd: bad argument");
     const long points = (long)frames * A * N;
-    hipLaunchKernelGGL(euclid_bwd_kernel, dim3(ew_grid(points)), dim3(256), 0, (hipStream_t)stream, out, tgt, ddist, points, N, dout);
+    hipLaunchKernelGGL(euclid_bwd_kernel, dim3(as_ew_grid(points)), dim3(256), 0, (hipStream_t)stream, out, tgt, ddist, points, N, dout);
     AS_LAUNCH_CHECK("as_euclid_bwd");
     return 0;
 }
@@ -537,7 +532,7 @@ int euclid_masked_launch(const char* who, const float* out, const float* tgt, in
     AS_REQUIRE(B > 0 && T > 0 && A > 0 && N > 0 && tgt_T >= T, AS_ERR_BAD_ARG, "%s: B=%d T=%d A=%d N=%d tgt_T=%ld", who, B, T, A, N,
                (long)tgt_T);
     const long points = (long)B * T * A * N;
-    int blocks = ew_grid(points);
+    int blocks = as_ew_grid(points);
     if (blocks > LOSS_BLOCKS) blocks = LOSS_BLOCKS;
     hipStream_t st = (hipStream_t)stream;
     hipLaunchKernelGGL(euclid_masked_kernel<PRESIG>, dim3(blocks), dim3(256), 0, st, out, tgt, (long)tgt_T, lengths, T, A, N, points,

@@ -296,16 +296,10 @@ extern "C" int as_edit_distance(const int32_t* pred, int32_t P_max, const int32_
     hipStream_t st = (hipStream_t)stream;
     const dim3 grid(as_cdiv(B, 4)), block(256);
     const int chunks = L_max / 64 + 1;   // columns 0 .. L_max
-#define RE_ED(KC)                                                                                                              \
-    hipLaunchKernelGGL((re_edit_distance_kernel<KC>), grid, block, 0, st, pred, P_max, pred_counts, target, L_max, target_counts, B, \
-                       class_map, n_map, dist)
-    if (chunks <= 1) RE_ED(1);
-    else if (chunks <= 2) RE_ED(2);
-    else if (chunks <= 4) RE_ED(4);
-    else if (chunks <= 8) RE_ED(8);
-    else if (chunks <= 16) RE_ED(16);
-    else RE_ED(32);
-#undef RE_ED
+    as_up_to<1, 2, 4, 8, 16, 32>(chunks, [&](auto kc) {
+        hipLaunchKernelGGL((re_edit_distance_kernel<decltype(kc)::value>), grid, block, 0, st, pred, P_max, pred_counts, target, L_max,
+                           target_counts, B, class_map, n_map, dist);
+    });
     AS_LAUNCH_CHECK("as_edit_distance");
     return 0;
 }

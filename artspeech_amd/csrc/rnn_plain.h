@@ -77,17 +77,11 @@ static inline int rnn_plain_lds(const char* name, int H, int floats_per_unit, si
 // *rc, true.  false: not a register-resident size, f was not called and the caller takes its plain kernel.
 template <typename F>
 int rnn_with_flags(bool a, bool b, F&& f) {
-    if (a) return b ? f(IC<1>{}, IC<1>{}) : f(IC<1>{}, IC<0>{});
-    return b ? f(IC<0>{}, IC<1>{}) : f(IC<0>{}, IC<0>{});
+    return as_flag(a, [&](auto fa) { return as_flag(b, [&](auto fb) { return f(fa, fb); }); });
 }
 template <typename F>
 bool rnn_resident(int H, int* rc, F&& f) {
-    switch (H) {
-        case 32: *rc = f(IC<32>{}); return true;
-        case 64: *rc = f(IC<64>{}); return true;
-        case 128: *rc = f(IC<128>{}); return true;
-        default: return false;
-    }
+    return as_exactly<32, 64, 128>(H, rc, f);
 }
 template <typename F>
 bool rnn_resident(int H, bool a, bool b, int* rc, F&& f) {

@@ -62,12 +62,21 @@ __global__ __launch_bounds__(256) void normalize_fwd_kernel(const float* __restr
     }
 }
 
+// A lane's index of its element c in a row of D: lane + 64 c, or an index inside the row where that lies beyond it (the load
+// is branch-free, the value unused).  WHOLE: D is a multiple of 64, so element c is either in the row for the whole wave or
+// for none of it: the index is lane + (a wave-uniform 64 c or 0) -- ONE address VGPR for all the loads instead of a clamped
+// index per element
+template <bool WHOLE>
+__device__ __forceinline__ int row_index(int lane, int c, int D) {
+    const int i = lane + 64 * c;
+    return WHOLE ? lane + (64 * c < D ? 64 * c : 0) : (i < D ? i : D - 1);
+}
+
 // ---- dx = rstd * (dy - mean(dy) - xhat * mean(dy * xhat)) * (relu_src > 0) ------------------------
 // dy and dx may alias (in-place): a lane reads all its elements before it writes any.
 // MASKED = false: no ReLU mask operand (no registers for it: 88 instead of 132 live values per lane at MW = 44, one wave per
 // SIMD became three)
-// WHOLE: D is a multiple of 64, so a lane's element c is either in the row for the whole wave or for none of it: the index
-// is lane + (a wave-uniform 64 c or 0) -- ONE address VGPR for all the loads instead of a clamped index per element
+// WHOLE: D % 64 == 0 (row_index)
 template <int MW, bool MASKED, bool WHOLE>
 __global__ __launch_bounds__(256) void normalize_bwd_kernel(const float* dy, const float* __restrict__ xhat,
                                                             const float* __restrict__ rstd,
@@ -82,8 +91,7 @@ __global__ __launch_bounds__(256) void normalize_bwd_kernel(const float* dy, con
     float g[MW], h[MW], m[MASKED ? MW : 1];
 #pragma unroll
     for (int c = 0; c < MW; ++c) {  // branch-free clamped loads: everything in flight together
-        const int i = lane + 64 * c;
-        const int ic = WHOLE ? lane + (64 * c < D ? 64 * c : 0) : (i < D ? i : D - 1);
+        const int ic = row_index<WHOLE>(lane, c, D);
         g[c] = dyr[ic];
         h[c] = xr[ic];
         if (MASKED) m[c] = 1.f;
@@ -92,8 +100,7 @@ __global__ __launch_bounds__(256) void normalize_bwd_kernel(const float* dy, con
     for (int sl = 1; sl < n_slab; ++sl) {
 #pragma unroll
         for (int c = 0; c < MW; ++c) {
-            const int i = lane + 64 * c;
-            const int ic = WHOLE ? lane + (64 * c < D ? 64 * c : 0) : (i < D ? i : D - 1);
+            const int ic = row_index<WHOLE>(lane, c, D);
             g[c] += dyr[sl * slab_stride + ic];
         }
     }
@@ -610,7 +617,7 @@ __global__ __launch_bounds__(256) void dropout_kernel(const float* x, float* y, 
 // ---- LayerNorm with optional residual input and grouped affine ------------------------------------
 // one wave per row, NW = ceil(D / 64) values per lane (template: rows are 20 .. 2816 wide in the models); branch-free
 // clamped loads so that all of a lane's loads are in flight together.
-template <int NW, bool AFFINE, bool WHOLE = false>   // WHOLE: D % 64 == 0, one address VGPR for all loads (see normalize_bwd_kernel)
+template <int NW, bool AFFINE, bool WHOLE = false>   // WHOLE: D % 64 == 0, one address VGPR for all loads (row_index)
 __global__ __launch_bounds__(256) void layernorm_fwd_kernel(const float* __restrict__ x, const float* __restrict__ res,
                                                             const float* __restrict__ gamma, const float* __restrict__ beta,
                                                             float* __restrict__ y, float* __restrict__ xhat,
@@ -629,8 +636,7 @@ __global__ __launch_bounds__(256) void layernorm_fwd_kernel(const float* __restr
     float v[NW], ga[AFFINE ? NW : 1], be[AFFINE ? NW : 1];   // (affine-free: no registers for the parameters)
 #pragma unroll
     for (int c = 0; c < NW; ++c) {
-        const int i = lane + 64 * c;
-        const int ic = WHOLE ? lane + (64 * c < D ? 64 * c : 0) : (i < D ? i : D - 1);
+        const int ic = row_index<WHOLE>(lane, c, D);
         long ro = ic;
         if (res_block > 0) {
             // block index of feature ic = lane + 64 c: wave-uniform c / (res_block / 64) when the blocks are whole multiples of the wave
@@ -840,21 +846,19 @@ __global__ __launch_bounds__(256) void row_scale_kernel(const float* __restrict_
     for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += stride) dst[i] = a[i] * rs[i / row_len];
 }
 
-inline int ew_grid(long n) {
-    long b = (n + 255) / 256;
-    return (int)(b < 1 ? 1 : (b > 2048 ? 2048 : b));
+// a one-wave-per-row kernel over `rows` rows: four rows per workgroup of 256 threads
+template <typename K, typename... A>
+inline void launch_rows(K kernel, long rows, hipStream_t st, A... args) {
+    hipLaunchKernelGGL(kernel, dim3(as_cdiv(rows, 4)), dim3(256), 0, st, args...);
 }
 
 }  // namespace
 
 int as_normalize_fwd(const float* x, float* xhat, float* rstd, long rows, int D, hipStream_t st, unsigned long long* pos_bits) {
     AS_REQUIRE(D > 0 && D <= 64 * MAXC, AS_ERR_UNSUPPORTED, "normalize: row length %d > %d", D, 64 * MAXC);
-#define AS_NORM_FWD(NW) hipLaunchKernelGGL(normalize_fwd_kernel<NW>, dim3(as_cdiv(rows, 4)), dim3(256), 0, st, x, xhat, rstd, rows, D, 1e-5f, pos_bits)
-    if (D <= 64) AS_NORM_FWD(1);
-    else if (D <= 128) AS_NORM_FWD(2);
-    else if (D <= 256) AS_NORM_FWD(4);
-    else AS_NORM_FWD(MAXC);
-#undef AS_NORM_FWD
+    as_up_to<1, 2, 4, MAXC>(as_cdiv(D, 64), [&](auto nw) {
+        launch_rows(normalize_fwd_kernel<decltype(nw)::value>, rows, st, x, xhat, rstd, rows, D, 1e-5f, pos_bits);
+    });
     AS_LAUNCH_CHECK("normalize_fwd");
     return 0;
 }
@@ -863,27 +867,20 @@ int as_normalize_bwd(const float* dy, const float* xhat, const float* rstd, cons
     AS_REQUIRE(D > 0 && D <= 64 * MAXCW, AS_ERR_UNSUPPORTED, "normalize: row length %d > %d", D, 64 * MAXCW);
     if (n_slab < 1) n_slab = 1;
     if (!relu_src && !relu_bits && n_slab == 1 && wide_ok(D, dy, xhat, dx)) {
-        hipLaunchKernelGGL(normalize_bwd_wide_kernel, dim3(as_cdiv(rows, 4)), dim3(256), 0, st, dy, xhat, rstd, dx, rows, D);
+        launch_rows(normalize_bwd_wide_kernel, rows, st, dy, xhat, rstd, dx, rows, D);
         AS_LAUNCH_CHECK("normalize_bwd");
         return 0;
     }
-#define AS_NORM_BWD(MW)                                                                                                                \
-    do {                                                                                                                               \
-        if (relu_src || relu_bits)                                                                                                     \
-            hipLaunchKernelGGL((normalize_bwd_kernel<MW, true, false>), dim3(as_cdiv(rows, 4)), dim3(256), 0, st, dy, xhat, rstd, relu_src, \
-                               dx, rows, D, relu_bits, n_slab, slab_stride);                                                           \
-        else if (D % 64 == 0)                                                                                                          \
-            hipLaunchKernelGGL((normalize_bwd_kernel<MW, false, true>), dim3(as_cdiv(rows, 4)), dim3(256), 0, st, dy, xhat, rstd, relu_src, \
-                               dx, rows, D, relu_bits, n_slab, slab_stride);                                                           \
-        else                                                                                                                           \
-            hipLaunchKernelGGL((normalize_bwd_kernel<MW, false, false>), dim3(as_cdiv(rows, 4)), dim3(256), 0, st, dy, xhat, rstd, relu_src, \
-                               dx, rows, D, relu_bits, n_slab, slab_stride);                                                           \
-    } while (0)
-    if (D <= 128) AS_NORM_BWD(2);
-    else if (D <= 256) AS_NORM_BWD(4);
-    else if (D <= 64 * MAXC) AS_NORM_BWD(MAXC);
-    else AS_NORM_BWD(MAXCW);
-#undef AS_NORM_BWD
+    int rc = 0;   // one three-way choice (0 masked, 1 whole, 2 plain): two nested flags would also build <MW, true, true>
+    const int mode = relu_src || relu_bits ? 0 : (D % 64 == 0 ? 1 : 2);
+    as_up_to<2, 4, MAXC, MAXCW>(as_cdiv(D, 64), [&](auto mw) {
+        as_exactly<0, 1, 2>(mode, &rc, [&](auto m) {
+            constexpr int M = decltype(m)::value;
+            launch_rows(normalize_bwd_kernel<decltype(mw)::value, M == 0, M == 1>, rows, st, dy, xhat, rstd, relu_src, dx, rows, D, relu_bits,
+                        n_slab, slab_stride);
+            return 0;
+        });
+    });
     AS_LAUNCH_CHECK("normalize_bwd");
     return 0;
 }
@@ -891,7 +888,7 @@ int as_fold(const float* W, const float* gamma, const float* beta, const float* 
             int K, hipStream_t st, int Rpad) {
     if (Rpad < R) Rpad = R;
     const long total = (long)heads * Rpad;
-    hipLaunchKernelGGL(fold_kernel, dim3(as_cdiv(total, 4)), dim3(256), 0, st, W, gamma, beta, b, Wf, bf, total, R, K, Rpad);
+    launch_rows(fold_kernel, total, st, W, gamma, beta, b, Wf, bf, total, R, K, Rpad);
     AS_LAUNCH_CHECK("fold");
     return 0;
 }
@@ -973,7 +970,7 @@ int as_emb_grads(const float* dtab, const float* emb, const float* W, int V, int
 }
 int as_gather_rows(const float* table, const int64_t* tokens, long tok_stride, int T, long rows, int C, float* out,
                    hipStream_t st, int V) {
-    hipLaunchKernelGGL(gather_rows_kernel, dim3(as_cdiv(rows, 4)), dim3(256), 0, st, table, tokens, tok_stride, T, rows, C, out, V);
+    launch_rows(gather_rows_kernel, rows, st, table, tokens, tok_stride, T, rows, C, out, V);
     AS_LAUNCH_CHECK("gather_rows");
     return 0;
 }
@@ -989,47 +986,43 @@ int as_count_bad_tokens(const int64_t* tokens, long tok_stride, int T, long rows
     return 0;
 }
 int as_sigmoid_bwd(const float* out, const float* dout, float* dpre, long n, hipStream_t st) {
-    hipLaunchKernelGGL(sigmoid_bwd_kernel, dim3(ew_grid(n / 4 + 1)), dim3(256), 0, st, out, dout, dpre, n);
+    hipLaunchKernelGGL(sigmoid_bwd_kernel, dim3(as_ew_grid(n / 4 + 1)), dim3(256), 0, st, out, dout, dpre, n);
     AS_LAUNCH_CHECK("sigmoid_bwd");
     return 0;
 }
 int as_dropout(const float* x, float* y, long n, float p, unsigned long long seed, hipStream_t st) {
-    hipLaunchKernelGGL(dropout_kernel, dim3(ew_grid(n)), dim3(256), 0, st, x, y, n, p, 1.0f / (1.0f - p), seed);
+    hipLaunchKernelGGL(dropout_kernel, dim3(as_ew_grid(n)), dim3(256), 0, st, x, y, n, p, 1.0f / (1.0f - p), seed);
     AS_LAUNCH_CHECK("dropout");
     return 0;
 }
 int as_relu_mask(const float* g, const float* act, float* dst, long n, hipStream_t st) {
-    hipLaunchKernelGGL(relu_mask_kernel, dim3(ew_grid(n)), dim3(256), 0, st, g, act, dst, n);
+    hipLaunchKernelGGL(relu_mask_kernel, dim3(as_ew_grid(n)), dim3(256), 0, st, g, act, dst, n);
     AS_LAUNCH_CHECK("relu_mask");
     return 0;
+}
+
+// One wave per row of layernorm_fwd_kernel; a three-way choice (0 affine, 1 whole, 2 plain): the affine kernels are not built WHOLE.
+// (a 16-byte forward kernel like normalize_bwd_wide_kernel was measured and dropped: it sums a row in a different order,
+// and the full-width transformer's contours -- 0.89 of the 1e-4 band against the reference with the scalar kernel -- landed
+// at 1.03 with it: rounding noise either way, but the band is the contract; the gain was 0.6 ms of a 70 ms forward)
+static void layernorm_fwd_launch(const float* x, const float* res, const float* gamma, const float* beta, float* y, float* xhat, float* rstd,
+                                 long rows, int D, long group_rows, int res_block, long res_rows, bool whole, hipStream_t st) {
+    int rc = 0;
+    as_up_to<1, 2, 4, 8, 16, 44>(as_cdiv(D, 64), [&](auto nw) {
+        as_exactly<0, 1, 2>(gamma ? 0 : (whole ? 1 : 2), &rc, [&](auto m) {
+            constexpr int M = decltype(m)::value;
+            launch_rows(layernorm_fwd_kernel<decltype(nw)::value, M == 0, M == 1>, rows, st, x, res, gamma, beta, y, xhat, rstd, rows, D,
+                        group_rows, 1e-5f, res_block, res_rows);
+            return 0;
+        });
+    });
 }
 
 extern "C" int as_layernorm_fwd(const float* x, const float* res, const float* gamma, const float* beta, float* y, float* xhat,
                                 float* rstd, int64_t rows, int32_t D, int64_t group_rows, void* stream) {
     AS_REQUIRE(x && (y || xhat) && rows > 0 && D > 0 && (!gamma == !beta), AS_ERR_BAD_ARG, "as_layernorm_fwd: bad argument");
     AS_REQUIRE(D <= 64 * 44, AS_ERR_UNSUPPORTED, "as_layernorm_fwd: row length %d > %d", D, 64 * 44);
-    // (a 16-byte forward kernel like normalize_bwd_wide_kernel was measured and dropped: it sums a row in a different order,
-    // and the full-width transformer's contours -- 0.89 of the 1e-4 band against the reference with the scalar kernel -- landed
-    // at 1.03 with it: rounding noise either way, but the band is the contract; the gain was 0.6 ms of a 70 ms forward)
-#define AS_LN_FWD(NW)                                                                                                                  \
-    do {                                                                                                                               \
-        if (gamma)                                                                                                                     \
-            hipLaunchKernelGGL((layernorm_fwd_kernel<NW, true>), dim3(as_cdiv(rows, 4)), dim3(256), 0, (hipStream_t)stream, x, res, gamma,  \
-                               beta, y, xhat, rstd, (long)rows, D, (long)group_rows, 1e-5f, 0, 0L);                                         \
-        else if (D % 64 == 0)                                                                                                          \
-            hipLaunchKernelGGL((layernorm_fwd_kernel<NW, false, true>), dim3(as_cdiv(rows, 4)), dim3(256), 0, (hipStream_t)stream, x, res,  \
-                               gamma, beta, y, xhat, rstd, (long)rows, D, (long)group_rows, 1e-5f, 0, 0L);                                  \
-        else                                                                                                                           \
-            hipLaunchKernelGGL((layernorm_fwd_kernel<NW, false>), dim3(as_cdiv(rows, 4)), dim3(256), 0, (hipStream_t)stream, x, res, gamma, \
-                               beta, y, xhat, rstd, (long)rows, D, (long)group_rows, 1e-5f, 0, 0L);                                         \
-    } while (0)
-    if (D <= 64) AS_LN_FWD(1);
-    else if (D <= 128) AS_LN_FWD(2);
-    else if (D <= 256) AS_LN_FWD(4);
-    else if (D <= 512) AS_LN_FWD(8);
-    else if (D <= 1024) AS_LN_FWD(16);
-    else AS_LN_FWD(44);
-#undef AS_LN_FWD
+    layernorm_fwd_launch(x, res, gamma, beta, y, xhat, rstd, (long)rows, D, (long)group_rows, 0, 0L, D % 64 == 0, (hipStream_t)stream);
     AS_LAUNCH_CHECK("as_layernorm_fwd");
     return 0;
 }
@@ -1039,25 +1032,8 @@ extern "C" int as_layernorm_fwd_blockres(const float* x, const float* res, float
     AS_REQUIRE(x && res && xhat && channels > 0 && rows > 0 && per > 0 && block > 0, AS_ERR_BAD_ARG, "as_layernorm_fwd_blockres: bad argument");
     const int D = per * block;
     AS_REQUIRE(D <= 64 * 44, AS_ERR_UNSUPPORTED, "as_layernorm_fwd_blockres: row length %d > %d", D, 64 * 44);
-    const long total = (long)channels * rows;
-#define AS_LN_FWD(NW)                                                                                                                \
-    do {                                                                                                                             \
-        if (block % 64 == 0)                                                                                                         \
-            hipLaunchKernelGGL((layernorm_fwd_kernel<NW, false, true>), dim3(as_cdiv(total, 4)), dim3(256), 0, (hipStream_t)stream, x, res, \
-                               (const float*)nullptr, (const float*)nullptr, (float*)nullptr, xhat, rstd, total, D, 0L, 1e-5f, block,      \
-                               (long)rows);                                                                                          \
-        else                                                                                                                         \
-            hipLaunchKernelGGL((layernorm_fwd_kernel<NW, false>), dim3(as_cdiv(total, 4)), dim3(256), 0, (hipStream_t)stream, x, res,      \
-                               (const float*)nullptr, (const float*)nullptr, (float*)nullptr, xhat, rstd, total, D, 0L, 1e-5f, block,      \
-                               (long)rows);                                                                                          \
-    } while (0)
-    if (D <= 64) AS_LN_FWD(1);
-    else if (D <= 128) AS_LN_FWD(2);
-    else if (D <= 256) AS_LN_FWD(4);
-    else if (D <= 512) AS_LN_FWD(8);
-    else if (D <= 1024) AS_LN_FWD(16);
-    else AS_LN_FWD(44);
-#undef AS_LN_FWD
+    layernorm_fwd_launch(x, res, nullptr, nullptr, nullptr, xhat, rstd, (long)channels * rows, D, 0L, block, (long)rows, block % 64 == 0,
+                         (hipStream_t)stream);
     AS_LAUNCH_CHECK("as_layernorm_fwd_blockres");
     return 0;
 }
@@ -1073,15 +1049,10 @@ extern "C" int as_attn_softmax(float* scores, int64_t Z, int32_t Tq, int32_t Tk,
     AS_REQUIRE(scores && Z > 0 && Tq > 0 && Tk > 0 && heads > 0 && B > 0, AS_ERR_BAD_ARG, "as_attn_softmax: bad argument");
     AS_REQUIRE(Tk <= 1024, AS_ERR_UNSUPPORTED, "as_attn_softmax: Tk=%d > 1024", Tk);
     const long rows = (long)Z * Tq;
-#define AS_SOFTMAX(NW)                                                                                                      \
-    hipLaunchKernelGGL(attn_softmax_kernel<NW>, dim3(as_cdiv(rows, 4)), dim3(256), 0, (hipStream_t)stream, scores, rows, Tq, Tk, \
-                       heads, B, scale, attn_mask, key_padding_mask)
-    if (Tk <= 64) AS_SOFTMAX(1);
-    else if (Tk <= 128) AS_SOFTMAX(2);
-    else if (Tk <= 256) AS_SOFTMAX(4);
-    else if (Tk <= 512) AS_SOFTMAX(8);
-    else AS_SOFTMAX(16);
-#undef AS_SOFTMAX
+    as_up_to<1, 2, 4, 8, 16>(as_cdiv(Tk, 64), [&](auto nw) {
+        launch_rows(attn_softmax_kernel<decltype(nw)::value>, rows, (hipStream_t)stream, scores, rows, Tq, Tk, heads, B, scale, attn_mask,
+                    key_padding_mask);
+    });
     AS_LAUNCH_CHECK("as_attn_softmax");
     return 0;
 }
@@ -1091,14 +1062,9 @@ extern "C" int as_attn_softmax_bwd(const float* probs, float* dprobs, int64_t Z,
     AS_REQUIRE(probs && dprobs && Z > 0 && Tq > 0 && Tk > 0, AS_ERR_BAD_ARG, "as_attn_softmax_bwd: bad argument");
     AS_REQUIRE(Tk <= 1024, AS_ERR_UNSUPPORTED, "as_attn_softmax_bwd: Tk=%d > 1024", Tk);
     const long rows = (long)Z * Tq;
-#define AS_SOFTMAX_BWD(NW) \
-    hipLaunchKernelGGL(attn_softmax_bwd_kernel<NW>, dim3(as_cdiv(rows, 4)), dim3(256), 0, (hipStream_t)stream, probs, dprobs, rows, Tk, scale)
-    if (Tk <= 64) AS_SOFTMAX_BWD(1);
-    else if (Tk <= 128) AS_SOFTMAX_BWD(2);
-    else if (Tk <= 256) AS_SOFTMAX_BWD(4);
-    else if (Tk <= 512) AS_SOFTMAX_BWD(8);
-    else AS_SOFTMAX_BWD(16);
-#undef AS_SOFTMAX_BWD
+    as_up_to<1, 2, 4, 8, 16>(as_cdiv(Tk, 64), [&](auto nw) {
+        launch_rows(attn_softmax_bwd_kernel<decltype(nw)::value>, rows, (hipStream_t)stream, probs, dprobs, rows, Tk, scale);
+    });
     AS_LAUNCH_CHECK("as_attn_softmax_bwd");
     return 0;
 }
@@ -1152,15 +1118,14 @@ extern "C" int as_gather_pad_rows(const void* src, const int64_t* first_row, con
 extern "C" int as_embed_posenc(const int64_t* tokens, int64_t tok_stride, const float* table, const float* pe, float* out,
                                int64_t rows, int32_t T, int32_t D, void* stream) {
     AS_REQUIRE(pe && out && rows > 0 && T > 0 && D > 0 && (!table || tokens), AS_ERR_BAD_ARG, "as_embed_posenc: bad argument");
-    hipLaunchKernelGGL(embed_posenc_kernel, dim3(as_cdiv(rows, 4)), dim3(256), 0, (hipStream_t)stream, tokens, (long)tok_stride, table,
-                       pe, out, (long)rows, T, D);
+    launch_rows(embed_posenc_kernel, (long)rows, (hipStream_t)stream, tokens, (long)tok_stride, table, pe, out, (long)rows, T, D);
     AS_LAUNCH_CHECK("as_embed_posenc");
     return 0;
 }
 
 extern "C" int as_add(const float* a, const float* b, float* dst, int64_t n, void* stream) {
     AS_REQUIRE(a && dst && n > 0, AS_ERR_BAD_ARG, "as_add: bad argument");
-    hipLaunchKernelGGL(add_kernel, dim3(ew_grid(n)), dim3(256), 0, (hipStream_t)stream, a, b, dst, (long)n);
+    hipLaunchKernelGGL(add_kernel, dim3(as_ew_grid(n)), dim3(256), 0, (hipStream_t)stream, a, b, dst, (long)n);
     AS_LAUNCH_CHECK("as_add");
     return 0;
 }
@@ -1168,7 +1133,7 @@ extern "C" int as_add(const float* a, const float* b, float* dst, int64_t n, voi
 extern "C" int as_row_scale(const float* a, const float* row_scale, float* dst, int64_t rows, int32_t row_len, void* stream) {
     AS_REQUIRE(a && row_scale && dst && rows > 0 && row_len > 0, AS_ERR_BAD_ARG, "as_row_scale: bad argument");
     const long n = (long)rows * row_len;
-    hipLaunchKernelGGL(row_scale_kernel, dim3(ew_grid(n)), dim3(256), 0, (hipStream_t)stream, a, row_scale, dst, n, row_len);
+    hipLaunchKernelGGL(row_scale_kernel, dim3(as_ew_grid(n)), dim3(256), 0, (hipStream_t)stream, a, row_scale, dst, n, row_len);
     AS_LAUNCH_CHECK("as_row_scale");
     return 0;
 }
@@ -1184,7 +1149,7 @@ extern "C" int as_adam_step(float* params, const float* grads, float* exp_avg, f
     AS_REQUIRE(params && grads && exp_avg && exp_avg_sq && n > 0 && step >= 1, AS_ERR_BAD_ARG, "as_adam_step: bad argument");
     const float bc1 = 1.f - powf(beta1, (float)step);
     const float bc2 = sqrtf(1.f - powf(beta2, (float)step));
-    hipLaunchKernelGGL(adam_kernel, dim3(ew_grid(n)), dim3(256), 0, (hipStream_t)stream, params, grads, exp_avg, exp_avg_sq,
+    hipLaunchKernelGGL(adam_kernel, dim3(as_ew_grid(n)), dim3(256), 0, (hipStream_t)stream, params, grads, exp_avg, exp_avg_sq,
                        (long)n, lr, beta1, beta2, eps, weight_decay, bc1, bc2, grad_scale);
     AS_LAUNCH_CHECK("as_adam_step");
     return 0;

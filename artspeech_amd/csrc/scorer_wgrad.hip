@@ -280,16 +280,10 @@ extern "C" int as_conv3x3_stem_wgrad(const float* x, int64_t sb, int64_t sc, int
     AS_REQUIRE(ws_floats >= need, AS_ERR_WORKSPACE, "as_conv3x3_stem_wgrad: workspace of %lld floats, %lld needed", (long long)ws_floats,
                (long long)need);
     hipStream_t s = (hipStream_t)stream;
-#define AS_STEM_WGRAD(CIN)                                                                                                          \
-    hipLaunchKernelGGL(conv3x3_stem_wgrad_kernel<CIN>, dim3(blocks), dim3(256), 0, s, x, (long)sb, (long)sc, (long)sd, (long)st, dy, ws, \
-                       B, T, D, chunk)
-    switch (Cin) {
-        case 1: AS_STEM_WGRAD(1); break;
-        case 2: AS_STEM_WGRAD(2); break;
-        case 3: AS_STEM_WGRAD(3); break;
-        default: AS_STEM_WGRAD(4);
-    }
-#undef AS_STEM_WGRAD
+    as_up_to<1, 2, 3, 4>(Cin, [&](auto cin) {
+        hipLaunchKernelGGL(conv3x3_stem_wgrad_kernel<decltype(cin)::value>, dim3(blocks), dim3(256), 0, s, x, (long)sb, (long)sc, (long)sd,
+                           (long)st, dy, ws, B, T, D, chunk);
+    });
     AS_LAUNCH_CHECK("as_conv3x3_stem_wgrad");
     return ordered_rowsum(ws, blocks, m, 9 * CO * Cin, dw, dbias, s, "as_conv3x3_stem_wgrad");
 }
