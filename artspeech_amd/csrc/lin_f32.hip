@@ -21,6 +21,13 @@
 // MFMA k-steps (k-step j of an 8-group pairs k = j in lanes 0-31 with k = j + 4 in lanes 32-63, for both operands alike).
 // Epilogue, 32 rows at a time: the accumulators go to LDS (the ring's memory), then one wave per row does exactly what
 // normalize_fwd_kernel / normalize_bwd_kernel (rowops.hip) do, reading the GEMM result from LDS instead of HBM.
+//
+// The file, top to bottom: what the five kernels share around their main loops, each written once (tile_of: tile-list decode,
+// Stamps: debug stamps, store_rows: the plain store); the LayerNorm epilogues; lin_f32_kernel (exact fp32, described above); the
+// split-arithmetic main loop s6_main_loop, its entry s6_tile, and lin_s6_kernel / lin_s6_plain_kernel on it; the output layer
+// (criterion_rows: the fused criterion; lin_out_kernel, lin_out_s6_kernel); the host half (tile lists, argument copies,
+// as_lin_try, as_lin_plain_s6, as_lin_out_try, as_linear_fwd).  The kernels differ in their main loops and in which of the
+// shared pieces they call.
 #include <cstdlib>
 
 #include <type_traits>
@@ -41,8 +48,7 @@ struct LinK {
     float* C; long ldc, c_batch;
     const float* bias; long bias_batch;
     int M, N, K, ka_valid, batch, act;
-    int n_big, big_per_batch, big_per_batch_rows, small_per_batch;   // tiles of 64 rows first, then tiles of 32 rows (see launch())
-    int tile_rows;
+    int n_big, big_per_batch, big_per_batch_rows, small_per_batch;   // tiles of 64 rows first, then tiles of 32 rows (see tile_list())
     unsigned long long* dbg; long dbg_max;   // diagnostic cycle stamps (as_lin_debug_stamps), normally null
     float eps;
     float* rstd;                      // EPI_LNF out: [M][batch]
@@ -51,6 +57,83 @@ struct LinK {
     const float* rstd_in;             // EPI_LNB in: [M][batch]
     const unsigned long long* bits_in;
 };
+
+// ---- what the five kernels share besides their main loops: the tile decode, the debug stamps, the plain store.
+// A workgroup's entry of the tile list (tile_list() below; LinK and LinOutK name its fields alike): the 64-row tiles of every
+// head first, then 32-row tiles over the remaining rows of every head.  Block b takes entry b (an XCD-contiguous map --
+// workgroups go to the eight XCDs round-robin by block index, each with its own 4 MB L2; XCD x took a contiguous range of
+// the list, two or three heads' weights per L2 instead of all eleven -- was measured: 5-10 % slower).
+// UNIFORM (the split-arithmetic kernels): the divisions run on the vector unit, and without readfirstlane head and first row
+// (and their 64-bit forms) sit in vector registers from here to the epilogue; lin_s6_kernel<EPI_LNB>, at its register limit
+// in the main loop, spills them.
+struct Tile { int bz, m0, tm; };   // head, first row, row blocks of 32 (2 | 1)
+template <bool UNIFORM, typename K>
+__device__ __forceinline__ Tile tile_of(const K& g) {
+    const int tile = blockIdx.x;
+    Tile t;
+    if (tile < g.n_big) {
+        t.bz = tile / g.big_per_batch;
+        t.m0 = (tile - t.bz * g.big_per_batch) * 64;
+        t.tm = 2;
+    } else {
+        const int j = tile - g.n_big;
+        t.bz = j / g.small_per_batch;
+        t.m0 = g.big_per_batch_rows + (j - t.bz * g.small_per_batch) * 32;
+        t.tm = 1;
+    }
+    if (UNIFORM) {
+        t.bz = __builtin_amdgcn_readfirstlane(t.bz);
+        t.m0 = __builtin_amdgcn_readfirstlane(t.m0);
+    }
+    return t;
+}
+
+// Diagnostic cycle stamps (as_lin_debug_stamps, tools/lin_stamps.py), normally off: thread 0 of each of the first dbg_max
+// workgroups fills eight 64-bit slots.  s_memtime: 0 start, 1 first k-tile staged, 2 main loop done, 3 epilogue stored;
+// s_memrealtime: 4 start, 6 end (0 until then); 5: hardware ids (s_getreg: HW_ID bits 0-3 | XCC_ID << 32).
+struct Stamps {
+    unsigned long long* dbg;
+    bool on;
+    __device__ __forceinline__ Stamps(const LinK& g, int tid) : dbg(g.dbg), on(g.dbg != nullptr && tid == 0 && blockIdx.x < g.dbg_max) {}
+    __device__ __forceinline__ unsigned long long* slot(int i) const { return on ? dbg + 8L * blockIdx.x + i : nullptr; }
+    __device__ __forceinline__ void begin() const {
+        if (!on) return;
+        unsigned long long* d = slot(0);
+        d[0] = __builtin_amdgcn_s_memtime();
+        d[4] = __builtin_amdgcn_s_memrealtime();
+        d[6] = 0;
+        d[5] = __builtin_amdgcn_s_getreg((4 - 1) << 11 | 0 << 6 | 4) | ((unsigned long long)__builtin_amdgcn_s_getreg((32 - 1) << 11 | 0 << 6 | 20) << 32);
+    }
+    __device__ __forceinline__ void mark(int i) const {
+        if (on) *slot(i) = __builtin_amdgcn_s_memtime();
+    }
+    __device__ __forceinline__ void end() const {
+        if (!on) return;
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        *slot(3) = __builtin_amdgcn_s_memtime();
+        *slot(6) = __builtin_amdgcn_s_memrealtime();
+    }
+};
+
+// The plain store of TM accumulators of 32 rows x this lane's column.  Element r of lane half lh is row
+// (r & 3) + 8 * (r >> 2) + 4 * lh of its block -- the accumulator layout of v_mfma_f32_32x32x2_f32 and of
+// v_mfma_f32_32x32x16_bf16 alike.  c0: the column's element of row 0 (ld: row pitch); bj: its bias (0 without);
+// act: 0 none, 1 ReLU, 2 sigmoid; rows from m0 on, below M; tm_eff: row blocks the tile has.
+template <int TM>
+__device__ __forceinline__ void store_rows(const f32x16* acc, float* c0, long ld, float bj, int act, int m0, int M, int tm_eff, int lh) {
+#pragma unroll
+    for (int i = 0; i < TM; ++i)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const int row = m0 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
+            if (i < tm_eff && row < M) {   // (a 32-row tile owns only its first row block)
+                float v = acc[i][r] + bj;
+                if (act == 1) v = as_relu(v);
+                else if (act == 2) v = as_sigmoid(v);
+                c0[(long)row * ld] = v;
+            }
+        }
+}
 
 // ---- the LayerNorm epilogues.  The accumulators of a block of 32 rows (per group of 8 column waves) go to LDS, then every
 // wave normalises FOUR rows at a time: lane = (row rr = lane >> 4, slot jj = lane & 15) holds the 16 features
@@ -178,8 +261,7 @@ __device__ __forceinline__ void lin_ln_rows(const LinK& g, f32x16 (&acc)[TM], fl
 }
 
 // ---- epilogue of the 256-column kernels (8 waves, wave w owns columns 32 w .. 32 w + 31 of all BM rows).
-// D[row][col]: col = wave * 32 + l31, row = i * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh -- the accumulator layout of
-// v_mfma_f32_32x32x2_f32 and of v_mfma_f32_32x32x16_bf16 alike.  `smem`: >= 32 * BN floats, free of readers (behind a barrier).
+// D[row][col]: col = wave * 32 + l31, row = i * 32 + store_rows' row of r.  `smem`: >= 32 * BN floats, free of readers (behind a barrier).
 template <int TM, int EPI>
 __device__ __forceinline__ void lin_epilogue(const LinK& g, f32x16 (&acc)[TM], float* smem, int bz, int m0, int tm_eff, int wave, int lane) {
     const int l31 = lane & 31, lh = lane >> 5;
@@ -187,19 +269,7 @@ __device__ __forceinline__ void lin_epilogue(const LinK& g, f32x16 (&acc)[TM], f
     if (EPI == EPI_PLAIN) {
         if (col < g.N) {
             const float bj = g.bias ? g.bias[(long)bz * g.bias_batch + col] : 0.f;
-            float* c0 = g.C + (long)bz * g.c_batch + col;
-#pragma unroll
-            for (int i = 0; i < TM; ++i)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const int row = m0 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
-                    if (i < tm_eff && row < g.M) {   // (a 32-row tile owns only its first row block)
-                        float v = acc[i][r] + bj;
-                        if (g.act == 1) v = as_relu(v);
-                        else if (g.act == 2) v = as_sigmoid(v);
-                        c0[(long)row * g.ldc] = v;
-                    }
-                }
+            store_rows<TM>(acc, g.C + (long)bz * g.c_batch + col, g.ldc, bj, g.act, m0, g.M, tm_eff, lh);
         }
         return;
     }
@@ -217,18 +287,9 @@ __global__ __launch_bounds__(NT, 4) void lin_f32_kernel(LinK g) {
     constexpr int AHEADT = NBUF - 1;     // k-tiles in flight besides the one being multiplied
     __shared__ __attribute__((aligned(16))) float smem[RING > EPIT ? RING : EPIT];
 
-    // tile list: the 64-row tiles of every head first, then 32-row tiles over the remaining rows of every head
-    int bz, m0, tm_eff;
-    if ((int)blockIdx.x < g.n_big) {
-        bz = blockIdx.x / g.big_per_batch;
-        m0 = (blockIdx.x - bz * g.big_per_batch) * BM;
-        tm_eff = TM;
-    } else {
-        const int j = blockIdx.x - g.n_big;
-        bz = j / g.small_per_batch;
-        m0 = g.big_per_batch_rows + (j - bz * g.small_per_batch) * 32;
-        tm_eff = 1;
-    }
+    static_assert(BM == 64, "tile_of: tiles of 64 and of 32 rows");
+    const Tile t = tile_of<false>(g);
+    const int bz = t.bz, m0 = t.m0, tm_eff = t.tm;
     const float* __restrict__ A = g.A + (long)bz * g.a_batch;
     const float* __restrict__ B = g.B + (long)bz * g.b_batch;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -282,14 +343,8 @@ __global__ __launch_bounds__(NT, 4) void lin_f32_kernel(LinK g) {
         for (int r = 0; r < 16; ++r) acc[i][r] = 0.f;
 
     const int nk = g.K / BK;
-    const bool stamp = g.dbg != nullptr && tid == 0 && blockIdx.x < g.dbg_max;
-    if (stamp) {
-        unsigned long long* d = g.dbg + 8L * blockIdx.x;
-        d[0] = __builtin_amdgcn_s_memtime();
-        d[4] = __builtin_amdgcn_s_memrealtime();
-        d[6] = 0;
-        d[5] = __builtin_amdgcn_s_getreg((4 - 1) << 11 | 0 << 6 | 4) | ((unsigned long long)__builtin_amdgcn_s_getreg((32 - 1) << 11 | 0 << 6 | 20) << 32);
-    }
+    const Stamps stamps(g, tid);
+    stamps.begin();
     const int swz = (l31 >> 2) & 3;   // rows i * 32 + l31 and wave * 32 + l31 share it (32 = 0 mod 16)
     // two k-tiles in flight; the older one is retired with vmcnt(3).  (A 2-slot ring with three workgroups per CU was no
     // faster: 108-118 us against 108-114 for head GEMM 2.)
@@ -298,7 +353,7 @@ __global__ __launch_bounds__(NT, 4) void lin_f32_kernel(LinK g) {
     if (nk > 1) asm volatile("s_waitcnt vmcnt(3)" ::: "memory");
     else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();
-    if (stamp) g.dbg[8L * blockIdx.x + 1] = __builtin_amdgcn_s_memtime();
+    stamps.mark(1);
     // Main loop, software-pipelined across the k-tile boundary.  A k-tile is two 8-deep fragment groups; the barrier that
     // ends a tile sits BETWEEN the two groups' MFMAs: when a wave reaches it, all its LDS reads of the tile are in registers
     // and eight MFMAs are still to be issued, and right behind it the first fragments of the NEXT tile are requested, so
@@ -358,14 +413,10 @@ __global__ __launch_bounds__(NT, 4) void lin_f32_kernel(LinK g) {
         mma(f1, -1);
         __builtin_amdgcn_sched_barrier(0);
     }
-    if (stamp) g.dbg[8L * blockIdx.x + 2] = __builtin_amdgcn_s_memtime();
+    stamps.mark(2);
 
     lin_epilogue<TM, EPI>(g, acc, smem, bz, m0, tm_eff, wave, lane);
-    if (stamp) {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        g.dbg[8L * blockIdx.x + 3] = __builtin_amdgcn_s_memtime();
-        g.dbg[8L * blockIdx.x + 6] = __builtin_amdgcn_s_memrealtime();
-    }
+    stamps.end();
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -387,13 +438,6 @@ __global__ __launch_bounds__(NT, 4) void lin_f32_kernel(LinK g) {
 //     {0-3, 12-15, 20-27}, {4-11, 16-19, 28-31} -- then touch each of the 64 banks once).  All eight
 //     waves read their A fragments from there: one barrier per 32-deep k-tile, two plane images (24 KB).
 //   * accumulator layout = that of the fp32 instruction: the LayerNorm epilogues above are shared.
-// Workgroups go to the eight XCDs round-robin by block index, and each XCD has its own 4 MB L2.  With tiles numbered head
-// by head, block b -> tile b puts every head's weights into every L2 (11 heads x 393 KB of planes do not fit one).  This map
-// gives XCD x a CONTIGUOUS range of the tile list instead (two or three heads): block b = x + 8 i -> tile start(x) + i.
-__device__ __forceinline__ int xcd_contiguous(int b, int total) {
-    const int q = total >> 3, r = total & 7, x = b & 7, i = b >> 3;
-    return x * q + min(x, r) + i;
-}
 
 constexpr int S6_BK = 32;                 // k-tile of the A image (two MFMA k-steps)
 constexpr int S6_PLANE = 64 * S6_BK * 2;  // bytes of one plane of one k-tile: 64 rows x 32 bf16
@@ -524,54 +568,40 @@ __device__ __forceinline__ void s6_main_loop(f32x16 (&acc)[2], unsigned char* sm
     if (kt + 1 < nk) tile(IC<1>{}, kt + 1);
 }
 
+// A split-arithmetic kernel's way into the main loop for its tile: zeroed accumulators, the tile's rows of A and its head's planes
+// from k0 on (klen deep, kav of them valid in A: lin_s6_plain_kernel's chunk of K, everywhere else 0 / K / ka_valid), this lane's
+// B fragment, the second half of the waves splitting late, and the 64- or the 32-row loop.
+template <int NW, typename K>
+__device__ __forceinline__ void s6_tile(const K& g, const Tile& t, f32x16 (&acc)[2], unsigned char* sm, int k0, int klen, int kav, int tid,
+                                        unsigned long long* stamp1 = nullptr) {
+    const int lane = tid & 63, wave = tid >> 6;
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[i][r] = 0.f;
+    const long bp_step = (long)g.bp_rows * 16;
+    const uint16_t* bp = g.Bp + (long)t.bz * g.bp_batch + (k0 / 16) * bp_step;
+    const unsigned b_lane = (unsigned)((wave * 32 + (lane & 31)) * 16 + (lane >> 5) * 8) * 2u;   // bytes
+    const float* A = g.A + (long)t.bz * g.a_batch + (long)t.m0 * g.lda + k0;
+    const bool late = __builtin_amdgcn_readfirstlane(wave) >= NW / 2;
+    if (t.tm == 2) s6_main_loop<NW, 2>(acc, sm, A, g.lda, g.M - t.m0, klen, kav, bp, b_lane, g.bp_plane, bp_step, tid, lane, late, stamp1);
+    else s6_main_loop<NW, 1>(acc, sm, A, g.lda, g.M - t.m0, klen, kav, bp, b_lane, g.bp_plane, bp_step, tid, lane, late, stamp1);
+}
+
 template <int EPI>
 __global__ __launch_bounds__(NT, 4) void lin_s6_kernel(LinK g) {
     constexpr int EPIT = 32 * BN;
     static_assert(EPIT * 4 >= 2 * S6_BUF, "the epilogue's staging area holds both plane images");
     __shared__ __attribute__((aligned(16))) float smem[EPIT];
-    int bz, m0, tm_eff;
-    const int tile = blockIdx.x;   // (an XCD-contiguous map of the tile list, xcd_contiguous(), was measured: 5-10 % slower)
-    if (tile < g.n_big) {
-        bz = tile / g.big_per_batch;
-        m0 = (tile - bz * g.big_per_batch) * 64;
-        tm_eff = 2;
-    } else {
-        const int j = tile - g.n_big;
-        bz = j / g.small_per_batch;
-        m0 = g.big_per_batch_rows + (j - bz * g.small_per_batch) * 32;
-        tm_eff = 1;
-    }
-    // the divisions above run on the vector unit: without this, head and first row (and their 64-bit forms) sit in vector
-    // registers from here to the epilogue, and the EPI_LNB kernel, at its register limit in the main loop, spills them
-    bz = __builtin_amdgcn_readfirstlane(bz);
-    m0 = __builtin_amdgcn_readfirstlane(m0);
+    const Tile t = tile_of<true>(g);
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const Stamps stamps(g, tid);
+    stamps.begin();
     f32x16 acc[2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[i][r] = 0.f;
-    const uint16_t* bp = g.Bp + (long)bz * g.bp_batch;
-    const unsigned b_lane = (unsigned)((wave * 32 + (lane & 31)) * 16 + (lane >> 5) * 8) * 2u;   // bytes
-    unsigned char* sm = reinterpret_cast<unsigned char*>(smem);
-    const float* A = g.A + (long)bz * g.a_batch + (long)m0 * g.lda;
-    const bool late = __builtin_amdgcn_readfirstlane(wave) >= 4;
-    const bool stamp = g.dbg != nullptr && tid == 0 && blockIdx.x < g.dbg_max;   // diagnostic cycle stamps (as_lin_debug_stamps)
-    unsigned long long* d = stamp ? g.dbg + 8L * blockIdx.x : nullptr;
-    if (stamp) {
-        d[0] = __builtin_amdgcn_s_memtime();
-        d[4] = __builtin_amdgcn_s_memrealtime();
-        d[5] = __builtin_amdgcn_s_getreg((4 - 1) << 11 | 0 << 6 | 4) | ((unsigned long long)__builtin_amdgcn_s_getreg((32 - 1) << 11 | 0 << 6 | 20) << 32);
-    }
-    if (tm_eff == 2) s6_main_loop<8, 2>(acc, sm, A, g.lda, g.M - m0, g.K, g.ka_valid, bp, b_lane, g.bp_plane, (long)g.bp_rows * 16, tid, lane, late, stamp ? d + 1 : nullptr);
-    else s6_main_loop<8, 1>(acc, sm, A, g.lda, g.M - m0, g.K, g.ka_valid, bp, b_lane, g.bp_plane, (long)g.bp_rows * 16, tid, lane, late, stamp ? d + 1 : nullptr);
-    if (stamp) d[2] = __builtin_amdgcn_s_memtime();
-    lin_epilogue<2, EPI>(g, acc, smem, bz, m0, tm_eff, wave, lane);
-    if (stamp) {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        d[3] = __builtin_amdgcn_s_memtime();
-        d[6] = __builtin_amdgcn_s_memrealtime();
-    }
+    s6_tile<8>(g, t, acc, reinterpret_cast<unsigned char*>(smem), 0, g.K, g.ka_valid, tid, stamps.slot(1));
+    stamps.mark(2);
+    lin_epilogue<2, EPI>(g, acc, smem, t.bz, t.m0, t.tm, wave, lane);
+    stamps.end();
 }
 
 // A plain Linear on the same main loop: C = act(A . B^T + bias), 64 (or 32) rows x 32 NW columns per workgroup (NW = 8:
@@ -584,54 +614,17 @@ __global__ __launch_bounds__(NT, 4) void lin_s6_kernel(LinK g) {
 template <int NW, int WPS>
 __global__ __launch_bounds__(NW * 64, WPS) void lin_s6_plain_kernel(LinK g) {
     __shared__ __attribute__((aligned(16))) unsigned char sm[2 * S6_BUF];
-    int bz, m0, tm_eff;
-    const int tile = blockIdx.x;   // (an XCD-contiguous map of the tile list, xcd_contiguous(), was measured: 5-10 % slower)
-    if (tile < g.n_big) {
-        bz = tile / g.big_per_batch;
-        m0 = (tile - bz * g.big_per_batch) * 64;
-        tm_eff = 2;
-    } else {
-        const int j = tile - g.n_big;
-        bz = j / g.small_per_batch;
-        m0 = g.big_per_batch_rows + (j - bz * g.small_per_batch) * 32;
-        tm_eff = 1;
-    }
-    bz = __builtin_amdgcn_readfirstlane(bz);   // (scalar registers: see lin_s6_kernel)
-    m0 = __builtin_amdgcn_readfirstlane(m0);
+    const Tile t = tile_of<true>(g);
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int l31 = lane & 31, lh = lane >> 5;
     const int ks = blockIdx.y, k0 = ks * g.kchunk;
     const int klen = min(g.kchunk, g.K - k0);
-    const int kav = max(0, min(klen, g.ka_valid - k0));
     f32x16 acc[2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[i][r] = 0.f;
-    const long bp_step = (long)g.bp_rows * 16;
-    const uint16_t* bp = g.Bp + (long)bz * g.bp_batch + (k0 / 16) * bp_step;
-    const unsigned b_lane = (unsigned)((wave * 32 + l31) * 16 + lh * 8) * 2u;   // bytes
-    const float* A = g.A + (long)bz * g.a_batch + (long)m0 * g.lda + k0;
-    const bool late = __builtin_amdgcn_readfirstlane(wave) >= NW / 2;
-    if (tm_eff == 2) s6_main_loop<NW, 2>(acc, sm, A, g.lda, g.M - m0, klen, kav, bp, b_lane, g.bp_plane, bp_step, tid, lane, late);
-    else s6_main_loop<NW, 1>(acc, sm, A, g.lda, g.M - m0, klen, kav, bp, b_lane, g.bp_plane, bp_step, tid, lane, late);
-    const int col = wave * 32 + l31;
+    s6_tile<NW>(g, t, acc, sm, k0, klen, max(0, min(klen, g.ka_valid - k0)), tid);
+    const int col = wave * 32 + (lane & 31);
     if (col >= g.N) return;
     const bool whole = gridDim.y == 1;
-    const float bj = (whole && g.bias) ? g.bias[(long)bz * g.bias_batch + col] : 0.f;
-    float* c0 = g.C + (long)ks * g.c_split + (long)bz * g.c_batch + col;
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int row = m0 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
-            if (i < tm_eff && row < g.M) {
-                float v = acc[i][r] + bj;
-                if (whole && g.act == 1) v = as_relu(v);
-                else if (whole && g.act == 2) v = as_sigmoid(v);
-                c0[(long)row * g.ldc] = v;
-            }
-        }
+    const float bj = (whole && g.bias) ? g.bias[(long)t.bz * g.bias_batch + col] : 0.f;
+    store_rows<2>(acc, g.C + (long)ks * g.c_split + (long)t.bz * g.c_batch + col, g.ldc, bj, whole ? g.act : 0, t.m0, g.M, t.tm, lane >> 5);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -666,7 +659,7 @@ struct LinOutK {
 // The criterion's workgroup sum goes out; with an arrival counter the workgroup that delivers the last one adds them all, thread
 // i taking partials i, i + 256, ... and the 256 sums meeting as in loss_final_kernel (metrics.hip): the same value, bit for bit.
 // Partials are written through to memory and read back at agent scope (another XCD's L2 does not see a plain store: gemm_f32.hip).
-__device__ __forceinline__ void criterion_tail(const LinOutK& g, int tile, float sum, int tid, float* red, int nwaves) {
+__device__ __forceinline__ void criterion_tail(const LinOutK& g, int tile, float sum, int tid, float* red) {
     if (g.counter == nullptr) {
         if (tid == 0) g.partial[tile] = sum;
         return;
@@ -689,24 +682,82 @@ __device__ __forceinline__ void criterion_tail(const LinOutK& g, int tile, float
     if ((tid & 63) == 0 && tid < 256) red[tid >> 6] = s;
     __syncthreads();
     if (tid == 0) g.loss[0] = ((red[0] + red[1]) + (red[2] + red[3])) * g.scale;
-    (void)nwaves;
+}
+
+// The fused criterion of a workgroup of NW waves, from the tile's sigmoid outputs in LDS (`tile`: [64][ON], complete behind a
+// barrier) on: out, d loss / d(pre-sigmoid), and the workgroup's share of the masked sum.  One wave per frame (row) at a time,
+// lanes over the points: frame index, utterance, validity and the target row are wave-uniform (computed once per row on the
+// scalar unit, no per-pair divisions).  A lane owns ONE point of each of the wave's 64 / NW frames: N <= ON outputs are at most
+// 64 points.  ALL target coordinates are requested before the first store goes out: vector memory operations retire in
+// order, so a target load issued behind a frame's stores waits for their acknowledgement -- frame after frame, that chain was
+// most of this epilogue (and two passes of 8 frames cost the second pass of lin_out_s6_kernel exactly that).
+static_assert(ON / 2 <= 64, "criterion_rows: a lane owns one point of a frame");
+template <int NW>
+__device__ __forceinline__ void criterion_rows(const LinOutK& g, const float* tile, const Tile& t, int tid) {
+    constexpr int FPW = 64 / NW;                                // frames per wave
+    static_assert(NW == 4 || NW == 8, "the workgroup sum below");
+    const int lane = tid & 63, wave = tid >> 6;
+    const int wave_u = __builtin_amdgcn_readfirstlane(wave);
+    const int bz = t.bz, m0 = t.m0, rows = 32 * t.tm;
+    const int Np = g.N >> 1;                                    // points per contour
+    float part = 0.f;
+    float tx[FPW], ty[FPW];
+    bool in[FPW], valid[FPW];
+    const int nl = min(lane, Np - 1);
+#pragma unroll
+    for (int k = 0; k < FPW; ++k) {
+        const int r = wave_u + NW * k;
+        const int frame = m0 + r;
+        in[k] = r < rows && frame < g.M;
+        const int fc = in[k] ? frame : m0;
+        const int b = fc / g.T, t_ = fc - b * g.T;
+        valid[k] = in[k] && t_ < g.lengths[b];
+        const float* tg = g.tgt + (((long)b * g.tgt_T + t_) * g.batch + bz) * g.N;
+        tx[k] = tg[nl];
+        ty[k] = tg[Np + nl];
+    }
+#pragma unroll
+    for (int k = 0; k < FPW; ++k) {
+        if (!in[k]) continue;                       // wave-uniform
+        const int r = wave_u + NW * k;
+        const long frame = m0 + r;
+        float* o = g.out + frame * g.ldo + (long)bz * g.o_batch;
+        float* dz = g.dout + frame * g.ldo + (long)bz * g.o_batch;
+        if (lane < Np) {
+            const float ox = tile[r * ON + lane], oy = tile[r * ON + Np + lane];
+            o[lane] = ox;
+            o[Np + lane] = oy;
+            float gx = 0.f, gy = 0.f;
+            if (valid[k]) {
+                const float dx = ox - tx[k], dy = oy - ty[k];
+                const float d = sqrtf(dx * dx + dy * dy);
+                part += d;
+                const float gg = g.scale / d;                   // NaN at zero distance, as torch autograd
+                gx = dx * gg * ox * (1.f - ox);                  // through the sigmoid (same product order as the unfused kernels)
+                gy = dy * gg * oy * (1.f - oy);
+            }
+            dz[lane] = gx;
+            dz[Np + lane] = gy;
+        }
+    }
+    part = as_wave_sum_dpp(part);
+    __shared__ float red[NW];
+    if (lane == 0) red[wave] = part;
+    __syncthreads();
+    float wg_sum = 0.f;      // (tile order and wave order alike for 8 and for 4 waves: the same final sum order)
+    if (tid == 0) {
+        wg_sum = (red[0] + red[1]) + (red[2] + red[3]);
+        if (NW == 8) wg_sum = wg_sum + ((red[4] + red[5]) + (red[6] + red[7]));
+    }
+    criterion_tail(g, blockIdx.x, wg_sum, tid, red);
 }
 
 __global__ __launch_bounds__(NT, 4) void lin_out_kernel(LinOutK g) {
     constexpr int TILE = BK * (64 + ON);
     constexpr int RING = NBUF * TILE;            // 9216 floats = 36 KB; the epilogue's [64][ON] tile (32 KB) reuses it
     __shared__ __attribute__((aligned(16))) float smem[RING];
-    int bz, m0, rows;
-    if ((int)blockIdx.x < g.n_big) {
-        bz = blockIdx.x / g.big_per_batch;
-        m0 = (blockIdx.x - bz * g.big_per_batch) * 64;
-        rows = 64;
-    } else {
-        const int j = blockIdx.x - g.n_big;
-        bz = j / g.small_per_batch;
-        m0 = g.big_per_batch_rows + (j - bz * g.small_per_batch) * 32;
-        rows = 32;
-    }
+    const Tile t = tile_of<false>(g);
+    const int bz = t.bz, m0 = t.m0;
     const float* __restrict__ A = g.A + (long)bz * g.a_batch;
     const float* __restrict__ B = g.B + (long)bz * g.b_batch;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -731,7 +782,7 @@ __global__ __launch_bounds__(NT, 4) void lin_out_kernel(LinOutK g) {
     for (int r = 0; r < 16; ++r) acc[r] = 0.f;
     const int nk = g.K / BK;
     const int swz = (l31 >> 2) & 3;
-    const bool active = wm == 0 || rows == 64;      // a 32-row tile has one row block: waves 4-7 only help with the DMAs
+    const bool active = wm == 0 || t.tm == 2;       // a 32-row tile has one row block: waves 4-7 only help with the DMAs
     issue(0);
     if (nk > 1) issue(1);
     if (nk > 1) asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
@@ -763,14 +814,7 @@ __global__ __launch_bounds__(NT, 4) void lin_out_kernel(LinOutK g) {
     const int col = wn * 32 + l31;
     const float bj = (g.bias && col < g.N) ? g.bias[(long)bz * g.bias_batch + col] : 0.f;
     if (g.tgt == nullptr) {
-        if (active && col < g.N) {
-            float* o0 = g.out + (long)bz * g.o_batch + col;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int row = m0 + wm * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
-                if (row < g.M) o0[(long)row * g.ldo] = as_sigmoid(acc[r] + bj);
-            }
-        }
+        if (active && col < g.N) store_rows<1>(&acc, g.out + (long)bz * g.o_batch + col, g.ldo, bj, 2, m0 + wm * 32, g.M, 1, lh);
         return;
     }
     // fused criterion: sigmoid outputs through LDS ([64][ON]; every ring read is behind the loop's last barrier)
@@ -779,141 +823,27 @@ __global__ __launch_bounds__(NT, 4) void lin_out_kernel(LinOutK g) {
         for (int r = 0; r < 16; ++r) smem[(wm * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh) * ON + col] = as_sigmoid(acc[r] + bj);
     }
     as_lds_barrier();
-    const int Np = g.N >> 1;                                    // points per contour
-    // one wave per frame (row) at a time, lanes over the points: frame index, utterance, validity and the target row are
-    // wave-uniform (computed once per row on the scalar unit, no per-pair divisions); rows of a wave are independent, so
-    // the next row's target loads are in flight while this row's stores go out
-    float part = 0.f;
-    const int wave_u = __builtin_amdgcn_readfirstlane(wave);
-    if (Np <= 64) {
-        // a lane owns one point of each of the wave's (up to 8) frames.  ALL target coordinates are requested before the first
-        // store goes out: vector memory operations retire in order, so a target load issued behind a frame's stores waits
-        // for their acknowledgement -- frame after frame, that chain was most of this epilogue
-        float tx[8], ty[8];
-        bool in[8], valid[8];
-        const int nl = min(lane, Np - 1);
-#pragma unroll
-        for (int k = 0; k < 8; ++k) {
-            const int r = wave_u + 8 * k;
-            const int frame = m0 + r;
-            in[k] = r < rows && frame < g.M;
-            const int fc = in[k] ? frame : m0;
-            const int b = fc / g.T, t = fc - b * g.T;
-            valid[k] = in[k] && t < g.lengths[b];
-            const float* tg = g.tgt + (((long)b * g.tgt_T + t) * g.batch + bz) * g.N;
-            tx[k] = tg[nl];
-            ty[k] = tg[Np + nl];
-        }
-#pragma unroll
-        for (int k = 0; k < 8; ++k) {
-            if (!in[k]) continue;                       // wave-uniform
-            const int r = wave_u + 8 * k;
-            const long frame = m0 + r;
-            float* o = g.out + frame * g.ldo + (long)bz * g.o_batch;
-            float* dz = g.dout + frame * g.ldo + (long)bz * g.o_batch;
-            if (lane < Np) {
-                const float ox = smem[r * ON + lane], oy = smem[r * ON + Np + lane];
-                o[lane] = ox;
-                o[Np + lane] = oy;
-                float gx = 0.f, gy = 0.f;
-                if (valid[k]) {
-                    const float dx = ox - tx[k], dy = oy - ty[k];
-                    const float d = sqrtf(dx * dx + dy * dy);
-                    part += d;
-                    const float gg = g.scale / d;                   // NaN at zero distance, as torch autograd
-                    gx = dx * gg * ox * (1.f - ox);                  // through the sigmoid (same product order as the unfused kernels)
-                    gy = dy * gg * oy * (1.f - oy);
-                }
-                dz[lane] = gx;
-                dz[Np + lane] = gy;
-            }
-        }
-    } else
-    for (int r = wave_u; r < rows; r += 8) {
-        const int frame = m0 + r;
-        if (frame >= g.M) break;
-        const int b = frame / g.T, t = frame - b * g.T;
-        const bool valid = t < g.lengths[b];
-        float* o = g.out + (long)frame * g.ldo + (long)bz * g.o_batch;
-        float* dz = g.dout + (long)frame * g.ldo + (long)bz * g.o_batch;
-        const float* tg = g.tgt + (((long)b * g.tgt_T + t) * g.batch + bz) * g.N;
-        for (int n = lane; n < Np; n += 64) {
-            const float ox = smem[r * ON + n], oy = smem[r * ON + Np + n];
-            o[n] = ox;
-            o[Np + n] = oy;
-            float gx = 0.f, gy = 0.f;
-            if (valid) {
-                const float dx = ox - tg[n], dy = oy - tg[Np + n];
-                const float d = sqrtf(dx * dx + dy * dy);
-                part += d;
-                const float gg = g.scale / d;                   // NaN at zero distance, as torch autograd
-                gx = dx * gg * ox * (1.f - ox);                  // through the sigmoid (same product order as the unfused kernels)
-                gy = dy * gg * oy * (1.f - oy);
-            }
-            dz[n] = gx;
-            dz[Np + n] = gy;
-        }
-    }
-    part = as_wave_sum_dpp(part);
-    __shared__ float red[8];
-    if (lane == 0) red[wave] = part;
-    __syncthreads();
-    float wg_sum = 0.f;
-    if (tid == 0) wg_sum = ((red[0] + red[1]) + (red[2] + red[3])) + ((red[4] + red[5]) + (red[6] + red[7]));
-    criterion_tail(g, blockIdx.x, wg_sum, tid, red, 8);
+    criterion_rows<8>(g, smem, t, tid);
 }
 
 // The output layer on the bf16 matrix instruction (see lin_s6_kernel): 4 waves, wave w = columns 32 w .. 32 w + 31 of all 64
 // rows (two accumulators), A split once per workgroup into the plane image, W3' planes from L2 into registers.  32 KB of
-// LDS, 139 VGPRs: THREE workgroups per CU (at four = 128 VGPRs the 64-row loop reloads from scratch behind vmcnt(0), see
-// lin_s6_plain_kernel).  Epilogue as lin_out_kernel's, with 16 instead of 8 frames per wave.
+// LDS, 138 VGPRs: THREE workgroups per CU (at four = 128 VGPRs the 64-row loop reloads from scratch behind vmcnt(0), see
+// lin_s6_plain_kernel).  Epilogue as lin_out_kernel's: criterion_rows with 16 instead of 8 frames per wave.
 constexpr int LOUT_WPS = 3;    // waves per SIMD = resident workgroups per CU of lin_out_s6_kernel
 __global__ __launch_bounds__(256, LOUT_WPS) void lin_out_s6_kernel(LinOutK g) {
     __shared__ __attribute__((aligned(16))) float smem[64 * ON];
     static_assert(64 * ON * 4 >= 2 * S6_BUF, "the epilogue's tile holds both plane images");
-    int bz, m0, rows;
-    const int tile = blockIdx.x;   // (an XCD-contiguous map of the tile list, xcd_contiguous(), was measured: 5-10 % slower)
-    if (tile < g.n_big) {
-        bz = tile / g.big_per_batch;
-        m0 = (tile - bz * g.big_per_batch) * 64;
-        rows = 64;
-    } else {
-        const int j = tile - g.n_big;
-        bz = j / g.small_per_batch;
-        m0 = g.big_per_batch_rows + (j - bz * g.small_per_batch) * 32;
-        rows = 32;
-    }
-    bz = __builtin_amdgcn_readfirstlane(bz);   // (scalar registers: see lin_s6_kernel)
-    m0 = __builtin_amdgcn_readfirstlane(m0);
+    const Tile t = tile_of<true>(g);
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int l31 = lane & 31, lh = lane >> 5;
     f32x16 acc[2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[i][r] = 0.f;
-    const uint16_t* bp = g.Bp + (long)bz * g.bp_batch;
-    const unsigned b_lane = (unsigned)((wave * 32 + l31) * 16 + lh * 8) * 2u;   // bytes
-    unsigned char* sm = reinterpret_cast<unsigned char*>(smem);
-    const float* A = g.A + (long)bz * g.a_batch + (long)m0 * g.lda;
-    const int wave_u = __builtin_amdgcn_readfirstlane(wave);
-    if (rows == 64) s6_main_loop<4, 2>(acc, sm, A, g.lda, g.M - m0, g.K, g.K, bp, b_lane, g.bp_plane, (long)g.bp_rows * 16, tid, lane, wave_u >= 2);
-    else s6_main_loop<4, 1>(acc, sm, A, g.lda, g.M - m0, g.K, g.K, bp, b_lane, g.bp_plane, (long)g.bp_rows * 16, tid, lane, wave_u >= 2);
+    s6_tile<4>(g, t, acc, reinterpret_cast<unsigned char*>(smem), 0, g.K, g.K, tid);
     // ---- epilogue.  D[row][col]: col = wave * 32 + l31, row = i * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh
     const int col = wave * 32 + l31;
-    const float bj = (g.bias && col < g.N) ? g.bias[(long)bz * g.bias_batch + col] : 0.f;
-    const int nblk = rows / 32;
+    const float bj = (g.bias && col < g.N) ? g.bias[(long)t.bz * g.bias_batch + col] : 0.f;
     if (g.tgt == nullptr) {
-        if (col < g.N) {
-            float* o0 = g.out + (long)bz * g.o_batch + col;
-#pragma unroll
-            for (int i = 0; i < 2; ++i)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const int row = m0 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
-                    if (i < nblk && row < g.M) o0[(long)row * g.ldo] = as_sigmoid(acc[i][r] + bj);
-                }
-        }
+        if (col < g.N) store_rows<2>(acc, g.out + (long)t.bz * g.o_batch + col, g.ldo, bj, 2, t.m0, g.M, t.tm, lh);
         return;
     }
     // fused criterion: sigmoid outputs through LDS ([64][ON]; every plane-image read is behind the loop's last barrier)
@@ -921,86 +851,9 @@ __global__ __launch_bounds__(256, LOUT_WPS) void lin_out_s6_kernel(LinOutK g) {
     for (int i = 0; i < 2; ++i)
 #pragma unroll
         for (int r = 0; r < 16; ++r)
-            if (i < nblk) smem[(i * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh) * ON + col] = as_sigmoid(acc[i][r] + bj);
+            if (i < t.tm) smem[(i * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh) * ON + col] = as_sigmoid(acc[i][r] + bj);
     as_lds_barrier();
-    const int Np = g.N >> 1;                                    // points per contour
-    float part = 0.f;
-    if (Np <= 64) {
-        // one wave per frame at a time, lanes over the points; ALL target coordinates of the wave's 16 frames are requested
-        // before the first store goes out (vector memory operations retire in order: a load issued behind a frame's stores
-        // waits for their acknowledgement -- two passes of 8 frames cost the second pass exactly that, see lin_out_kernel)
-        const int nl = min(lane, Np - 1);
-        float tx[16], ty[16];
-        bool in[16], valid[16];
-#pragma unroll
-        for (int k = 0; k < 16; ++k) {
-            const int r = wave_u + 4 * k;
-            const int frame = m0 + r;
-            in[k] = r < rows && frame < g.M;
-            const int fc = in[k] ? frame : m0;
-            const int b = fc / g.T, t = fc - b * g.T;
-            valid[k] = in[k] && t < g.lengths[b];
-            const float* tg = g.tgt + (((long)b * g.tgt_T + t) * g.batch + bz) * g.N;
-            tx[k] = tg[nl];
-            ty[k] = tg[Np + nl];
-        }
-#pragma unroll
-        for (int k = 0; k < 16; ++k) {
-            if (!in[k]) continue;                       // wave-uniform
-            const int r = wave_u + 4 * k;
-            const long frame = m0 + r;
-            float* o = g.out + frame * g.ldo + (long)bz * g.o_batch;
-            float* dz = g.dout + frame * g.ldo + (long)bz * g.o_batch;
-            if (lane < Np) {
-                const float ox = smem[r * ON + lane], oy = smem[r * ON + Np + lane];
-                o[lane] = ox;
-                o[Np + lane] = oy;
-                float gx = 0.f, gy = 0.f;
-                if (valid[k]) {
-                    const float dx = ox - tx[k], dy = oy - ty[k];
-                    const float d = sqrtf(dx * dx + dy * dy);
-                    part += d;
-                    const float gg = g.scale / d;                   // NaN at zero distance, as torch autograd
-                    gx = dx * gg * ox * (1.f - ox);                  // through the sigmoid (same product order as the unfused kernels)
-                    gy = dy * gg * oy * (1.f - oy);
-                }
-                dz[lane] = gx;
-                dz[Np + lane] = gy;
-            }
-        }
-    } else
-    for (int r = wave_u; r < rows; r += 4) {
-        const int frame = m0 + r;
-        if (frame >= g.M) break;
-        const int b = frame / g.T, t = frame - b * g.T;
-        const bool valid = t < g.lengths[b];
-        float* o = g.out + (long)frame * g.ldo + (long)bz * g.o_batch;
-        float* dz = g.dout + (long)frame * g.ldo + (long)bz * g.o_batch;
-        const float* tg = g.tgt + (((long)b * g.tgt_T + t) * g.batch + bz) * g.N;
-        for (int n = lane; n < Np; n += 64) {
-            const float ox = smem[r * ON + n], oy = smem[r * ON + Np + n];
-            o[n] = ox;
-            o[Np + n] = oy;
-            float gx = 0.f, gy = 0.f;
-            if (valid) {
-                const float dx = ox - tg[n], dy = oy - tg[Np + n];
-                const float d = sqrtf(dx * dx + dy * dy);
-                part += d;
-                const float gg = g.scale / d;
-                gx = dx * gg * ox * (1.f - ox);
-                gy = dy * gg * oy * (1.f - oy);
-            }
-            dz[n] = gx;
-            dz[Np + n] = gy;
-        }
-    }
-    part = as_wave_sum_dpp(part);
-    __shared__ float red[4];
-    if (lane == 0) red[wave] = part;
-    __syncthreads();
-    float wg_sum = 0.f;
-    if (tid == 0) wg_sum = (red[0] + red[1]) + (red[2] + red[3]);   // (tile order, like lin_out_kernel: same final sum order)
-    criterion_tail(g, tile, wg_sum, tid, red, 4);
+    criterion_rows<4>(g, smem, t, tid);
 }
 
 // The kernels' tile list from x, the number of 64-row tiles per batch member: those are dispatched first, then the remaining
@@ -1054,7 +907,6 @@ LinK lin_args(const as_lin* a) {
     k.C = a->C; k.ldc = a->ldc; k.c_batch = a->c_batch;
     k.bias = a->bias; k.bias_batch = a->bias_batch;
     k.M = a->M; k.N = a->N; k.K = a->K; k.ka_valid = a->ka_valid > 0 ? a->ka_valid : a->K; k.batch = a->batch; k.act = a->act;
-    k.tile_rows = a->tile_rows;
     k.eps = 1e-5f;
     k.dbg = g_dbg; k.dbg_max = g_dbg_max;
     k.rstd = a->rstd; k.bits = a->bits;
@@ -1062,14 +914,11 @@ LinK lin_args(const as_lin* a) {
     return k;
 }
 
-// Tile list for two workgroups per CU = 512 slots (whole_round_tiles), or what as_lin.tile_rows asks for
+// Tile list for two workgroups per CU = 512 slots (whole_round_tiles)
 template <bool B_KC, int EPI>
 int launch(const LinK& k, hipStream_t st) {
     LinK kk = k;
-    int x = whole_round_tiles(k.M, k.batch, 512, false);
-    if (k.tile_rows == 64) x = k.M / 64;
-    if (k.tile_rows == 32) x = 0;
-    const long total = tile_list(kk, x);
+    const long total = tile_list(kk, whole_round_tiles(k.M, k.batch, 512, false));
     // with B as planes the products run on the bf16 matrix instruction (lin_s6_kernel)
     if (kk.Bp) hipLaunchKernelGGL((lin_s6_kernel<EPI>), dim3((unsigned)total), dim3(NT), 0, st, kk);
     else hipLaunchKernelGGL((lin_f32_kernel<64, B_KC, EPI>), dim3((unsigned)total), dim3(NT), 0, st, kk);
@@ -1122,10 +971,8 @@ int as_lin_plain_s6(const as_lin* a, int ksplit, long c_split, hipStream_t st, i
     ksplit = as_cdiv(a->K, k.kchunk);
     k.c_split = c_split;
     // tiles: 64 rows unless that leaves CUs idle (fewer workgroups than 1.5 x 256)
-    int tile = a->tile_rows;
-    if (tile != 32 && tile != 64) tile = (long)as_cdiv(a->M, 64) * a->batch * ksplit >= 384 ? 64 : 32;
-    const int x = tile == 64 ? a->M / 64 : 0;
-    const long total = tile_list(k, x);
+    const bool rows64 = (long)as_cdiv(a->M, 64) * a->batch * ksplit >= 384;
+    const long total = tile_list(k, rows64 ? a->M / 64 : 0);
     if (total > (1L << 30) || ksplit > 65535) return 0;
     if (nw == 4 && waves_per_simd == 2) hipLaunchKernelGGL((lin_s6_plain_kernel<4, 2>), dim3((unsigned)total, ksplit), dim3(256), 0, st, k);
     else if (nw == 4) hipLaunchKernelGGL((lin_s6_plain_kernel<4, 4>), dim3((unsigned)total, ksplit), dim3(256), 0, st, k);

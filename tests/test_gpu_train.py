@@ -651,25 +651,30 @@ def test_hbm_resident_dataset_collates_like_the_host_collate(dev):
     assert a["loss"] == b["loss"]
 
 
-def test_criterion_fused_into_the_output_layer_equals_the_separate_kernel(dev):
+@pytest.mark.parametrize("n_samp,T", [(50, 100), (64, 101), (2, 101)])
+def test_criterion_fused_into_the_output_layer_equals_the_separate_kernel(dev, n_samp, T):
     """TrainStep asks as_artspeech_fwd to fuse the masked Euclidean criterion (and its gradient through the sigmoid) into the
     epilogue of the heads' output layer (as_opts.loss_*).  Against the same engine with the separate criterion kernel:
-    contours and every gradient bit for bit (same arithmetic per element), the loss to summation order (1e-7)."""
+    contours and every gradient bit for bit (same arithmetic per element), the loss to summation order (1e-7).
+    n_samp = 64: 128 outputs, the kernel's full column tile, every lane of a wave owns a point; n_samp = 2: 4 outputs, the
+    least the kernel takes, 62 lanes idle.  T = 101: 808 frames = twelve 64-row tiles, then a full and an 8-row 32-row tile
+    per head.  In the default arithmetic this is lin_out_s6_kernel's epilogue (4 waves), in the exact one (the twin below)
+    lin_out_kernel's (8 waves)."""
     from artspeech_amd.engine import TrainStep
     from artspeech_amd.phoneme_to_articulation.encoder_decoder.models import ArtSpeech
-    V, A, B, T = 45, 4, 8, 100                      # 800 frames: 64-row tiles + a ragged 32-row tail per head
-    lengths = torch.tensor([100, 97, 64, 63, 40, 33, 8, 1], dtype=torch.int32)
+    V, A, B = 45, 4, 8                              # T = 100: 800 frames, 64-row tiles + a ragged 32-row tail per head
+    lengths = torch.tensor([T, 97, 64, 63, 40, 33, 8, 1], dtype=torch.int32)
     g = torch.Generator().manual_seed(5)
     x = torch.randint(1, V, (B, T), generator=g)
-    tgt = torch.rand(B, T + 3, A, 2, 50, generator=g)       # targets padded beyond T: tgt_T > T
+    tgt = torch.rand(B, T + 3, A, 2, n_samp, generator=g)   # targets padded beyond T: tgt_T > T
     for b, l in enumerate(lengths):
         x[b, l:] = 0
     x, tgt, ld = x.to(dev), tgt.to(dev), lengths.to(dev)
-    scale = 1.0 / (float(lengths.sum()) * A * 50)
+    scale = 1.0 / (float(lengths.sum()) * A * n_samp)
     res = []
     for fused in (False, True):
         torch.manual_seed(2)
-        model = ArtSpeech(V, A).to(dev)
+        model = ArtSpeech(V, A, n_samples=n_samp).to(dev)
         step = TrainStep(model, B, T, optimizer=False)
         assert step.fuse_loss
         step.fuse_loss = fused
@@ -680,6 +685,13 @@ def test_criterion_fused_into_the_output_layer_equals_the_separate_kernel(dev):
     assert torch.equal(res[0][1], res[1][1]), "d loss / d(pre-sigmoid) differs"
     assert torch.equal(res[0][2], res[1][2]), "gradients differ"
     assert abs(res[0][3] - res[1][3]) < 1e-7 and np.isfinite(res[0][3])
+
+
+@pytest.mark.parametrize("n_samp,T", [(50, 100), (64, 101), (2, 101)])
+def test_criterion_fused_into_the_output_layer_equals_the_separate_kernel_exact_fp32(dev, matrix_arith, n_samp, T):
+    """The same in the exact-fp32 matrix arithmetic: the fused criterion is then lin_out_kernel's epilogue."""
+    matrix_arith(0)
+    test_criterion_fused_into_the_output_layer_equals_the_separate_kernel(dev, n_samp, T)
 
 
 def test_rccl_single_rank_engine_is_bit_identical(dev):

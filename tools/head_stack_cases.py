@@ -35,6 +35,9 @@ HEAD_CASES = [
     (300, 70, 512),   # l1 general (300 % 16 = 12); dx1 general (H > 256); lin plain
     (300, 50, 37),
 ]
+# (H, N, rows) at A = 11 heads: 48 x 11 = 528 whole 64-row tiles, from 512 on the 64-row loops of lin_s6_kernel run (rows and
+# shapes of tests/test_gpu_head_tiles.py); the cases above stay below that and run its 32-row loops only
+WIDE_HEAD_CASES = [(128, 50, 3021), (96, 40, 3021)]
 
 
 def sha(t):
@@ -134,6 +137,8 @@ def main():
         L.as_set_matrix_arith(mode)
         for H, N, rows in HEAD_CASES:
             emit(f"head H={H} N={N} rows={rows}", mode, head_case(torch, _lib, dev, H, N, rows))
+        for H, N, rows in WIDE_HEAD_CASES:
+            emit(f"head A=11 H={H} N={N} rows={rows}", mode, head_case(torch, _lib, dev, H, N, rows, A=11))
         for ov in ((0, 1) if args.overlap == "both" else (int(args.overlap),)):
             L.as_set_overlap(ov)
             for H in (128, 64):     # H = 128: the trunk's weight gradient rides in the multi launch (2H = 256); H = 64: it does not
@@ -142,6 +147,10 @@ def main():
             emit(f"ArtSpeech dropout H=128 4x128 overlap={ov}", mode, model_case(torch, dev, ArtSpeech, 128, 50, 4, 128, True, 0.3, 12))
             emit(f"engine defer_dw2 H=128 4x128 overlap={ov}", mode, engine_case(torch, dev, 128, 50, 4, 128, True, 13))
             emit(f"engine separate criterion N=70 H=128 4x128 overlap={ov}", mode, engine_case(torch, dev, 128, 70, 4, 128, False, 14))
+            # 808 frames: 64-row tiles, a full and an 8-row 32-row tile per head; the fused criterion at its widest (a point per
+            # lane) and at its narrowest (4 outputs)
+            for N in (64, 2):
+                emit(f"engine fused criterion N={N} H=128 8x101 overlap={ov}", mode, engine_case(torch, dev, 128, N, 8, 101, False, 16))
         L.as_set_overlap(1)
         for p in (0.0, 0.3):
             emit(f"SimpleArtSpeech dropout={p} 4x128", mode, model_case(torch, dev, SimpleArtSpeech, 128, 50, 4, 128, False, p, 15))
