@@ -22,16 +22,20 @@
 // Epilogue, 32 rows at a time: the accumulators go to LDS (the ring's memory), then one wave per row does exactly what
 // normalize_fwd_kernel / normalize_bwd_kernel (rowops.hip) do, reading the GEMM result from LDS instead of HBM.
 //
-// The file, top to bottom: what the five kernels share around their main loops, each written once (tile_of: tile-list decode,
+// The file, top to bottom: what the kernels share around their main loops, each written once (tile_of: tile-list decode,
 // Stamps: debug stamps, store_rows: the plain store); the LayerNorm epilogues; lin_f32_kernel (exact fp32, described above); the
-// split-arithmetic main loop s6_main_loop, its entry s6_tile, and lin_s6_kernel / lin_s6_plain_kernel on it; the output layer
-// (criterion_rows: the fused criterion; lin_out_kernel, lin_out_s6_kernel); the host half (tile lists, argument copies,
+// split-arithmetic main loop s6_main_loop, its entry s6_tile, and lin_s6_kernel on it; the short reductions (K <= 128: the whole
+// A image resident, s6_resident_loop without barriers; lin_s6_lnf_shared_kernel = Linear 1, one image per row tile for a group
+// of heads, lin_s6_lnb_short_kernel = dx3); lin_s6_plain_kernel; the output layer (criterion_rows: the fused criterion;
+// lin_out_kernel, lin_out_s6_kernel); the host half (tile lists, argument copies, launch_short_k and as_set_head_short_k,
 // as_lin_try, as_lin_plain_s6, as_lin_out_try, as_linear_fwd).  The kernels differ in their main loops and in which of the
 // shared pieces they call.
 #include <cstdlib>
 
+#include <atomic>
 #include <type_traits>
 
+#include "as_launch.h"
 #include "gemm_internal.h"
 #include "split_arith.h"
 
@@ -49,6 +53,7 @@ struct LinK {
     const float* bias; long bias_batch;
     int M, N, K, ka_valid, batch, act;
     int n_big, big_per_batch, big_per_batch_rows, small_per_batch;   // tiles of 64 rows first, then tiles of 32 rows (see tile_list())
+    int groups;                       // lin_s6_lnf_shared_kernel: head groups (the tile list then counts groups, not heads)
     unsigned long long* dbg; long dbg_max;   // diagnostic cycle stamps (as_lin_debug_stamps), normally null
     float eps;
     float* rstd;                      // EPI_LNF out: [M][batch]
@@ -604,6 +609,197 @@ __global__ __launch_bounds__(NT, 4) void lin_s6_kernel(LinK g) {
     stamps.end();
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// Short reductions (K <= S6R_MAXK = 128: Linear 1 at H <= 128, dx3): the plane image of the tile's WHOLE A operand fits in
+// LDS at once ([nk][plane][64 rows][32 k] bf16: nk x S6_BUF <= 48 KB), so the k-loop needs neither the A pipeline nor its
+// barriers.  s6_main_loop is built for long reductions -- per 32-deep k-tile an A load two tiles ahead, a split, an LDS store
+// and a barrier -- at four k-tiles four barriers and four load-to-fragment chains for 6.1 k cycles of matrix instructions
+// (loop 14.6 k cycles per workgroup, here 10.3 k; what that is worth in time: DESIGN 5, "Short reductions" -- the two tenants
+// of a CU meet in their epilogues, and most of Linear 1's gain is the image it shares).  Here every thread requests its A values of
+// all k-tiles up front, splits them into the image, ONE barrier follows, and the 2 nk k-steps run with the B look-ahead, the
+// fragment reads and the MFMAs only.  Every accumulator sees the sequence it sees in s6_main_loop (k-steps ascending, the six
+// plane products in the same order): the results are bit-identical.  8-wave workgroups (one float4 per thread and k-tile).
+constexpr int S6R_MAXK = 128, S6R_MAXT = S6R_MAXK / S6_BK;
+
+// This thread's A values of all k-tiles (s6_main_loop's a_load for every tile at once: row clamped to rows_valid - 1, tiles
+// beyond nk repeat the last one, chunks at or beyond ka_valid re-read chunk 0 of the row) ...
+__device__ __forceinline__ void s6r_image_load(f32x4 (&aq)[S6R_MAXT], const float* __restrict__ A, long lda, int rows_valid, int nk, int ka_valid,
+                                               int tid) {
+    const int a_chunk = tid & 7, row = tid >> 3;
+    const unsigned a_off = (unsigned)(min(row, rows_valid - 1) * (int)lda + a_chunk * 4) * 4u;   // bytes
+    const gptr Au = as_uniform_ptr(A);
+#pragma unroll
+    for (int q = 0; q < S6R_MAXT; ++q) {
+        const int kt = min(q, nk - 1);
+        const unsigned ko = kt * S6_BK + a_chunk * 4 + 4 <= ka_valid ? (unsigned)(kt * S6_BK) * 4u : 0u - (unsigned)a_chunk * 16u;
+        aq[q] = *reinterpret_cast<gptr_f4>(Au + (a_off + ko));
+    }
+}
+// ... and their planes into the image (s6_main_loop's a_store; a repeated tile writes the same bytes to the same place)
+__device__ __forceinline__ void s6r_image_store(const f32x4 (&aq)[S6R_MAXT], unsigned char* sm, int nk, int tid) {
+    const int a_chunk = tid & 7, row = tid >> 3;
+    const int a_wr = row * 64 + (((a_chunk >> 1) ^ ((row >> 2) & 3)) * 16) + (a_chunk & 1) * 8;
+#pragma unroll
+    for (int q = 0; q < S6R_MAXT; ++q) {
+        unsigned h0, m0, l0, h1, m1, l1;
+        split_pair(aq[q].x, aq[q].y, h0, m0, l0);
+        split_pair(aq[q].z, aq[q].w, h1, m1, l1);
+        unsigned char* d = sm + min(q, nk - 1) * S6_BUF + a_wr;
+        *reinterpret_cast<uint2*>(d) = make_uint2(h0, h1);
+        *reinterpret_cast<uint2*>(d + S6_PLANE) = make_uint2(m0, m1);
+        *reinterpret_cast<uint2*>(d + 2 * S6_PLANE) = make_uint2(l0, l1);
+    }
+}
+
+// The B fragments of one head as the loops address them (s6_tile's arguments) and the load of k-step j into a register set
+struct S6B { const uint16_t* bp; long bp_plane, bp_step; unsigned b_lane; int nj; };
+template <typename K>
+__device__ __forceinline__ S6B s6_b_of(const K& g, int bz, int nk, int tid) {
+    const int lane = tid & 63, wave = tid >> 6;
+    S6B b;
+    b.bp_step = (long)g.bp_rows * 16;
+    b.bp = g.Bp + (long)bz * g.bp_batch;
+    b.bp_plane = g.bp_plane;
+    b.b_lane = (unsigned)((wave * 32 + (lane & 31)) * 16 + (lane >> 5) * 8) * 2u;   // bytes
+    b.nj = 2 * nk;
+    return b;
+}
+__device__ __forceinline__ void s6_b_load(u32x4 (&dst)[3], const S6B& b, int j) {
+    j = min(j, b.nj - 1);
+#pragma unroll
+    for (int p = 0; p < 3; ++p) dst[p] = *reinterpret_cast<gptr_u4>(as_uniform_ptr(b.bp + p * b.bp_plane + j * b.bp_step) + b.b_lane);
+}
+
+// The k-steps over a resident image (complete behind a barrier).  bq[0], bq[1]: k-steps 0 and 1 of B, requested by the caller
+// (in front of the image's split, or of the previous head's epilogue); the look-ahead stays two k-steps in three name-rotated
+// register sets as in s6_main_loop, and so does the tail tiles' opaque lane index.
+template <int TME>
+__device__ __forceinline__ void s6_resident_loop(f32x16 (&acc)[2], const unsigned char* sm, int nk, const S6B& b, u32x4 (&bq)[3][3], int lane) {
+    const int l31 = lane & 31;
+    int sw = (l31 >> 2) & 3;
+    const unsigned char* a_rd = sm + l31 * 64;
+    int lh_rd = lane >> 5;
+    auto tile = [&](auto Uc, int kt) {
+        constexpr int U = decltype(Uc)::value;
+        const unsigned char* img = a_rd + kt * S6_BUF;
+#pragma unroll
+        for (int s = 0; s < 2; ++s) {
+            s6_b_load(bq[(2 * U + s + 2) % 3], b, 2 * kt + s + 2);
+            __builtin_amdgcn_sched_barrier(0);   // the look-ahead loads stay HERE, two k-steps in front of their first use
+            bf16x8 fa[TME][3];
+#pragma unroll
+            for (int p = 0; p < 3; ++p)
+#pragma unroll
+                for (int i = 0; i < TME; ++i)
+                    fa[i][p] = *reinterpret_cast<const bf16x8*>(img + p * S6_PLANE + i * 32 * 64 + (((2 * s + lh_rd) ^ sw) * 16));
+            const u32x4(&bs)[3] = bq[(2 * U + s) % 3];
+            bf16x8 fb[3];
+#pragma unroll
+            for (int p = 0; p < 3; ++p) fb[p] = __builtin_bit_cast(bf16x8, bs[p]);
+            constexpr int PA[6] = {0, 0, 0, 1, 1, 2}, PB[6] = {0, 1, 2, 0, 1, 0};   // s6_main_loop's order
+#pragma unroll
+            for (int o = 0; o < 6; ++o)
+#pragma unroll
+                for (int i = 0; i < TME; ++i)
+                    acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[i][PA[o]], fb[PB[o]], acc[i], 0, 0, 0);
+            __builtin_amdgcn_sched_barrier(0);
+        }
+    };
+    int kt = 0;
+    if (nk >= 3) {
+        tile(IC<0>{}, 0);
+        tile(IC<1>{}, 1);
+        tile(IC<2>{}, 2);
+        kt = 3;
+    }
+    {
+        int ln = lane;
+        asm volatile("" : "+v"(ln));
+        lh_rd = ln >> 5;
+        sw = ((ln & 31) >> 2) & 3;
+        a_rd = sm + (ln & 31) * 64;
+    }
+    if (kt < nk) tile(IC<0>{}, kt);
+    if (kt + 1 < nk) tile(IC<1>{}, kt + 1);
+}
+__device__ __forceinline__ void s6_zero(f32x16 (&acc)[2]) {
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[i][r] = 0.f;
+}
+
+// Linear 1 (EPI_LNF, every head reads the same x_hat: a_batch == 0) from ONE image per row tile: a workgroup owns a row tile
+// and group t.bz of g.groups groups of consecutive heads (the tile list counts groups where lin_s6_kernel's counts heads),
+// builds the image once and runs, head after head, the resident loop on that head's planes and lin_ln_rows into that head's
+// C, rstd and bits.  The next head's first two B fragments are requested in front of the epilogue.  The image lives across
+// the heads, so the epilogue's 32 KB staging area lies BEHIND it: nk x 12 + 32 KB of dynamic LDS (80 KB at K = 128: two
+// workgroups take the CU's whole 160 KB).
+__global__ __launch_bounds__(NT, 4) void lin_s6_lnf_shared_kernel(LinK g) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char dsm[];
+    const Tile t = tile_of<true>(g);
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const Stamps stamps(g, tid);
+    stamps.begin();
+    const int nk = g.K / S6_BK;
+    float* stage = reinterpret_cast<float*>(dsm + nk * S6_BUF);
+    const int h0 = t.bz * g.batch / g.groups, h1 = (t.bz + 1) * g.batch / g.groups;
+    f32x4 aq[S6R_MAXT];
+    u32x4 bq[3][3];
+    s6r_image_load(aq, g.A + (long)t.m0 * g.lda, g.lda, g.M - t.m0, nk, g.ka_valid, tid);
+    S6B b = s6_b_of(g, h0, nk, tid);
+    s6_b_load(bq[0], b, 0);
+    s6_b_load(bq[1], b, 1);
+    s6r_image_store(aq, dsm, nk, tid);
+    as_lds_barrier();
+    stamps.mark(1);
+    const int col = wave * 32 + (lane & 31);
+    for (int h = h0; h < h1; ++h) {
+        f32x16 acc[2];
+        s6_zero(acc);
+        if (t.tm == 2) s6_resident_loop<2>(acc, dsm, nk, b, bq, lane);
+        else s6_resident_loop<1>(acc, dsm, nk, b, bq, lane);
+        b = s6_b_of(g, min(h + 1, h1 - 1), nk, tid);   // (behind the last head: a repeat)
+        s6_b_load(bq[0], b, 0);
+        s6_b_load(bq[1], b, 1);
+        const float bj = g.bias ? g.bias[(long)h * g.bias_batch + col] : 0.f;
+        if (h > h0) as_lds_barrier();    // the previous head's staged rows are all read
+        lin_ln_rows<2, EPI_LNF, 8>(g, acc, stage, h, t.m0, t.tm, 1, wave, lane, bj);
+    }
+    stamps.mark(2);                      // (slot 2 - slot 1: every head's loop and epilogue)
+    stamps.end();
+}
+
+// dx3 (EPI_LNB at Npad <= 128) on the resident loop: one head per workgroup as in lin_s6_kernel; the image is dead behind the
+// loop, so the epilogue's staging area lies over it: 48 KB, two workgroups per CU.
+__global__ __launch_bounds__(NT, 4) void lin_s6_lnb_short_kernel(LinK g) {
+    constexpr int EPIT = 32 * BN;
+    __shared__ __attribute__((aligned(16))) unsigned char sm[S6R_MAXT * S6_BUF];
+    static_assert(S6R_MAXT * S6_BUF >= EPIT * 4, "the image's memory holds the epilogue's staging area");
+    const Tile t = tile_of<true>(g);
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const Stamps stamps(g, tid);
+    stamps.begin();
+    const int nk = g.K / S6_BK;
+    f32x4 aq[S6R_MAXT];
+    u32x4 bq[3][3];
+    s6r_image_load(aq, g.A + (long)t.bz * g.a_batch + (long)t.m0 * g.lda, g.lda, g.M - t.m0, nk, g.ka_valid, tid);
+    const S6B b = s6_b_of(g, t.bz, nk, tid);
+    s6_b_load(bq[0], b, 0);
+    s6_b_load(bq[1], b, 1);
+    s6r_image_store(aq, sm, nk, tid);
+    as_lds_barrier();
+    stamps.mark(1);
+    f32x16 acc[2];
+    s6_zero(acc);
+    if (t.tm == 2) s6_resident_loop<2>(acc, sm, nk, b, bq, lane);
+    else s6_resident_loop<1>(acc, sm, nk, b, bq, lane);
+    stamps.mark(2);
+    as_lds_barrier();                    // every wave's fragments are in registers: the staging area may overwrite the image
+    lin_ln_rows<2, EPI_LNB, 8>(g, acc, reinterpret_cast<float*>(sm), t.bz, t.m0, t.tm, 1, wave, lane, 0.f);
+    stamps.end();
+}
+
 // A plain Linear on the same main loop: C = act(A . B^T + bias), 64 (or 32) rows x 32 NW columns per workgroup (NW = 8:
 // N <= 256, NW = 4: N <= 128; four workgroups per CU at NW = 4), optionally split over K (gridDim.y chunks of kchunk, each
 // writing its partial sums -- no bias, no activation -- to its own slab C + y * c_split: the consumer adds them in a fixed order).
@@ -896,6 +1092,9 @@ bool take_planes(K& k, const L* a, int min_rows) {
     return true;
 }
 
+// as_set_head_short_k (include/artspeech_hip.h)
+std::atomic<int> g_short_k{1};
+
 unsigned long long* g_dbg = nullptr;
 long g_dbg_max = 0;
 
@@ -914,9 +1113,48 @@ LinK lin_args(const as_lin* a) {
     return k;
 }
 
+
+// The short-reduction kernels for a layer whose planes were taken: *took = launched; else it is not their case (lin_s6_kernel
+// runs).  Returns a launch error or 0.
+//   dx3: lin_s6_kernel's tile list.
+//   Linear 1: as many head groups as keep the launch within ONE round of the 512 resident slots (at 6400 frames and 11 heads
+//   5 groups of 2, 2, 2, 2, 3 heads x 100 row tiles = 500 workgroups), 64-row tiles + a ragged end unless that leaves CUs idle
+//   (fewer workgroups than 1.5 x 256: 32-row tiles then).  Measured at 6400 x 11 (profiles/head_short_k_ab.log): 5 or 6 groups
+//   -4 us against lin_s6_kernel, 11 groups (one head each) -1, 4 groups no gain, 3 and fewer slower -- the longest workgroup
+//   sets the time.
+int launch_short_k(const LinK& k, int epi, hipStream_t st, bool* took) {
+    *took = false;
+    if (!g_short_k.load(std::memory_order_relaxed) || !k.Bp || k.K > S6R_MAXK) return 0;
+    LinK kk = k;
+    if (epi == EPI_LNB) {
+        const long total = tile_list(kk, whole_round_tiles(k.M, k.batch, 512, false));
+        hipLaunchKernelGGL(lin_s6_lnb_short_kernel, dim3((unsigned)total), dim3(NT), 0, st, kk);
+        AS_LAUNCH_CHECK("as_lin_s6_lnb_short");
+        *took = true;
+        return 0;
+    }
+    if (epi != EPI_LNF || k.a_batch != 0) return 0;
+    const int lds = (k.K / S6_BK) * S6_BUF + 32 * BN * 4;
+    if (lds > 64 * 1024 && as_allow_dynamic_lds(lin_s6_lnf_shared_kernel, lds) != hipSuccess) return 0;
+    const int row_tiles = as_cdiv(k.M, 64);
+    kk.groups = 512 / row_tiles < 1 ? 1 : 512 / row_tiles > k.batch ? k.batch : 512 / row_tiles;
+    kk.batch = kk.groups;                // the tile list counts head groups
+    const long total = tile_list(kk, (long)row_tiles * kk.groups >= 384 ? k.M / 64 : 0);
+    kk.batch = k.batch;
+    hipLaunchKernelGGL(lin_s6_lnf_shared_kernel, dim3((unsigned)total), dim3(NT), lds, st, kk);
+    AS_LAUNCH_CHECK("as_lin_s6_lnf_shared");
+    *took = true;
+    return 0;
+}
+
 // Tile list for two workgroups per CU = 512 slots (whole_round_tiles)
 template <bool B_KC, int EPI>
 int launch(const LinK& k, hipStream_t st) {
+    if (EPI != EPI_PLAIN) {
+        bool took;
+        const int e = launch_short_k(k, EPI, st, &took);
+        if (e || took) return e;
+    }
     LinK kk = k;
     const long total = tile_list(kk, whole_round_tiles(k.M, k.batch, 512, false));
     // with B as planes the products run on the bf16 matrix instruction (lin_s6_kernel)
@@ -932,6 +1170,8 @@ extern "C" void as_lin_debug_stamps(uint64_t* buf, int64_t max_workgroups) {
     g_dbg = (unsigned long long*)buf;
     g_dbg_max = buf ? max_workgroups : 0;
 }
+
+extern "C" void as_set_head_short_k(int32_t on) { g_short_k.store(on ? 1 : 0, std::memory_order_relaxed); }
 
 // see gemm_internal.h.  Returns 1 if launched, 0 if the arguments are outside what the kernel is built for (the caller
 // then takes the general GEMM + row kernels), < 0 on a launch error.

@@ -156,6 +156,12 @@ int as_copy_f32(const float* src, float* dst, int64_t n, void* stream);
 void as_set_matrix_arith(int32_t mode);
 int32_t as_get_matrix_arith(void);
 
+/* The head layers whose reduction is at most 128 deep (Linear 1 at H <= 128, H % 32 == 0; the input gradient of the output layer,
+ * "dx3") run, in mode 1 above, on kernels that keep the tile's whole split A operand resident in LDS (csrc/lin_f32.hip).
+ * as_set_head_short_k(0) selects the long-reduction kernels that every other head layer uses, for both; the results are the
+ * same bit for bit.  Default on.  Process-wide; read at launch time.  For tests and A/B timings. */
+void as_set_head_short_k(int32_t on);
+
 /* Data-parallel hook: make `waiting_stream` wait until the most recent as_artspeech_bwd enqueued on `compute_stream` (same
  * device) has finished the gradients of the trunk Linear and of all heads, i.e. the tail [layout.lin_w, layout.total) of
  * the flat gradient buffer (74 % of the parameters) -- their all-reduce can then run while the GRU backward recurrences
