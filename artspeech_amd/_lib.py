@@ -137,6 +137,7 @@ PROTOTYPES = {
     "as_set_matrix_arith": (None, [_I32]),
     "as_get_matrix_arith": (_I32, []),
     "as_set_head_short_k": (None, [_I32]),
+    "as_set_lin_out_row_epilogue": (None, [_I32]),
     "as_conv3x3_stem": (_I32, [_P, _I64, _I64, _I64, _I64, _P, _P, _P, _P, _I32, _I32, _I32, _I32, _S]),
     "as_conv3x3_c32": (_I32, [_P, _P, _P, _P, _P, _I32, _I32, _I32, _S]),
     "as_ln_feat_gelu": (_I32, [_P, _P, _P, _P, _I64, _I32, _I32, _S]),

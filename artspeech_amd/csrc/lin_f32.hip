@@ -26,8 +26,9 @@
 // Stamps: debug stamps, store_rows: the plain store); the LayerNorm epilogues; lin_f32_kernel (exact fp32, described above); the
 // split-arithmetic main loop s6_main_loop, its entry s6_tile, and lin_s6_kernel on it; the short reductions (K <= 128: the whole
 // A image resident, s6_resident_loop without barriers; lin_s6_lnf_shared_kernel = Linear 1, one image per row tile for a group
-// of heads, lin_s6_lnb_short_kernel = dx3); lin_s6_plain_kernel; the output layer (criterion_rows: the fused criterion;
-// lin_out_kernel, lin_out_s6_kernel); the host half (tile lists, argument copies, launch_short_k and as_set_head_short_k,
+// of heads, lin_s6_lnb_short_kernel = dx3); lin_s6_plain_kernel; the output layer (criterion_rows: the fused criterion,
+// criterion_rows_f4: the same through float4 rows; lin_out_kernel, lin_out_s6_kernel); the host half (tile lists, argument
+// copies, launch_short_k and as_set_head_short_k, as_set_lin_out_row_epilogue,
 // as_lin_try, as_lin_plain_s6, as_lin_out_try, as_linear_fwd).  The kernels differ in their main loops and in which of the
 // shared pieces they call.
 #include <cstdlib>
@@ -850,6 +851,7 @@ struct LinOutK {
     float* dout; float* partial;
     const uint16_t* Bp; long bp_plane, bp_batch; int bp_rows;   // lin_out_s6_kernel: W3' as bfloat16 planes (as_lin_out.Bp)
     float* loss; int* counter;                                  // the last workgroup sums the partials (as_lin_out.loss)
+    int row_epi;                                                // fused criterion through criterion_rows_f4 (as_lin_out_try decides)
 };
 
 // The criterion's workgroup sum goes out; with an arrival counter the workgroup that delivers the last one adds them all, thread
@@ -888,6 +890,38 @@ __device__ __forceinline__ void criterion_tail(const LinOutK& g, int tile, float
 // order, so a target load issued behind a frame's stores waits for their acknowledgement -- frame after frame, that chain was
 // most of this epilogue (and two passes of 8 frames cost the second pass of lin_out_s6_kernel exactly that).
 static_assert(ON / 2 <= 64, "criterion_rows: a lane owns one point of a frame");
+
+// One point of a frame: its distance added to `part`, d loss / d(pre-sigmoid) to gx, gy (zeros for a padded frame).  Written
+// once: criterion_rows and criterion_rows_f4 must round alike.
+__device__ __forceinline__ void criterion_point(float ox, float oy, float tx, float ty, bool valid, float scale, float& part, float& gx, float& gy) {
+    gx = 0.f;
+    gy = 0.f;
+    if (valid) {
+        const float dx = ox - tx, dy = oy - ty;
+        const float d = sqrtf(dx * dx + dy * dy);
+        part += d;
+        const float gg = scale / d;                     // NaN at zero distance, as torch autograd
+        gx = dx * gg * ox * (1.f - ox);                  // through the sigmoid (same product order as the unfused kernels)
+        gy = dy * gg * oy * (1.f - oy);
+    }
+}
+
+// The lanes' sums of a workgroup of NW waves -> one partial per tile (criterion_tail).
+template <int NW>
+__device__ __forceinline__ void criterion_sum(const LinOutK& g, float part, int tid) {
+    static_assert(NW == 4 || NW == 8, "the workgroup sum below");
+    part = as_wave_sum_dpp(part);
+    __shared__ float red[NW];
+    if ((tid & 63) == 0) red[tid >> 6] = part;
+    __syncthreads();
+    float wg_sum = 0.f;      // (tile order and wave order alike for 8 and for 4 waves: the same final sum order)
+    if (tid == 0) {
+        wg_sum = (red[0] + red[1]) + (red[2] + red[3]);
+        if (NW == 8) wg_sum = wg_sum + ((red[4] + red[5]) + (red[6] + red[7]));
+    }
+    criterion_tail(g, blockIdx.x, wg_sum, tid, red);
+}
+
 template <int NW>
 __device__ __forceinline__ void criterion_rows(const LinOutK& g, const float* tile, const Tile& t, int tid) {
     constexpr int FPW = 64 / NW;                                // frames per wave
@@ -923,29 +957,100 @@ __device__ __forceinline__ void criterion_rows(const LinOutK& g, const float* ti
             const float ox = tile[r * ON + lane], oy = tile[r * ON + Np + lane];
             o[lane] = ox;
             o[Np + lane] = oy;
-            float gx = 0.f, gy = 0.f;
-            if (valid[k]) {
-                const float dx = ox - tx[k], dy = oy - ty[k];
-                const float d = sqrtf(dx * dx + dy * dy);
-                part += d;
-                const float gg = g.scale / d;                   // NaN at zero distance, as torch autograd
-                gx = dx * gg * ox * (1.f - ox);                  // through the sigmoid (same product order as the unfused kernels)
-                gy = dy * gg * oy * (1.f - oy);
-            }
+            float gx, gy;
+            criterion_point(ox, oy, tx[k], ty[k], valid[k], g.scale, part, gx, gy);
             dz[lane] = gx;
             dz[Np + lane] = gy;
         }
     }
-    part = as_wave_sum_dpp(part);
-    __shared__ float red[NW];
-    if (lane == 0) red[wave] = part;
-    __syncthreads();
-    float wg_sum = 0.f;      // (tile order and wave order alike for 8 and for 4 waves: the same final sum order)
-    if (tid == 0) {
-        wg_sum = (red[0] + red[1]) + (red[2] + red[3]);
-        if (NW == 8) wg_sum = wg_sum + ((red[4] + red[5]) + (red[6] + red[7]));
+    criterion_sum<NW>(g, part, tid);
+}
+
+// The same criterion with row-contiguous 16-byte global accesses (LinOutK::row_epi: N % 4 == 0, out, dout and tgt 16-byte
+// aligned; as_set_lin_out_row_epilogue).  Above, a lane owns a point, so a frame costs two dword loads and four dword stores of
+// N / 2 live lanes each (200 bytes per instruction at N = 100): 6 x 64 / NW vector-memory instructions per lane and tile.  Here
+// the targets come in and out / d(out) leave as float4 chunks of whole rows, two rows per instruction (lanes 0-31 one row, lanes
+// 32-63 the next): 3 x 32 / NW instructions, and the arithmetic between them meets its operands in LDS.
+// The tile goes in halves of 32 rows (the accumulators' row blocks), so that the 32 KB the kernels own suffice:
+//   O[32][ON]  the half's sigmoid outputs, from write_half(IC<h>, O) (the kernel's accumulator layout);
+//   T[32][N]   the half's targets, then its d(out), overwritten in place.
+// All target loads of both halves are issued before the first store (vector memory operations retire in order).  The
+// arithmetic keeps criterion_rows' mapping -- wave w: rows w, w + NW, ...; lane p: point p; rows ascending through the first
+// half, then the second -- so every lane adds the same distances in the same order: out, dout and the partial sum are
+// criterion_rows' bit for bit.
+template <int NW, typename W>
+__device__ __forceinline__ void criterion_rows_f4(const LinOutK& g, float* smem, const Tile& t, int tid, W&& write_half) {
+    constexpr int FPH = 32 / NW;                                // frames per wave and half (arithmetic)
+    constexpr int PPH = 16 / NW;                                // row pairs per wave and half (global accesses)
+    const int lane = tid & 63;
+    const int wave_u = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int bz = t.bz, m0 = t.m0;
+    const int N = g.N, Np = N >> 1;
+    const int c4 = 4 * (lane & 31), hw = lane >> 5;             // this lane's chunk of its row; which row of the pair
+    const bool chunk = c4 < N;
+    float* O = smem;
+    float* T = smem + 32 * ON;
+    // Lane l works out utterance, time step and validity of tile row l ONCE (one division, one load of lengths[] per wave;
+    // criterion_rows does both per frame, and each of its 64 / NW loads of lengths[] is a round trip the next one waits for);
+    // a row's values are then read from its lane.  Rows beyond the tile or beyond M take row 0's (valid) target address and are
+    // not stored.
+    const int rows_in = min(32 * t.tm, g.M - m0);
+    const int fc = lane < rows_in ? m0 + lane : m0;
+    const int b_l = fc / g.T, t_l = fc - b_l * g.T;
+    const int len_l = g.lengths[b_l];
+    // rows of pair j of half h: 32 h + 2 * (j * NW + wave) + hw
+    bool stored[2][PPH];
+    f32x4 tq[2][PPH];
+#pragma unroll
+    for (int h = 0; h < 2; ++h)
+#pragma unroll
+        for (int j = 0; j < PPH; ++j) {
+            const int r0 = 32 * h + 2 * (j * NW + wave_u);
+            stored[h][j] = r0 + hw < rows_in;
+            tq[h][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+            if (h >= t.tm) continue;                    // a 32-row tile has no second half
+            const long off0 = (((long)__builtin_amdgcn_readlane(b_l, r0) * g.tgt_T + __builtin_amdgcn_readlane(t_l, r0)) * g.batch + bz) * N;
+            const long off1 = (((long)__builtin_amdgcn_readlane(b_l, r0 + 1) * g.tgt_T + __builtin_amdgcn_readlane(t_l, r0 + 1)) * g.batch + bz) * N;
+            if (chunk) tq[h][j] = *reinterpret_cast<const f32x4*>(g.tgt + (hw ? off1 : off0) + c4);
+        }
+    const unsigned long long vmask = __ballot(lane < rows_in && t_l < len_l);   // bit r: row r is a frame of its utterance
+    float part = 0.f;
+    auto half = [&](auto hc) {
+        constexpr int h = decltype(hc)::value;
+        write_half(hc, O);
+#pragma unroll
+        for (int j = 0; j < PPH; ++j)
+            if (chunk) *reinterpret_cast<f32x4*>(T + (2 * (j * NW + wave_u) + hw) * N + c4) = tq[h][j];
+        as_lds_barrier();
+#pragma unroll
+        for (int k = 0; k < FPH; ++k) {
+            const int r = wave_u + NW * k;
+            if (32 * h + r >= rows_in) continue;        // wave-uniform
+            if (lane < Np) {
+                float* tr = T + r * N;
+                float gx, gy;
+                criterion_point(O[r * ON + lane], O[r * ON + Np + lane], tr[lane], tr[Np + lane], (vmask >> (32 * h + r)) & 1, g.scale, part, gx, gy);
+                tr[lane] = gx;
+                tr[Np + lane] = gy;
+            }
+        }
+        as_lds_barrier();
+#pragma unroll
+        for (int j = 0; j < PPH; ++j) {
+            const int r = 2 * (j * NW + wave_u) + hw;
+            if (chunk && stored[h][j]) {
+                const long at = (long)(m0 + 32 * h + r) * g.ldo + (long)bz * g.o_batch + c4;
+                *reinterpret_cast<f32x4*>(g.out + at) = *reinterpret_cast<const f32x4*>(O + r * ON + c4);
+                *reinterpret_cast<f32x4*>(g.dout + at) = *reinterpret_cast<const f32x4*>(T + r * N + c4);
+            }
+        }
+    };
+    half(IC<0>{});
+    if (t.tm == 2) {
+        as_lds_barrier();                               // the second half reuses O and T
+        half(IC<1>{});
     }
-    criterion_tail(g, blockIdx.x, wg_sum, tid, red);
+    criterion_sum<NW>(g, part, tid);
 }
 
 __global__ __launch_bounds__(NT, 4) void lin_out_kernel(LinOutK g) {
@@ -1014,6 +1119,14 @@ __global__ __launch_bounds__(NT, 4) void lin_out_kernel(LinOutK g) {
         return;
     }
     // fused criterion: sigmoid outputs through LDS ([64][ON]; every ring read is behind the loop's last barrier)
+    if (g.row_epi) {                                // row block h is waves 4 h .. 4 h + 3's
+        criterion_rows_f4<8>(g, smem, t, tid, [&](auto hc, float* O) {
+            if (wm != decltype(hc)::value) return;
+#pragma unroll
+            for (int r = 0; r < 16; ++r) O[((r & 3) + 8 * (r >> 2) + 4 * lh) * ON + col] = as_sigmoid(acc[r] + bj);
+        });
+        return;
+    }
     if (active) {
 #pragma unroll
         for (int r = 0; r < 16; ++r) smem[(wm * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh) * ON + col] = as_sigmoid(acc[r] + bj);
@@ -1024,8 +1137,10 @@ __global__ __launch_bounds__(NT, 4) void lin_out_kernel(LinOutK g) {
 
 // The output layer on the bf16 matrix instruction (see lin_s6_kernel): 4 waves, wave w = columns 32 w .. 32 w + 31 of all 64
 // rows (two accumulators), A split once per workgroup into the plane image, W3' planes from L2 into registers.  32 KB of
-// LDS, 138 VGPRs: THREE workgroups per CU (at four = 128 VGPRs the 64-row loop reloads from scratch behind vmcnt(0), see
-// lin_s6_plain_kernel).  Epilogue as lin_out_kernel's: criterion_rows with 16 instead of 8 frames per wave.
+// LDS; built for THREE workgroups per CU (forced to four = 128 VGPRs the 64-row loop reloaded from scratch behind vmcnt(0),
+// see lin_s6_plain_kernel).  The bound is a minimum: with both epilogues in the kernel the compiler's own choice is 125 VGPRs
+// without scratch (138 with criterion_rows alone), so a fourth workgroup may be resident; the main loop is the same source.
+// Epilogue as lin_out_kernel's: criterion_rows / criterion_rows_f4 with 16 instead of 8 frames per wave.
 constexpr int LOUT_WPS = 3;    // waves per SIMD = resident workgroups per CU of lin_out_s6_kernel
 __global__ __launch_bounds__(256, LOUT_WPS) void lin_out_s6_kernel(LinOutK g) {
     __shared__ __attribute__((aligned(16))) float smem[64 * ON];
@@ -1043,6 +1158,13 @@ __global__ __launch_bounds__(256, LOUT_WPS) void lin_out_s6_kernel(LinOutK g) {
         return;
     }
     // fused criterion: sigmoid outputs through LDS ([64][ON]; every plane-image read is behind the loop's last barrier)
+    if (g.row_epi) {
+        criterion_rows_f4<4>(g, smem, t, tid, [&](auto hc, float* O) {
+#pragma unroll
+            for (int r = 0; r < 16; ++r) O[((r & 3) + 8 * (r >> 2) + 4 * lh) * ON + col] = as_sigmoid(acc[decltype(hc)::value][r] + bj);
+        });
+        return;
+    }
 #pragma unroll
     for (int i = 0; i < 2; ++i)
 #pragma unroll
@@ -1094,6 +1216,8 @@ bool take_planes(K& k, const L* a, int min_rows) {
 
 // as_set_head_short_k (include/artspeech_hip.h)
 std::atomic<int> g_short_k{1};
+// as_set_lin_out_row_epilogue (include/artspeech_hip.h)
+std::atomic<int> g_row_epi{1};
 
 unsigned long long* g_dbg = nullptr;
 long g_dbg_max = 0;
@@ -1173,6 +1297,8 @@ extern "C" void as_lin_debug_stamps(uint64_t* buf, int64_t max_workgroups) {
 
 extern "C" void as_set_head_short_k(int32_t on) { g_short_k.store(on ? 1 : 0, std::memory_order_relaxed); }
 
+extern "C" void as_set_lin_out_row_epilogue(int32_t on) { g_row_epi.store(on ? 1 : 0, std::memory_order_relaxed); }
+
 // see gemm_internal.h.  Returns 1 if launched, 0 if the arguments are outside what the kernel is built for (the caller
 // then takes the general GEMM + row kernels), < 0 on a launch error.
 int as_lin_try(const as_lin* a, hipStream_t st) {
@@ -1236,12 +1362,15 @@ int as_lin_out_try(const as_lin_out* a, int* n_partials, hipStream_t st) {
     k.tgt = a->tgt; k.tgt_T = a->tgt_T; k.lengths = a->lengths; k.T = a->T; k.scale = a->scale; k.dout = a->dout; k.partial = a->partial;
     if (k.tgt && (!k.lengths || !k.dout || !k.partial || k.T < 1 || k.ldo != (long)k.batch * k.N || k.o_batch != k.N)) return 0;
     // tile list as for the 256-column kernel, over rounds of 4 x 256 slots; less than one round: plain 64-row tiles.
-    // The split-arithmetic kernel has LOUT_WPS = 3 workgroups of a CU resident, not 4, and keeps this list all the same: one
+    // The split-arithmetic kernel is built for LOUT_WPS = 3 workgroups of a CU, not 4, and keeps this list all the same: one
     // of 3 x 256 slots (759 + 682 tiles at 6400 frames x 11 heads instead of 1023 + 154) was measured 4 us slower, as slow as
     // the kernel with scratch -- a 32-row tile loads the same W3' planes for half the rows.  (Besides, the criterion's partial
     // sums are per tile: with the list unchanged the loss is added in the order it always was.)
     const long total = tile_list(k, whole_round_tiles(k.M, k.batch, 1024, true));
     if (k.tgt && total > a->partial_capacity) return 0;
+    // the criterion's float4 rows (criterion_rows_f4): whole chunks per row, every row 16-byte aligned (ldo = batch * N)
+    k.row_epi = k.tgt && g_row_epi.load(std::memory_order_relaxed) && k.N % 4 == 0 && as_aligned16(k.out) && as_aligned16(k.dout) &&
+                as_aligned16(k.tgt);
     if (k.tgt && a->loss) {
         k.counter = as_arrival_counter(st);
         k.loss = k.counter ? a->loss : nullptr;

@@ -162,6 +162,12 @@ int32_t as_get_matrix_arith(void);
  * same bit for bit.  Default on.  Process-wide; read at launch time.  For tests and A/B timings. */
 void as_set_head_short_k(int32_t on);
 
+/* The criterion fused into the heads' output layer (as_opts.loss_*) reads its targets and writes out and d(out) as 16-byte
+ * chunks of whole rows when 2 * n_samples is a multiple of 4 and the three buffers are 16-byte aligned (csrc/lin_f32.hip,
+ * criterion_rows_f4).  as_set_lin_out_row_epilogue(0) selects the point-per-lane epilogue that every other case runs; the
+ * results are the same bit for bit.  Default on.  Process-wide; read at launch time.  For tests and A/B timings. */
+void as_set_lin_out_row_epilogue(int32_t on);
+
 /* Data-parallel hook: make `waiting_stream` wait until the most recent as_artspeech_bwd enqueued on `compute_stream` (same
  * device) has finished the gradients of the trunk Linear and of all heads, i.e. the tail [layout.lin_w, layout.total) of
  * the flat gradient buffer (74 % of the parameters) -- their all-reduce can then run while the GRU backward recurrences
