@@ -22,6 +22,7 @@ SOURCES = {
     "error.cpp": [],
     "prof.hip": [],
     "gemm_plan.cpp": [],
+    "lin_plan.cpp": [],
     "gemm_f32.hip": [],
     "wgrad_f32.hip": [],
     "lin_f32.hip": [],

@@ -379,22 +379,22 @@ int head_bwd_dx(const HeadStack& s, const float* out, const float* dout, float* 
     AS_TRY(lin_or_general(lin_bwd(s, 1, s.l[1].dz), nullptr, "headb.dx2", "headb.norm1", "head dx2", st));
     // d(x_hat) = dz1 . W1' summed over the heads: N = H columns under an A * 256-long reduction.  Split arithmetic: 64 x 128
     // tiles, the reduction cut into chunks whose partial sums the LayerNorm backward below adds (as_lin_plain_s6); else the
-    // general kernel (100 x 2 tiles of 64 x 64, split K over the main-stream slab)
+    // general kernel (100 x 2 tiles of 64 x 64, split K over the main-stream slab).  The planner (lin_plan.h) says ahead of the
+    // launch whether the kernel takes it and how many slabs it will write: they must fit the slab.
     int dx1_slabs = 0;
-    if (H <= 256 && H % 4 == 0) {
-        as_lin l{};
-        l.A = l1.dz; l.lda = l1.ldz;
-        use_planes(l, l1.tr);
-        l.C = slab; l.ldc = H;
-        l.M = R; l.N = H; l.K = (int)l1.ldz; l.batch = 1;
-        const int want = (int)std::max<int64_t>(1, std::min<int64_t>(8, 512 / std::max(1, as_cdiv(R, 64))));
-        const int slabs = as_lin_plain_s6_slabs(l.K, want);
-        if ((int64_t)slabs * R * H <= SLAB_FLOATS) {
-            AS_PROF("headb.dx1", st);
-            const int took1 = as_lin_plain_s6(&l, want, (long)R * H, st, 2);   // <= 512 workgroups (want): at most two per CU
-            AS_REQUIRE(took1 >= 0, took1, "head dx1: launch failed");
-            if (took1) dx1_slabs = slabs;
-        }
+    as_lin l{};
+    l.A = l1.dz; l.lda = l1.ldz;
+    use_planes(l, l1.tr);
+    l.C = slab; l.ldc = H;
+    l.M = R; l.N = H; l.K = (int)l1.ldz; l.batch = 1;
+    const as_lin_env env = as_lin_env_of(st);
+    as_lin_plan plan;
+    as_lin_plain_plan_make(&l, AS_LIN_KSPLIT_AUTO, 2, &env, &plan);
+    if (plan.family != AS_LIN_NONE && (int64_t)plan.ksplit * R * H <= SLAB_FLOATS) {
+        AS_PROF("headb.dx1", st);
+        const int took1 = as_lin_plain_s6(&l, AS_LIN_KSPLIT_AUTO, (long)R * H, st, 2);
+        AS_REQUIRE(took1 >= 0, took1, "head dx1: launch failed");
+        if (took1) dx1_slabs = plan.ksplit;
     }
     if (!dx1_slabs)
         AS_STEP("headb.dx1", st, run_split_k(gemm_nn(l1.dz, l1.ldz, l1.wf, H, dxhat, H, R, H, (int)l1.ldz), slab, st));

@@ -2,6 +2,7 @@
 #pragma once
 #include "as_common.h"
 #include "gemm_plan.h"
+#include "lin_plan.h"
 
 // The launchers as_gemm_f32 switches into once gemm_plan.cpp has validated the descriptor and chosen the kernel: each copies
 // descriptor fields into its kernel-argument struct and picks the instantiation from the plan.  0, or a launch error.
@@ -36,59 +37,22 @@ void* as_stop_event_take_raw();
 inline void as_stop_event_set(hipEvent_t ev) { as_stop_event_set_raw((void*)ev); }
 inline hipEvent_t as_stop_event_take() { return (hipEvent_t)as_stop_event_take_raw(); }
 
-// lin_f32.hip: one Linear of the ArticulatorPredictor heads with the adjoining LayerNorm fused in (batched over heads):
-//   C[bz] = epilogue(A[bz] [M][K] . B[bz]),  B[bz] = [N][K] (b_kc: forward) or [K][N] (backward); N <= 256, K % 32 == 0.
-//   epi 0: act(. + bias) (act as as_gemm: 0 none, 1 ReLU, 2 sigmoid)
-//   epi 1: x = relu(. + bias); C = (x - mean) * rstd over the 256 features; rstd [M][batch]; bits [M][batch][4] = x > 0
-//   epi 2: g = .; C = relu'(bits_in) * rstd_in * (g - mean g - xhat * mean(g xhat))   (LayerNorm + ReLU backward)
-// ka_valid (0 = K): k >= ka_valid of A is not read (the caller's B has zero rows there).  Strides in floats.
-// 1 = launched, 0 = not a case for this kernel (take the general GEMM + row kernels), < 0 = error.
-struct as_lin {
-    const float* A; long lda, a_batch;
-    const float* B; long ldb, b_batch; int b_kc;
-    // optional: the same B as three bfloat16 planes [plane][batch][K / 16][bp_rows][16] (as_emit_planes; rows >= N zero,
-    // strides in bf16 elements).  With as_matrix_arith() == AS_ARITH_BF16X6 and K % 32 == 0 the layer then runs on the bf16
-    // matrix instruction (six plane products per fp32 product, fp32 accumulate: lin_s6_kernel); B itself is not read.
-    const uint16_t* Bp; long bp_plane, bp_batch; int bp_rows;
-    float* C; long ldc, c_batch;
-    const float* bias; long bias_batch;
-    int M, N, K, ka_valid, batch, act, epi;
-    float* rstd; unsigned long long* bits;
-    const float* xhat; long ldx, x_batch; const float* rstd_in; const unsigned long long* bits_in;
-};
+// lin_f32.hip: the head layers (descriptors and the planner that picks each kernel: lin_plan.h).  Every entry point makes its
+// plan and launches what the plan names: 1 = launched, 0 = not a case for these kernels (take the general GEMM + row kernels),
+// < 0 = error.
+// What the planner reads besides the descriptor, as of now.  ask_counter: also whether the stream has an arrival counter
+// (asking creates it: only the output layer with a loss to sum asks).
+as_lin_env as_lin_env_of(hipStream_t st, bool ask_counter = false);
 int as_lin_try(const as_lin* a, hipStream_t st);
-// lin_f32.hip: epi 0 on the bf16 matrix instruction (a->Bp required; a->B unused): C = act(A . B^T + bias), N <= 256, K % 32 == 0.
-// ksplit > 1: the reduction is cut into that many chunks, chunk y writes its partial sums (no bias / activation allowed) to
-// C + y * c_split floats; the CONSUMER adds the slabs.  1 = launched, 0 = not a case (mode fp32, shapes), < 0 = error.
+// epi 0 on the bf16 matrix instruction (a->Bp required; a->B unused): C = act(A . B^T + bias), N <= 256, K % 32 == 0.
+// ksplit > 1: the reduction is cut into chunks, chunk y writes its partial sums (no bias / activation allowed) to
+// C + y * c_split floats; the CONSUMER adds the slabs.  How many chunks there really are, as_lin_plain_plan_make says ahead of
+// the launch (as_lin_plan.ksplit; ksplit = AS_LIN_KSPLIT_AUTO: the planner's own split for the heads' dx1).
 // waves_per_simd: 4, or 2 for a launch (N <= 128) that never has more than three workgroups of a CU resident: the instantiation
 // with registers for the whole 64-row loop (same instructions per accumulator: same result, bit for bit).
 int as_lin_plain_s6(const as_lin* a, int ksplit, long c_split, hipStream_t st, int waves_per_simd = 4);
-// the number of k-chunks (slabs) as_lin_plain_s6 really uses for a requested ksplit
-static inline int as_lin_plain_s6_slabs(int K, int ksplit) {
-    if (ksplit < 1) ksplit = 1;
-    const int kchunk = (int)as_round_up(as_cdiv(K, ksplit), 32);
-    return as_cdiv(K, kchunk);
-}
-
-// lin_f32.hip: the heads' output layer out[M][batch][N] = sigmoid(A[M][batch][K] . B[batch][>= 128 rows][K]^T + bias), N <= 128,
-// optionally with the masked Euclidean criterion fused (tgt != NULL): loss partials (one per workgroup, `partial`, at most
-// partial_capacity) and d loss / d(pre-sigmoid) in `dout` (layout of out).  1 = launched, 0 = not a case, < 0 = error.
-struct as_lin_out {
-    const float* A; long lda, a_batch;
-    const float* B; long ldb, b_batch; int b_rows;
-    const float* bias; long bias_batch;
-    float* out; long ldo, o_batch;
-    int M, N, K, batch;
-    const float* tgt; long tgt_T; const int* lengths; int T; float scale;
-    float* dout; float* partial; long partial_capacity;
-    const uint16_t* Bp; long bp_plane, bp_batch; int bp_rows;   // optional: B as bfloat16 planes, bp_rows >= 128 (see as_lin.Bp)
-    // optional with tgt: the device scalar that receives scale * sum of the partials.  The workgroup that delivers the LAST partial
-    // adds them all itself, in the order of as_loss_final (same value): no second launch on the critical stream.  Needs an arrival
-    // counter (as_arrival_counter); without one the partials are left for as_loss_final as before (*n_partials > 0).
-    float* loss;
-};
-// 1 = launched (fused criterion: *n_partials workgroup sums were written to `partial` and await as_loss_final; 0 of them when the
-// kernel has summed them into a->loss itself), 0 = not a case, < 0 = error
+// the heads' output layer.  Fused criterion: *n_partials workgroup sums were written to `partial` and await as_loss_final; 0 of
+// them when the kernel has summed them into a->loss itself.
 int as_lin_out_try(const as_lin_out* a, int* n_partials, hipStream_t st);
 // gemm_f32.hip: one of the stream's arrival counters (a device word that every launch leaves zero), or nullptr
 int* as_arrival_counter(hipStream_t st);

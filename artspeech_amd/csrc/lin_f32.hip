@@ -27,10 +27,10 @@
 // split-arithmetic main loop s6_main_loop, its entry s6_tile, and lin_s6_kernel on it; the short reductions (K <= 128: the whole
 // A image resident, s6_resident_loop without barriers; lin_s6_lnf_shared_kernel = Linear 1, one image per row tile for a group
 // of heads, lin_s6_lnb_short_kernel = dx3); lin_s6_plain_kernel; the output layer (criterion_rows: the fused criterion,
-// criterion_rows_f4: the same through float4 rows; lin_out_kernel, lin_out_s6_kernel); the host half (tile lists, argument
-// copies, launch_short_k and as_set_head_short_k, as_set_lin_out_row_epilogue,
-// as_lin_try, as_lin_plain_s6, as_lin_out_try, as_linear_fwd).  The kernels differ in their main loops and in which of the
-// shared pieces they call.
+// criterion_rows_f4: the same through float4 rows; lin_out_kernel, lin_out_s6_kernel); the host half (the kernels' constants
+// asserted against lin_plan.h, the two switches as_set_head_short_k and as_set_lin_out_row_epilogue, argument copies, and
+// as_lin_try, as_lin_plain_s6, as_lin_out_try, as_linear_fwd: each makes its plan in lin_plan.cpp and launches what the plan
+// names).  The kernels differ in their main loops and in which of the shared pieces they call.
 #include <cstdlib>
 
 #include <atomic>
@@ -65,7 +65,7 @@ struct LinK {
 };
 
 // ---- what the five kernels share besides their main loops: the tile decode, the debug stamps, the plain store.
-// A workgroup's entry of the tile list (tile_list() below; LinK and LinOutK name its fields alike): the 64-row tiles of every
+// A workgroup's entry of the tile list (tile_list(), lin_plan.cpp; LinK and LinOutK name its fields alike): the 64-row tiles of every
 // head first, then 32-row tiles over the remaining rows of every head.  Block b takes entry b (an XCD-contiguous map --
 // workgroups go to the eight XCDs round-robin by block index, each with its own 4 MB L2; XCD x took a contiguous range of
 // the list, two or three heads' weights per L2 instead of all eleven -- was measured: 5-10 % slower).
@@ -1174,45 +1174,12 @@ __global__ __launch_bounds__(256, LOUT_WPS) void lin_out_s6_kernel(LinOutK g) {
     criterion_rows<4>(g, smem, t, tid);
 }
 
-// The kernels' tile list from x, the number of 64-row tiles per batch member: those are dispatched first, then the remaining
-// rows as 32-row tiles.  Returns the number of tiles (workgroups).
-template <typename K>
-long tile_list(K& k, int x) {
-    const int rest = k.M - x * 64;
-    k.big_per_batch = x > 0 ? x : 1;
-    k.big_per_batch_rows = x * 64;
-    k.n_big = x * k.batch;
-    k.small_per_batch = as_cdiv(rest, 32);
-    const long total = (long)k.n_big + (long)k.small_per_batch * k.batch;
-    if (k.small_per_batch == 0) k.small_per_batch = 1;
-    return total;
-}
-
-// How many 64-row tiles per batch member fill whole rounds of `slots` resident workgroups.  A launch of T equal tiles takes
-// ceil(T / slots) rounds, and the head layers' 1100 tiles of 64 rows were 3 rounds of 512 of which the last held 76 tiles
-// (measured: 31 us of a 118 us launch with 180 CUs idle).  So: as many 64-row tiles as fill whole rounds, dispatched first,
-// then the remaining rows as 32-row tiles (half the matrix work each), which pack the last round about half as high.
-// short_64: what a launch of LESS than one round gets -- false: 32-row tiles only (they spread over more CUs), true: plain
-// 64-row tiles + a ragged end (the output layer: a 32-row tile loads the same W3' planes for half the rows).
-int whole_round_tiles(int M, int batch, int slots, bool short_64) {
-    const long units = (long)as_cdiv(M, 64) * batch;      // work in 64-row tiles
-    const long rounds = units / slots;
-    if (rounds == 0 && short_64) return M / 64;
-    const long x = rounds * slots / batch;
-    return x > M / 64 ? M / 64 : (int)x;
-}
-
-// B as bfloat16 planes (as_emit_planes) can feed a split-arithmetic kernel whose column tile is min_rows wide: the arithmetic
-// is on, K is whole 32-deep k-tiles, the image has the tile's rows, planes and batch members start 16-byte aligned, and a row
-// offset of A fits the kernels' 32-bit byte offsets.  Then the kernel argument gets them; else the exact fp32 kernel
-// (as_lin_try, as_lin_out_try) or no launch (as_lin_plain_s6).
-template <typename K, typename L>
-bool take_planes(K& k, const L* a, int min_rows) {
-    if (!a->Bp || as_matrix_arith() != AS_ARITH_BF16X6 || a->K % S6_BK || a->bp_rows < min_rows || !as_aligned16(a->Bp) ||
-        a->bp_plane % 8 || a->bp_batch % 8 || a->lda >= (1L << 23)) return false;
-    k.Bp = a->Bp; k.bp_plane = a->bp_plane; k.bp_batch = a->bp_batch; k.bp_rows = a->bp_rows;
-    return true;
-}
+// ---- the host half.  lin_plan.cpp decides everything (kernel, planes, tile list, head groups, LDS, k-split, epilogue); here
+// the environment is filled, descriptor and plan fields are copied into the kernel argument, and the instantiation the plan
+// names is launched.
+static_assert(BN == AS_LIN_BN && ON == AS_LIN_ON && BK == AS_LIN_BK && S6_BK == AS_LIN_S6_BK, "lin_plan.cpp plans for these tiles");
+static_assert(S6R_MAXK == AS_LIN_SHORT_MAXK && S6_BUF == AS_LIN_S6_IMAGE && 32 * BN * 4 == AS_LIN_STAGE, "lin_plan.cpp sizes the resident image with these");
+static_assert(AS_LIN_SLOTS == 2 * 256 && AS_LIN_OUT_SLOTS == 4 * 256 && 2 * AS_LIN_SPREAD == 3 * 256, "slots of the MI355X's 256 CUs");
 
 // as_set_head_short_k (include/artspeech_hip.h)
 std::atomic<int> g_short_k{1};
@@ -1222,8 +1189,15 @@ std::atomic<int> g_row_epi{1};
 unsigned long long* g_dbg = nullptr;
 long g_dbg_max = 0;
 
-// as_lin as the kernels' argument: every field but the planes (take_planes), the k-split and the tile list
-LinK lin_args(const as_lin* a) {
+// the plan's share of both kernel arguments: the planes where they were taken, and the tile list
+template <typename K, typename L>
+void plan_args(K& k, const L* a, const as_lin_plan& p) {
+    if (p.planes) { k.Bp = a->Bp; k.bp_plane = a->bp_plane; k.bp_batch = a->bp_batch; k.bp_rows = a->bp_rows; }
+    k.n_big = p.n_big; k.big_per_batch = p.big_per_batch; k.big_per_batch_rows = p.big_per_batch_rows; k.small_per_batch = p.small_per_batch;
+}
+
+// as_lin and its plan as the kernels' argument
+LinK lin_args(const as_lin* a, const as_lin_plan& p) {
     LinK k{};
     k.A = a->A; k.lda = a->lda; k.a_batch = a->a_batch;
     k.B = a->B; k.ldb = a->ldb; k.b_batch = a->b_batch;
@@ -1234,58 +1208,9 @@ LinK lin_args(const as_lin* a) {
     k.dbg = g_dbg; k.dbg_max = g_dbg_max;
     k.rstd = a->rstd; k.bits = a->bits;
     k.xhat = a->xhat; k.ldx = a->ldx; k.x_batch = a->x_batch; k.rstd_in = a->rstd_in; k.bits_in = a->bits_in;
+    plan_args(k, a, p);
+    k.groups = p.groups; k.kchunk = p.kchunk;
     return k;
-}
-
-
-// The short-reduction kernels for a layer whose planes were taken: *took = launched; else it is not their case (lin_s6_kernel
-// runs).  Returns a launch error or 0.
-//   dx3: lin_s6_kernel's tile list.
-//   Linear 1: as many head groups as keep the launch within ONE round of the 512 resident slots (at 6400 frames and 11 heads
-//   5 groups of 2, 2, 2, 2, 3 heads x 100 row tiles = 500 workgroups), 64-row tiles + a ragged end unless that leaves CUs idle
-//   (fewer workgroups than 1.5 x 256: 32-row tiles then).  Measured at 6400 x 11 (profiles/head_short_k_ab.log): 5 or 6 groups
-//   -4 us against lin_s6_kernel, 11 groups (one head each) -1, 4 groups no gain, 3 and fewer slower -- the longest workgroup
-//   sets the time.
-int launch_short_k(const LinK& k, int epi, hipStream_t st, bool* took) {
-    *took = false;
-    if (!g_short_k.load(std::memory_order_relaxed) || !k.Bp || k.K > S6R_MAXK) return 0;
-    LinK kk = k;
-    if (epi == EPI_LNB) {
-        const long total = tile_list(kk, whole_round_tiles(k.M, k.batch, 512, false));
-        hipLaunchKernelGGL(lin_s6_lnb_short_kernel, dim3((unsigned)total), dim3(NT), 0, st, kk);
-        AS_LAUNCH_CHECK("as_lin_s6_lnb_short");
-        *took = true;
-        return 0;
-    }
-    if (epi != EPI_LNF || k.a_batch != 0) return 0;
-    const int lds = (k.K / S6_BK) * S6_BUF + 32 * BN * 4;
-    if (lds > 64 * 1024 && as_allow_dynamic_lds(lin_s6_lnf_shared_kernel, lds) != hipSuccess) return 0;
-    const int row_tiles = as_cdiv(k.M, 64);
-    kk.groups = 512 / row_tiles < 1 ? 1 : 512 / row_tiles > k.batch ? k.batch : 512 / row_tiles;
-    kk.batch = kk.groups;                // the tile list counts head groups
-    const long total = tile_list(kk, (long)row_tiles * kk.groups >= 384 ? k.M / 64 : 0);
-    kk.batch = k.batch;
-    hipLaunchKernelGGL(lin_s6_lnf_shared_kernel, dim3((unsigned)total), dim3(NT), lds, st, kk);
-    AS_LAUNCH_CHECK("as_lin_s6_lnf_shared");
-    *took = true;
-    return 0;
-}
-
-// Tile list for two workgroups per CU = 512 slots (whole_round_tiles)
-template <bool B_KC, int EPI>
-int launch(const LinK& k, hipStream_t st) {
-    if (EPI != EPI_PLAIN) {
-        bool took;
-        const int e = launch_short_k(k, EPI, st, &took);
-        if (e || took) return e;
-    }
-    LinK kk = k;
-    const long total = tile_list(kk, whole_round_tiles(k.M, k.batch, 512, false));
-    // with B as planes the products run on the bf16 matrix instruction (lin_s6_kernel)
-    if (kk.Bp) hipLaunchKernelGGL((lin_s6_kernel<EPI>), dim3((unsigned)total), dim3(NT), 0, st, kk);
-    else hipLaunchKernelGGL((lin_f32_kernel<64, B_KC, EPI>), dim3((unsigned)total), dim3(NT), 0, st, kk);
-    AS_LAUNCH_CHECK(kk.Bp ? "as_lin_s6" : "as_lin_f32");
-    return 0;
 }
 
 }  // namespace
@@ -1299,50 +1224,70 @@ extern "C" void as_set_head_short_k(int32_t on) { g_short_k.store(on ? 1 : 0, st
 
 extern "C" void as_set_lin_out_row_epilogue(int32_t on) { g_row_epi.store(on ? 1 : 0, std::memory_order_relaxed); }
 
-// see gemm_internal.h.  Returns 1 if launched, 0 if the arguments are outside what the kernel is built for (the caller
+// see gemm_internal.h
+as_lin_env as_lin_env_of(hipStream_t st, bool ask_counter) {
+    as_lin_env e{};
+    e.arith = as_matrix_arith();
+    e.short_k = g_short_k.load(std::memory_order_relaxed) != 0;
+    e.row_epi = g_row_epi.load(std::memory_order_relaxed) != 0;
+    e.counter = ask_counter && as_arrival_counter(st) != nullptr;
+    e.lds_limit = AS_LIN_LDS_MI355X;
+    return e;
+}
+
+// see gemm_internal.h.  Returns 1 if launched, 0 if the arguments are outside what the kernels are built for (the caller
 // then takes the general GEMM + row kernels), < 0 on a launch error.
 int as_lin_try(const as_lin* a, hipStream_t st) {
-    if (a->K % BK || a->K < BK || a->N > BN || a->N < 4 || a->M < 1 || a->batch < 1) return 0;
-    if (!as_aligned16(a->A) || !as_aligned16(a->B) || a->lda % 4 || a->ldb % 4 || a->a_batch % 4 || a->b_batch % 4) return 0;
-    if (!a->b_kc && a->N % 4) return 0;
-    if (a->epi != EPI_PLAIN && (a->N != BN || !a->C)) return 0;
-    if (a->epi == EPI_PLAIN && a->N <= BN / 2) return 0;  // half of the 8 feature-side waves would multiply padding
-    if ((long)as_cdiv(a->M, 64) * a->batch > (1L << 30)) return 0;
-    LinK k = lin_args(a);
-    if (k.ka_valid % 4) return 0;
-    take_planes(k, a, BN);   // taken: the bf16-MFMA kernel; else the exact fp32 one
-    if (a->epi == EPI_LNF) {
-        if (!a->rstd || !a->bits || !a->b_kc) return 0;
-        return launch<true, EPI_LNF>(k, st) == 0 ? 1 : -1;
+    const as_lin_env env = as_lin_env_of(st);
+    as_lin_plan p;
+    as_lin_plan_make(a, &env, &p);
+    if (p.family == AS_LIN_NONE) return 0;
+    const LinK k = lin_args(a, p);
+    const dim3 grid((unsigned)p.tiles);
+    int rc = 0;
+    switch (p.family) {
+        case AS_LIN_LNF_SHARED:
+            // (more than the 64 KB a kernel has without asking; the planner has kept it within the device's limit)
+            if (p.lds > 64 * 1024 && as_allow_dynamic_lds(lin_s6_lnf_shared_kernel, p.lds) != hipSuccess) {
+                as_set_error("as_lin_s6_lnf_shared: %d bytes of dynamic LDS refused", p.lds);
+                return -1;
+            }
+            hipLaunchKernelGGL(lin_s6_lnf_shared_kernel, grid, dim3(NT), p.lds, st, k);
+            break;
+        case AS_LIN_LNB_SHORT: hipLaunchKernelGGL(lin_s6_lnb_short_kernel, grid, dim3(NT), 0, st, k); break;
+        case AS_LIN_S6:   // B as planes: the products run on the bf16 matrix instruction
+            as_exactly<EPI_LNF, EPI_LNB, EPI_PLAIN>(p.epi, &rc, [&](auto e) {
+                hipLaunchKernelGGL((lin_s6_kernel<decltype(e)::value>), grid, dim3(NT), 0, st, k);
+                return 0;
+            });
+            break;
+        default:          // AS_LIN_F32; 2 epi + b_kc: the LayerNorm epilogues exist for one orientation of B each
+            as_exactly<2 * EPI_LNF + 1, 2 * EPI_LNB, 2 * EPI_PLAIN + 1, 2 * EPI_PLAIN>(2 * p.epi + p.b_kc, &rc, [&](auto c) {
+                constexpr int C = decltype(c)::value;
+                hipLaunchKernelGGL((lin_f32_kernel<64, C % 2 == 1, C / 2>), grid, dim3(NT), 0, st, k);
+                return 0;
+            });
     }
-    if (a->epi == EPI_LNB) {
-        if (!a->xhat || !a->rstd_in || !a->bits_in || a->b_kc) return 0;
-        return launch<false, EPI_LNB>(k, st) == 0 ? 1 : -1;
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) {
+        as_set_error("as_lin_try: launch failed: %s", hipGetErrorString(e));
+        return -1;
     }
-    if (a->b_kc) return launch<true, EPI_PLAIN>(k, st) == 0 ? 1 : -1;
-    return launch<false, EPI_PLAIN>(k, st) == 0 ? 1 : -1;
+    return 1;
 }
 
 // see gemm_internal.h
 int as_lin_plain_s6(const as_lin* a, int ksplit, long c_split, hipStream_t st, int waves_per_simd) {
-    const int nw = a->N <= 128 ? 4 : 8;
-    LinK k = lin_args(a);
-    if (!take_planes(k, a, nw * 32)) return 0;
-    if (a->epi != EPI_PLAIN || a->K < S6_BK || a->N > BN || a->N < 1 || a->M < 1 || a->batch < 1 || !a->C) return 0;
-    if (!as_aligned16(a->A) || a->lda % 4 || a->a_batch % 4) return 0;
-    if (ksplit < 1) ksplit = 1;
-    if (ksplit > 1 && (a->bias || a->act)) return 0;
-    if (k.ka_valid % 4) return 0;
-    k.kchunk = (int)as_round_up(as_cdiv(a->K, ksplit), S6_BK);
-    ksplit = as_cdiv(a->K, k.kchunk);
+    const as_lin_env env = as_lin_env_of(st);
+    as_lin_plan p;
+    as_lin_plain_plan_make(a, ksplit, waves_per_simd, &env, &p);
+    if (p.family == AS_LIN_NONE) return 0;
+    LinK k = lin_args(a, p);
     k.c_split = c_split;
-    // tiles: 64 rows unless that leaves CUs idle (fewer workgroups than 1.5 x 256)
-    const bool rows64 = (long)as_cdiv(a->M, 64) * a->batch * ksplit >= 384;
-    const long total = tile_list(k, rows64 ? a->M / 64 : 0);
-    if (total > (1L << 30) || ksplit > 65535) return 0;
-    if (nw == 4 && waves_per_simd == 2) hipLaunchKernelGGL((lin_s6_plain_kernel<4, 2>), dim3((unsigned)total, ksplit), dim3(256), 0, st, k);
-    else if (nw == 4) hipLaunchKernelGGL((lin_s6_plain_kernel<4, 4>), dim3((unsigned)total, ksplit), dim3(256), 0, st, k);
-    else hipLaunchKernelGGL((lin_s6_plain_kernel<8, 4>), dim3((unsigned)total, ksplit), dim3(512), 0, st, k);
+    const dim3 grid((unsigned)p.tiles, p.ksplit);
+    if (p.nw == 4 && p.wps == 2) hipLaunchKernelGGL((lin_s6_plain_kernel<4, 2>), grid, dim3(256), 0, st, k);
+    else if (p.nw == 4) hipLaunchKernelGGL((lin_s6_plain_kernel<4, 4>), grid, dim3(256), 0, st, k);
+    else hipLaunchKernelGGL((lin_s6_plain_kernel<8, 4>), grid, dim3(512), 0, st, k);
     AS_LAUNCH_CHECK("as_lin_plain_s6");
     return 1;
 }
@@ -1350,9 +1295,11 @@ int as_lin_plain_s6(const as_lin* a, int ksplit, long c_split, hipStream_t st, i
 // Output layer of the heads, optionally with the masked Euclidean criterion and its gradient fused in (see lin_out_kernel).
 // 1 = launched (fused: *n_partials workgroup sums were written to `partial`), 0 = not a case, < 0 = error.
 int as_lin_out_try(const as_lin_out* a, int* n_partials, hipStream_t st) {
-    if (a->K % BK || a->K < BK || a->N > ON || a->N < 4 || a->N % 2 || a->M < 1 || a->batch < 1) return 0;
-    if (!as_aligned16(a->A) || !as_aligned16(a->B) || a->lda % 4 || a->ldb % 4 || a->a_batch % 4 || a->b_batch % 4) return 0;
-    if (a->b_rows < a->N) return 0;
+    // (asking for the stream's arrival counter creates it: only a launch that can use one asks)
+    const as_lin_env env = as_lin_env_of(st, a->tgt && a->loss);
+    as_lin_plan p;
+    as_lin_out_plan_make(a, &env, &p);
+    if (p.family == AS_LIN_NONE) return 0;
     LinOutK k{};
     k.A = a->A; k.lda = a->lda; k.a_batch = a->a_batch;
     k.B = a->B; k.ldb = a->ldb; k.b_batch = a->b_batch; k.b_rows = a->b_rows;
@@ -1360,41 +1307,20 @@ int as_lin_out_try(const as_lin_out* a, int* n_partials, hipStream_t st) {
     k.out = a->out; k.ldo = a->ldo; k.o_batch = a->o_batch;
     k.M = a->M; k.N = a->N; k.K = a->K; k.batch = a->batch;
     k.tgt = a->tgt; k.tgt_T = a->tgt_T; k.lengths = a->lengths; k.T = a->T; k.scale = a->scale; k.dout = a->dout; k.partial = a->partial;
-    if (k.tgt && (!k.lengths || !k.dout || !k.partial || k.T < 1 || k.ldo != (long)k.batch * k.N || k.o_batch != k.N)) return 0;
-    // tile list as for the 256-column kernel, over rounds of 4 x 256 slots; less than one round: plain 64-row tiles.
-    // The split-arithmetic kernel is built for LOUT_WPS = 3 workgroups of a CU, not 4, and keeps this list all the same: one
-    // of 3 x 256 slots (759 + 682 tiles at 6400 frames x 11 heads instead of 1023 + 154) was measured 4 us slower, as slow as
-    // the kernel with scratch -- a 32-row tile loads the same W3' planes for half the rows.  (Besides, the criterion's partial
-    // sums are per tile: with the list unchanged the loss is added in the order it always was.)
-    const long total = tile_list(k, whole_round_tiles(k.M, k.batch, 1024, true));
-    if (k.tgt && total > a->partial_capacity) return 0;
-    // the criterion's float4 rows (criterion_rows_f4): whole chunks per row, every row 16-byte aligned (ldo = batch * N)
-    k.row_epi = k.tgt && g_row_epi.load(std::memory_order_relaxed) && k.N % 4 == 0 && as_aligned16(k.out) && as_aligned16(k.dout) &&
-                as_aligned16(k.tgt);
-    if (k.tgt && a->loss) {
-        k.counter = as_arrival_counter(st);
-        k.loss = k.counter ? a->loss : nullptr;
-    }
-    if (n_partials) *n_partials = k.counter ? 0 : (int)total;   // partials that still await as_loss_final
-    if (take_planes(k, a, ON)) hipLaunchKernelGGL(lin_out_s6_kernel, dim3((unsigned)total), dim3(256), 0, st, k);
-    else hipLaunchKernelGGL(lin_out_kernel, dim3((unsigned)total), dim3(NT), 0, st, k);
-    AS_LAUNCH_CHECK(k.Bp ? "as_lin_out_s6" : "as_lin_out");
+    plan_args(k, a, p);
+    k.row_epi = p.row_epi;
+    if (p.sums_loss) { k.counter = as_arrival_counter(st); k.loss = a->loss; }
+    if (n_partials) *n_partials = p.partials;
+    if (p.family == AS_LIN_OUT_S6) hipLaunchKernelGGL(lin_out_s6_kernel, dim3((unsigned)p.tiles), dim3(256), 0, st, k);
+    else hipLaunchKernelGGL(lin_out_kernel, dim3((unsigned)p.tiles), dim3(NT), 0, st, k);
+    AS_LAUNCH_CHECK(p.planes ? "as_lin_out_s6" : "as_lin_out");
     return 1;
 }
 
 // ---- include/artspeech_hip.h: as_linear_fwd
-namespace {
-// column blocks of the split-arithmetic plain kernel for an N-column Linear: block width (rows of the plane image) and count
-inline bool linear_blocks(int N, int* bn, int* nb) {
-    if (N <= 256) { *bn = N <= 128 ? 128 : 256; *nb = 1; return true; }
-    if (N % 256 == 0) { *bn = 256; *nb = N / 256; return true; }
-    return false;
-}
-}  // namespace
-
 extern "C" int64_t as_linear_planes_floats(int32_t N, int32_t K) {
     int bn, nb;
-    if (N < 1 || K < 1 || !linear_blocks(N, &bn, &nb)) return 0;
+    if (N < 1 || K < 1 || !as_linear_blocks(N, &bn, &nb)) return 0;
     return as_round_up(as_planes_floats(nb, bn, (int)as_round_up(K, 32)), 64);
 }
 
@@ -1404,7 +1330,7 @@ extern "C" int as_linear_fwd(const float* A, int64_t lda, const float* W, int64_
                "as_linear_fwd: bad argument");
     hipStream_t st = (hipStream_t)stream;
     int bn, nb;
-    if (as_matrix_arith() == AS_ARITH_BF16X6 && planes_ws && K % S6_BK == 0 && lda % 4 == 0 && linear_blocks(N, &bn, &nb) &&
+    if (as_matrix_arith() == AS_ARITH_BF16X6 && planes_ws && K % S6_BK == 0 && lda % 4 == 0 && as_linear_blocks(N, &bn, &nb) &&
         as_aligned16(planes_ws)) {
         const int rows_last = N - (nb - 1) * bn;   // (nb > 1: whole blocks)
         as_planes_job j{W, ldw, 1, (long)bn * ldw, nb, nb > 1 ? bn : rows_last, K, bn, K, reinterpret_cast<uint16_t*>(planes_ws)};

@@ -7,7 +7,11 @@
 // so that every fallback is posed -- also those no legal as_dims reaches on the GPU (head.gemm2, headb.dx2).  Two commits
 // enqueue the same work with the same arguments when their outputs are equal: no GPU needed.
 //   hipcc -O1 -std=c++17 -Iinclude -Iartspeech_amd/csrc -x hip --offload-arch=gfx950 -c tools/head_stack_host_trace.cpp -o trace.o
-//   hipcc --offload-arch=gfx950 trace.o artspeech_amd/csrc/build/artspeech.o -o head_stack_host_trace && ./head_stack_host_trace | sha256sum
+//   hipcc --offload-arch=gfx950 trace.o artspeech_amd/csrc/build/artspeech.o artspeech_amd/csrc/build/lin_plan.o -o head_stack_host_trace && ./head_stack_host_trace | sha256sum
+// The heads' dx1 asks the planner (lin_plan.cpp, linked in as it is) how many slabs as_lin_plain_s6 will write.  With
+// -DDX1_BEFORE_PLANNER (and without lin_plan.o) a stub answers as the code before the planner computed it -- every H <= 256 with
+// H % 4 == 0 taken, min(8, 512 / row tiles) chunks asked for, rounded to whole 32-deep k-tiles -- and the as_lin_plain_s6 line
+// shows the chunks asked for: that output is equal to the one of the commit before lin_plan.cpp.
 #include <stdarg.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -37,7 +41,19 @@ int as_sigmoid_bwd(const float* a, const float* b, float* c, long d, hipStream_t
 int as_token_table(const float* a, const float* b, const float* c, int d, int e, int f, float* g, hipStream_t s) { logc("as_token_table", a, b, c, d, e, f, g, s); return 0; }
 int as_wgrad_multi(const as_wgrad_job* j, int n, float* slab, long sf, int cu, hipStream_t s, bool exact) {
     printf("as_wgrad_multi "); for (int i = 0; i < n; ++i) put1(j[i]); put1(n); put1(slab); put1(sf); put1(cu); put1(s); put1(exact); printf("\n"); return (g_mode & 8) ? 0 : 1; }
+as_lin_env as_lin_env_of(hipStream_t, bool) { return as_lin_env{AS_ARITH_BF16X6, true, true, false, AS_LIN_LDS_MI355X}; }
+#ifdef DX1_BEFORE_PLANNER
+static int dx1_want(const as_lin* a) { const int t = (a->M + 63) / 64, w = 512 / (t > 1 ? t : 1); return w > 8 ? 8 : w < 1 ? 1 : w; }
+void as_lin_plain_plan_make(const as_lin* a, int, int, const as_lin_env*, as_lin_plan* p) {
+    *p = as_lin_plan{};
+    if (a->N > 256 || a->N % 4) return;
+    const int kchunk = ((a->K + dx1_want(a) - 1) / dx1_want(a) + 31) / 32 * 32;
+    p->family = AS_LIN_PLAIN; p->ksplit = (a->K + kchunk - 1) / kchunk;
+}
+int as_lin_plain_s6(const as_lin* a, int k, long c, hipStream_t s, int w) { logc("as_lin_plain_s6", *a, k == AS_LIN_KSPLIT_AUTO ? dx1_want(a) : k, c, s, w); return (g_mode & 4) ? 0 : 1; }
+#else
 int as_lin_plain_s6(const as_lin* a, int k, long c, hipStream_t s, int w) { logc("as_lin_plain_s6", *a, k, c, s, w); return (g_mode & 4) ? 0 : 1; }
+#endif
 int as_sum_partials(const float* a, long b, int c, float* d, hipStream_t s) { logc("as_sum_partials", a, b, c, d, s); return 0; }
 int as_token_segsum(const float* a, const int64_t* b, long c, int d, long e, int f, int g, float* h, hipStream_t s, float* i, long j) { logc("as_token_segsum", a, b, c, d, e, f, g, h, s, i, j); return 0; }
 int as_normalize_bwd(const float* a, const float* b, const float* c, const float* d, float* e, long f, int g, hipStream_t s, const unsigned long long* h, int i, long j) { logc("as_normalize_bwd", a, b, c, d, e, f, g, s, h, i, j); return 0; }
