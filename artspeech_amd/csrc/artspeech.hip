@@ -225,11 +225,14 @@ as_gemm gemm_nn(const float* A, long lda, const float* B, long ldb, float* C, lo
 as_gemm gemm_tn(const float* A, long lda, const float* B, long ldb, float* C, long ldc, int M, int N, int K) {
     return gemm_of(A, lda, false, B, ldb, false, C, ldc, M, N, K);
 }
-// few output tiles under a long reduction: split K over `slab` (every slab of the carve holds SLAB_FLOATS or more; the split
-// factor depends on the size stated).  cu_budget: CUs the launch can count on (0 = all): 192 beside a 64-workgroup recurrence
-int run_split_k(as_gemm g, float* slab, hipStream_t st, int cu_budget = 0) {
-    g.splitk_ws = slab; g.splitk_ws_floats = SLAB_FLOATS; g.cu_budget = cu_budget;
-    return as_gemm_f32(&g, st);
+// One stream of a call with what a launch on it needs: the stream's own split-K slab and its size, and the CUs the heads'
+// weight gradients are planned with there (0 = all; 192 beside a recurrence, whose 2 * B workgroups hold 64 CUs)
+struct Lane { hipStream_t stream; float* slab; long slab_floats; int cu_budget; };
+// few output tiles under a long reduction: split K over the lane's slab (every slab of the carve holds SLAB_FLOATS or more; the
+// split factor depends on the size stated).  cu_budget: CUs the launch can count on (0 = all)
+int run_split_k(as_gemm g, const Lane& ln, int cu_budget = 0) {
+    g.splitk_ws = ln.slab; g.splitk_ws_floats = SLAB_FLOATS; g.cu_budget = cu_budget;
+    return as_gemm_f32(&g, ln.stream);
 }
 
 // hand a plane image to the kernel that reads it (as_lin.Bp / as_lin_out.Bp)
@@ -397,7 +400,7 @@ int head_bwd_dx(const HeadStack& s, const float* out, const float* dout, float* 
         if (took1) dx1_slabs = plan.ksplit;
     }
     if (!dx1_slabs)
-        AS_STEP("headb.dx1", st, run_split_k(gemm_nn(l1.dz, l1.ldz, l1.wf, H, dxhat, H, R, H, (int)l1.ldz), slab, st));
+        AS_STEP("headb.dx1", st, run_split_k(gemm_nn(l1.dz, l1.ldz, l1.wf, H, dxhat, H, R, H, (int)l1.ldz), Lane{st, slab, SLAB_FLOATS, 0}));
     AS_STEP("headb.norm0", st, as_normalize_bwd(dx1_slabs ? slab : dxhat, l1.x, l1.rstd, relu_src, dx, R, H, st, nullptr,
                                                  dx1_slabs ? dx1_slabs : 1, (long)R * H));
     return 0;
@@ -429,53 +432,55 @@ as_wgrad_job wgrad1(const HeadStack& s, float* G, bool transposed) {
     return j;
 }
 
-// part: 0 = everything; 1 = layers 3 and 1 (+ the trunk's); 2 = layer 2 + the LayerNorm-affine unfold of all three.  The
-// model's backward issues part 1 beside the layer-1 recurrence and part 2 beside the layer-0 recurrence: each is one round
-// of <= 192 long-lived workgroups, so that the GRU input-gradient GEMM between the two recurrences finds the chip free
-// (a single launch of all four problems kept 184 CUs for ~240 us and that GEMM waited for CUs: 113 us instead of 52).
-// trunk (optional): the trunk Linear's weight gradient dzlin^T . y1, which rides in the same launch at N = 2H = 256 (ArtSpeech).
+// Which weight gradients one call computes.  The model's backward issues Layers31Trunk beside the layer-1 recurrence and
+// Layer2 beside the layer-0 recurrence: each is one round of <= 192 long-lived workgroups, so that the GRU input-gradient
+// GEMM between the two recurrences finds the chip free (a single launch of all four problems kept 184 CUs for ~240 us and
+// that GEMM waited for CUs: 113 us instead of 52).
+enum class DwPart { All, Layers31Trunk, Layer2 };
+// Whose LayerNorm affines a call unfolds (one launch): all three once every dW' is there, i.e. with All or Layer2
+enum { UNFOLD_NONE = 0, UNFOLD_L3 = 1, UNFOLD_L2 = 2, UNFOLD_L1 = 4, UNFOLD_ALL = 7 };
+// ln: the stream the gradients go to, its slab and CU budget (> 0: beside a recurrence, exact, see gemm_internal.h).  trunk
+// (optional): the trunk Linear's weight gradient dzlin^T . y1, which rides in the same launch at N = 2H = 256 (ArtSpeech).
 // From 512 rows on several problems go as ONE launch of 128 x 256 tiles + one reduce (as_wgrad_multi); what it declines goes
 // to as_gemm_f32 as the same as_gemm plus the two fields the multi launch ignores, slab and CU budget (run_split_k).
-int head_bwd_dw(const HeadStack& s, const float* P, float* G, float* slab, hipStream_t st, const float* dpre3_in = nullptr,
-                int cu_budget = 0, long slab_floats = SLAB_FLOATS, const as_gemm* trunk = nullptr, int part = 0,
-                int unfold_layers = -1) {
+int head_bwd_dw(const HeadStack& s, const float* P, float* G, const Lane& ln, DwPart part, int unfold_layers,
+                const float* dpre3_in = nullptr, const as_gemm* trunk = nullptr) {
+    const hipStream_t st = ln.stream; const int cu_budget = ln.cu_budget;
     const bool multi_ok = s.R % 32 == 0 && s.R >= 512;
     const as_wgrad_job job3 = wgrad(s, 2, dpre3_in ? dpre3_in : s.l[2].dz, G), job2 = wgrad(s, 1, s.l[1].dz, G);
     auto multi = [&](const as_wgrad_job* jobs, int n, const char* phase, int* took) {
         *took = 0;
         if (!multi_ok) return 0;
         AS_PROF(phase, st);
-        *took = as_wgrad_multi(jobs, n, slab, slab_floats, cu_budget, st, cu_budget > 0);   // (beside a recurrence: exact, see gemm_internal.h)
+        *took = as_wgrad_multi(jobs, n, ln.slab, ln.slab_floats, cu_budget, st, cu_budget > 0);
         AS_REQUIRE(*took >= 0, *took, "head weight gradients: launch failed");
         return 0;
     };
     int took;
-    if (part == 0 || part == 1) {
+    if (part != DwPart::Layer2) {
+        const bool all = part == DwPart::All;
         as_wgrad_job jobs[4] = {job3, wgrad1(s, G, true)};
         int n = 2;
         const bool trunk_rides = trunk && trunk->N == 256;
         if (trunk_rides) jobs[n++].g = *trunk;
-        if (part == 0) jobs[n++] = job2;
-        AS_TRY(multi(jobs, n, part == 0 ? "headb.dw_fused" : "headb.dw31", &took));
+        if (all) jobs[n++] = job2;
+        AS_TRY(multi(jobs, n, all ? "headb.dw_fused" : "headb.dw31", &took));
         if (!took) {
-            AS_STEP("headb.dw3", st, run_split_k(job3.g, slab, st, cu_budget));
-            AS_STEP("headb.dw1", st, run_split_k(wgrad1(s, G, false).g, slab, st, cu_budget));
-            if (part == 0) AS_STEP("headb.dw2", st, run_split_k(job2.g, slab, st, cu_budget));
+            AS_STEP("headb.dw3", st, run_split_k(job3.g, ln, cu_budget));
+            AS_STEP("headb.dw1", st, run_split_k(wgrad1(s, G, false).g, ln, cu_budget));
+            if (all) AS_STEP("headb.dw2", st, run_split_k(job2.g, ln, cu_budget));
         }
-        if (trunk && !(took && trunk_rides)) AS_STEP("trunkb.dw", st, run_split_k(*trunk, slab, st));
+        if (trunk && !(took && trunk_rides)) AS_STEP("trunkb.dw", st, run_split_k(*trunk, ln));
     } else {
         AS_TRY(multi(&job2, 1, "headb.dw2", &took));
-        if (!took) AS_STEP("headb.dw2", st, run_split_k(job2.g, slab, st, cu_budget));
+        if (!took) AS_STEP("headb.dw2", st, run_split_k(job2.g, ln, cu_budget));
     }
-    // unfold the LayerNorm affines (bit 0: layer 3, bit 1: layer 2, bit 2: layer 1; default: all three once everything is
-    // there, i.e. with part 0 or 2): one launch
-    if (unfold_layers < 0) unfold_layers = part == 1 ? 0 : 7;
-    if (unfold_layers == 0) return 0;
+    if (unfold_layers == UNFOLD_NONE) return 0;
     const float* dWf[3]; const float* dbf[3]; const float* Wp[3]; const float* gm[3]; const float* bt[3];
     float* dWo[3]; float* dgm[3]; float* dbt[3];
     int Rs[3], Ks[3], cnt = 0;
     for (int i = 2; i >= 0; --i) {
-        if (!(unfold_layers & (1 << (2 - i)))) continue;
+        if (!(unfold_layers & (UNFOLD_L3 << (2 - i)))) continue;
         const HeadLayer& l = s.l[i];
         dWf[cnt] = l.dwf; dbf[cnt] = G + l.b; Wp[cnt] = P + l.w; gm[cnt] = P + l.ln_g; bt[cnt] = P + l.ln_b;
         dWo[cnt] = G + l.w; dgm[cnt] = G + l.ln_g; dbt[cnt] = G + l.ln_b; Rs[cnt] = l.N; Ks[cnt] = l.K; ++cnt;
@@ -491,12 +496,12 @@ int head_bwd_dw(const HeadStack& s, const float* P, float* G, float* slab, hipSt
 // drive the library on different streams of one device never share a side stream or an event; calls on ONE stream are
 // ordered by that stream anyway.
 struct StreamState {
-    int dev = -1;
-    hipStream_t owner = nullptr;
-    hipStream_t side = nullptr, side2 = nullptr;                  // created on first use with overlap on
-    hipEvent_t fork[3] = {nullptr, nullptr, nullptr}, join = nullptr;
-    hipEvent_t fork2[3] = {nullptr, nullptr, nullptr}, join2 = nullptr;   // second side stream
-    hipEvent_t heads = nullptr;                                   // recorded by as_artspeech_bwd
+    int dev = -1; hipStream_t owner = nullptr;
+    hipStream_t side = nullptr, side2 = nullptr;   // weight-gradient (and fold) side stream, tail side stream: created on first use with overlap on
+    hipEvent_t fold_fork = nullptr, fold_join = nullptr;            // forward: caller -> weight folds -> head GEMM 1
+    hipEvent_t fork_trunk = nullptr, fork_dx1 = nullptr, fork_l0 = nullptr;   // backward: behind the trunk's dx, behind dx1, behind the layer-0 recurrence
+    hipEvent_t side_to_tail = nullptr, tail_to_caller = nullptr;    // backward joins
+    hipEvent_t heads = nullptr;                                     // "head gradients are final": recorded by as_artspeech_bwd
 };
 int g_overlap = -1;  // -1: not decided yet (environment), 0: off, 1: on
 std::mutex g_state_mu;
@@ -513,13 +518,10 @@ StreamState* state_for(hipStream_t st) {
     hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
     if (hipStreamIsCapturing(st, &cap) != hipSuccess || cap != hipStreamCaptureStatusNone) return nullptr;
     StreamState* p = new StreamState;
-    p->dev = dev;
-    p->owner = st;
-    bool ok = hipEventCreateWithFlags(&p->heads, hipEventDisableTiming) == hipSuccess &&
-              hipEventCreateWithFlags(&p->join, hipEventDisableTiming) == hipSuccess;
-    ok = ok && hipEventCreateWithFlags(&p->join2, hipEventDisableTiming) == hipSuccess;
-    for (auto& e : p->fork) ok = ok && hipEventCreateWithFlags(&e, hipEventDisableTiming) == hipSuccess;
-    for (auto& e : p->fork2) ok = ok && hipEventCreateWithFlags(&e, hipEventDisableTiming) == hipSuccess;
+    p->dev = dev; p->owner = st;
+    bool ok = true;
+    for (hipEvent_t* e : {&p->heads, &p->fold_fork, &p->fold_join, &p->fork_trunk, &p->fork_dx1, &p->fork_l0, &p->side_to_tail, &p->tail_to_caller})
+        ok = ok && hipEventCreateWithFlags(e, hipEventDisableTiming) == hipSuccess;
     if (!ok) {
         delete p;
         return nullptr;
@@ -550,40 +552,64 @@ StreamState* side_for(hipStream_t st) {
     }
     return p;
 }
+// The event calls of the schedule: a failure is the HIP error, reported in one form.  join: `to` continues behind what `from` holds
+int stream_call(hipError_t e) { AS_REQUIRE(e == hipSuccess, (int)e, "stream fork / join failed: %s", hipGetErrorString(e)); return 0; }
+int stream_record(hipEvent_t ev, hipStream_t s) { return stream_call(hipEventRecord(ev, s)); }
+int stream_wait(hipStream_t s, hipEvent_t ev) { return stream_call(hipStreamWaitEvent(s, ev, 0)); }
+int join(hipStream_t from, hipStream_t to, hipEvent_t ev) { AS_TRY(stream_record(ev, from)); return stream_wait(to, ev); }
 // "gradients of the trunk Linear and of all heads are final" -- recorded by as_artspeech_bwd on the stream that produced
 // them, so that a data-parallel host can start their all-reduce while the GRU backward is still running.
 int record_heads_done(hipStream_t owner, hipStream_t s) {
     StreamState* p = state_for(owner);
-    // no per-stream state (more than 256 distinct caller streams, or the first call on a stream inside a capture): the
-    // backward itself does not need the event -- everything then runs in order on the caller's stream -- only
-    // as_artspeech_wait_head_grads() does, and it reports the missing state itself
-    if (!p) return 0;
-    const hipError_t e = hipEventRecord(p->heads, s);
-    AS_REQUIRE(e == hipSuccess, (int)e, "as_artspeech_bwd: hipEventRecord failed: %s", hipGetErrorString(e));
-    return 0;
+    // no per-stream state (more than 256 distinct caller streams, or the first call on a stream inside a capture): the backward
+    // then runs in order on the caller's stream and needs no event; as_artspeech_wait_head_grads() reports the missing state itself
+    return p ? stream_record(p->heads, s) : 0;
 }
-
-// fork whose event the producing kernel may already carry (an AsStopEventScope around its launch): `left` = what the
-// scope's take() returned after the launch -- non-null: nobody consumed it, record it the ordinary way
-int fork_after(hipStream_t from, hipStream_t to, hipEvent_t ev, hipEvent_t left) {
-    hipError_t e = left ? hipEventRecord(ev, from) : hipSuccess;
-    if (e == hipSuccess) e = hipStreamWaitEvent(to, ev, 0);
-    if (e != hipSuccess) {
-        as_set_error("stream fork failed: %s", hipGetErrorString(e));
-        return (int)e;
+// The lanes of one call, resolved once: the caller's stream, the weight-gradient side stream and the tail side stream, each
+// with its slab.  The degenerate schedules are states of this value: without a second side stream the tail lane IS the
+// weight-gradient lane; flat (sd null: overlap off, no state for the stream, or its first call inside a capture) all three
+// are the caller's stream and the main slab, and every fork and join is nothing.
+struct Lanes {
+    StreamState* sd;   // the events; null: flat
+    Lane caller, wgrad, tail;
+    // forks are ordinary event records on the caller's stream: while the per-phase timers are on (as_profile_enable: a timing
+    // event recorded right behind an event-carrying dispatch reads ~20 us late, which would inflate the phase) and inside a
+    // stream capture (graph edges).  Found out only for a call whose forks could ride on a launch (forks_ride: the backward)
+    bool plain;
+};
+Lanes lanes_for(StreamState* sd, hipStream_t st, const HeadStack& hs, bool forks_ride) {
+    const Lane caller{st, hs.ws + hs.w.slab, SLAB_FLOATS, 0};
+    Lanes ln{sd, caller, caller, caller, true};
+    if (!sd) return ln;
+    ln.wgrad = Lane{sd->side, hs.ws + hs.w.slab2, SLAB2_FLOATS, 192};
+    // second side stream: the small hidden-to-hidden weight gradients (few workgroups, latency bound), so that they run
+    // beside the head / input-projection ones instead of queueing behind them: -9 us per step
+    ln.tail = sd->side2 ? Lane{sd->side2, hs.ws + hs.w.slab3, SLAB_FLOATS, 192} : ln.wgrad;
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    if (forks_ride) ln.plain = as_profile_active() || hipStreamIsCapturing(st, &cap) != hipSuccess || cap != hipStreamCaptureStatusNone;
+    return ln;
+}
+// A fork of the caller's stream behind the launch enqueued while the scope is open.  Unless the lanes are `plain` or the caller
+// says the fork cannot ride (something else follows the launch), the event is armed in the stop-event slot and the launch
+// carries it on its own dispatch: no marker packet on the critical stream between the launch and what follows it.  to()
+// records the event the ordinary way only if no launch took it, then makes the target(s) wait: ONE record on the critical
+// stream however many streams fork (every record is a barrier packet there).  seal() ends the riding early, for a fork whose
+// to() comes after launches that must not pick the event up.  Flat lanes: nothing happens.  The slot is empty on every way
+// out of the scope, an error return included (AsStopEventScope).
+struct Fork {
+    Fork(const Lanes& ln, hipEvent_t StreamState::*which, bool can_ride = true)
+        : from(ln.caller.stream), ev(ln.sd ? ln.sd->*which : nullptr), left(ln.plain || !can_ride ? ev : nullptr), slot(left ? nullptr : ev) {}
+    void seal() { if (hipEvent_t e = slot.take()) left = e; }
+    int to(hipStream_t a, hipStream_t b = nullptr) {
+        if (!ev) return 0;
+        seal();
+        if (left) AS_TRY(stream_record(ev, from));
+        left = nullptr;
+        AS_TRY(stream_wait(a, ev));
+        return b && b != a ? stream_wait(b, ev) : 0;
     }
-    return 0;
-}
-
-int fork_to(hipStream_t from, hipStream_t to, hipEvent_t ev) {
-    hipError_t e = hipEventRecord(ev, from);
-    if (e == hipSuccess) e = hipStreamWaitEvent(to, ev, 0);
-    if (e != hipSuccess) {
-        as_set_error("stream fork/join failed: %s", hipGetErrorString(e));
-        return (int)e;
-    }
-    return 0;
-}
+    hipStream_t from; hipEvent_t ev, left; AsStopEventScope slot;   // left: still to be recorded (armed: only if no launch takes it)
+};
 
 // C = act(A . B^T + bias) on dense operands (an nn.Linear forward: ld = row length)
 int linear_fwd(as_gemm g, const float* bias, int act, hipStream_t st) {
@@ -598,6 +624,182 @@ as_gemm gru_dw_hh(const float* dgh, const float* y, float* dW, float* db, int H,
     g.b_kshift = -1; g.b_kT = T; g.b_kshift_batch = 2;
     g.colsum = db; g.colsum_batch = 3 * H;
     return g;
+}
+// What one call of the model works on, and the phases of the step as its members (instead of a dozen parameters each)
+struct Step {
+    int V, E, H, B, T, R;
+    const float* P; const int64_t* tokens; int64_t tok_stride; const int32_t* lengths; float* ws; const as_opts* opts; float pdrop;
+    as_layout L; ModelWs w; HeadStack hs;
+    int fold_beside(const Lanes& ln) const;
+    int gru_trunk_fwd(int train, hipStream_t st) const;
+    int simple_trunk_dropout_fwd(hipStream_t st) const, simple_trunk_fwd(hipStream_t st) const;
+    int simple_bwd(float* G, const float* dzlin, const float* dpre3, hipStream_t st) const;
+    int gru_bwd(float* G, const float* dzlin, const float* dpre3, hipStream_t st) const;
+};
+int step_of(const as_dims* d, const float* P, const int64_t* tokens, int64_t tok_stride, const int32_t* lengths, int B, int T,
+            float* ws, const as_opts* opts, float pdrop, Step* c) {
+    *c = Step{d->vocab, d->embed, d->hidden, B, T, B * T, P, tokens, tok_stride, lengths, ws, opts, pdrop, {}, {}, {}};
+    AS_TRY(as_artspeech_layout(d, &c->L));
+    c->w = model_ws(*d, B, T);
+    c->hs = head_stack(*d, c->L, c->R, ws + c->w.head);
+    return 0;
+}
+// The side work of the forward, on the weight-gradient lane: fold the heads' weights and count the bad tokens.  Leaves
+// fold_join recorded behind it; the caller's stream waits for that before head GEMM 1.
+int Step::fold_beside(const Lanes& ln) const {
+    const hipStream_t fs = ln.wgrad.stream;
+    const bool late = opts && opts->fold_wait_event;   // a deferred parameter update (as_opts) must land before the folds
+    if (late) AS_TRY(stream_wait(fs, (hipEvent_t)opts->fold_wait_event));
+    // the folds read the parameters: behind everything the caller's stream holds (the previous optimizer step).  With a
+    // deferred update the event above already stands behind that (the update was enqueued after it), and an event record on
+    // the caller's stream is a barrier packet in front of the step's first kernel: skipped then
+    if (ln.sd && !late) AS_TRY(join(ln.caller.stream, fs, ln.sd->fold_fork));
+    AS_TRY(head_fold(hs, P, fs));
+    AS_TRY(as_count_bad_tokens(tokens, tok_stride, T, R, V, reinterpret_cast<int*>(ws + w.tokflag), fs));
+    return ln.sd ? stream_record(ln.sd->fold_join, fs) : 0;
+}
+// embedding -> two bidirectional GRU layers -> trunk Linear + ReLU into w.lin
+int Step::gru_trunk_fwd(int train, hipStream_t st) const {
+    // token table of layer-0 input projections, both directions: [V][2][3H]
+    // the step's first kernel, on its critical path: a small dedicated kernel (rowops.hip) while its staging area --
+    // (4 E + 64 (E + 1)) floats of dynamic LDS -- stays inside the 64 KB a launch gets without asking (E <= 240)
+    if ((long)V * E <= 16384 && ((size_t)4 * E + 64 * ((size_t)E + 1)) * sizeof(float) <= 65536)
+        AS_STEP("gru.table0", st, as_token_table(P + L.embedding, P + L.w_ih[0], P + L.b_ih[0], V, 6 * H, E, ws + w.tab0, st));
+    else
+        AS_STEP("gru.table0", st, linear_fwd(gemm_nt(P + L.embedding, E, P + L.w_ih[0], E, ws + w.tab0, 6 * H, V, 6 * H, E), P + L.b_ih[0], 0, st));
+    AS_STEP("gru.fwd_l0", st, as_gru_bidir_fwd_tokens(ws + w.tab0, tokens, tok_stride, V, P + L.w_hh[0], P + L.b_hh[0], lengths, B, T, H, ws + w.y0,
+                            train ? ws + w.g0 : nullptr, st));
+    const float* l1_in = ws + w.y0;
+    if (pdrop > 0.f) {  // nn.GRU inter-layer dropout: layer 1 sees the dropped layer-0 output
+        AS_STEP("gru.dropout", st, as_dropout(ws + w.y0, ws + w.y0d, (long)R * 2 * H, pdrop, opts->dropout_seed, st));
+        l1_in = ws + w.y0d;
+    }
+    // input projection of GRU layer 1: [R][2H] . [6H][2H]^T + b.
+    // (split arithmetic measured here twice and not kept: the plane-fed kernel of the heads 39.5 vs 43 us + a 10-us plane
+    // launch in front of the step's first kernel; both operands split in the kernel, gemm_s6.hip, 35.3 vs 33.1 us alone,
+    // tools/bench_linear.py -- at 2.5 GFLOP the launch is bound by its prologue and fill, not by the matrix pipe)
+    AS_STEP("gru.xproj1", st, linear_fwd(gemm_nt(l1_in, 2 * H, P + L.w_ih[1], 2 * H, ws + w.xp1, 6 * H, R, 6 * H, 2 * H), P + L.b_ih[1], 0, st));
+    AS_STEP("gru.fwd_l1", st, as_gru_bidir_fwd(ws + w.xp1, nullptr, 0, P + L.w_hh[1], P + L.b_hh[1], lengths, B, T, H, ws + w.y1,
+                            train ? ws + w.g1 : nullptr, st));
+    // (trunk Linear: 10.5 us on the fp32 instruction, 14 - 23 us on either split kernel: 50 - 200 short workgroups)
+    AS_STEP("trunk.linear", st, linear_fwd(gemm_nt(ws + w.y1, 2 * H, P + L.lin_w, 2 * H, ws + w.lin, H, R, H, 2 * H), P + L.lin_b, 1, st));
+    return 0;
+}
+// SimpleArtSpeech in training mode (models.py:64,85): Dropout acts on the embedded frame, so every position has its own
+// mask and the token-table fold of simple_trunk_fwd does not apply: gather -> counter mask -> Linear + ReLU on all frames
+int Step::simple_trunk_dropout_fwd(hipStream_t st) const {
+    AS_TRY(as_gather_rows(P + L.embedding, tokens, tok_stride, T, R, E, ws + w.y0, st, V));
+    AS_TRY(as_dropout(ws + w.y0, ws + w.y0, (long)R * E, pdrop, opts->dropout_seed, st));
+    return linear_fwd(gemm_nt(ws + w.y0, E, P + L.lin_w, E, ws + w.lin, H, R, H, E), P + L.lin_b, 1, st);
+}
+// SimpleArtSpeech otherwise: relu(Emb Wl^T + bl) per token, gathered by token id
+int Step::simple_trunk_fwd(hipStream_t st) const {
+    AS_TRY(linear_fwd(gemm_nt(P + L.embedding, E, P + L.lin_w, E, ws + w.tab0, H, V, H, E), P + L.lin_b, 1, st));
+    return as_gather_rows(ws + w.tab0, tokens, tok_stride, T, R, H, ws + w.lin, st, V);
+}
+// ---- backward (behind the heads' input-gradient chain: dzlin = d(trunk pre-activation) [R][H]; dpre3: see head_bwd_dw)
+int Step::simple_bwd(float* G, const float* dzlin, const float* dpre3, hipStream_t st) const {
+    const Lane me{st, hs.ws + hs.w.slab, SLAB_FLOATS, 0};
+    AS_TRY(head_bwd_dw(hs, P, G, me, DwPart::All, UNFOLD_ALL, dpre3));
+    AS_TRY(record_heads_done(st, st));
+    // The trunk Linear's backward over the rows its forward ran on.  Per frame (dropout): all R frames, then the mask regenerated from
+    // the seed and a segmented sum.  Else V token rows: lin = gather(relu(Emb Wl^T + bl)), dzlin carries the ReLU mask: its token sums first
+    const bool per_frame = pdrop > 0.f;
+    if (!per_frame) AS_TRY(as_token_segsum(dzlin, tokens, tok_stride, T, R, H, V, ws + w.dtab0, st, me.slab, SLAB_FLOATS));
+    const float* dz = per_frame ? dzlin : ws + w.dtab0;
+    const int rows = per_frame ? R : V;
+    as_gemm dw = gemm_tn(dz, H, per_frame ? ws + w.y0 : P + L.embedding, E, G + L.lin_w, E, H, E, rows);
+    dw.colsum = G + L.lin_b;
+    AS_TRY(run_split_k(dw, me));
+    const as_gemm gdx = gemm_nn(dz, H, P + L.lin_w, E, per_frame ? ws + w.dy0 : G + L.embedding, E, rows, E, H);
+    AS_TRY(as_gemm_f32(&gdx, st));
+    if (!per_frame) return 0;
+    AS_TRY(as_dropout(ws + w.dy0, ws + w.dy0, (long)R * E, pdrop, opts->dropout_seed, st));
+    return as_token_segsum(ws + w.dy0, tokens, tok_stride, T, R, E, V, G + L.embedding, st, me.slab, SLAB_FLOATS);
+}
+// The GRU model's backward: the recurrences on the caller's stream, the weight gradients beside them on the weight-gradient lane,
+// the small hidden-to-hidden ones and one of the two jobs behind the last recurrence on the tail lane (see lanes_for).
+int Step::gru_bwd(float* G, const float* dzlin, const float* dpre3, hipStream_t st) const {
+    const Lanes ln = lanes_for(side_for(st), st, hs, true);
+    // ---- trunk dx + fork: the head + trunk weight gradients run beside the layer-1 recurrence
+    {
+        Fork fork(ln, &StreamState::fork_trunk);
+        const as_gemm gdx = gemm_nn(dzlin, H, P + L.lin_w, 2 * H, ws + w.dy1, 2 * H, R, 2 * H, H);
+        AS_STEP("trunkb.dx", st, as_gemm_f32(&gdx, st));
+        AS_TRY(fork.to(ln.wgrad.stream));
+    }
+    // ---- layer-1 recurrence
+    AS_STEP("gru.bwd_l1", st, as_gru_bidir_bwd(ws + w.dy1, ws + w.y1, ws + w.g1, P + L.w_hh[1], lengths, B, T, H, ws + w.dgi1, ws + w.dgh1, st));
+    // ---- side work, part 1 (see DwPart): all of it when flat, unless layer 2's is computed later by as_artspeech_dw2()
+    as_gemm trunk = gemm_tn(dzlin, H, ws + w.y1, 2 * H, G + L.lin_w, 2 * H, H, 2 * H, R);
+    trunk.colsum = G + L.lin_b;
+    const bool defer = opts && opts->defer_dw2;
+    const bool two_parts = ln.sd != nullptr || defer;
+    AS_TRY(head_bwd_dw(hs, P, G, ln.wgrad, two_parts ? DwPart::Layers31Trunk : DwPart::All,
+                       defer ? UNFOLD_L3 | UNFOLD_L1 : two_parts ? UNFOLD_NONE : UNFOLD_ALL, dpre3, &trunk));
+    // [lin_w, total) of the flat gradient buffer is final from here on ([lin_w, ln2_g) with defer_dw2)
+    if (!two_parts || defer) AS_TRY(record_heads_done(st, ln.wgrad.stream));
+    // ---- dx1 + fork: the layer-1 weight gradients run beside the layer-0 recurrence.  Input gradient of GRU layer 1:
+    // [R][6H] . [6H][2H] (split arithmetic measured slower here, 56 vs 52 us: 200 workgroups x 1.2 MB of weight planes each
+    // from L2), then back through the inter-layer dropout: same mask, regenerated from the seed -- the fork cannot ride then
+    {
+        Fork fork(ln, &StreamState::fork_dx1, !(pdrop > 0.f));
+        AS_STEP("grub.dx1", st, run_split_k(gemm_nn(ws + w.dgi1, 6 * H, P + L.w_ih[1], 2 * H, ws + w.dy0, 2 * H, R, 2 * H, 6 * H), ln.caller));
+        if (pdrop > 0.f) AS_STEP("gru.dropout", st, as_dropout(ws + w.dy0, ws + w.dy0, (long)R * 2 * H, pdrop, opts->dropout_seed, st));
+        AS_TRY(fork.to(ln.wgrad.stream, ln.tail.stream));
+    }
+    // ---- layer-0 recurrence + fork (the tail's second job; sealed: the side work below is enqueued before the tail forks).
+    // Layer 0 sits under the token table: the recurrence keeps per-token sums of its input-side gate gradients in LDS and leaves
+    // B tables [V][6H] where dgi0 would have gone (V <= T: they fit): no dgi0, no segmented-sum pass; else dgi0 + as_token_segsum
+    const int tok_sums = V <= T && as_gru_bwd_tokens_fits(V, H, T);
+    Fork tail_fork(ln, &StreamState::fork_l0);
+    if (tok_sums) {
+        AS_PROF("gru.bwd_l0", st);
+        const int rc = as_gru_bidir_bwd_tokens(ws + w.dy0, ws + w.y0, ws + w.g0, P + L.w_hh[0], lengths, B, T, H, ws + w.dgh0, tokens,
+                                               tok_stride, V, ws + w.dgi0, st);
+        AS_REQUIRE(rc == 1, rc < 0 ? rc : AS_ERR_UNSUPPORTED, "gru.bwd_l0: launch failed");
+    } else {
+        AS_STEP("gru.bwd_l0", st, as_gru_bidir_bwd(ws + w.dy0, ws + w.y0, ws + w.g0, P + L.w_hh[0], lengths, B, T, H, ws + w.dgi0, ws + w.dgh0, st));
+    }
+    tail_fork.seal();
+    // ---- side work, part 2
+    if (two_parts && !defer) {
+        AS_TRY(head_bwd_dw(hs, P, G, ln.wgrad, DwPart::Layer2, UNFOLD_ALL, dpre3));
+        AS_TRY(record_heads_done(st, ln.wgrad.stream));  // [lin_w, total) of the flat gradient buffer is final from here on
+    }
+    as_gemm dw_ih1 = gemm_tn(ws + w.dgi1, 6 * H, pdrop > 0.f ? ws + w.y0d : ws + w.y0, 2 * H, G + L.w_ih[1], 2 * H, 6 * H, 2 * H, R);
+    dw_ih1.colsum = G + L.b_ih[1];
+    AS_STEP("grub.dw_ih1", ln.wgrad.stream, run_split_k(dw_ih1, ln.wgrad));
+    AS_STEP("grub.dw_hh", ln.tail.stream, run_split_k(gru_dw_hh(ws + w.dgh1, ws + w.y1, G + L.w_hh[1], G + L.b_hh[1], H, R, T), ln.tail));
+    // ---- tail: the layer-0 gradients.  What follows the last recurrence is the step's tail, and a cross-stream wait costs
+    // ~10 us each way on top of the work it guards (measured on the timeline): the LONGER of the two remaining jobs therefore
+    // stays on the caller's stream, back to back with the recurrence, and the shorter one forks off.
+    //   token sums in the recurrence: hidden-to-hidden GEMM (~30 us) here, table reduction + embedding grads (~13 us) aside;
+    //   otherwise: segmented sum + embedding grads (~40 us) here, the GEMM aside.
+    const Lane &hh = tok_sums ? ln.caller : ln.tail, &emb = tok_sums ? ln.tail : ln.caller;
+    // The weight-gradient lane has its last work of this call queued: the tail lane waits for it HERE, before its own tail work -- a
+    // wait that resolves while it idles through the recurrence -- so that the final join is one hop (tail lane -> caller) instead
+    // of two (14.6 -> 11 us between the last kernel and Adam).
+    if (ln.tail.stream != ln.wgrad.stream) AS_TRY(join(ln.wgrad.stream, ln.tail.stream, ln.sd->side_to_tail));
+    AS_TRY(tail_fork.to(ln.tail.stream));
+    AS_STEP("grub.dw_hh", hh.stream, run_split_k(gru_dw_hh(ws + w.dgh0, ws + w.y0, G + L.w_hh[0], G + L.b_hh[0], H, R, T), hh));
+    // embedding + layer-0 input projection through the token table
+    if (tok_sums)
+        AS_STEP("grub.segsum", emb.stream, as_sum_partials(ws + w.dgi0, (long)V * 6 * H, B, ws + w.dtab0, emb.stream));
+    else
+        AS_STEP("grub.segsum", emb.stream, as_token_segsum(ws + w.dgi0, tokens, tok_stride, T, R, 6 * H, V, ws + w.dtab0, emb.stream, emb.slab, SLAB_FLOATS));
+    if (E <= 256 && V <= 128 && (6 * H) % 16 == 0) {  // embedding + input-projection gradients of layer 0 from the token sums: one small launch
+        AS_STEP("grub.dw_ih0", emb.stream, as_emb_grads(ws + w.dtab0, P + L.embedding, P + L.w_ih[0], V, 6 * H, E, G + L.w_ih[0], G + L.b_ih[0],
+                                                  G + L.embedding, emb.stream));
+    } else {
+        // (only reached on the caller's lane or with the tail lane's slab free: token sums need V <= T, these need V > 128)
+        as_gemm dw_ih0 = gemm_tn(ws + w.dtab0, 6 * H, P + L.embedding, E, G + L.w_ih[0], E, 6 * H, E, V);
+        dw_ih0.colsum = G + L.b_ih[0];
+        AS_STEP("grub.dw_ih0", emb.stream, run_split_k(dw_ih0, emb));
+        AS_STEP("grub.demb", emb.stream, run_split_k(gemm_nn(ws + w.dtab0, 6 * H, P + L.w_ih[0], E, G + L.embedding, E, V, E, 6 * H), emb));
+    }
+    // ---- join: ONE wait on the caller's stream (each costs the tail a few microseconds): the tail lane has waited for the other, or is it
+    return ln.sd ? join(ln.tail.stream, st, ln.sd->tail_to_caller) : 0;
 }
 
 }  // namespace
@@ -682,7 +884,7 @@ extern "C" int as_head_bwd(const as_dims* d, const as_layout* lay, const float* 
                "as_head_bwd: bad argument");
     const HeadStack hs = head_stack(*d, *lay, rows, ws);
     AS_TRY(head_bwd_dx(hs, out, dout, dx, nullptr, (hipStream_t)stream));
-    return head_bwd_dw(hs, params, grads, ws + hs.w.slab, (hipStream_t)stream);
+    return head_bwd_dw(hs, params, grads, Lane{(hipStream_t)stream, ws + hs.w.slab, SLAB_FLOATS, 0}, DwPart::All, UNFOLD_ALL);
 }
 
 extern "C" int as_artspeech_fwd(const as_dims* d, const float* P, const int64_t* tokens, int64_t tok_stride,
@@ -695,89 +897,27 @@ extern "C" int as_artspeech_fwd(const as_dims* d, const float* P, const int64_t*
     AS_REQUIRE(d->simple || lengths, AS_ERR_BAD_ARG, "as_artspeech_fwd: lengths required for the GRU model");
     AS_REQUIRE((int64_t)B * T < (1LL << 31), AS_ERR_BAD_ARG, "as_artspeech_fwd: B*T too large");
     hipStream_t st = (hipStream_t)stream;
-    as_layout L;
-    AS_TRY(as_artspeech_layout(d, &L));
-    const ModelWs w = model_ws(*d, B, T);
-    const int V = d->vocab, E = d->embed, H = d->hidden, R = B * T;
-    const HeadStack hs = head_stack(*d, L, R, ws + w.head);
-    // the weight folds depend on the parameters only: run them on the side stream beside the recurrences
-    StreamState* sd = d->simple ? nullptr : side_for(st);
-    const bool late = opts && opts->fold_wait_event;
-    if (late) {   // a deferred parameter update (as_opts) must land before the heads' weights are folded
-        const hipError_t e = hipStreamWaitEvent(sd ? sd->side : st, (hipEvent_t)opts->fold_wait_event, 0);
-        AS_REQUIRE(e == hipSuccess, (int)e, "as_artspeech_fwd: cannot wait for fold_wait_event: %s", hipGetErrorString(e));
-    }
-    if (sd) {
-        // the folds read the parameters: behind everything `st` holds (the previous optimizer step).  With a deferred update
-        // the event above already stands behind that (the update was enqueued after it), and an event record on `st` is a
-        // barrier packet in front of the step's first kernel: skipped then
-        if (!late) AS_TRY(fork_to(st, sd->side, sd->fork[0]));
-        AS_TRY(head_fold(hs, P, sd->side));
-        AS_TRY(as_count_bad_tokens(tokens, tok_stride, T, R, V, reinterpret_cast<int*>(ws + w.tokflag), sd->side));
-        if (hipEventRecord(sd->join, sd->side) != hipSuccess) {
-            as_set_error("as_artspeech_fwd: event record failed");
-            return AS_ERR_BAD_ARG;
-        }
-    } else {
-        AS_TRY(head_fold(hs, P, st));
-        AS_TRY(as_count_bad_tokens(tokens, tok_stride, T, R, V, reinterpret_cast<int*>(ws + w.tokflag), st));
-    }
-    if (!d->simple) {
-        // token table of layer-0 input projections, both directions: [V][2][3H]
-        // the step's first kernel, on its critical path: a small dedicated kernel (rowops.hip) while its staging area --
-        // (4 E + 64 (E + 1)) floats of dynamic LDS -- stays inside the 64 KB a launch gets without asking (E <= 240)
-        if ((long)V * E <= 16384 && ((size_t)4 * E + 64 * ((size_t)E + 1)) * sizeof(float) <= 65536)
-            AS_STEP("gru.table0", st, as_token_table(P + L.embedding, P + L.w_ih[0], P + L.b_ih[0], V, 6 * H, E, ws + w.tab0, st));
-        else
-            AS_STEP("gru.table0", st, linear_fwd(gemm_nt(P + L.embedding, E, P + L.w_ih[0], E, ws + w.tab0, 6 * H, V, 6 * H, E), P + L.b_ih[0], 0, st));
-        AS_STEP("gru.fwd_l0", st, as_gru_bidir_fwd_tokens(ws + w.tab0, tokens, tok_stride, V, P + L.w_hh[0], P + L.b_hh[0], lengths, B, T, H, ws + w.y0,
-                                train ? ws + w.g0 : nullptr, st));
-        const float* l1_in = ws + w.y0;
-        if (pdrop > 0.f) {  // nn.GRU inter-layer dropout: layer 1 sees the dropped layer-0 output
-            AS_STEP("gru.dropout", st, as_dropout(ws + w.y0, ws + w.y0d, (long)R * 2 * H, pdrop, opts->dropout_seed, st));
-            l1_in = ws + w.y0d;
-        }
-        // input projection of GRU layer 1: [R][2H] . [6H][2H]^T + b.
-        // (split arithmetic measured here twice and not kept: the plane-fed kernel of the heads 39.5 vs 43 us + a 10-us plane
-        // launch in front of the step's first kernel; both operands split in the kernel, gemm_s6.hip, 35.3 vs 33.1 us alone,
-        // tools/bench_linear.py -- at 2.5 GFLOP the launch is bound by its prologue and fill, not by the matrix pipe)
-        AS_STEP("gru.xproj1", st, linear_fwd(gemm_nt(l1_in, 2 * H, P + L.w_ih[1], 2 * H, ws + w.xp1, 6 * H, R, 6 * H, 2 * H), P + L.b_ih[1], 0, st));
-        AS_STEP("gru.fwd_l1", st, as_gru_bidir_fwd(ws + w.xp1, nullptr, 0, P + L.w_hh[1], P + L.b_hh[1], lengths, B, T, H, ws + w.y1,
-                                train ? ws + w.g1 : nullptr, st));
-        // (trunk Linear: 10.5 us on the fp32 instruction, 14 - 23 us on either split kernel: 50 - 200 short workgroups)
-        AS_STEP("trunk.linear", st, linear_fwd(gemm_nt(ws + w.y1, 2 * H, P + L.lin_w, 2 * H, ws + w.lin, H, R, H, 2 * H), P + L.lin_b, 1, st));
-    } else if (pdrop > 0.f) {
-        // SimpleArtSpeech in training mode (models.py:64,85): Dropout acts on the embedded frame, so every position has its
-        // own mask and the token-table fold below does not apply: gather -> counter mask -> Linear + ReLU on all frames
-        AS_TRY(as_gather_rows(P + L.embedding, tokens, tok_stride, T, R, E, ws + w.y0, st, V));
-        AS_TRY(as_dropout(ws + w.y0, ws + w.y0, (long)R * E, pdrop, opts->dropout_seed, st));
-        AS_TRY(linear_fwd(gemm_nt(ws + w.y0, E, P + L.lin_w, E, ws + w.lin, H, R, H, E), P + L.lin_b, 1, st));
-    } else {
-        AS_TRY(linear_fwd(gemm_nt(P + L.embedding, E, P + L.lin_w, E, ws + w.tab0, H, V, H, E), P + L.lin_b, 1, st));
-        AS_TRY(as_gather_rows(ws + w.tab0, tokens, tok_stride, T, R, H, ws + w.lin, st, V));
-    }
-    if (sd && hipStreamWaitEvent(st, sd->join, 0) != hipSuccess) {  // folded weights ready before head GEMM 1
-        as_set_error("as_artspeech_fwd: stream wait failed");
-        return AS_ERR_BAD_ARG;
-    }
-    if (opts && opts->loss_targets) {
-        AS_REQUIRE(train && lengths && opts->loss_out && opts->loss_dout && opts->loss_tgt_T >= T, AS_ERR_BAD_ARG,
-                   "as_artspeech_fwd: fused criterion needs train, lengths, loss_out, loss_dout and loss_tgt_T >= T");
-        const Criterion crit{opts->loss_targets, (long)opts->loss_tgt_T, lengths, T, opts->loss_scale, opts->loss_out, opts->loss_dout};
-        return head_fwd_impl(hs, ws + w.lin, out, st, &crit);
-    }
-    return head_fwd_impl(hs, ws + w.lin, out, st);
+    Step c;
+    AS_TRY(step_of(d, P, tokens, tok_stride, lengths, B, T, ws, opts, pdrop, &c));
+    // the weight folds depend on the parameters only: they run on the side stream beside the recurrences
+    const Lanes ln = lanes_for(d->simple ? nullptr : side_for(st), st, c.hs, false);
+    AS_TRY(c.fold_beside(ln));
+    AS_TRY(!d->simple ? c.gru_trunk_fwd(train, st) : pdrop > 0.f ? c.simple_trunk_dropout_fwd(st) : c.simple_trunk_fwd(st));
+    if (ln.sd) AS_TRY(stream_wait(st, ln.sd->fold_join));   // folded weights ready before head GEMM 1
+    if (!(opts && opts->loss_targets)) return head_fwd_impl(c.hs, ws + c.w.lin, out, st);
+    AS_REQUIRE(train && lengths && opts->loss_out && opts->loss_dout && opts->loss_tgt_T >= T, AS_ERR_BAD_ARG,
+               "as_artspeech_fwd: fused criterion needs train, lengths, loss_out, loss_dout and loss_tgt_T >= T");
+    const Criterion crit{opts->loss_targets, (long)opts->loss_tgt_T, lengths, T, opts->loss_scale, opts->loss_out, opts->loss_dout};
+    return head_fwd_impl(c.hs, ws + c.w.lin, out, st, &crit);
 }
 
 extern "C" int as_artspeech_dw2(const as_dims* d, const float* P, int32_t B, int32_t T, float* G, float* ws, void* stream) {
     AS_TRY(check_dims(d, "as_artspeech_dw2"));
     AS_REQUIRE(!d->simple && P && G && ws && B > 0 && T > 0, AS_ERR_BAD_ARG, "as_artspeech_dw2: bad argument");
-    as_layout L;
-    AS_TRY(as_artspeech_layout(d, &L));
-    const ModelWs w = model_ws(*d, B, T);
-    const HeadStack hs = head_stack(*d, L, (int64_t)B * T, ws + w.head);
-    // beside a forward recurrence (2 B workgroups): 192 CUs to count on
-    return head_bwd_dw(hs, P, G, hs.ws + hs.w.slab2, (hipStream_t)stream, nullptr, 192, SLAB2_FLOATS, nullptr, 2, 2);
+    Step c;
+    AS_TRY(step_of(d, P, nullptr, 0, nullptr, B, T, ws, nullptr, 0.f, &c));
+    // beside a forward recurrence (2 B workgroups): 192 CUs to count on, and the weight-gradient lane's slab
+    return head_bwd_dw(c.hs, P, G, Lane{(hipStream_t)stream, c.hs.ws + c.hs.w.slab2, SLAB2_FLOATS, 192}, DwPart::Layer2, UNFOLD_L2);
 }
 
 extern "C" int as_artspeech_bwd(const as_dims* d, const float* P, const int64_t* tokens, int64_t tok_stride,
@@ -790,152 +930,12 @@ extern "C" int as_artspeech_bwd(const as_dims* d, const float* P, const int64_t*
                "as_artspeech_bwd: bad argument");
     AS_REQUIRE(d->simple || lengths, AS_ERR_BAD_ARG, "as_artspeech_bwd: lengths required for the GRU model");
     hipStream_t st = (hipStream_t)stream;
-    as_layout L;
-    AS_TRY(as_artspeech_layout(d, &L));
-    const ModelWs w = model_ws(*d, B, T);
-    const int V = d->vocab, E = d->embed, H = d->hidden, R = B * T;
-    const HeadStack hs = head_stack(*d, L, R, ws + w.head);
-    float* slab = hs.ws + hs.w.slab;
-    float* slab2 = hs.ws + hs.w.slab2;
-    float* dzlin = hs.ws + hs.w.dxhat;  // reused: d(trunk pre-activation) [R][H]
+    Step c;
+    AS_TRY(step_of(d, P, tokens, tok_stride, lengths, B, T, ws, opts, pdrop, &c));
+    float* dzlin = c.hs.ws + c.hs.w.dxhat;  // reused: d(trunk pre-activation) [R][H]
     // heads: input-gradient chain (+ the trunk ReLU mask fused into the last normalize-backward)
     const bool presig = opts && opts->dout_presigmoid;
-    const float* dpre3 = presig ? dout : nullptr;
-    AS_TRY(head_bwd_dx(hs, out, dout, dzlin, ws + w.lin, st, presig));
+    AS_TRY(head_bwd_dx(c.hs, out, dout, dzlin, ws + c.w.lin, st, presig));
     AS_REQUIRE(!(d->simple && opts && opts->defer_dw2), AS_ERR_UNSUPPORTED, "as_artspeech_bwd: defer_dw2 is for the GRU model");
-    if (d->simple) {
-        AS_TRY(head_bwd_dw(hs, P, G, slab, st, dpre3));
-        AS_TRY(record_heads_done(st, st));
-        if (pdrop > 0.f) {  // per-frame path of the forward: Linear backward on all frames, mask regenerated from the seed
-            as_gemm dw = gemm_tn(dzlin, H, ws + w.y0, E, G + L.lin_w, E, H, E, R);
-            dw.colsum = G + L.lin_b;
-            AS_TRY(run_split_k(dw, slab, st));
-            const as_gemm gdx = gemm_nn(dzlin, H, P + L.lin_w, E, ws + w.dy0, E, R, E, H);
-            AS_TRY(as_gemm_f32(&gdx, st));
-            AS_TRY(as_dropout(ws + w.dy0, ws + w.dy0, (long)R * E, pdrop, opts->dropout_seed, st));
-            AS_TRY(as_token_segsum(ws + w.dy0, tokens, tok_stride, T, R, E, V, G + L.embedding, st, slab, SLAB_FLOATS));
-            return 0;
-        }
-        // lin = gather(relu(Emb Wl^T + bl)); dzlin already carries the ReLU mask of the gathered rows
-        AS_TRY(as_token_segsum(dzlin, tokens, tok_stride, T, R, H, V, ws + w.dtab0, st, slab, SLAB_FLOATS));
-        as_gemm dw = gemm_tn(ws + w.dtab0, H, P + L.embedding, E, G + L.lin_w, E, H, E, V);
-        dw.colsum = G + L.lin_b;
-        AS_TRY(run_split_k(dw, slab, st));
-        const as_gemm demb = gemm_nn(ws + w.dtab0, H, P + L.lin_w, E, G + L.embedding, E, V, E, H);
-        AS_TRY(as_gemm_f32(&demb, st));
-        return 0;
-    }
-    StreamState* sd = side_for(st);
-    hipStream_t s2 = sd ? sd->side : st;      // no side stream: everything in order on `st`
-    float* sl2 = sd ? slab2 : slab;
-    // second side stream: the small hidden-to-hidden weight gradients (few workgroups, latency bound), so that they run
-    // beside the head / input-projection ones instead of queueing behind them: -9 us per step
-    hipStream_t s3 = (sd && sd->side2) ? sd->side2 : s2;
-    float* sl3 = (sd && sd->side2) ? hs.ws + hs.w.slab3 : sl2;
-    // every fork an event record on `st` while the per-phase timers are on (as_profile_enable): a timing event recorded
-    // right behind an event-carrying dispatch reads ~20 us late, which would inflate the phase.
-    hipStreamCaptureStatus cap_ = hipStreamCaptureStatusNone;   // inside a stream capture: ordinary event records (graph edges)
-    const bool capturing = hipStreamIsCapturing(st, &cap_) != hipSuccess || cap_ != hipStreamCaptureStatusNone;
-    const bool plain_forks = as_profile_active() || capturing;
-    // ---- fork 0: head + trunk weight gradients run beside the layer-1 recurrence.  The fork's event rides on the GEMM's own
-    // dispatch (AsStopEventScope): no marker packet on `st` between it and the recurrence
-    {
-        AsStopEventScope fork0(sd && !plain_forks ? sd->fork[0] : nullptr);
-        const as_gemm gdx = gemm_nn(dzlin, H, P + L.lin_w, 2 * H, ws + w.dy1, 2 * H, R, 2 * H, H);
-        AS_STEP("trunkb.dx", st, as_gemm_f32(&gdx, st));
-        if (sd) AS_TRY(fork_after(st, s2, sd->fork[0], plain_forks ? sd->fork[0] : fork0.take()));
-    }
-    AS_STEP("gru.bwd_l1", st, as_gru_bidir_bwd(ws + w.dy1, ws + w.y1, ws + w.g1, P + L.w_hh[1], lengths, B, T, H, ws + w.dgi1, ws + w.dgh1, st));
-    const int side_cus = sd ? 192 : 0;  // the recurrence's 2 * B workgroups hold 64 CUs while the side stream works
-    as_gemm trunk = gemm_tn(dzlin, H, ws + w.y1, 2 * H, G + L.lin_w, 2 * H, H, 2 * H, R);
-    trunk.colsum = G + L.lin_b;
-    // with a side stream: layers 3, 1 and the trunk now, layer 2 + unfold beside the layer-0 recurrence (see head_bwd_dw)
-    const bool defer = opts && opts->defer_dw2;   // layer 2's is computed later by as_artspeech_dw2()
-    const bool two_parts = sd != nullptr || defer;
-    AS_TRY(head_bwd_dw(hs, P, G, sl2, s2, dpre3, side_cus, sd ? SLAB2_FLOATS : SLAB_FLOATS, &trunk, two_parts ? 1 : 0, defer ? 5 : -1));
-    // [lin_w, total) of the flat gradient buffer is final from here on ([lin_w, ln2_g) with defer_dw2)
-    if (!two_parts || defer) AS_TRY(record_heads_done(st, s2));
-    // input gradient of GRU layer 1: [R][6H] . [6H][2H]
-    // (split arithmetic measured slower here, 56 vs 52 us: 200 workgroups x 1.2 MB of weight planes each from L2)
-    const bool fork1_armed = sd && !plain_forks && !(pdrop > 0.f);
-    hipEvent_t fork1_left = nullptr;
-    {
-        AsStopEventScope fork1(fork1_armed ? sd->fork[1] : nullptr);   // fork 1 rides on this GEMM (see fork 0)
-        AS_STEP("grub.dx1", st, run_split_k(gemm_nn(ws + w.dgi1, 6 * H, P + L.w_ih[1], 2 * H, ws + w.dy0, 2 * H, R, 2 * H, 6 * H), slab, st));
-        fork1_left = fork1.take();
-    }
-    if (pdrop > 0.f)  // back through the inter-layer dropout: same mask, regenerated from the seed
-        AS_STEP("gru.dropout", st, as_dropout(ws + w.dy0, ws + w.dy0, (long)R * 2 * H, pdrop, opts->dropout_seed, st));
-    // ---- fork 1: layer-1 weight gradients run beside the layer-0 recurrence
-    if (sd) AS_TRY(fork_after(st, s2, sd->fork[1], fork1_armed ? fork1_left : sd->fork[1]));
-    if (s3 != s2) {   // ONE record on `st` for both side streams (every event record is a barrier packet on the critical stream)
-        const hipError_t e = hipStreamWaitEvent(s3, sd->fork[1], 0);
-        AS_REQUIRE(e == hipSuccess, (int)e, "as_artspeech_bwd: stream wait failed: %s", hipGetErrorString(e));
-    }
-    // layer 0 sits under the token table: the recurrence keeps per-token sums of its input-side gate gradients in LDS and
-    // leaves B tables [V][6H] where dgi0 would have gone (V <= T: they fit), so there is no dgi0 and no segmented-sum
-    // pass; else dgi0 + as_token_segsum below
-    const int tok_sums = V <= T && as_gru_bwd_tokens_fits(V, H, T);
-    // fork 2 (the tail's second job, below) rides on the recurrence's dispatch
-    const hipEvent_t fork2_ev = sd ? (s3 != s2 ? sd->fork2[2] : sd->fork[2]) : nullptr;
-    hipEvent_t fork2_left = fork2_ev;
-    {
-        AsStopEventScope fork2(plain_forks ? nullptr : fork2_ev);
-        if (tok_sums) {
-            AS_PROF("gru.bwd_l0", st);
-            const int rc = as_gru_bidir_bwd_tokens(ws + w.dy0, ws + w.y0, ws + w.g0, P + L.w_hh[0], lengths, B, T, H, ws + w.dgh0, tokens,
-                                                   tok_stride, V, ws + w.dgi0, st);
-            AS_REQUIRE(rc == 1, rc < 0 ? rc : AS_ERR_UNSUPPORTED, "gru.bwd_l0: launch failed");
-        } else {
-            AS_STEP("gru.bwd_l0", st, as_gru_bidir_bwd(ws + w.dy0, ws + w.y0, ws + w.g0, P + L.w_hh[0], lengths, B, T, H, ws + w.dgi0, ws + w.dgh0, st));
-        }
-        if (sd && !plain_forks) fork2_left = fork2.take();
-    }
-    if (two_parts && !defer) {
-        AS_TRY(head_bwd_dw(hs, P, G, sl2, s2, dpre3, side_cus, sd ? SLAB2_FLOATS : SLAB_FLOATS, nullptr, 2));
-        AS_TRY(record_heads_done(st, s2));  // [lin_w, total) of the flat gradient buffer is final from here on
-    }
-    as_gemm dw_ih1 = gemm_tn(ws + w.dgi1, 6 * H, pdrop > 0.f ? ws + w.y0d : ws + w.y0, 2 * H, G + L.w_ih[1], 2 * H, 6 * H, 2 * H, R);
-    dw_ih1.colsum = G + L.b_ih[1];
-    AS_STEP("grub.dw_ih1", s2, run_split_k(dw_ih1, sl2, s2));
-    AS_STEP("grub.dw_hh", s3, run_split_k(gru_dw_hh(ws + w.dgh1, ws + w.y1, G + L.w_hh[1], G + L.b_hh[1], H, R, T), sl3, s3));
-    // ---- layer-0 gradients.  What follows the last recurrence is the step's tail, and a cross-stream wait costs ~10 us
-    // each way on top of the work it guards (measured on the timeline): the LONGER of the two remaining jobs therefore
-    // stays on the caller's stream, back to back with the recurrence, and the shorter one forks off.
-    //   token sums in the recurrence: hidden-to-hidden GEMM (~30 us) here, table reduction + embedding grads (~13 us) aside;
-    //   otherwise: segmented sum + embedding grads (~40 us) here, the GEMM aside.
-    // The first side stream has its last work of this call queued: the second one waits for it HERE, before its own tail work --
-    // a wait that resolves while that stream idles through the recurrence -- so that the final join is one hop (second side
-    // stream -> `st`) instead of two (14.6 -> 11 us between the last kernel and Adam).
-    if (sd && s3 != s2) AS_TRY(fork_to(s2, s3, sd->join));
-    hipStream_t s_hh = tok_sums ? st : s3, s_emb = tok_sums ? s3 : st;
-    float* sl_hh = tok_sums ? slab : sl3;
-    if (sd) AS_TRY(fork_after(st, s3, fork2_ev, fork2_left));
-    AS_STEP("grub.dw_hh", s_hh, run_split_k(gru_dw_hh(ws + w.dgh0, ws + w.y0, G + L.w_hh[0], G + L.b_hh[0], H, R, T), sl_hh, s_hh));
-    // embedding + layer-0 input projection through the token table
-    if (tok_sums)
-        AS_STEP("grub.segsum", s_emb, as_sum_partials(ws + w.dgi0, (long)V * 6 * H, B, ws + w.dtab0, s_emb));
-    else
-        AS_STEP("grub.segsum", s_emb, as_token_segsum(ws + w.dgi0, tokens, tok_stride, T, R, 6 * H, V, ws + w.dtab0, s_emb, slab, SLAB_FLOATS));
-    if (E <= 256 && V <= 128 && (6 * H) % 16 == 0) {  // embedding + input-projection gradients of layer 0 from the token sums: one small launch
-        AS_STEP("grub.dw_ih0", s_emb, as_emb_grads(ws + w.dtab0, P + L.embedding, P + L.w_ih[0], V, 6 * H, E, G + L.w_ih[0], G + L.b_ih[0],
-                                                G + L.embedding, s_emb));
-    } else {
-        // (only reached with s_emb == st or with the main slab free: token sums need V <= T, these need V > 128)
-        float* sl_e = tok_sums ? sl3 : slab;
-        as_gemm dw_ih0 = gemm_tn(ws + w.dtab0, 6 * H, P + L.embedding, E, G + L.w_ih[0], E, 6 * H, E, V);
-        dw_ih0.colsum = G + L.b_ih[0];
-        AS_STEP("grub.dw_ih0", s_emb, run_split_k(dw_ih0, sl_e, s_emb));
-        AS_STEP("grub.demb", s_emb, run_split_k(gemm_nn(ws + w.dtab0, 6 * H, P + L.w_ih[0], E, G + L.embedding, E, V, E, 6 * H), sl_e, s_emb));
-    }
-    // join: `st` continues only after the side streams' work.  One wait on `st` (each costs the tail a few microseconds):
-    // the second side stream first waits for the first one, then `st` waits for it alone.
-    if (sd && s3 != s2) {
-        // the second side stream already waited for the first one (above, before its tail work): one record behind its last
-        // kernel, one wait on `st`
-        AS_TRY(fork_to(s3, st, sd->join2));
-    } else if (sd) {
-        AS_TRY(fork_to(s2, st, sd->join));
-    }
-    return 0;
+    return d->simple ? c.simple_bwd(G, dzlin, presig ? dout : nullptr, st) : c.gru_bwd(G, dzlin, presig ? dout : nullptr, st);
 }

@@ -126,7 +126,7 @@ def _check_fwd(out, pt, lse, ref, T, Tk, what):
 
 
 # --- a. masked forward at every key-block count --------------------------------------------------------------------------
-# launch_attn_nb rounds nb = ceil(Tk / 32) up to a compiled NB in {1, 2, 4, 6, 7, 8}: these Tk give nb = NB for every NB and
+# attn_with_shape (attention.hip) rounds nb = ceil(Tk / 32) up to a compiled NB in {1, 2, 4, 6, 7, 8}: these Tk give nb = NB for every NB and
 # nb < NB for the two rounded ones (nb = 3 -> 4: Tk 65-96, nb = 5 -> 6: Tk 129-160), at every head width
 _TKS = [1, 31, 32, 33, 64, 65, 80, 96, 97, 128, 129, 150, 160, 161, 192, 193, 224, 225, 255, 256]
 _DHS = (16, 32, 64)
