@@ -43,6 +43,7 @@ SOURCES = {
     "pc_eval.hip": ["-ffp-contract=off"],
     "report.hip": ["-ffp-contract=off"],
     "contours.hip": ["-ffp-contract=off"],
+    "melspec.hip": [],
     "artspeech.hip": [],
 }
 

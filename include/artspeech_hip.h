@@ -867,6 +867,28 @@ int as_prepare_contours(const float* raw, const float* refs, const int32_t* kind
 int as_column_mean_std(const float* x, int64_t rows, int32_t cols, float* mean, float* std, double* ws, int64_t ws_doubles,
                        void* stream);
 
+/* Log-mel spectrogram front end of the acoustic recogniser (reference phoneme_recognition/datasets.py:84-92 the transform,
+ * :123-132 load_melspec with its mono-to-stereo copy, :47-48 dynamic_range_compression, and the feature part of collate_fn
+ * :258-260): torchaudio.transforms.MelSpectrogram's defaults, log(max(., clip)), the channel copy and the padded batch in one
+ * launch, from the padded waveforms to the collated tensor.
+ *   wave [B] rows of wave_pitch floats, n_samples [B] int64 on the device: utterance b has n_b = n_samples[b] samples
+ *   framing             reflect padding by n_fft / 2 on both sides without repeating the edge (index -j reads x[j], index
+ *                       n_b - 1 + j reads x[n_b - 1 - j]); frame t covers the padded samples [t hop, t hop + n_fft);
+ *                       T_b = 1 + n_b / hop (integer division)
+ *   window [n_fft]      the analysis window already centred in the frame
+ *   fbanks [n_fft / 2 + 1][n_mels]   mel[m] = sum_k fbanks[k][m] (re^2 + im^2)(X[k]), X the DFT of the windowed frame
+ *   clip                > 0: out = log(max(mel, clip)); <= 0: out = mel (power)
+ *                       (a NaN sample gives NaN in the frames that read it, as torch.clamp does)
+ *   out [B][channels][n_mels][T_max]  the result at t < T_b, bit-identical in every plane; pad_value at T_b <= t < T_max; every
+ *                       element is written.  lengths_out [B] int64 (optional) = T_b
+ * Supported: n_fft a power of two in [64, 2048], hop >= 1, 1 <= n_mels <= 128, channels 1 or 2, wave_pitch <= 0x3fff0000;
+ * AS_ERR_UNSUPPORTED before any launch otherwise.  window and fbanks are 16-byte aligned.  The kernel never reads outside row b: n_b is clamped to [0, wave_pitch], n_b <= n_fft / 2 (where the
+ * reflection is undefined; callers refuse it) gives T_b = 0, an all-padding row, and T_b is clamped to T_max.  fp32 throughout,
+ * twiddles rounded from fp64; no atomics on global memory: repeats, and a row alone or inside a batch, are bit-identical. */
+int as_melspec_fwd(const float* wave, int64_t wave_pitch, const int64_t* n_samples, int32_t B, int32_t n_fft, int32_t hop,
+                   const float* window, const float* fbanks, int32_t n_mels, float clip, int32_t channels, float pad_value,
+                   float* out, int64_t T_max, int64_t* lengths_out, void* stream);
+
 /* Optional per-kernel-phase timing with HIP events recorded on the launch stream (for bench.py's
  * roofline object).  as_profile_report writes "name count total_ms\n" lines (NUL terminated, truncated
  * to buflen) and returns the untruncated length; it waits for the recorded events to complete. */
