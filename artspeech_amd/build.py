@@ -33,6 +33,7 @@ SOURCES = {
     "conv.hip": [],
     "scorer_wgrad.hip": [],
     "ctc.hip": [],
+    "ctc_align.hip": [],
     "recog_eval.hip": [],
     "attention.hip": [],
     "metrics.hip": ["-ffp-contract=off"],

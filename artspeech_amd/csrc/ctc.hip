@@ -17,10 +17,9 @@
 #include <math.h>
 
 #include "as_common.h"
+#include "ctc_common.h"
 
 namespace {
-
-constexpr int CTC_MAX_L = 2047;  // S = 2L + 1 <= 4095 states: 16 per thread of the 256-thread recursion
 
 __device__ __forceinline__ float lse2(float a, float b) {
     const float m = fmaxf(a, b);
@@ -31,24 +30,6 @@ __device__ __forceinline__ float lse3(float a, float b, float c) {
     const float m = fmaxf(a, fmaxf(b, c));
     if (m == -INFINITY) return -INFINITY;
     return m + logf(expf(a - m) + expf(b - m) + expf(c - m));
-}
-
-// validated per-utterance sizes (false: inconsistent lengths; the caller writes NaN instead of reading out of bounds)
-__device__ __forceinline__ bool ctc_sizes(const int64_t* in_len, const int64_t* tgt_len, const int64_t* targets, int64_t tgt_stride,
-                                          int b, int T, int maxL, int& L, int& Tb, long& toff) {
-    const long l = tgt_len[b], tb = in_len[b];
-    if (l < 0 || l > maxL || tb < 0 || tb > T) return false;
-    L = (int)l;
-    Tb = (int)tb;
-    if (tgt_stride > 0) {
-        toff = (long)b * tgt_stride;
-    } else {   // torch's concatenated 1-D form
-        long o = 0;
-        for (int i = 0; i < b; ++i) o += tgt_len[i];
-        toff = o;
-    }
-    (void)targets;
-    return true;
 }
 
 __global__ __launch_bounds__(256) void ctc_row_lse_kernel(const float* __restrict__ x, long sxt, long sxb, int T, int B, int C,

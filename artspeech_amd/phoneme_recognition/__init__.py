@@ -15,6 +15,7 @@ from ..settings import BLANK, SIL, TRAIN, UNKNOWN  # noqa: F401
 from .align import align_counts, confusion_counts, decode_top1, edit_distance  # noqa: F401
 from .ctc import CTCLoss, ctc_loss
 from .deepspeech2 import DeepSpeech2, TrainableDeepSpeech2, top1_phonemes  # noqa: F401
+from .forced_align import Alignment, align_test, forced_align  # noqa: F401
 from .metrics import normalize_counts
 
 CLASSES_NAMES = {

@@ -603,6 +603,33 @@ int as_ctc_grad(const float* x, int64_t sx_t, int64_t sx_b, int32_t T, int32_t B
                 const float* ws, int64_t ws_floats, const float* nll, const float* scale, int32_t zero_infinity, float* grad, int64_t sg_t,
                 int64_t sg_b, void* stream);
 
+/* CTC forced alignment (artspeech_amd/csrc/ctc_align.hip): the Viterbi path of the known label sequence through the emissions,
+ * expanded into one phoneme token per frame.  It replaces, as a call site, the TextGrid-derived per-frame sequences of
+ * generate_vocal_tract_shape_v2.py:135-158 (get_repeated_phoneme / get_phonetic_sequences); the reference has no alignment of its
+ * own.  Inputs exactly as as_ctc_loss takes them (x rows, logits, targets padded or concatenated, int64 lengths on the device);
+ * max_target_length <= 2047 and T <= 8192, else AS_ERR_UNSUPPORTED before any launch.  State graph and moves are as_ctc_loss's
+ * (S = 2L + 1 states; stay, step, skip between different labels; start in state 0 or 1, end in S-1 or S-2), the recursion is
+ * max-plus over fp32 log-probabilities, accumulated in fp32 in time order.  Ties: candidates in the order stay, step, skip, a
+ * later one wins only if strictly greater; at the end the label state S-2 wins when >= state S-1.  Where the rule of
+ * torchaudio.functional.forced_align is well defined these choices coincide with it.
+ * For utterance b, Tb = input_lengths[b], L = target_lengths[b]:
+ *   score[b]           the path's log-probability; -inf when no alignment exists (Tb < L + adjacent equal labels, a forbidden
+ *                      label, Tb == 0 < L); 0 for Tb == 0 == L; NaN for inconsistent lengths.
+ *   frame_index[b][t]  the target entry j emitted at frame t < Tb, -1 on a blank frame;  frame_token[b][t]: targets[j] or blank.
+ *   frame_filled[b][t] the entry with blanks absorbed: a blank frame belongs to the preceding entry, leading blanks to entry 0;
+ *                      -1 with L == 0.
+ *   spans[b][j]        (first frame, last frame + 1) of entry j itself;  span_score[b][j]: the mean log-probability of its label
+ *                      over those frames.
+ * Frames t >= Tb get -1 in the three frame arrays, entries j >= L get (-1, -1) and NaN; an utterance without an alignment gets
+ * that fill in all its rows.  Any of the five arrays may be NULL.  The 2-bit back-pointers live in LDS when
+ * as_ctc_align_workspace_bytes(...) is 0 (T * (6 + 4 * ceil((2 * max_target_length + 1) / 16)) bytes within 56 KiB), else in ws
+ * (that many bytes; too small: AS_ERR_WORKSPACE).  One launch in both input modes, no atomics: repeats are bit-identical. */
+int64_t as_ctc_align_workspace_bytes(int32_t T, int32_t B, int32_t max_target_length);
+int as_ctc_align(const float* x, int64_t sx_t, int64_t sx_b, int32_t T, int32_t B, int32_t C, int32_t logits, const int64_t* targets,
+                 int64_t tgt_stride, const int64_t* input_lengths, const int64_t* target_lengths, int32_t max_target_length, int32_t blank,
+                 void* ws, int64_t ws_bytes, float* score, int32_t* frame_index, int32_t* frame_token, int32_t* frame_filled,
+                 int32_t* spans, float* span_score, void* stream);
+
 /* ---- evaluating the scorer (test_phoneme_recognition.py): decoding, edit distance, alignment, confusion counts -----------------
  * Integer kernels (artspeech_amd/csrc/recog_eval.hip).  Token batches are int32 rows padded to a pitch (pred [B][P_max],
  * target [B][L_max]) with int32 counts per row (clamped to [0, pitch]; entries past a count are never read).  class_map (int32
