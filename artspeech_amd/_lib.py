@@ -160,6 +160,9 @@ PROTOTYPES = {
                            _I64, _S]),
     "as_ctc_align_workspace_bytes": (_I64, [_I32, _I32, _I32]),
     "as_ctc_align": (_I32, [_P, _I64, _I64, _I32, _I32, _I32, _I32, _P, _I64, _P, _P, _I32, _I32, _P, _I64, _P, _P, _P, _P, _P, _P, _S]),
+    "as_ctc_beam_workspace_bytes": (_I64, [_I32, _I32, _I32, _I32]),
+    "as_ctc_beam_search": (_I32, [_P, _I64, _I64, _I32, _I32, _I32, _I32, _P, _I32, _I32, _F, _I32, _I32, _F, _I32, _I32, _P, _P, _P, _P,
+                                  _P, _I64, _S]),
     "as_decode_top1": (_I32, [_P, _I64, _I64, _I32, _I32, _I32, _P, _I32, _P, _P, _P, _S]),
     "as_edit_distance": (_I32, [_P, _I32, _P, _P, _I32, _P, _I32, _P, _I32, _P, _S]),
     "as_align_workspace_bytes": (_I64, [_I32, _I32, _I32]),

@@ -34,6 +34,7 @@ SOURCES = {
     "scorer_wgrad.hip": [],
     "ctc.hip": [],
     "ctc_align.hip": [],
+    "ctc_beam.hip": [],
     "recog_eval.hip": [],
     "attention.hip": [],
     "metrics.hip": ["-ffp-contract=off"],

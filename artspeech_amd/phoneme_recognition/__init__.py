@@ -13,7 +13,9 @@ import torch
 
 from ..settings import BLANK, SIL, TRAIN, UNKNOWN  # noqa: F401
 from .align import align_counts, confusion_counts, decode_top1, edit_distance  # noqa: F401
+from .beam_search import BeamResult, ctc_beam_search  # noqa: F401
 from .ctc import CTCLoss, ctc_loss
+from .decoders import GreedyCTCDecoder, TopKDecoder
 from .deepspeech2 import DeepSpeech2, TrainableDeepSpeech2, top1_phonemes  # noqa: F401
 from .forced_align import Alignment, align_test, forced_align  # noqa: F401
 from .metrics import normalize_counts
@@ -162,14 +164,18 @@ def _pad(rows, value):
 def substitution_counts(emissions, targets, input_lengths, target_lengths, decoder, class_map, n_classes, out=None):
     """Decode on the device and add the batch's alignment counts to ``out`` ((n_classes + 1)-square int32 on the device; see
     align.align_counts).  emissions: (B, T, C) on the device, or a list of per-utterance (T_b, C) tensors, each decoded over its
-    own rows (and no further than its input length when the decoder uses lengths); targets: (B, S) or a list of 1-D tensors."""
+    own rows (and no further than its input length when the decoder uses lengths) -- by decode_top1 for the two top-1 decoders,
+    by its own decode_device for any other (BeamSearchCTCDecoder); targets: (B, S) or a list of 1-D tensors."""
     if not hasattr(decoder, "decode_device"):
         raise TypeError("substitution_counts: the decoder has no decode_device (TopKDecoder and GreedyCTCDecoder have)")
     if isinstance(emissions, (list, tuple)):
         rows = torch.tensor([e.shape[0] for e in emissions], dtype=torch.int64)
         if decoder.uses_lengths:
             rows = torch.minimum(rows, torch.as_tensor([int(n) for n in input_lengths], dtype=torch.int64))
-        tokens, counts = decode_top1(_pad(emissions, 0.0), rows, decoder.blank_index)
+        if isinstance(decoder, (TopKDecoder, GreedyCTCDecoder)):
+            tokens, counts = decode_top1(_pad(emissions, 0.0), rows, decoder.blank_index)
+        else:   # a decoder of its own kind (the beam search) decodes the padded batch itself, over each utterance's rows
+            tokens, counts = decoder.decode_device(_pad(emissions, 0.0), rows)
     else:
         tokens, counts = decoder.decode_device(emissions, input_lengths)
     if isinstance(targets, (list, tuple)):

@@ -26,7 +26,7 @@ def _counts(v, B, dev, what):
     t = torch.as_tensor(v).reshape(-1)
     if t.numel() != B:
         raise ValueError(f"{what} must have one entry per utterance ({B}), got {t.numel()}")
-    return t.to(device=dev, dtype=torch.int32)
+    return t.to(device=dev, dtype=torch.int32).contiguous()   # a strided view (one column of a (B, n) tensor) becomes dense
 
 
 def _ptr(t):

@@ -630,6 +630,30 @@ int as_ctc_align(const float* x, int64_t sx_t, int64_t sx_b, int32_t T, int32_t 
                  void* ws, int64_t ws_bytes, float* score, int32_t* frame_index, int32_t* frame_token, int32_t* frame_filled,
                  int32_t* spans, float* span_score, void* stream);
 
+/* CTC beam search over prefixes (artspeech_amd/csrc/ctc_beam.hip): the nbest most probable labellings of every utterance with
+ * their scores.  It replaces, as a call site, torchaudio.models.decoder.ctc_decoder(lexicon=None, ...) of
+ * test_phoneme_recognition.py:84-91 (flashlight's lexicon-free decoder with a zero language model), with two stated differences:
+ * the search starts from "no previous label" (no silence at either end of a result), and identical labellings are merged at the
+ * end.  tests/ctc_beam_fp64.py is the contract.  x rows as as_ctc_loss takes them (x[t * sx_t + b * sx_b + c]); input_mode 0:
+ * additive scores as given, 1: probabilities (log taken inside, log(0) = -inf), 2: logits (row log-softmax taken inside); NaN
+ * counts as -inf.  lengths: int64 on the device, or NULL for T frames each.  Per frame: the beam_size_token classes with the
+ * highest x (equal values in ascending class index); every live hypothesis (prefix, ends-in-blank, score) and shortlisted class
+ * n contributes score + x[n] (+ sil_score if n == sil; sil = -1: none) to (prefix, blank) / (prefix, label) / (prefix + n,
+ * label); contributions below best - beam_threshold are dropped, those with one target merge by max (log_add 0) or logaddexp
+ * (1), the beam_size best stay.  Live scores are kept relative to the frame's best, the offset in double.
+ *   tokens [B][nbest][T] int32, -1 past a labelling's count;  counts [B][nbest];  scores [B][nbest] float32, -inf where there
+ *   is no hypothesis;  num_hyps [B]: min(nbest, live prefixes), 0 when every contribution of some frame was -inf; a length of 0
+ *   gives the empty labelling with score 0.
+ * Supported: beam_size 1..64, C 2..128, beam_size_token 1..C, T <= 8192, any nbest >= 1; otherwise AS_ERR_UNSUPPORTED before
+ * any launch.  ws holds each utterance's prefix trie: as_ctc_beam_workspace_bytes = B * 4 * (N + H) with N = beam_size * T + 1
+ * nodes and H = the power of two >= max(64, 2 * N) table entries (0 outside the supported range; host only).  One launch, no
+ * float atomics: repeats are bit-identical. */
+int64_t as_ctc_beam_workspace_bytes(int32_t T, int32_t B, int32_t C, int32_t beam_size);
+int as_ctc_beam_search(const float* x, int64_t sx_t, int64_t sx_b, int32_t T, int32_t B, int32_t C, int32_t input_mode,
+                       const int64_t* lengths, int32_t blank, int32_t sil, float sil_score, int32_t beam_size, int32_t beam_size_token,
+                       float beam_threshold, int32_t log_add, int32_t nbest, int32_t* tokens, int32_t* counts, float* scores,
+                       int32_t* num_hyps, void* ws, int64_t ws_bytes, void* stream);
+
 /* ---- evaluating the scorer (test_phoneme_recognition.py): decoding, edit distance, alignment, confusion counts -----------------
  * Integer kernels (artspeech_amd/csrc/recog_eval.hip).  Token batches are int32 rows padded to a pitch (pred [B][P_max],
  * target [B][L_max]) with int32 counts per row (clamped to [0, pitch]; entries past a count are never read).  class_map (int32
