@@ -46,6 +46,8 @@ SOURCES = {
     "report.hip": ["-ffp-contract=off"],
     "contours.hip": ["-ffp-contract=off"],
     "melspec.hip": [],
+    "resample_plan.cpp": [],
+    "resample.hip": [],
     "artspeech.hip": [],
 }
 

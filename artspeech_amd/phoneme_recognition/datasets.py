@@ -1,6 +1,13 @@
 """Data of the phoneme recogniser (reference ``phoneme_recognition/datasets.py``, ``synthetic_shapes.py``): the collate function
 (:253-302), a seeded synthetic data set with the reference's item layout (synthetic_shapes.py:146-158), and the real-data class,
-which needs the reference's MRI data stack and raises without it."""
+which needs the reference's MRI data stack and raises without it.  For the speech signal: seeded synthetic waveforms, WAV
+recordings listed in a manifest (``read_wav``, ``RecordedAcousticRecognitionDataset``), and ``acoustic_collate_fn``, which brings
+a batch to the model's rate (:124-126) and computes its log-mel features on the device."""
+import json
+import os
+import wave
+
+import numpy as np
 import torch
 from torch.nn.utils.rnn import pad_sequence
 from torch.utils.data import Dataset
@@ -75,11 +82,20 @@ class SyntheticAcousticRecognitionDataset(Dataset):
     (the token of every frame at ``framerate``) with ``voicing``, and ``ctc_target = unique_consecutive`` of the token
     sequence.  No spectrogram: the features of a batch are computed on the device by ``acoustic_collate_fn``; with the
     attribute ``melspectrogram`` set, items carry that transform (key ``melspectrogram``) and ``collate_fn(batch, [Feature.MELSPEC])``
-    does the same."""
+    does the same.  With ``orig_sample_rate`` the waveforms are generated at that rate instead (``sample_rate`` of the data set
+    and the key ``sample_rate`` of its items then name it; durations and labels stay in seconds, and the prototypes stay below
+    0.45 of the lower of the two rates), and ``acoustic_collate_fn`` resamples them to the transform's rate on the device."""
 
     def __init__(self, num_sentences, vocabulary, sample_rate=16000, min_seconds=0.5, max_seconds=2.0, framerate=50, noise=0.01,
-                 seed=0, voiced_tokens=None, num_special=2, prototype_seed=0):
+                 seed=0, voiced_tokens=None, num_special=2, prototype_seed=0, orig_sample_rate=None):
         self.vocabulary = vocabulary
+        if orig_sample_rate is not None:   # recordings at a foreign rate: generated there, resampled on the device while collating
+            if int(orig_sample_rate) != orig_sample_rate or orig_sample_rate < 1:
+                raise ValueError(f"SyntheticAcousticRecognitionDataset: orig_sample_rate {orig_sample_rate} must be a positive integer")
+            self.orig_sample_rate = int(orig_sample_rate)
+            lower_rate, sample_rate = min(sample_rate, self.orig_sample_rate), self.orig_sample_rate
+        else:
+            self.orig_sample_rate, lower_rate = None, sample_rate
         self.num_sentences, self.sample_rate, self.framerate, self.noise = num_sentences, sample_rate, framerate, noise
         self.min_samples, self.max_samples = int(round(min_seconds * sample_rate)), int(round(max_seconds * sample_rate))
         self.voiced = set(voiced_tokens or [])
@@ -88,7 +104,8 @@ class SyntheticAcousticRecognitionDataset(Dataset):
         V = max(vocabulary.values()) + 1
         gp = torch.Generator().manual_seed(prototype_seed)   # shared by every split
         self.melspectrogram = None   # features.MelSpectrogram that collate_fn launches on this data set's batches (set by the owner)
-        self.frequencies = 200.0 + (0.45 * sample_rate - 200.0) * torch.rand(V, 3, generator=gp, dtype=torch.float64)
+        # below 0.45 of the lower of the two rates: the prototypes survive the resampler's low-pass
+        self.frequencies = 200.0 + (0.45 * lower_rate - 200.0) * torch.rand(V, 3, generator=gp, dtype=torch.float64)
         self.amplitudes = (0.1 + 0.3 * torch.rand(V, 3, generator=gp, dtype=torch.float64))
         g = torch.Generator().manual_seed(seed)
         self._seeds = torch.randint(0, 2 ** 31 - 1, (num_sentences,), generator=g).tolist()
@@ -120,6 +137,8 @@ class SyntheticAcousticRecognitionDataset(Dataset):
         voicing = torch.tensor([self.names[int(t)] in self.voiced for t in sentence], dtype=torch.float)
         ctc_target = torch.unique_consecutive(torch.tensor(tokens, dtype=torch.long))
         item = {} if self.melspectrogram is None else {"melspectrogram": self.melspectrogram}
+        if self.orig_sample_rate is not None:
+            item["sample_rate"] = sr
         return {
             **item,
             "waveform": waveform,
@@ -133,6 +152,109 @@ class SyntheticAcousticRecognitionDataset(Dataset):
             "ctc_target": ctc_target,
             "ctc_target_length": len(ctc_target),
         }
+
+
+def read_wav(path):
+    """(samples (n,) int16, sample_rate) of a 16-bit PCM WAV file, read with the standard library's ``wave``: the first channel of
+    a multi-channel file (the reference treats the signal as mono).  Any other sample width raises.  The samples stay int16 --
+    what the file holds and half the upload; the resampler and ``acoustic_collate_fn`` read them as value / 32768, which is
+    the float32 torchaudio.load returns."""
+    with wave.open(str(path), "rb") as f:
+        channels, sample_width, rate, frames = f.getnchannels(), f.getsampwidth(), f.getframerate(), f.getnframes()
+        if sample_width != 2:
+            raise ValueError(f"read_wav: {path} holds {8 * sample_width}-bit samples; only 16-bit PCM is read")
+        data = f.readframes(frames)
+    samples = np.frombuffer(data, dtype="<i2").reshape(-1, channels)[:, 0]
+    return torch.from_numpy(samples.astype(np.int16)), rate
+
+
+class RecordedAcousticRecognitionDataset(Dataset):
+    """Recordings with phoneme intervals, for ``feature: melspec``: ``manifest`` is a JSON file (or the list itself) of
+    ``{"audio_filepath": a 16-bit PCM WAV, relative paths taken from the manifest's folder, "phonemes": [[token, start, end], ...]}``
+    with the times in seconds.  Items carry the keys of SyntheticAcousticRecognitionDataset plus ``sample_rate`` (the file's):
+    ``waveform`` is int16 (read_wav), ``phoneme_tokens`` are ``vocabulary.get(token, unknown)``, ``articulatory_target`` is the
+    token of every frame centre at ``framerate`` (the unknown token where no interval covers it), ``ctc_target`` the
+    ``unique_consecutive`` token sequence.  The files are read per item; ``acoustic_collate_fn`` resamples a batch to the
+    transform's rate on the device."""
+
+    def __init__(self, manifest, vocabulary, framerate=50, voiced_tokens=None, unknown_token="<unk>"):
+        self.vocabulary, self.framerate, self.unknown = vocabulary, framerate, vocabulary[unknown_token]
+        self.voiced = set(voiced_tokens or [])
+        self.names = {i: tok for tok, i in vocabulary.items()}
+        self.melspectrogram = None   # as in SyntheticAcousticRecognitionDataset
+        folder = ""
+        if isinstance(manifest, (str, os.PathLike)):
+            folder = os.path.dirname(os.path.abspath(manifest))
+            with open(manifest) as f:
+                manifest = json.load(f)
+        self.entries = []
+        for entry in manifest:
+            if "audio_filepath" not in entry or "phonemes" not in entry:
+                raise ValueError(f"RecordedAcousticRecognitionDataset: a manifest entry needs audio_filepath and phonemes, got {sorted(entry)}")
+            spans = [(str(tok), float(start), float(end)) for tok, start, end in entry["phonemes"]]
+            self.entries.append((os.path.join(folder, entry["audio_filepath"]), spans))
+
+    def __len__(self):
+        return len(self.entries)
+
+    def __getitem__(self, index):
+        path, spans = self.entries[index]
+        waveform, sr = read_wav(path)
+        n = len(waveform)
+        if n == 0:
+            raise ValueError(f"RecordedAcousticRecognitionDataset: {path} holds no samples")
+        duration = n / sr
+        tokens = [self.vocabulary.get(tok, self.unknown) for tok, _, _ in spans]
+        T = max(1, int(duration * self.framerate))
+        sentence = torch.full((T,), self.unknown, dtype=torch.long)
+        centres = (torch.arange(T, dtype=torch.float64) + 0.5) / self.framerate
+        for (_, start, end), tok in zip(spans, tokens):
+            sentence[(centres >= start) & (centres < end)] = tok
+        voicing = torch.tensor([self.names[int(t)] in self.voiced for t in sentence], dtype=torch.float)
+        ctc_target = torch.unique_consecutive(torch.tensor(tokens, dtype=torch.long))
+        item = {} if self.melspectrogram is None else {"melspectrogram": self.melspectrogram}
+        return {
+            **item,
+            "waveform": waveform,
+            "waveform_length": n,
+            "sample_rate": sr,
+            "audio_duration": duration,
+            "phonemes_with_time": spans,
+            "phoneme_tokens": tokens,
+            "articulatory_target": sentence,
+            "articulatory_target_length": T,
+            "voicing": voicing,
+            "ctc_target": ctc_target,
+            "ctc_target_length": len(ctc_target),
+        }
+
+
+def resample_to_model_rate(batch, sample_rate, device):
+    """(batch in launch order, waveforms (B, m_max) float32 on the device, lengths (B,) int64 on the host) of items whose
+    ``sample_rate`` is not all the model's: the items are ordered by their rate (a stable sort, so a batch of one rate keeps
+    its order), the rows of each rate are padded and uploaded together -- int16 as int16 -- and one ``Resample.resample_batch``
+    launch per distinct foreign rate writes them into its rows of the one padded buffer; rows already at the model's rate
+    are copied there.  Everything runs on the current stream, ahead of the log-mel launch on the same buffer."""
+    from .features import resampled_length, resampler
+    batch = sorted(batch, key=lambda item: item.get("sample_rate", sample_rate))
+    rates = [int(item.get("sample_rate", sample_rate)) for item in batch]
+    lengths = torch.tensor([item["waveform_length"] if r == sample_rate else resampled_length(item["waveform_length"], r, sample_rate)
+                            for item, r in zip(batch, rates)], dtype=torch.long)
+    waves = torch.empty(len(batch), int(lengths.max()), dtype=torch.float32, device=device)
+    at = 0
+    while at < len(batch):
+        end = at + rates[at:].count(rates[at])
+        rows = [item["waveform"] for item in batch[at:end]]
+        if len({row.dtype for row in rows}) > 1 or rows[0].dtype != torch.int16:
+            rows = [row.float() / 32768.0 if row.dtype == torch.int16 else row.float() for row in rows]
+        group = pad_sequence(rows, batch_first=True, padding_value=0).to(device)
+        if rates[at] == sample_rate:
+            waves[at:end, :group.shape[1]] = group.float() / 32768.0 if group.dtype == torch.int16 else group
+            waves[at:end, group.shape[1]:] = 0.0
+        else:
+            resampler(rates[at], sample_rate).resample_batch(group, [item["waveform_length"] for item in batch[at:end]], out=waves[at:end])
+        at = end
+    return batch, waves, lengths
 
 
 def acoustic_target(phonemes_with_time, tokens, melspec_length, audio_duration):
@@ -151,7 +273,10 @@ def acoustic_collate_fn(batch, melspectrogram, device=None, vocabulary=None, unk
     once, ``melspectrogram.log_mel_batch`` (features.MelSpectrogram) computes the (B, 2, n_mels, T) log-mel batch with its -1
     padding on the device, and the acoustic targets follow from the frame counts.  Same keys, dtypes and padding as collate_fn;
     ``melspec`` is on the device.  With ``vocabulary`` the token of an interval is ``vocabulary.get(phoneme, unknown)`` as in the
-    reference (:215), for any item with ``phonemes_with_time``; without it the item's own ``phoneme_tokens`` are taken.  It
+    reference (:215), for any item with ``phonemes_with_time``; without it the item's own ``phoneme_tokens`` are taken.  Items
+    whose ``sample_rate`` is not the transform's are resampled on the device first (``resample_to_model_rate``: the batch is
+    ordered by rate, one launch per distinct rate, then the one log-mel launch on the same stream); without such an item the
+    calls are the ones made before, and int16 waveforms (``read_wav``) are read as value / 32768.  It
     launches a kernel, so it runs in the main process: the DataLoader gets num_workers=0 (a worker process raises)."""
     if torch.utils.data.get_worker_info() is not None:
         raise ValueError("acoustic_collate_fn computes its features on the device while collating: num_workers must be 0")
@@ -160,9 +285,14 @@ def acoustic_collate_fn(batch, melspectrogram, device=None, vocabulary=None, unk
         if not torch.cuda.is_available():
             raise RuntimeError("artspeech_amd: acoustic_collate_fn computes the mel spectrogram on an MI355X device; there is no CPU path")
         device = torch.device("cuda", torch.cuda.current_device())
-    waves = pad_sequence([item["waveform"] for item in batch], batch_first=True, padding_value=0.0)
-    lengths = torch.tensor([item["waveform_length"] for item in batch], dtype=torch.long)
-    feats, feat_lengths = melspectrogram.log_mel_batch(waves.to(device), lengths, channels=2)
+    if any(item.get("sample_rate", melspectrogram.sample_rate) != melspectrogram.sample_rate for item in batch):
+        # recordings at a foreign rate (reference :124-126): resampled on the device, then the same one log-mel launch
+        batch, waves, lengths = resample_to_model_rate(batch, melspectrogram.sample_rate, device)
+    else:
+        waves = pad_sequence([item["waveform"] for item in batch], batch_first=True, padding_value=0.0)
+        lengths = torch.tensor([item["waveform_length"] for item in batch], dtype=torch.long)
+        waves = waves.to(device).float() / 32768.0 if waves.dtype == torch.int16 else waves.to(device)   # int16: read_wav's samples
+    feats, feat_lengths = melspectrogram.log_mel_batch(waves, lengths, channels=2)
     out = {Feature.MELSPEC.value: feats, f"{Feature.MELSPEC.value}_length": feat_lengths}
     def tokens(item):
         if vocabulary is None:

@@ -940,6 +940,42 @@ int as_melspec_fwd(const float* wave, int64_t wave_pitch, const int64_t* n_sampl
                    const float* window, const float* fbanks, int32_t n_mels, float clip, int32_t channels, float pad_value,
                    float* out, int64_t T_max, int64_t* lengths_out, void* stream);
 
+/* Sample-rate conversion ahead of the log-mel (reference phoneme_recognition/datasets.py:124-126: torchaudio.load, then
+ * F.resample(audio, orig_freq, new_freq) when the file's rate is not the model's): the polyphase windowed-sinc resampler of
+ * torchaudio's documentation, one launch from a padded batch of rows at the rate `orig` to a padded batch at `new`.
+ * With g = gcd(orig, new), o = orig / g input samples step per n = new / g outputs ("phases"), and the dense filter
+ * h [n][2 width + o] of the documentation,
+ *     y[j n + i] = sum_k h[i][k] xz[j o + k - width],      xz = x inside [0, L) and ZERO outside it (no reflection),
+ * cut to M = ceil(n L / o) = (n L + o - 1) / o samples in integers.  The clamp of the filter's argument leaves each phase a
+ * band of non-zero taps; the caller hands the band alone:
+ *   x [B] rows of x_pitch samples: float32, or (x_int16 != 0) int16 read as value / 32768; n_samples [B] int64 on the
+ *                       device: row b has L_b = n_samples[b] samples (clamped to [0, x_pitch]); nothing behind them is read
+ *   first [n] int32     tap index k of the first band tap of phase i
+ *   coef [band][n]      coef[q][i] = h[i][first[i] + q]: tap-major, so that lanes on adjacent phases read adjacent words
+ *   width               the filter's half width in input samples (the k - width above)
+ *   lead_min, lead_max  bounds of lead[i] = first[i] - width - floor(i o / n) over the phases: output m = j n + i reads the
+ *                       input samples [floor(m o / n) + lead[i], ... + band).  They size the tile's staged span; a first[] that
+ *                       breaks them is clamped into the span (wrong values there, never an access outside it)
+ *   out [B] rows of out_pitch floats: y at m < M_b, pad_value at M_b <= m < m_max (M_b is clamped to m_max); every element
+ *                       of [0, m_max) is written.  lengths_out [B] int64 (optional) = M_b
+ * Each output is summed in an order that depends on its phase and the band alone (four interleaved partial sums over q, then
+ * (s0 + s1) + (s2 + s3)), never on the batch or the tile; no atomics: repeats, and a row alone or inside a batch, are
+ * bit-identical.  as_resample_tile is the host's tile choice: the largest power of two of outputs per workgroup, at most
+ * AS_RESAMPLE_MAX_TILE, whose input span as_resample_span(tile, o, n, band, spread = lead_max - lead_min)
+ * = floor((tile - 1) o / n) + 2 + spread + band fits AS_RESAMPLE_SPAN_FLOATS floats of LDS; 0 when none does or a limit is broken.
+ * Limits: n <= AS_RESAMPLE_MAX_PHASES, band <= AS_RESAMPLE_MAX_BAND, o, x_pitch, out_pitch and m_max <= AS_RESAMPLE_MAX_ROW, B <= 65535;
+ * AS_ERR_UNSUPPORTED before any launch beyond them. */
+#define AS_RESAMPLE_MAX_PHASES 1024
+#define AS_RESAMPLE_MAX_BAND 512
+#define AS_RESAMPLE_MAX_ROW 0x3fff0000
+#define AS_RESAMPLE_MAX_TILE 1024
+#define AS_RESAMPLE_SPAN_FLOATS 12288
+int64_t as_resample_span(int64_t tile, int32_t o, int32_t n, int32_t band, int32_t spread);
+int32_t as_resample_tile(int32_t o, int32_t n, int32_t band, int32_t spread);
+int as_resample_fwd(const void* x, int32_t x_int16, int64_t x_pitch, const int64_t* n_samples, int32_t B, int32_t o, int32_t n,
+                    const float* coef, const int32_t* first, int32_t band, int32_t width, int32_t lead_min, int32_t lead_max,
+                    float pad_value, float* out, int64_t out_pitch, int64_t m_max, int64_t* lengths_out, void* stream);
+
 /* Optional per-kernel-phase timing with HIP events recorded on the launch stream (for bench.py's
  * roofline object).  as_profile_report writes "name count total_ms\n" lines (NUL terminated, truncated
  * to buflen) and returns the untruncated length; it waits for the recorded events to complete. */

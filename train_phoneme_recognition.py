@@ -10,7 +10,9 @@
 # (waveforms) and a batch's log-mel features are computed on the device while collating
 # (datasets.acoustic_collate_fn); `melspec:` holds the MelSpectrogram keywords (default
 # the reference's: 16 kHz, n_fft 1024, win_length 1024, hop_length 256, 80 mels; `synthetic: {melspec: ...}`
-# is read too, which is how test_phoneme_recognition.py's config passes them).  TrainableDeepSpeech2 + the engine's CTCLoss(**loss_params), Adam(lr, weight_decay) and
+# is read too, which is how test_phoneme_recognition.py's config passes them).  Waveforms at another rate -- `synthetic:
+# {orig_sample_rate: 44100}`, or WAV recordings listed in a JSON manifest with `datadir: recordings` and `manifest:` in each
+# sequence dict -- are resampled to the transform's rate on the device first (features.Resample).  TrainableDeepSpeech2 + the engine's CTCLoss(**loss_params), Adam(lr, weight_decay) and
 # CyclicLR(lr / 25, lr, cycle_momentum=False) stepped per batch; early stopping on the validation edit
 # distance (greedy CTC decoding); best_model.pt, last_model.pt and checkpoint.pt like the reference, then
 # a test-split pass of the best model written to info_test.json, with substitution_matrix.npy and (given `plot_target`)
@@ -30,8 +32,9 @@ from torch.utils.data import DataLoader
 from artspeech_amd.helpers import sequences_from_dict, set_seeds
 from artspeech_amd.phoneme_recognition import (BLANK, SIL, UNKNOWN, Criterion, Feature, Target, TrainableDeepSpeech2, run_epoch,
                                                run_test)
-from artspeech_amd.phoneme_recognition.datasets import (PhonemeRecognitionDataset, SyntheticAcousticRecognitionDataset,
-                                                        SyntheticPhonemeRecognitionDataset, acoustic_collate_fn, collate_fn)
+from artspeech_amd.phoneme_recognition.datasets import (PhonemeRecognitionDataset, RecordedAcousticRecognitionDataset,
+                                                        SyntheticAcousticRecognitionDataset, SyntheticPhonemeRecognitionDataset,
+                                                        acoustic_collate_fn, collate_fn)
 from artspeech_amd.phoneme_recognition.features import MelSpectrogram
 from artspeech_amd.phoneme_recognition.decoders import GreedyCTCDecoder
 from artspeech_amd.phoneme_recognition.metrics import EditDistance
@@ -52,7 +55,10 @@ VOICING_WITH_MELSPEC = "feature: melspec takes no voicing_filepath: voicing is p
 def _make_dataset(datadir, database_name, seq_dict, vocabulary, feature, voiced_tokens, synthetic, seed, melspec=None):
     """The split's data set.  With datadir: synthetic and feature: melspec it is the waveform data set, carrying the MelSpectrogram
     that collate_fn launches on its batches: MELSPEC_DEFAULTS, overridden by `synthetic: {melspec: {...}}` (the way
-    test_phoneme_recognition.py passes it, whose main() has no melspec keyword), then by `melspec`."""
+    test_phoneme_recognition.py passes it, whose main() has no melspec keyword), then by `melspec`.  `synthetic: {orig_sample_rate:
+    44100}` generates the waveforms at that rate, and `datadir: recordings` reads the WAV files of the sequence dict's `manifest:`
+    (RecordedAcousticRecognitionDataset; `synthetic:` then holds its keywords and `melspec`): either way the collate function
+    resamples a batch to the transform's rate on the device before the log-mel launch."""
     if datadir == "synthetic":
         n, cfg = synthetic_size(seq_dict, synthetic, "num_sentences", 32)
         mel_kw = {**MELSPEC_DEFAULTS, **(cfg.pop("melspec", None) or {}), **(melspec or {})}
@@ -63,6 +69,16 @@ def _make_dataset(datadir, database_name, seq_dict, vocabulary, feature, voiced_
             ds.melspectrogram = MelSpectrogram(**mel_kw)
             return ds
         return SyntheticPhonemeRecognitionDataset(n, vocabulary, seed=seed, voiced_tokens=voiced_tokens, **cfg)
+    if datadir == "recordings":
+        manifest, cfg = synthetic_size(seq_dict, synthetic, "manifest", None)
+        if feature != Feature.MELSPEC or manifest is None:
+            raise ValueError("datadir: recordings reads `manifest:` from the sequence dict and takes feature: melspec alone")
+        if voiced_tokens is not None:
+            raise ValueError(VOICING_WITH_MELSPEC)
+        mel_kw = {**MELSPEC_DEFAULTS, **(cfg.pop("melspec", None) or {}), **(melspec or {})}
+        ds = RecordedAcousticRecognitionDataset(manifest, vocabulary, **cfg)
+        ds.melspectrogram = MelSpectrogram(**mel_kw)
+        return ds
     return PhonemeRecognitionDataset(datadir=datadir, database_name=database_name, sequences=sequences_from_dict(datadir, seq_dict),
                                      vocabulary=vocabulary, features=[feature], voiced_tokens=voiced_tokens)
 
@@ -70,7 +86,7 @@ def _make_dataset(datadir, database_name, seq_dict, vocabulary, feature, voiced_
 def make_collate_fn(datadir, feature, num_workers, dataset=None):
     """collate_fn over the feature; on the synthetic waveforms of feature: melspec, acoustic_collate_fn around the data set's
     MelSpectrogram and vocabulary (its launch has to happen in the main process)."""
-    if feature != Feature.MELSPEC or datadir != "synthetic":
+    if feature != Feature.MELSPEC or datadir not in ("synthetic", "recordings"):
         return partial(collate_fn, features_names=[feature])
     if num_workers != 0:
         raise ValueError("feature: melspec computes its features on the device while collating: num_workers must be 0")
