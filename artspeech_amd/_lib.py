@@ -168,6 +168,10 @@ PROTOTYPES = {
     "as_align_workspace_bytes": (_I64, [_I32, _I32, _I32]),
     "as_align_counts": (_I32, [_P, _I32, _P, _P, _I32, _P, _I32, _P, _I32, _I32, _P, _P, _P, _I64, _S]),
     "as_confusion_counts": (_I32, [_P, _I32, _P, _I32, _P, _I32, _P, _I32, _I32, _P, _S]),
+    "as_frame_ce_workspace_bytes": (_I64, [_I32, _I32]),
+    "as_frame_ce_loss": (_I32, [_P, _I64, _I64, _I32, _I32, _I32, _P, _I64, _P, _P, _I64, _F, _P, _P, _P, _I64, _S]),
+    "as_frame_ce_grad": (_I32, [_P, _I64, _I64, _I32, _I32, _I32, _P, _I64, _P, _P, _I64, _F, _P, _P, _P, _I32, _P, _I64, _I64, _S]),
+    "as_frame_auroc": (_I32, [_P, _I64, _I64, _I32, _I32, _I32, _P, _I64, _P, _I64, _I32, _P, _P, _P, _S]),
     "as_intersect_semipolar_grid":(_I32, [_P, _P, _I64, _I32, _I32, _I32, _P, _P, _P, _S]),
     "as_artspeech_wait_head_grads": (_I32, [_P, _P]),
     "as_gather_pad_rows": (_I32, [_P, _P, _P, _I32, _I32, _I64, _I32, _D, _P, _S]),

@@ -36,6 +36,7 @@ SOURCES = {
     "ctc_align.hip": [],
     "ctc_beam.hip": [],
     "recog_eval.hip": [],
+    "frame_ce.hip": [],
     "attention.hip": [],
     "metrics.hip": ["-ffp-contract=off"],
     "p2cp_loss.hip": ["-ffp-contract=off"],

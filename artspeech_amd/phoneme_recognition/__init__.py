@@ -4,7 +4,10 @@ decoding that config 5 of BASELINE.json puts behind the phoneme-to-articulation 
 train_phoneme_recognition.py (``run_epoch`` / ``run_test``, reference :63-153 and :156-329), and the evaluation products of
 test_phoneme_recognition.py: the substitution matrix (``compute_substitution_matrix``, :470-526) and the frame-level confusion
 matrix (``compute_confusion_matrix``, :410-432), counted on the device (align.py) and normalised on the host in float64 as the
-reference does.  CTC only: the reference's CE criterion, the plots and the t-SNE feature plot are not ported."""
+reference does.  The frame-level criterion and metrics of the reference's ``loss: CE`` branch (``CrossEntropyLoss`` /
+``frame_cross_entropy``, and ``Accuracy``, ``F1Score``, ``AUROC`` in metrics.py) run on the device too and are trained by
+`python -m train_frame_recognition`; ``Criterion.CE`` and the four CTC entry scripts still refuse ``loss: CE``.  The plots and the t-SNE
+feature plot are not ported."""
 import os
 from enum import Enum
 
@@ -18,7 +21,8 @@ from .ctc import CTCLoss, ctc_loss
 from .decoders import GreedyCTCDecoder, TopKDecoder
 from .deepspeech2 import DeepSpeech2, TrainableDeepSpeech2, top1_phonemes  # noqa: F401
 from .forced_align import Alignment, align_test, forced_align  # noqa: F401
-from .metrics import normalize_counts
+from .frame_ce import frame_cross_entropy  # noqa: F401
+from .metrics import CrossEntropyLoss, normalize_counts  # noqa: F401
 
 CLASSES_NAMES = {
     0: "dental",

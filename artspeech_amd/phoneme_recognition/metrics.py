@@ -15,7 +15,18 @@ path: decode per utterance, Levenshtein in Python.
   host.  The reference finds its path with a best-first walk over the edit table (``shortest_path``, :218-270); that walk ends on
   the back-trace that steps, from the corner, to the predecessor with the smallest table entry -- ties to the diagonal, then to the
   previous prediction row, then to the previous target column -- which is what is built here and in as_align_counts
-  (tests/golden/recognizer_eval.npz holds the reference's own results)."""
+  (tests/golden/recognizer_eval.npz holds the reference's own results).
+
+* ``CrossEntropyLoss``, ``Accuracy``, ``F1Score``, ``AUROC``: the frame-level criterion and metrics of the reference's ``loss: CE``
+  branch (:87-120, :155-197), one target per frame.  The criterion runs on as_frame_ce_loss / as_frame_ce_grad (frame_ce.py);
+  Accuracy and F1 are ratios of the confusion counts of the device's per-frame arg-max (as_decode_top1, as_confusion_counts),
+  the AUROC of the rank statistic as_frame_auroc counts.  The emissions stay on the device: a handful of integers is
+  downloaded and divided on the host in float64, as ``normalize_counts`` does.  Two departures from torch / torchmetrics:
+  ``reduction="none"`` is not built, and a class without a positive or a negative frame is NaN in the AUROC's per-class vector
+  and left out of its averages."""
+import json
+import os
+
 import numpy as np
 import torch
 
@@ -109,6 +120,167 @@ class WordInfoLost:
             return _wil(*_device_sums(self.decoder, emissions, targets, emissions_lengths, targets_lengths))
         preds, tgts = make_pred_and_target_sentences(self.decoder, emissions, targets, emissions_lengths, targets_lengths)
         return word_information_lost(preds, tgts)
+
+
+# ------------------------------------------------------------------------------------------ frame-level classification
+def _ce_arguments(weight=None, size_average=None, ignore_index=-100, reduce=None, reduction="mean", label_smoothing=0.0):
+    """nn.CrossEntropyLoss's own arguments, positional or by name."""
+    if size_average is not None or reduce is not None:
+        raise NotImplementedError("CrossEntropyLoss: the deprecated size_average / reduce arguments are not taken; use reduction")
+    return weight, int(ignore_index), reduction, float(label_smoothing)
+
+
+class CrossEntropyLoss(torch.nn.Module):
+    """The reference's CE criterion (metrics.py:87-120): ``nn.CrossEntropyLoss(*args, weight=..., **kwargs)`` over the valid frames
+    of a padded batch, on the kernels of frame_ce.py (loss, division and gradient on the device, no boolean gathers).
+
+    ``class_weights`` is a {token name: weight} dict or the path of a JSON file that holds one.  The weight vector is
+    ``[1.0] + [w for _, w in sorted(class_weights.items())]``: 1.0 for the unknown class at index 0, then the weights SORTED BY
+    TOKEN NAME, not by vocabulary index -- exactly the reference's order, so it fits a vocabulary whose tokens are listed in
+    name order.  The remaining arguments are nn.CrossEntropyLoss's (``ignore_index``, ``reduction``, ``label_smoothing``; ``weight``
+    only without class_weights, as in the reference, where giving both is a TypeError).  ``reduction="none"`` is not built."""
+
+    def __init__(self, *args, class_weights=None, **kwargs):
+        super().__init__()
+        if class_weights is not None:
+            if "weight" in kwargs:
+                raise TypeError("CrossEntropyLoss: got multiple values for keyword argument 'weight' (class_weights sets it)")
+            if isinstance(class_weights, (str, os.PathLike)):
+                with open(class_weights) as f:
+                    class_weights = json.load(f)
+            kwargs["weight"] = torch.tensor([1.0] + [w for _, w in sorted(class_weights.items(), key=lambda t: t[0])])
+        weight, self.ignore_index, self.reduction, self.label_smoothing = _ce_arguments(*args, **kwargs)
+        if self.reduction == "none":
+            raise NotImplementedError("CrossEntropyLoss: reduction='none' is not built (the reference never asks for it)")
+        if self.reduction not in ("mean", "sum"):
+            raise ValueError(f"CrossEntropyLoss: unknown reduction {self.reduction!r}")
+        self.register_buffer("weight", None if weight is None else torch.as_tensor(weight, dtype=torch.float32))
+
+    def forward(self, emissions, targets, emissions_lengths, targets_lengths):
+        """emissions (T, B, C) (raw logits in the reference's CE branch), targets (B, S), one per frame."""
+        from .frame_ce import frame_cross_entropy
+        if self.weight is not None and self.weight.device != emissions.device:
+            self.weight = self.weight.to(emissions.device)   # once: the module follows its input
+        return frame_cross_entropy(emissions, targets, emissions_lengths, targets_lengths, self.weight, self.ignore_index,
+                                   self.reduction, self.label_smoothing)
+
+
+_AVERAGES = ("macro", "micro", "weighted", "none", None)
+
+
+def accuracy_from_counts(cm, average="macro"):
+    """torchmetrics' MulticlassAccuracy from confusion counts cm[target, prediction], in float64: per-class accuracy is recall
+    tp / (tp + fn) (0 without support); macro is its mean over the classes with tp + fp + fn > 0, weighted its support-weighted
+    mean, micro sum(tp) / sum(cm); none / None the per-class vector (0 for a class that never occurs)."""
+    return _average(*_class_counts(cm), average, lambda tp, fp, fn: (tp, tp + fn))
+
+
+def f1_from_counts(cm, average="macro"):
+    """torchmetrics' MulticlassF1Score from confusion counts, in float64: per class 2 tp / (2 tp + fp + fn) (0 when that is 0 / 0);
+    the averages as in accuracy_from_counts."""
+    return _average(*_class_counts(cm), average, lambda tp, fp, fn: (2 * tp, 2 * tp + fp + fn))
+
+
+def _class_counts(cm):
+    cm = np.asarray(cm, dtype=np.int64)
+    tp = np.diag(cm)
+    return tp, cm.sum(axis=0) - tp, cm.sum(axis=1) - tp
+
+
+def _average(tp, fp, fn, average, ratio):
+    if average not in _AVERAGES:
+        raise ValueError(f"average must be one of 'macro', 'micro', 'weighted', 'none' or None, got {average!r}")
+    with np.errstate(all="ignore"):
+        if average == "micro":
+            num, den = ratio(tp.sum(), fp.sum(), fn.sum())
+            return float(np.float64(num) / np.float64(den)) if den else 0.0
+        num, den = ratio(tp, fp, fn)
+        per_class = np.where(den > 0, num.astype(np.float64) / np.maximum(den, 1), 0.0)
+        if average in ("none", None):
+            return per_class
+        weights = (tp + fp + fn > 0).astype(np.float64) if average == "macro" else (tp + fn).astype(np.float64)
+        return float((per_class * weights).sum() / weights.sum()) if weights.sum() else 0.0
+
+
+def auroc_from_counts(n_pos, n_neg, u2, average="macro"):
+    """One-vs-rest AUROC from as_frame_auroc's integers, in float64: per class u2 / (2 n_pos n_neg), NaN for a class without a
+    positive or without a negative frame; macro is the mean over the other classes, weighted their n_pos-weighted mean (NaN if
+    there is none); none / None the per-class vector."""
+    if average not in ("macro", "weighted", "none", None):
+        raise ValueError(f"AUROC: average must be one of 'macro', 'weighted', 'none' or None, got {average!r}")
+    n_pos, n_neg, u2 = (np.asarray(v, dtype=np.int64) for v in (n_pos, n_neg, u2))
+    with np.errstate(all="ignore"):
+        per_class = u2.astype(np.float64) / (2.0 * n_pos.astype(np.float64) * n_neg.astype(np.float64))
+    per_class[(n_pos == 0) | (n_neg == 0)] = np.nan
+    if average in ("none", None):
+        return per_class
+    keep = ~np.isnan(per_class)
+    weights = keep.astype(np.float64) if average == "macro" else np.where(keep, n_pos, 0).astype(np.float64)
+    if not weights.sum():
+        return float("nan")
+    return float((np.where(keep, per_class, 0.0) * weights).sum() / weights.sum())
+
+
+def _frame_confusion(emissions, targets, emissions_lengths, targets_lengths, num_classes):
+    """The (num_classes, num_classes) confusion counts [target, arg-max] of the valid frames, counted on the device
+    (as_decode_top1's arg-max: the lowest index among equal scores, a NaN is the maximum; as_confusion_counts), downloaded once."""
+    from .align import confusion_counts, decode_top1
+    from .frame_ce import check_frame_lengths
+    lengths = check_frame_lengths("frame metrics", emissions_lengths, targets_lengths, emissions.shape[0], emissions.shape[1])
+    argmax = decode_top1(emissions, lengths, return_argmax=True)[2]
+    return confusion_counts(argmax, targets, lengths, num_classes).cpu().numpy()
+
+
+class Accuracy:
+    """The reference's Accuracy (metrics.py:170-182, torchmetrics' MulticlassAccuracy) from the device's confusion counts of the
+    per-frame arg-max; emissions (B, T, C) on the device.  See accuracy_from_counts for the averages."""
+
+    def __init__(self, num_classes, average="macro"):
+        if average not in _AVERAGES:
+            raise ValueError(f"Accuracy: unknown average {average!r}")
+        self.num_classes, self.average = int(num_classes), average
+
+    def __call__(self, emissions, targets, emissions_lengths, targets_lengths):
+        return accuracy_from_counts(_frame_confusion(emissions, targets, emissions_lengths, targets_lengths, self.num_classes), self.average)
+
+
+class F1Score:
+    """The reference's F1Score (metrics.py:155-167, torchmetrics' MulticlassF1Score), as Accuracy; see f1_from_counts."""
+
+    def __init__(self, num_classes, average="macro"):
+        if average not in _AVERAGES:
+            raise ValueError(f"F1Score: unknown average {average!r}")
+        self.num_classes, self.average = int(num_classes), average
+
+    def __call__(self, emissions, targets, emissions_lengths, targets_lengths):
+        return f1_from_counts(_frame_confusion(emissions, targets, emissions_lengths, targets_lengths, self.num_classes), self.average)
+
+
+class AUROC:
+    """The reference's AUROC (metrics.py:185-197, torchmetrics' MulticlassAUROC with exact thresholds): one-vs-rest, from the rank
+    statistic as_frame_auroc counts on the device; emissions (B, T, C) on the device.  If a score of a valid frame lies outside
+    [0, 1] the emissions go through ``torch.softmax`` first (torchmetrics' rule).  A class without a positive or without a
+    negative frame is NaN in the per-class vector and left out of the averages -- this project's rule (auroc_from_counts)."""
+
+    def __init__(self, num_classes, average="macro"):
+        if average not in ("macro", "weighted", "none", None):
+            raise ValueError(f"AUROC: unknown average {average!r}")
+        self.num_classes, self.average = int(num_classes), average
+
+    def __call__(self, emissions, targets, emissions_lengths, targets_lengths):
+        from .frame_ce import check_frame_lengths, frame_auroc_counts
+        B, T, Cn = emissions.shape
+        if Cn != self.num_classes:
+            raise ValueError(f"AUROC: emissions of {Cn} classes, num_classes is {self.num_classes}")
+        lengths = check_frame_lengths("AUROC", emissions_lengths, targets_lengths, B, T)
+        emissions = emissions.detach()
+        if emissions.numel():
+            valid = (torch.arange(T)[None, :] < lengths[:, None]).to(emissions.device)
+            lo, hi = torch.aminmax(emissions.masked_fill(~valid[:, :, None], 0.5))
+            if bool((lo < 0) | (hi > 1)):
+                emissions = torch.softmax(emissions, dim=-1)
+        counts = torch.stack(frame_auroc_counts(emissions, targets, lengths)).cpu().numpy()
+        return auroc_from_counts(*counts, self.average)
 
 
 # ------------------------------------------------------------------------------------------ the string-level alignment API

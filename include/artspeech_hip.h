@@ -691,6 +691,42 @@ int as_align_counts(const int32_t* pred, int32_t P_max, const int32_t* pred_coun
 int as_confusion_counts(const int32_t* argmax, int32_t T, const int32_t* targets, int32_t S, const int64_t* lengths, int32_t B,
                         const int32_t* class_map, int32_t n_map, int32_t n, int32_t* counts, void* stream);
 
+/* ---- frame-level phoneme classification (artspeech_amd/csrc/frame_ce.hip) ------------------------------------------------
+ * The criterion and the ranking metric of the reference's `loss: CE` branch: CrossEntropyLoss.forward (phoneme_recognition/
+ * metrics.py:110-120: nn.CrossEntropyLoss over the emission rows that the pad masks keep) and AUROC.__call__ (:189-197:
+ * torchmetrics' MulticlassAUROC over the same rows).  Inputs follow as_ctc_loss: rows x[t*sx_t + b*sx_b + c] with class stride
+ * 1, int64 targets targets[b*tgt_stride + t] (tgt_stride >= T), int64 lengths [B] on the device (clamped to [0, T]); one target
+ * per frame.  A frame (b, t) is valid when t < lengths[b] and its target is not ignore_index.
+ * as_frame_ce_loss : per valid frame  (1 - eps) w[y] (-logp_y) + (eps / C) sum_c w[c] (-logp_c),  logp = x - logsumexp(x), w =
+ *     weight [C] or 1 (NULL), eps = label_smoothing in [0, 1].  lse [B][T] receives every row's logsumexp (kept for the
+ *     backward; frames that are not valid are not written), sums[0] = sum of the frame losses, sums[1] = sum of w[y], both float64:
+ *     each frame in float32, the sums in float64 in an order fixed by (T, B) alone -- no float atomics, repeats are bit-identical.
+ *     A target outside [0, C) that is not ignore_index never indexes x or weight: it makes sums[0] NaN (and as_frame_ce_grad's
+ *     row NaN).  ws: as_frame_ce_workspace_bytes(T, B) bytes (too small: AS_ERR_WORKSPACE); its first 8 bytes are an integer
+ *     ticket that must be zero before the first call and that every call leaves zero again -- one call at a time per workspace.
+ *     1 <= C <= 4096, else AS_ERR_UNSUPPORTED before any launch.  One launch.
+ * as_frame_ce_grad : the gradient with respect to x in the caller's strides, every (t, b, c) written: zero on frames that are
+ *     not valid, elsewhere  scale [(1 - eps) w[y] (p_c - [c = y]) + (eps / C) (p_c sum_k w[k] - w[c])],  p_c = exp(x_c - lse);
+ *     scale = gout[0] (mean == 0) or gout[0] / sums[1] (mean != 0), both read on the device.  One launch, nothing synchronises.
+ * as_frame_auroc : for every class c the one-vs-rest rank statistic over the frames that are valid and whose target lies in
+ *     [0, C): n_pos[c] = #{y_i = c}, n_neg[c] = #{y_i != c},  u2[c] = 2 #{(i, j): y_i = c, y_j != c, s_i[c] > s_j[c]} + #{the same
+ *     pairs with s_i[c] = s_j[c]}, all int64 [C]; AUROC_c = u2 / (2 n_pos n_neg).  Scores are ranked as given (no softmax inside;
+ *     -0 equals +0; finite scores are the contract).  One workgroup per class sorts the class column in LDS: max_frames, the
+ *     caller's upper bound on the number of such frames (B * T always is one), may be at most 16384, else AS_ERR_UNSUPPORTED
+ *     before any launch -- there is no workspace path; if more frames than max_frames turn out valid the three outputs of every
+ *     class are -1 and nothing is written out of bounds.  Integer results: repeats are bit-identical. */
+int64_t as_frame_ce_workspace_bytes(int32_t T, int32_t B);
+int as_frame_ce_loss(const float* x, int64_t sx_t, int64_t sx_b, int32_t T, int32_t B, int32_t C, const int64_t* targets,
+                     int64_t tgt_stride, const int64_t* lengths, const float* weight, int64_t ignore_index, float label_smoothing,
+                     float* lse, double* sums, void* ws, int64_t ws_bytes, void* stream);
+int as_frame_ce_grad(const float* x, int64_t sx_t, int64_t sx_b, int32_t T, int32_t B, int32_t C, const int64_t* targets,
+                     int64_t tgt_stride, const int64_t* lengths, const float* weight, int64_t ignore_index, float label_smoothing,
+                     const float* lse, const double* sums, const float* gout, int32_t mean, float* grad, int64_t sg_t, int64_t sg_b,
+                     void* stream);
+int as_frame_auroc(const float* x, int64_t sx_t, int64_t sx_b, int32_t T, int32_t B, int32_t C, const int64_t* targets,
+                   int64_t tgt_stride, const int64_t* lengths, int64_t ignore_index, int32_t max_frames, int64_t* n_pos,
+                   int64_t* n_neg, int64_t* u2, void* stream);
+
 /* intersect_semipolar_grid (area_function.py:175-223), float64, batched over frames: air_column [frames][2 walls][2][n_pts]
  * (internal wall first, x row then y row -- the air-column file layout), grid [n_lines][grid_res][2].  For every frame and
  * grid line: flags bit 0 / 1 = the internal / external wall is crossed (0: the reference skips the line), bit 2 = more than
