@@ -49,6 +49,7 @@ SOURCES = {
     "melspec.hip": [],
     "resample_plan.cpp": [],
     "resample.hip": [],
+    "contour_spline.hip": [],
     "artspeech.hip": [],
 }
 

@@ -1012,6 +1012,36 @@ int as_resample_fwd(const void* x, int32_t x_int16, int64_t x_pitch, const int64
                     const float* coef, const int32_t* first, int32_t band, int32_t width, int32_t lead_min, int32_t lead_max,
                     float pad_value, float* out, int64_t out_pitch, int64_t m_max, int64_t* lengths_out, void* stream);
 
+/* Contour smoothing: a penalised least-squares B-spline through every contour of a batch, one launch.  The reference smooths
+ * each predicted contour with vt_tools.bs_regularization.regularize_Bsplines(contour, 3) before it saves or draws it
+ * (generate_vocal_tract_shape_v2.py:173,252; generate_vocal_tract_shape.py:155; phoneme_to_articulation/__init__.py:178-180).
+ * vt_tools is not vendored and not pinned by the reference: the definition below is this project's own, an
+ * ASSUMPTION whose parity with vt_tools is unpinned.
+ * For one contour of N points p_i (float32, widened to float64 once), degree d, K control points:
+ *   parameter   s_0 = 0, s_i = s_{i-1} + |p_i - p_{i-1}|; u_i = s_i / s_{N-1}, u_{N-1} = 1 exactly
+ *   basis       the clamped uniform knot vector [0]*d + linspace(0, 1, K-d+1) + [1]*d; the span of u is
+ *               min(floor(u (K-d)), K-d-1); values by Cox-de Boor
+ *   fit         minimise sum_i |S(u_i) - p_i|^2 + lambda sum_j |c_j - 2 c_{j+1} + c_{j+2}|^2, i.e. solve
+ *               (B'B + lambda D'D) c = B'p, x and y two right-hand sides of one symmetric positive definite band matrix
+ *               (half-bandwidth max(d, 2)), by a square-root-free banded Cholesky factorisation (L diag(d) L')
+ *   evaluate    S(v_m), v_m = m / (M-1), m = 0 .. M-1, rounded to float32 once
+ * All arithmetic is float64; there is no float32 variant (the matrices reach condition numbers of 1e7).
+ *   contours            coordinate xy of point i of contour c at contours[c s_contour + xy s_coord + i s_point] (element strides):
+ *                       (B, T, A, 2, N) model outputs and (F, A, N, 2) raw contours both go in as they lie
+ *   lengths [B] int64   optional, on the device, with T and A and n_contours = B T A: the contours of frame t >= lengths[b] are
+ *                       written as zeros (status 0) and not read
+ *   out                 coordinate xy of output m of contour c at out[(2 c + xy) out_pitch + m]; the M outputs of every row
+ *                       are written and nothing behind them
+ *   status [n_contours] optional int32: bit 0 = zero length (s_{N-1} == 0: every output is p_0, copied bit for bit), bit 1 = a
+ *                       non-finite coordinate (this contour's outputs are NaN; no other row is touched by it)
+ * Every sum has a fixed order and there are no atomics: two launches give equal bits, and a contour alone or inside a batch
+ * gives equal bits.  Limits, refused with AS_ERR_UNSUPPORTED / AS_ERR_BAD_ARG before any launch (never truncated):
+ * 1 <= degree <= 3, 2 <= N <= 256, degree + 1 <= K <= 32, 2 <= M <= 1024, lambda > 0 and finite (with lambda = 0 clustered or
+ * repeated points leave the matrix singular). */
+int as_contour_spline(const float* contours, int64_t s_contour, int64_t s_coord, int64_t s_point, int64_t n_contours, int32_t N,
+                      int32_t K, int32_t degree, double lambda, int32_t M, const int64_t* lengths, int32_t T, int32_t A, float* out,
+                      int64_t out_pitch, int32_t* status, void* stream);
+
 /* Optional per-kernel-phase timing with HIP events recorded on the launch stream (for bench.py's
  * roofline object).  as_profile_report writes "name count total_ms\n" lines (NUL terminated, truncated
  * to buflen) and returns the untruncated length; it waits for the recorded events to complete. */
