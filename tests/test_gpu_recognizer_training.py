@@ -28,14 +28,23 @@ def _lib():
 
 
 # --------------------------------------------------------------------------------------------------------------- CTC
-def _ctc_case(B, T, C, L_max, seed, min_in=None, repeats=False, zero_len=False):
+def _ctc_case(B, T, C, L_max, seed, min_in=None, repeats=False, zero_len=False, blank=0, lengths=None):
+    """repeats: True repeats the label pairs (2k, 2k+1), "across" the pairs (2k-1, 2k); blank: the class the labels avoid (labels
+    then include class 0); lengths: the target lengths, instead of drawn ones."""
     g = torch.Generator().manual_seed(seed)
     tl = torch.randint(0 if zero_len else 1, L_max + 1, (B,), generator=g)
     if zero_len:
         tl[0] = 0
     tl[-1] = L_max
+    if lengths is not None:
+        tl = torch.tensor(lengths)
     tgts = torch.randint(1, C, (B, L_max), generator=g)
-    if repeats:
+    if blank:   # the C - 1 classes other than blank
+        tgts = tgts - 1
+        tgts = tgts + (tgts >= blank)
+    if repeats == "across":
+        tgts[:, 2::2] = tgts[:, 1::2][:, : tgts[:, 2::2].shape[1]]
+    elif repeats:
         tgts[:, 1::2] = tgts[:, 0::2][:, : tgts[:, 1::2].shape[1]]
     for b in range(B):
         tgts[b, tl[b]:] = -1
@@ -47,7 +56,7 @@ def _ctc_case(B, T, C, L_max, seed, min_in=None, repeats=False, zero_len=False):
     return x, tgts, il, tl
 
 
-def _check_ctc(x32, tgts, il, tl, dev, reduction, zero_infinity, logits, one_d=False, permuted=False, label=""):
+def _check_ctc(x32, tgts, il, tl, dev, reduction, zero_infinity, logits, one_d=False, permuted=False, label="", blank=0):
     from artspeech_amd.phoneme_recognition.ctc import ctc_loss
     T, B, C = x32.shape
     t_in = torch.cat([tgts[b, : tl[b]] for b in range(B)]) if one_d else tgts
@@ -56,7 +65,7 @@ def _check_ctc(x32, tgts, il, tl, dev, reduction, zero_infinity, logits, one_d=F
     for name, dt in (("f64", torch.float64), ("f32", torch.float32)):
         xi = x32.to(dt).clone().requires_grad_(True)
         lp = F.log_softmax(xi, -1) if logits else xi
-        loss = F.ctc_loss(lp, torch.cat([tgts[b, : tl[b]] for b in range(B)]), il, tl, 0, reduction, zero_infinity)
+        loss = F.ctc_loss(lp, torch.cat([tgts[b, : tl[b]] for b in range(B)]), il, tl, blank, reduction, zero_infinity)
         (loss.sum() if reduction == "none" else loss).backward()
         res[name] = (loss.detach().double(), xi.grad.double())
     if permuted:   # the (T, B, C) view of a (B, T, C) tensor
@@ -65,7 +74,7 @@ def _check_ctc(x32, tgts, il, tl, dev, reduction, zero_infinity, logits, one_d=F
     else:
         xd = x32.to(dev).requires_grad_(True)
         xv = xd
-    out = ctc_loss(xv, t_in.to(dev), il, tl, reduction=reduction, zero_infinity=zero_infinity, logits=logits)
+    out = ctc_loss(xv, t_in.to(dev), il, tl, blank=blank, reduction=reduction, zero_infinity=zero_infinity, logits=logits)
     (out.sum() if reduction == "none" else out).backward()
     got_l, got_g = out.detach().double().cpu(), xd.grad.double().cpu()
     if permuted:
@@ -128,6 +137,90 @@ def test_ctc_past_the_limit_raises(dev):
     x = torch.randn(4200, 1, 5, device=dev)
     with pytest.raises(ValueError, match="exceeds"):
         ctc_loss(x, torch.ones(1, 2048, dtype=torch.long), [4200], [2048])
+
+
+@pytest.mark.parametrize("logits", [False, True])
+@pytest.mark.parametrize("C", [2, 63, 64, 65, 130])
+def test_ctc_class_widths_around_the_wave(C, logits, dev):
+    """ctc_row_lse_kernel and ctc_grad_kernel stride the classes over 64 lanes: one partial pass, one whole, a second pass of one
+    class, two whole passes and a third; C = 2 leaves one label, so every neighbouring pair is a repeat."""
+    x, tgts, il, tl = _ctc_case(3, 12, C, 4, seed=10 + C)
+    _check_ctc(x, tgts, il, tl, dev, "mean", False, logits, label=f"C={C} logits={logits}")
+
+
+@pytest.mark.parametrize("one_d", [False, True])
+@pytest.mark.parametrize("blank", [4, 2])
+def test_ctc_blank_is_not_class_zero(blank, one_d, dev):
+    x, tgts, il, tl = _ctc_case(4, 20, 5, 6, seed=20 + blank, repeats=True, blank=blank)
+    tgts[-1, 2] = 0   # (the last utterance has all 6 labels)
+    assert (tgts == 0).any() and not (tgts == blank).any()
+    for logits in (False, True):
+        _check_ctc(x, tgts, il, tl, dev, "sum", False, logits, one_d=one_d, label=f"blank={blank} 1-D={one_d} logits={logits}", blank=blank)
+
+
+@pytest.mark.parametrize("repeats", [True, "across"])
+@pytest.mark.parametrize("L", [127, 128])
+def test_ctc_state_count_boundary_of_the_two_exchange_paths(L, repeats, dev):
+    """S = 2 L + 1 = 255 states run in one wave of 4 states per thread (cross-lane shifts), 257 in 256 threads of 16 (LDS exchange).
+    A repeat inside a label pair (2k, 2k+1) forbids a skip between two states of one thread; a repeat across pairs (2k-1, 2k) forbids
+    the skip into a thread's first label state, whose r - 2 neighbour is the previous thread's."""
+    x, tgts, il, tl = _ctc_case(4, 280, 20, L, seed=30 + L, repeats=repeats, lengths=[L, 0, 1, L])
+    for b in (0, 3):   # the frames allow the alignment: il >= L + repeats
+        n_rep = int((tgts[b, 1:L] == tgts[b, :L - 1]).sum())
+        assert n_rep >= L // 2 - 1 and int(il[b]) >= L + n_rep
+    _check_ctc(x, tgts, il, tl, dev, "mean", True, True, label=f"L={L} repeats={repeats}")
+    if L == 128:
+        _check_ctc(x, tgts, il, tl, dev, "sum", False, False, one_d=True, label=f"L={L} repeats={repeats} 1-D")
+
+
+@pytest.mark.parametrize("reduction", ["none", "sum", "mean"])
+def test_ctc_single_frame_and_no_frames(reduction, dev):
+    g = torch.Generator().manual_seed(40)
+    # one frame: the empty target and a single label
+    x = torch.randn(1, 2, 6, generator=g) * 2
+    tgts, il, tl = torch.tensor([[-1], [3]]), torch.tensor([1, 1]), torch.tensor([0, 1])
+    # no frames: loss 0 for the empty target, +inf for a label, an all-zero gradient either way (torch's own result)
+    x0 = torch.randn(5, 3, 6, generator=g) * 2
+    tgts0, il0, tl0 = torch.tensor([[2, 4], [-1, -1], [5, -1]]), torch.tensor([5, 0, 0]), torch.tensor([2, 0, 1])
+    for zero_infinity in (False, True):
+        for logits in (False, True):
+            label = f"{reduction}/{zero_infinity}/{logits}"
+            _check_ctc(x, tgts, il, tl, dev, reduction, zero_infinity, logits, label="T=1 " + label)
+            _, grad = _check_ctc(x0, tgts0, il0, tl0, dev, reduction, zero_infinity, logits, label="no frames " + label)
+            assert not bool(grad[:, 1:].any())
+    out, _ = _check_ctc(x0, tgts0, il0, tl0, dev, "none", False, False, one_d=True, label="no frames 1-D")
+    assert out[1].item() == 0.0 and out[2].item() == float("inf")
+
+
+@pytest.mark.parametrize("zero_infinity", [False, True])
+def test_ctc_forbidden_label(zero_infinity, dev):
+    """A label of utterance 1 has log-probability -inf on every frame: its loss is +inf and its in-length gradient rows are NaN
+    (torch's), or 0 and exact zeros with zero_infinity; the other utterances are unaffected.  Log-probability input only: with
+    -inf among raw scores torch's log-softmax backward spreads the NaN over the whole row and the fused kernel does not, so no
+    pattern is asserted in logits mode."""
+    x, tgts, il, tl = _ctc_case(3, 15, 7, 4, seed=50)
+    tl[1], il[1] = 3, 11
+    tgts[1] = torch.tensor([2, 5, 3, -1])
+    x[:, 1, 5] = float("-inf")
+    out, grad = _check_ctc(x, tgts, il, tl, dev, "none", zero_infinity, False, label=f"forbidden label zi={zero_infinity}")
+    if zero_infinity:
+        assert out[1].item() == 0.0 and not bool(grad[:, 1].any())
+    else:
+        assert out[1].item() == float("inf") and bool(torch.isnan(grad[:11, 1]).all()) and not bool(grad[11:, 1].any())
+    assert bool(torch.isfinite(out[[0, 2]]).all()) and bool(torch.isfinite(grad[:, [0, 2]]).all())
+
+
+@pytest.mark.parametrize("L_max", [9, 140])   # both recursion kernels
+def test_ctc_loss_without_gradient_is_the_same_loss(L_max, dev):
+    """x.requires_grad = False runs the alpha recursion alone (with_beta = 0): bit-equal to the differentiable call's loss."""
+    from artspeech_amd.phoneme_recognition.ctc import ctc_loss
+    x, tgts, il, tl = _ctc_case(4, 300, 12, L_max, seed=60, repeats=True, zero_len=True)
+    for logits in (False, True):
+        xd = x.to(dev)
+        plain = ctc_loss(xd, tgts.to(dev), il, tl, reduction="none", logits=logits)
+        diff = ctc_loss(xd.clone().requires_grad_(True), tgts.to(dev), il, tl, reduction="none", logits=logits)
+        assert not plain.requires_grad and diff.requires_grad
+        assert torch.equal(plain, diff.detach()), (plain, diff)
 
 
 # ------------------------------------------------------------------------------------- convolution / LN parameter gradients
