@@ -99,6 +99,16 @@ __device__ __forceinline__ float as_wave_sum(float v) {
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
     return v;
 }
+__device__ __forceinline__ float as_wave_max(float v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
+    return v;
+}
+__device__ __forceinline__ float as_wave_min(float v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = fminf(v, __shfl_xor(v, o, 64));
+    return v;
+}
 __device__ __forceinline__ double as_wave_sum_d(double v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
@@ -114,6 +124,22 @@ __device__ __forceinline__ double as_wave_max_d(double v) {
     for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o, 64));
     return v;
 }
+// Inclusive scan over the 64 lanes: lane l gets op(v_0, ..., v_l), combined in log steps over __shfl_up (lane = threadIdx.x & 63)
+struct AsAdd { template <typename T> __device__ __forceinline__ T operator()(T a, T b) const { return a + b; } };
+struct AsMin { template <typename T> __device__ __forceinline__ T operator()(T a, T b) const { return min(a, b); } };
+struct AsMax { template <typename T> __device__ __forceinline__ T operator()(T a, T b) const { return max(a, b); } };
+template <typename T, typename Op>
+__device__ __forceinline__ T as_wave_scan(T v, int lane, Op op) {
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const T t = __shfl_up(v, o, 64);
+        if (lane >= o) v = op(v, t);
+    }
+    return v;
+}
+// A length as the kernels that clamp read it: n into [0, T], in n's own type.  (The CTC kernels refuse instead: ctc_sizes.)
+template <typename I>
+__device__ __forceinline__ I as_clamp_length(I n, int T) { return n < 0 ? 0 : (n > T ? (I)T : n); }
 // ReLU that keeps a NaN a NaN, like torch.relu (fmaxf(NaN, 0) = 0 would hide an invalid activation: the transformer's test
 // loop finds utterances with NaN predictions by exactly that propagation, transformer/evaluation.py:69-86)
 __device__ __forceinline__ float as_relu(float v) { return v < 0.f ? 0.f : v; }

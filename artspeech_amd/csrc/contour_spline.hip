@@ -49,15 +49,6 @@ __device__ __forceinline__ void cs_wave_sync() {
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
-__device__ __forceinline__ double cs_scan_add(double v, int lane) {
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const double t = __shfl_up(v, o, 64);
-        if (lane >= o) v += t;
-    }
-    return v;
-}
-
 // 1 / d in float64 without the division sequence: v_rcp_f64 (about 2^-23 relative) and two Newton steps
 __device__ __forceinline__ double cs_rcp(double d) {
     double r = __builtin_amdgcn_rcp(d);
@@ -161,7 +152,7 @@ __global__ __launch_bounds__(CS_WAVES * 64) void cs_kernel(const float* __restri
                 const double dx = (double)px[i] - (double)px[i - 1], dy = (double)py[i] - (double)py[i - 1];
                 seg = sqrt(dx * dx + dy * dy);
             }
-            s[q] = carry + cs_scan_add(seg, lane);
+            s[q] = carry + as_wave_scan(seg, lane, AsAdd{});
             carry = __shfl(s[q], 63, 64);
         }
     }

@@ -27,16 +27,6 @@
 
 namespace {
 
-__device__ __forceinline__ float ct_wave_max(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
-    return v;
-}
-__device__ __forceinline__ float ct_wave_min(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fminf(v, __shfl_xor(v, o, 64));
-    return v;
-}
 // position of the s-th (0-based) set bit of mask; s < popcount(mask)
 __device__ __forceinline__ int ct_select_bit(unsigned long long mask, int s) {
     int pos = 0;
@@ -120,9 +110,9 @@ __global__ __launch_bounds__(256) void prepare_contours_kernel(const float* __re
             const float lo = first ? __fsub_rn(u.y, thr3) : __fsub_rn(u.y, thr2);
             mask = __ballot(pt && y > lo);
         } else {
-            const float li_max = ct_wave_max(pt ? r_li[lane].y : -INFINITY);
+            const float li_max = as_wave_max(pt ? r_li[lane].y : -INFINITY);
             if (kind == 1) {   // tongue: front tail below the lower incisor's top, back tail below the epiglottis' bottom + margin
-                const float ep_min = ct_wave_min(pt ? r_ep[lane].y : INFINITY);
+                const float ep_min = as_wave_min(pt ? r_ep[lane].y : INFINITY);
                 const float hi = first ? __fadd_rn(ep_min, thr0) : li_max;
                 mask = __ballot(pt && y < hi);
             } else {           // lower lip, stage 1: the second half against the incisor's top + margin, then resampled

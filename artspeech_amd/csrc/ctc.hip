@@ -41,8 +41,7 @@ __global__ __launch_bounds__(256) void ctc_row_lse_kernel(const float* __restric
     const float* xr = x + t * sxt + b * sxb;
     float m = -INFINITY;
     for (int k = lane; k < C; k += 64) m = fmaxf(m, xr[k]);
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
+    m = as_wave_max(m);
     float s = 0.f;
     if (m != -INFINITY)
         for (int k = lane; k < C; k += 64) s += expf(xr[k] - m);
@@ -199,12 +198,10 @@ extern "C" int64_t as_ctc_workspace_floats(int32_t T, int32_t B, int32_t max_tar
     return (long)B * T + 2L * B * T * (2L * max_target_length + 1);
 }
 
-static int ctc_check(const char* who, const float* x, int32_t T, int32_t B, int32_t C, const int64_t* targets, const int64_t* in_len,
-                     const int64_t* tgt_len, int32_t maxL, int32_t blank, int64_t ws_floats, const float* ws) {
-    AS_REQUIRE(x && in_len && tgt_len && ws && T > 0 && B > 0 && C > 0 && maxL >= 0 && blank >= 0 && blank < C, AS_ERR_BAD_ARG,
-               "%s: bad argument", who);
-    AS_REQUIRE(targets || maxL == 0, AS_ERR_BAD_ARG, "%s: null targets", who);
-    AS_REQUIRE(maxL <= CTC_MAX_L, AS_ERR_UNSUPPORTED, "%s: target length %d (at most %d supported)", who, maxL, CTC_MAX_L);
+// the shared check, then the workspace that the loss fills and the gradient reads
+static int ctc_check_ws(const char* who, const float* x, int32_t T, int32_t B, int32_t C, const int64_t* targets, const int64_t* in_len,
+                        const int64_t* tgt_len, int32_t maxL, int32_t blank, int64_t ws_floats, const float* ws) {
+    AS_TRY(ctc_check(who, x, T, B, C, targets, in_len, tgt_len, maxL, blank, ws != nullptr));
     AS_REQUIRE(ws_floats >= as_ctc_workspace_floats(T, B, maxL), AS_ERR_WORKSPACE, "%s: workspace of %lld floats, %lld needed", who,
                (long long)ws_floats, (long long)as_ctc_workspace_floats(T, B, maxL));
     return 0;
@@ -214,7 +211,7 @@ extern "C" int as_ctc_loss(const float* x, int64_t sx_t, int64_t sx_b, int32_t T
                            const int64_t* targets, int64_t tgt_stride, const int64_t* input_lengths, const int64_t* target_lengths,
                            int32_t max_target_length, int32_t blank, int32_t with_beta, float* ws, int64_t ws_floats, float* nll,
                            void* stream) {
-    AS_TRY(ctc_check("as_ctc_loss", x, T, B, C, targets, input_lengths, target_lengths, max_target_length, blank, ws_floats, ws));
+    AS_TRY(ctc_check_ws("as_ctc_loss", x, T, B, C, targets, input_lengths, target_lengths, max_target_length, blank, ws_floats, ws));
     AS_REQUIRE(nll, AS_ERR_BAD_ARG, "as_ctc_loss: null output");
     hipStream_t st = (hipStream_t)stream;
     const long S = 2L * max_target_length + 1;
@@ -226,12 +223,11 @@ extern "C" int as_ctc_loss(const float* x, int64_t sx_t, int64_t sx_b, int32_t T
         AS_LAUNCH_CHECK("as_ctc_loss");
     }
     const dim3 grid(B, with_beta ? 2 : 1);
-    if (S <= 64 * 4)
-        hipLaunchKernelGGL((ctc_alpha_beta_kernel<64, 4>), grid, dim3(64), 0, st, x, (long)sx_t, (long)sx_b, T, lse, targets, tgt_stride,
+    ctc_layout(max_target_length, [&](auto nt, auto spt) {
+        constexpr int NT = decltype(nt)::value, SPT = decltype(spt)::value;
+        hipLaunchKernelGGL((ctc_alpha_beta_kernel<NT, SPT>), grid, dim3(NT), 0, st, x, (long)sx_t, (long)sx_b, T, lse, targets, tgt_stride,
                            input_lengths, target_lengths, max_target_length, blank, alpha, beta, nll);
-    else
-        hipLaunchKernelGGL((ctc_alpha_beta_kernel<256, 16>), grid, dim3(256), 0, st, x, (long)sx_t, (long)sx_b, T, lse, targets,
-                           tgt_stride, input_lengths, target_lengths, max_target_length, blank, alpha, beta, nll);
+    });
     AS_LAUNCH_CHECK("as_ctc_loss");
     return 0;
 }
@@ -240,7 +236,7 @@ extern "C" int as_ctc_grad(const float* x, int64_t sx_t, int64_t sx_b, int32_t T
                            const int64_t* targets, int64_t tgt_stride, const int64_t* input_lengths, const int64_t* target_lengths,
                            int32_t max_target_length, int32_t blank, const float* ws, int64_t ws_floats, const float* nll,
                            const float* scale, int32_t zero_infinity, float* grad, int64_t sg_t, int64_t sg_b, void* stream) {
-    AS_TRY(ctc_check("as_ctc_grad", x, T, B, C, targets, input_lengths, target_lengths, max_target_length, blank, ws_floats, ws));
+    AS_TRY(ctc_check_ws("as_ctc_grad", x, T, B, C, targets, input_lengths, target_lengths, max_target_length, blank, ws_floats, ws));
     AS_REQUIRE(nll && grad, AS_ERR_BAD_ARG, "as_ctc_grad: null argument");
     const long S = 2L * max_target_length + 1;
     const float* lse = logits ? ws : nullptr;

@@ -261,11 +261,7 @@ extern "C" int as_ctc_align(const float* x, int64_t sx_t, int64_t sx_b, int32_t 
                             int32_t max_target_length, int32_t blank, void* ws, int64_t ws_bytes, float* score, int32_t* frame_index,
                             int32_t* frame_token, int32_t* frame_filled, int32_t* spans, float* span_score, void* stream) {
     const int maxL = max_target_length;
-    AS_REQUIRE(x && input_lengths && target_lengths && score && T > 0 && B > 0 && C > 0 && maxL >= 0 && blank >= 0 && blank < C &&
-                   tgt_stride >= 0,
-               AS_ERR_BAD_ARG, "as_ctc_align: bad argument");
-    AS_REQUIRE(targets || maxL == 0, AS_ERR_BAD_ARG, "as_ctc_align: null targets");
-    AS_REQUIRE(maxL <= CTC_MAX_L, AS_ERR_UNSUPPORTED, "as_ctc_align: target length %d (at most %d supported)", maxL, CTC_MAX_L);
+    AS_TRY(ctc_check("as_ctc_align", x, T, B, C, targets, input_lengths, target_lengths, maxL, blank, score && tgt_stride >= 0));
     AS_REQUIRE(T <= CA_MAX_T, AS_ERR_UNSUPPORTED, "as_ctc_align: %d frames (at most %d supported)", T, CA_MAX_T);
     const int64_t need = as_ctc_align_workspace_bytes(T, B, maxL);
     AS_REQUIRE(need == 0 || (ws && ws_bytes >= need), AS_ERR_WORKSPACE, "as_ctc_align: workspace of %lld bytes, %lld needed",
@@ -273,18 +269,16 @@ extern "C" int as_ctc_align(const float* x, int64_t sx_t, int64_t sx_b, int32_t 
     const int pitch = ca_pitch(maxL);
     const bool in_ws = need > 0;
     const size_t lds = (size_t)(ca_frame_bytes(T) + (in_ws ? 0 : (long)T * pitch));
-    auto launch = [&](auto kernel, int nt) {
-        hipLaunchKernelGGL(kernel, dim3(B), dim3(nt), lds, (hipStream_t)stream, x, (long)sx_t, (long)sx_b, T, C, logits, targets, tgt_stride,
-                           input_lengths, target_lengths, maxL, blank, (unsigned char*)ws, pitch, score, frame_index, frame_token,
-                           frame_filled, spans, span_score);
-    };
-    if (2 * maxL + 1 <= 64 * 4) {
-        if (in_ws) launch(ctc_align_kernel<64, 4, true>, 64);
-        else launch(ctc_align_kernel<64, 4, false>, 64);
-    } else {
-        if (in_ws) launch(ctc_align_kernel<256, 16, true>, 256);
-        else launch(ctc_align_kernel<256, 16, false>, 256);
-    }
+    ctc_layout(maxL, [&](auto nt, auto spt) {
+        constexpr int NT = decltype(nt)::value, SPT = decltype(spt)::value;
+        auto launch = [&](auto kernel) {
+            hipLaunchKernelGGL(kernel, dim3(B), dim3(NT), lds, (hipStream_t)stream, x, (long)sx_t, (long)sx_b, T, C, logits, targets,
+                               tgt_stride, input_lengths, target_lengths, maxL, blank, (unsigned char*)ws, pitch, score, frame_index,
+                               frame_token, frame_filled, spans, span_score);
+        };
+        if (in_ws) launch(ctc_align_kernel<NT, SPT, true>);
+        else launch(ctc_align_kernel<NT, SPT, false>);
+    });
     AS_LAUNCH_CHECK("as_ctc_align");
     return 0;
 }

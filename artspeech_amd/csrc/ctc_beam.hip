@@ -60,12 +60,7 @@ __device__ __forceinline__ float cb_merge(float acc, float v, bool log_add) {
 // caller wrote to LDS before the call
 __device__ __forceinline__ int cb_scan(int v, int* wsum, int& total) {
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    int inc = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const int n = __shfl_up(inc, o, 64);
-        if (lane >= o) inc += n;
-    }
+    const int inc = as_wave_scan(v, lane, AsAdd{});
     __syncthreads();
     if (lane == 63) wsum[w] = inc;
     __syncthreads();
@@ -110,8 +105,7 @@ __global__ __launch_bounds__(CB_NT) void ctc_beam_kernel(const float* __restrict
     int* table = nodekey + n_nodes;               // [1 << table_log2]: node, 0 = empty (the root is never looked up)
     const unsigned table_mask = (1u << table_log2) - 1u;
     const float* xb = x + (long)b * sxb;
-    int Tb = lengths ? (int)lengths[b] : T;
-    Tb = Tb < 0 ? 0 : (Tb > T ? T : Tb);
+    const int Tb = as_clamp_length(lengths ? (int)lengths[b] : T, T);
 
     for (long k = tid; k < ((long)1 << table_log2); k += CB_NT) table[k] = 0;
     for (int k = tid; k < 2 * CB_G * CB_MAX_C; k += CB_NT) (&sl_class[0][0][0])[k] = 0;
@@ -141,9 +135,7 @@ __global__ __launch_bounds__(CB_NT) void ctc_beam_kernel(const float* __restrict
             v0 = v0 > 0.f ? logf(v0) : -INFINITY;
             v1 = v1 > 0.f ? logf(v1) : -INFINITY;
         } else if (mode == 2) {
-            float m = fmaxf(v0, v1);
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
+            const float m = as_wave_max(fmaxf(v0, v1));
             float s = 0.f;
             if (m > -INFINITY) s = (c0 < C ? expf(v0 - m) : 0.f) + (c1 < C ? expf(v1 - m) : 0.f);
             s = as_wave_sum(s);
@@ -175,8 +167,7 @@ __global__ __launch_bounds__(CB_NT) void ctc_beam_kernel(const float* __restrict
                 if (r1 < K) sl_class[buf][wave][r1] = (short)c1, sl_x[buf][wave][r1] = xs, best = fmaxf(best, xs);
             }
         }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) best = fmaxf(best, __shfl_xor(best, o, 64));
+        best = as_wave_max(best);
         if (live && lane == 0) row_best[buf][wave] = best;
         __syncthreads();
     };

@@ -48,9 +48,9 @@ __device__ __forceinline__ float fc_logsumexp(const float* __restrict__ xr, int 
     return m + logf(s);
 }
 
+// (the load stays behind a __restrict__ parameter of its own: without that scope the three kernels allocate registers differently)
 __device__ __forceinline__ long fc_length(const int64_t* __restrict__ lengths, int b, int T) {
-    const long n = lengths[b];
-    return n < 0 ? 0 : (n > T ? T : n);
+    return as_clamp_length<long>(lengths[b], T);
 }
 
 // ws: [0] the ticket (uint64), then per workgroup (numerator, denominator) as doubles
@@ -153,15 +153,6 @@ __global__ __launch_bounds__(256) void fc_grad_kernel(const float* __restrict__ 
     }
 }
 
-__device__ __forceinline__ unsigned fa_scan_add(unsigned v, int lane) {
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const unsigned t = __shfl_up(v, o, 64);
-        if (lane >= o) v += t;
-    }
-    return v;
-}
-
 // One workgroup per class.  fa_buf holds pow2ceil(cap) 64-bit entries: (key << 32) | positive flag, later
 // (key << 32) | (negatives in front << 1) | positive flag.
 __global__ __launch_bounds__(FA_THREADS) void fa_kernel(const float* __restrict__ x, long sx_t, long sx_b, int T, int B, int C,
@@ -213,7 +204,7 @@ __global__ __launch_bounds__(FA_THREADS) void fa_kernel(const float* __restrict_
     const unsigned k0 = min(tid * per, N), k1 = min(k0 + per, N);
     unsigned negs = 0;
     for (unsigned k = k0; k < k1; ++k) negs += 1u - (unsigned)(fa_buf[k] & 1u);
-    const unsigned incl = fa_scan_add(negs, lane);
+    const unsigned incl = as_wave_scan(negs, lane, AsAdd{});
     if (lane == 63) fa_wave[wave] = incl;
     __syncthreads();
     unsigned before = incl - negs, total = 0;

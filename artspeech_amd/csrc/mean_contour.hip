@@ -27,14 +27,6 @@
 
 namespace {
 
-__device__ __forceinline__ int mc_scan_max(int v, int lane) {
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const int t = __shfl_up(v, o, 64);
-        if (lane >= o) v = max(v, t);
-    }
-    return v;
-}
 __device__ __forceinline__ int mc_scan_min_rev(int v, int lane) {
 #pragma unroll
     for (int o = 1; o < 64; o <<= 1) {
@@ -79,7 +71,7 @@ __global__ __launch_bounds__(MC_SCAN) void mc_runs_kernel(const int64_t* __restr
         if (is_head) head = (int)i;
         if (is_tail) tail = (int)i;
     }
-    head = mc_scan_max(head, lane);
+    head = as_wave_scan(head, lane, AsMax{});
     tail = mc_scan_min_rev(tail, lane);
     if (lane == 63) s_head[wave] = head;
     if (lane == 0) s_tail[wave] = tail;
@@ -114,7 +106,7 @@ __global__ __launch_bounds__(64) void mc_runs_carry_kernel(int32_t* agg, int nbl
     int run = -1;
     for (int b0 = 0; b0 < nblocks; b0 += 64) {
         const int b = b0 + lane;
-        const int v = mc_scan_max(b < nblocks ? agg[2 * b] : -1, lane);
+        const int v = as_wave_scan(b < nblocks ? agg[2 * b] : -1, lane, AsMax{});
         int prev = __shfl_up(v, 1, 64);
         if (lane == 0) prev = -1;
         if (b < nblocks) carry[2 * b] = max(run, prev);

@@ -118,8 +118,7 @@ __global__ __launch_bounds__(256) void pca_cross_kernel(as_pca p, PcaWs w) {
 
 // maximum over the workgroup (independent of the order and of the workgroup's size); every thread gets the result
 __device__ __forceinline__ double pca_block_max(double v, double* red) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o, 64));
+    v = as_wave_max_d(v);
     __syncthreads();
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
     __syncthreads();

@@ -43,8 +43,7 @@ __global__ __launch_bounds__(256) void re_argmax_kernel(const float* __restrict_
     const int lane = threadIdx.x & 63;
     if (row >= (long)B * T) return;   // wave-uniform
     const int b = (int)(row / T), t = (int)(row % T);
-    long len = lengths ? lengths[b] : T;
-    len = len < 0 ? 0 : (len > T ? T : len);
+    const long len = as_clamp_length<long>(lengths ? lengths[b] : T, T);
     if (t >= len) {
         if (lane == 0) raw[row] = -1;
         return;
@@ -65,23 +64,6 @@ __global__ __launch_bounds__(256) void re_argmax_kernel(const float* __restrict_
     if (lane == 0) raw[row] = idx;
 }
 
-__device__ __forceinline__ int re_scan_add(int v, int lane) {
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const int t = __shfl_up(v, o, 64);
-        if (lane >= o) v += t;
-    }
-    return v;
-}
-__device__ __forceinline__ int re_scan_min(int v, int lane) {
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const int t = __shfl_up(v, o, 64);
-        if (lane >= o) v = min(v, t);
-    }
-    return v;
-}
-
 // raw [B][T] (-1 past the utterance's length) -> tokens [B][T]: runs collapsed, then blank dropped, padded with -1.  raw may be
 // tokens itself: the row is staged in LDS before anything is written.
 __global__ __launch_bounds__(256) void re_collapse_kernel(const int* raw, int T, int blank, int* tokens, int* __restrict__ counts) {
@@ -98,7 +80,7 @@ __global__ __launch_bounds__(256) void re_collapse_kernel(const int* raw, int T,
         const int r = re_row[t];
         n += r >= 0 && r != blank && (t == 0 || r != re_row[t - 1]);
     }
-    const int incl = re_scan_add(n, lane);
+    const int incl = as_wave_scan(n, lane, AsAdd{});
     if (lane == 63) wave_sum[wave] = incl;
     __syncthreads();
     int before = incl - n, total = 0;
@@ -158,7 +140,7 @@ __global__ __launch_bounds__(256) void re_edit_distance_kernel(const int* __rest
                 carry_old = __shfl(old, 63, 64);
                 int x = min(old + 1, up + (p != tg[c]));
                 if (j == 0) x = i;
-                int y = min(re_scan_min(x - j, lane), carry_min);
+                int y = min(as_wave_scan(x - j, lane, AsMin{}), carry_min);
                 carry_min = __shfl(y, 63, 64);
                 row[c] = y + j;
             }
@@ -197,7 +179,7 @@ __global__ __launch_bounds__(64) void re_align_kernel(const int* __restrict__ pr
             int x = RE_BIG;   // columns past L: they follow every valid one in the scan and are not stored
             if (j == 0) x = i;
             else if (j <= L) x = min((int)prev[j] + 1, (int)prev[j - 1] + (p != tc[j - 1]));
-            const int y = min(re_scan_min(x - j, lane), carry_min);
+            const int y = min(as_wave_scan(x - j, lane, AsMin{}), carry_min);
             carry_min = __shfl(y, 63, 64);
             if (j <= L) cur[j] = (uint16_t)(y + j);
         }

@@ -752,8 +752,7 @@ __global__ __launch_bounds__(256) void attn_softmax_kernel(float* __restrict__ s
         v[c] = x;
         m = fmaxf(m, x);
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
+    m = as_wave_max(m);
     float sum = 0.f;
 #pragma unroll
     for (int c = 0; c < NW; ++c) {

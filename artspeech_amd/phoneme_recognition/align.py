@@ -12,10 +12,11 @@ sides before comparing, which is how the reference aligns phonetic groups instea
 import torch
 
 from .. import _lib
+from . import emission_args as args
+from .emission_args import MAX_TARGET   # as_edit_distance / as_align_counts: the CTC kernels' limit
 
 MAX_FRAMES = 8192   # as_decode_top1
 MAX_PRED = 4096     # as_edit_distance / as_align_counts
-MAX_TARGET = 2047
 
 
 def _i32(t, dev):
@@ -47,27 +48,17 @@ def decode_top1(emissions, lengths=None, blank=-1, return_argmax=False):
     with return_argmax, the raw per-frame arg-max (B, T) int32 (-1 past the length).  lengths: one entry per utterance, or None
     for all T frames; blank < 0 or None: no blank token."""
     _lib.require_gpu(emissions, "emissions")
-    if emissions.dim() != 3:
-        raise ValueError("decode_top1: emissions must be (B, T, C)")
-    if emissions.dtype != torch.float32:
-        raise TypeError(f"decode_top1: float32 emissions expected, got {emissions.dtype}")
-    B, T, Cn = emissions.shape
+    emissions, T, B, Cn, st, sb = args.emissions(emissions, "decode_top1", False, detach=True)
     dev = emissions.device
     if T > MAX_FRAMES:
         raise ValueError(f"decode_top1: {T} frames exceeds the supported {MAX_FRAMES}")
-    emissions = emissions.detach()
-    if emissions.stride(2) != 1:
-        emissions = emissions.contiguous()
     tokens = torch.empty(B, T, device=dev, dtype=torch.int32)
     counts = torch.empty(B, device=dev, dtype=torch.int32)
     argmax = torch.empty(B, T, device=dev, dtype=torch.int32) if return_argmax else None
     if lengths is not None:
-        lengths = torch.as_tensor(lengths).reshape(-1)
-        if lengths.numel() != B:
-            raise ValueError(f"decode_top1: lengths must have one entry per utterance ({B}), got {lengths.numel()}")
-        lengths = lengths.to(device=dev, dtype=torch.int64)
+        _, lengths = args.lengths(lengths, B, "decode_top1", device=dev)
     if B and T and Cn:
-        _lib.call("as_decode_top1", emissions, emissions.stride(0), emissions.stride(1), B, T, Cn, lengths,
+        _lib.call("as_decode_top1", emissions, sb, st, B, T, Cn, lengths,
                   -1 if blank is None else int(blank), tokens, counts, argmax)
     else:
         tokens.fill_(-1)
@@ -144,10 +135,7 @@ def confusion_counts(argmax, targets, lengths, n, class_map=None, out=None):
     if n <= 0:
         raise ValueError("confusion_counts: n must be positive")
     if lengths is not None:
-        lengths = torch.as_tensor(lengths).reshape(-1)
-        if lengths.numel() != B:
-            raise ValueError(f"confusion_counts: lengths must have one entry per utterance ({B}), got {lengths.numel()}")
-        lengths = lengths.to(device=dev, dtype=torch.int64)
+        _, lengths = args.lengths(lengths, B, "confusion_counts", device=dev)
     cm, n_map = _class_map(class_map, dev)
     if out is None:
         out = torch.zeros(n, n, device=dev, dtype=torch.int32)

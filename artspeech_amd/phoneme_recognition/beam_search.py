@@ -9,6 +9,7 @@ from dataclasses import dataclass
 import torch
 
 from .. import _lib
+from . import emission_args as args
 
 MAX_BEAM = 64      # live prefixes of one utterance (as_ctc_beam_search)
 MAX_CLASSES = 128
@@ -37,16 +38,9 @@ def ctc_beam_search(emissions, lengths=None, blank=0, beam_size=50, beam_size_to
     contributions further than this below the frame's best are dropped; log_add: merge the alignments of a labelling by
     logaddexp rather than max; sil / sil_score: a class whose emissions get sil_score added (-1: none).  One kernel launch."""
     _lib.require_gpu(emissions, "emissions")
-    if emissions.dim() != 3:
-        raise ValueError("ctc_beam_search: emissions must be (B, T, C)")
-    if emissions.dtype != torch.float32:
-        raise TypeError(f"ctc_beam_search (HIP): float32 emissions expected, got {emissions.dtype}")
+    x, T, B, Cn, st, sb = args.emissions(emissions, "ctc_beam_search", False, detach=True)
     if input not in _MODES:
         raise ValueError(f"ctc_beam_search: input must be one of {sorted(_MODES)}, got {input!r}")
-    x = emissions.detach()
-    if x.stride(2) != 1:
-        x = x.contiguous()
-    B, T, Cn = x.shape
     dev = x.device
     beam_size, nbest = int(beam_size), int(nbest)
     K = Cn if beam_size_token is None else int(beam_size_token)
@@ -67,10 +61,7 @@ def ctc_beam_search(emissions, lengths=None, blank=0, beam_size=50, beam_size_to
     if not float(beam_threshold) >= 0.0:
         raise ValueError(f"ctc_beam_search: beam_threshold {beam_threshold} must be at least 0")
     if lengths is not None:
-        lengths = torch.as_tensor(lengths).reshape(-1)
-        if lengths.numel() != B:
-            raise ValueError(f"ctc_beam_search: lengths must have one entry per utterance ({B}), got {lengths.numel()}")
-        lengths = lengths.to(device=dev, dtype=torch.int64)
+        _, lengths = args.lengths(lengths, B, "ctc_beam_search", device=dev)
     tokens = torch.empty(B, nbest, T, device=dev, dtype=torch.int32)
     counts = torch.empty(B, nbest, device=dev, dtype=torch.int32)
     scores = torch.empty(B, nbest, device=dev, dtype=torch.float32)
@@ -81,7 +72,7 @@ def ctc_beam_search(emissions, lengths=None, blank=0, beam_size=50, beam_size_to
     else:
         wsn = int(_lib.call("as_ctc_beam_workspace_bytes", T, B, Cn, beam_size))
         ws = torch.empty(wsn, device=dev, dtype=torch.uint8)
-        _lib.call("as_ctc_beam_search", x, x.stride(1), x.stride(0), T, B, Cn, _MODES[input], lengths, int(blank), int(sil),
+        _lib.call("as_ctc_beam_search", x, st, sb, T, B, Cn, _MODES[input], lengths, int(blank), int(sil),
                   float(sil_score), beam_size, K, float(beam_threshold), int(bool(log_add)), nbest, tokens, counts, scores, num_hyps,
                   ws, wsn)
     return BeamResult(tokens, counts, scores, num_hyps)

@@ -12,8 +12,8 @@ import numpy as np
 import torch
 
 from .. import _lib
+from . import emission_args as args
 
-_MAX_TARGET = 2047  # S = 2L + 1 <= 4095 states (as_ctc_align)
 _MAX_FRAMES = 8192  # the per-frame scratch of one utterance lives in LDS
 
 
@@ -57,13 +57,6 @@ def filled_runs(filled):
     return [(int(filled[s]), int(s), int(e)) for s, e in zip(starts, ends)]
 
 
-def _lengths(v, B, dev, what):
-    t = torch.as_tensor(v).reshape(-1).to(torch.int64)
-    if t.numel() != B:
-        raise ValueError(f"forced_align: {what} must have one entry per utterance ({B}), got {t.numel()}")
-    return t.cpu(), t.to(dev)
-
-
 def forced_align(emissions, targets, input_lengths, target_lengths, blank=0, logits=False):
     """The best CTC alignment of ``targets`` to ``emissions`` for every utterance, as an ``Alignment``.
 
@@ -72,39 +65,13 @@ def forced_align(emissions, targets, input_lengths, target_lengths, blank=0, log
     (B, S) with -1 padding, or 1-D concatenated, as ``ctc_loss`` takes them; lengths: one entry per utterance.  One kernel launch,
     nothing synchronises beyond reading the lengths that the caller passed on the host."""
     _lib.require_gpu(emissions, "emissions")
-    if emissions.dim() != 3:
-        raise ValueError("forced_align: emissions must be (B, T, C)")
-    if emissions.dtype != torch.float32:
-        raise TypeError(f"forced_align (HIP): float32 emissions expected, got {emissions.dtype}")
-    x = emissions if emissions.stride(2) == 1 else emissions.contiguous()
-    B, T, Cn = x.shape
+    x, T, B, Cn, st, sb = args.emissions(emissions, "forced_align", False)
     dev = x.device
-    il_h, il = _lengths(input_lengths, B, dev, "input_lengths")
-    tl_h, tl = _lengths(target_lengths, B, dev, "target_lengths")
-    if (il_h < 0).any() or (il_h > T).any():
-        raise ValueError(f"forced_align: input_lengths must lie in [0, {T}]")
-    if (tl_h < 0).any():
-        raise ValueError("forced_align: negative target length")
-    max_l = int(tl_h.max()) if B else 0
-    if max_l > _MAX_TARGET:
-        raise ValueError(f"forced_align (HIP): target length {max_l} exceeds the supported {_MAX_TARGET}")
+    _, il = args.lengths(input_lengths, B, "forced_align", "input_lengths", T=T, device=dev)
+    tl_h, tl = args.lengths(target_lengths, B, "forced_align", "target_lengths", host=True, device=dev)
     if T > _MAX_FRAMES:
         raise ValueError(f"forced_align (HIP): {T} frames exceed the supported {_MAX_FRAMES}")
-    targets = torch.as_tensor(targets).to(device=dev, dtype=torch.int64)
-    if targets.dim() == 2:
-        if targets.shape[0] != B or targets.shape[1] < max_l:
-            raise ValueError("forced_align: padded targets must be (B, S) with S >= max(target_lengths)")
-        targets = targets.contiguous()
-        tstride = targets.shape[1]
-    elif targets.dim() == 1:
-        if targets.numel() < int(tl_h.sum()):
-            raise ValueError("forced_align: 1-D targets shorter than sum(target_lengths)")
-        targets = targets.contiguous()
-        tstride = 0
-    else:
-        raise ValueError("forced_align: targets must be 1-D (concatenated) or 2-D (padded)")
-    if not 0 <= blank < Cn:
-        raise ValueError(f"forced_align: blank {blank} outside [0, {Cn})")
+    targets, tstride, max_l = args.ctc_targets(targets, tl_h, B, "forced_align", blank, Cn, dev)
     score = torch.empty(B, device=dev, dtype=torch.float32)
     frames = torch.empty(3, B, T, device=dev, dtype=torch.int32)
     spans = torch.empty(B, max_l, 2, device=dev, dtype=torch.int32)
@@ -116,9 +83,8 @@ def forced_align(emissions, targets, input_lengths, target_lengths, blank=0, log
     else:
         wsn = int(_lib.call("as_ctc_align_workspace_bytes", T, B, max_l))
         ws = torch.empty(wsn, device=dev, dtype=torch.uint8) if wsn else None
-        _lib.call("as_ctc_align", x, x.stride(1), x.stride(0), T, B, Cn, int(logits), targets if targets.numel() else None, tstride,
-                  il, tl, max_l, int(blank), ws, wsn, score, frames[0], frames[1], frames[2], spans if max_l else None,
-                  span_score if max_l else None)
+        _lib.call("as_ctc_align", x, st, sb, T, B, Cn, int(logits), targets, tstride, il, tl, max_l, int(blank), ws, wsn, score,
+                  frames[0], frames[1], frames[2], spans if max_l else None, span_score if max_l else None)
     return Alignment(score, torch.isfinite(score), frames[0], frames[1], frames[2], spans, span_score)
 
 

@@ -11,6 +11,7 @@ backward's scale stay on the device: nothing synchronises."""
 import torch
 
 from .. import _lib
+from . import emission_args as args
 
 MAX_CLASSES = 4096        # as_frame_ce_loss
 MAX_AUROC_FRAMES = 16384  # as_frame_auroc sorts a class column in LDS
@@ -28,18 +29,14 @@ def _workspace(dev, nbytes):
 
 def check_frame_lengths(who, input_lengths, target_lengths, B, T):
     """The two length vectors as one host int64 (B,) tensor; ValueError unless they are equal entry by entry and lie in [0, T]."""
-    il = torch.as_tensor(input_lengths).reshape(-1).to(torch.int64).cpu()
-    tl = torch.as_tensor(target_lengths).reshape(-1).to(torch.int64).cpu()
-    if il.numel() != B or tl.numel() != B:
-        raise ValueError(f"{who}: the lengths must have one entry per utterance ({B}), got {il.numel()} and {tl.numel()}")
+    il, _ = args.lengths(input_lengths, B, who, "input_lengths", host=True)
+    tl, _ = args.lengths(target_lengths, B, who, "target_lengths", host=True)
     differ = (il != tl).nonzero()
     if differ.numel():
         b = int(differ[0])
         raise ValueError(f"{who}: one target per frame is required, but utterance {b} has {int(il[b])} frames and {int(tl[b])} "
                          f"target entries")
-    if B and ((il < 0).any() or (il > T).any()):
-        raise ValueError(f"{who}: lengths must lie in [0, {T}]")
-    return il
+    return args.lengths(il, B, who, T=T)[0]
 
 
 def _frame_targets(who, targets, B, T, dev):
@@ -51,35 +48,33 @@ def _frame_targets(who, targets, B, T, dev):
 
 class _FrameCE(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, targets, lengths, weight, ignore_index, mean, label_smoothing):
+    def forward(ctx, x, st, sb, targets, lengths, weight, ignore_index, mean, label_smoothing):
         T, B, Cn = x.shape
         dev = x.device
-        if x.stride(2) != 1:
-            x = x.contiguous()
         lse = torch.empty(B, T, device=dev, dtype=torch.float32)
         sums = torch.empty(2, device=dev, dtype=torch.float64)
         nbytes = int(_lib.call("as_frame_ce_workspace_bytes", T, B))
         ws = _workspace(dev, nbytes)
-        _lib.call("as_frame_ce_loss", x, x.stride(0), x.stride(1), T, B, Cn, targets, targets.shape[1], lengths, weight, ignore_index,
+        _lib.call("as_frame_ce_loss", x, st, sb, T, B, Cn, targets, targets.shape[1], lengths, weight, ignore_index,
                   label_smoothing, lse, sums, ws, ws.numel())
         out = (sums[0] / sums[1] if mean else sums[0]).to(torch.float32)
         if ctx.needs_input_grad[0]:
             ctx.save_for_backward(x, targets, lengths, lse, sums, *([weight] if weight is not None else []))
-            ctx.meta = (ignore_index, mean, label_smoothing)
+            ctx.meta = (ignore_index, mean, label_smoothing, st, sb)
         return out
 
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, gout):
         x, targets, lengths, lse, sums, *weight = ctx.saved_tensors
-        ignore_index, mean, label_smoothing = ctx.meta
+        ignore_index, mean, label_smoothing, st, sb = ctx.meta
         T, B, Cn = x.shape
         gout = gout.to(torch.float32).reshape(1).contiguous()
         grad = torch.empty(x.shape, device=x.device, dtype=torch.float32)
-        _lib.call("as_frame_ce_grad", x, x.stride(0), x.stride(1), T, B, Cn, targets, targets.shape[1], lengths,
+        _lib.call("as_frame_ce_grad", x, st, sb, T, B, Cn, targets, targets.shape[1], lengths,
                   weight[0] if weight else None, ignore_index, label_smoothing, lse, sums, gout, int(mean), grad, grad.stride(0),
                   grad.stride(1))
-        return grad, None, None, None, None, None, None
+        return grad, None, None, None, None, None, None, None, None
 
 
 def frame_cross_entropy(x, targets, input_lengths, target_lengths, weight=None, ignore_index=-100, reduction="mean",
@@ -91,15 +86,12 @@ def frame_cross_entropy(x, targets, input_lengths, target_lengths, weight=None, 
                                   "use 'mean' or 'sum'")
     if reduction not in ("sum", "mean"):
         raise ValueError(f"frame_cross_entropy: unknown reduction {reduction!r}")
-    if x.dim() != 3:
-        raise ValueError("frame_cross_entropy: x must be (T, B, C)")
-    T, B, Cn = x.shape
+    T, B, Cn = args.emissions_shape(x, "frame_cross_entropy", True, "x")
     il = check_frame_lengths("frame_cross_entropy", input_lengths, target_lengths, B, T)
     if not 0.0 <= float(label_smoothing) <= 1.0:
         raise ValueError(f"frame_cross_entropy: label_smoothing {label_smoothing} outside [0, 1]")
     _lib.require_gpu(x, "x")
-    if x.dtype != torch.float32:
-        raise TypeError(f"frame_cross_entropy (HIP): float32 input expected, got {x.dtype}")
+    x, T, B, Cn, st, sb = args.emissions(x, "frame_cross_entropy", True, name="x")
     if not 1 <= Cn <= MAX_CLASSES:
         raise ValueError(f"frame_cross_entropy (HIP): {Cn} classes outside the supported 1..{MAX_CLASSES}")
     dev = x.device
@@ -115,7 +107,7 @@ def frame_cross_entropy(x, targets, input_lengths, target_lengths, weight=None, 
         return zero / zero if reduction == "mean" else zero
     if targets.shape[1] < T:   # the kernel reads targets[b, t] for t < lengths[b] <= S only, but takes one pitch >= T
         targets = torch.nn.functional.pad(targets, (0, T - targets.shape[1]), value=int(ignore_index))
-    return _FrameCE.apply(x, targets, il.to(dev), weight, int(ignore_index), reduction == "mean", float(label_smoothing))
+    return _FrameCE.apply(x, st, sb, targets, il.to(dev), weight, int(ignore_index), reduction == "mean", float(label_smoothing))
 
 
 def frame_auroc_counts(scores, targets, lengths, ignore_index=-100):
@@ -124,19 +116,10 @@ def frame_auroc_counts(scores, targets, lengths, ignore_index=-100):
     negative frames and twice the number of (positive, negative) pairs the positive outranks, ties counted once.
     AUROC_c = u2 / (2 n_pos n_neg).  At most MAX_AUROC_FRAMES frames (ValueError beyond: there is no workspace path)."""
     _lib.require_gpu(scores, "scores")
-    if scores.dim() != 3:
-        raise ValueError("frame_auroc_counts: scores must be (B, T, C)")
-    if scores.dtype != torch.float32:
-        raise TypeError(f"frame_auroc_counts: float32 scores expected, got {scores.dtype}")
-    B, T, Cn = scores.shape
+    scores, T, B, Cn, st, sb = args.emissions(scores, "frame_auroc_counts", False, detach=True, name="scores")
     dev = scores.device
-    scores = scores.detach()
-    if scores.stride(2) != 1:
-        scores = scores.contiguous()
     targets = _frame_targets("frame_auroc_counts", targets, B, T, dev)
-    lengths = torch.as_tensor(lengths).reshape(-1).to(torch.int64)
-    if lengths.numel() != B:
-        raise ValueError(f"frame_auroc_counts: lengths must have one entry per utterance ({B}), got {lengths.numel()}")
+    lengths, lengths_dev = args.lengths(lengths, B, "frame_auroc_counts", device=dev)
     out = torch.zeros(3, max(Cn, 1), device=dev, dtype=torch.int64)
     if B == 0 or T == 0 or Cn == 0:
         return out[0, :Cn], out[1, :Cn], out[2, :Cn]
@@ -146,6 +129,6 @@ def frame_auroc_counts(scores, targets, lengths, ignore_index=-100):
         raise ValueError(f"frame_auroc_counts: {frames} frames exceeds the supported {MAX_AUROC_FRAMES}")
     if targets.shape[1] < T:
         targets = torch.nn.functional.pad(targets, (0, T - targets.shape[1]), value=int(ignore_index))
-    _lib.call("as_frame_auroc", scores, scores.stride(1), scores.stride(0), T, B, Cn, targets, targets.shape[1], lengths.to(dev),
+    _lib.call("as_frame_auroc", scores, st, sb, T, B, Cn, targets, targets.shape[1], lengths_dev,
               int(ignore_index), max(frames, 1), out[0], out[1], out[2])
     return out[0], out[1], out[2]
