@@ -50,6 +50,7 @@ SOURCES = {
     "resample_plan.cpp": [],
     "resample.hip": [],
     "contour_spline.hip": [],
+    "tsne.hip": [],
     "artspeech.hip": [],
 }
 

@@ -6,8 +6,10 @@ test_phoneme_recognition.py: the substitution matrix (``compute_substitution_mat
 matrix (``compute_confusion_matrix``, :410-432), counted on the device (align.py) and normalised on the host in float64 as the
 reference does.  The frame-level criterion and metrics of the reference's ``loss: CE`` branch (``CrossEntropyLoss`` /
 ``frame_cross_entropy``, and ``Accuracy``, ``F1Score``, ``AUROC`` in metrics.py) run on the device too and are trained by
-`python -m train_frame_recognition`; ``Criterion.CE`` and the four CTC entry scripts still refuse ``loss: CE``.  The plots and the t-SNE
-feature plot are not ported."""
+`python -m train_frame_recognition`; ``Criterion.CE`` and the five CTC entry scripts still refuse ``loss: CE``.  The t-SNE map of the
+recogniser's features (``plot_features``, :332-399) is embedded on the device (tsne.py) and written by ``run_test`` where it is
+asked for (embed_phoneme_recognition.py); the plots of the two matrices are not ported."""
+import json
 import os
 from enum import Enum
 
@@ -23,6 +25,7 @@ from .deepspeech2 import DeepSpeech2, TrainableDeepSpeech2, top1_phonemes  # noq
 from .forced_align import Alignment, align_test, forced_align  # noqa: F401
 from .frame_ce import frame_cross_entropy  # noqa: F401
 from .metrics import CrossEntropyLoss, normalize_counts  # noqa: F401
+from .tsne import TSNE, _embed_features, draw_embedding, feature_embedding, plot_features, sample_features_per_class  # noqa: F401
 
 CLASSES_NAMES = {
     0: "dental",
@@ -230,15 +233,44 @@ def compute_confusion_matrix(predictions, targets, vocabulary, groups=None, norm
     return _finish_confusion(counts.cpu().numpy(), normalize)
 
 
+def _save_model_features(features, targets, vocabulary, groups, options, save_dir):
+    """The files of run_test's ``model_features`` (see there)."""
+    max_items = int(options.pop("max_items_per_class", 100))
+    seed = int(options.pop("seed", 0))
+    groups = options.pop("groups", None) or groups
+    embedding, tokens, group_idx, tsne = _embed_features(features.detach(), targets, vocabulary, groups, max_items, seed, options)
+    embedding, tokens, group_idx = embedding.cpu().numpy(), tokens.cpu().numpy(), group_idx.cpu().numpy()
+    np.save(os.path.join(save_dir, "model_features_tsne.npy"), embedding.astype(np.float32))
+    np.save(os.path.join(save_dir, "model_features_tokens.npy"), tokens.astype(np.int64))
+    np.save(os.path.join(save_dir, "model_features_groups.npy"), group_idx.astype(np.int64))
+    with open(os.path.join(save_dir, "model_features.json"), "w") as f:
+        json.dump({"kl_divergence": tsne.kl_divergence_, "n_iter": tsne.n_iter_, "learning_rate": tsne.learning_rate_,
+                   "perplexity": float(tsne.perplexity), "seed": seed, "max_items_per_class": max_items, "points": int(len(tokens)),
+                   "points_per_group": {str(key): int((group_idx == g).sum()) for g, key in enumerate(groups)}}, f, indent=2)
+    draw_embedding(embedding, group_idx, groups, os.path.join(save_dir, "model_features.pdf"))
+
+
 def run_test(model, dataloader, fn_metrics, target, feature=Feature.MELSPEC, use_voicing=False, device=None, criterion=None, *,
-             decoder=None, plot_target=None, save_dir=None, groups=PHONETIC_CLASSES):
+             decoder=None, plot_target=None, save_dir=None, groups=PHONETIC_CLASSES, model_features=None):
     """The test pass of train_phoneme_recognition.py / test_phoneme_recognition.py (reference run_test :156-329): eval-mode
     outputs, the metrics on their softmax and, with a criterion, the loss on their log-softmax.  Returns {"loss": ..., metric: ...}.
 
     With ``save_dir`` (and a ``decoder``) the counts of both matrices are accumulated on the device across the batches and
     written as the reference writes them: ``substitution_matrix.npy`` (decoded predictions against ``target``, over ``groups``,
     row-normalised) and, with a ``plot_target``, ``confusion_matrix.npy`` (the per-frame arg-max against ``plot_target``, frame by
-    frame, over ``groups``, normalize="true").  The plots are not ported."""
+    frame, over ``groups``, normalize="true").  The plots of the two matrices are not ported.
+
+    ``model_features`` (a dict; needs ``save_dir`` and ``plot_target``) asks for the reference's third product, the t-SNE map of
+    the last hidden features (:228-233, :246-261): the model is called with ``return_features=True``, the valid frames' features
+    and plot targets stay on the device, and after the loop ``feature_embedding`` (tsne.py) samples ``max_items_per_class``
+    (100) frames per token of ``groups`` with ``seed`` (0) and embeds them; a ``groups`` key of its own ({group: [tokens]}) replaces
+    ``groups`` for the map alone (a synthetic vocabulary has none of the phonetic tokens); every other key is a ``TSNE`` keyword
+    (perplexity, max_iter, ...).  Written: ``model_features_tsne.npy`` (M x 2 float32), ``model_features_tokens.npy``,
+    ``model_features_groups.npy`` (int64), ``model_features.json`` (KL divergence, iterations, learning rate, perplexity, seed,
+    points per group) and, with matplotlib, ``model_features.pdf`` and its legend.  With None nothing of this runs."""
+    if model_features is not None and (save_dir is None or plot_target is None):
+        raise ValueError("run_test: model_features needs a save_dir and a plot_target")
+    feats, feat_targets = [], []
     if device is None:
         device = torch.device("cuda")
     model.eval()
@@ -262,7 +294,15 @@ def run_test(model, dataloader, fn_metrics, target, feature=Feature.MELSPEC, use
             targets = batch[target.value].to(device)
             target_lengths = batch[f"{target.value}_length"]
             voicing = batch["voicing"].to(device) if use_voicing else None
-            outputs = model(inputs, voicing)
+            if model_features is None:
+                outputs = model(inputs, voicing)
+            else:
+                outputs, features = model(inputs, voicing, return_features=True)
+                frame_targets = batch[plot_target.value].to(device)
+                for b, (n_in, n_tgt) in enumerate(zip(input_lengths, batch[f"{plot_target.value}_length"])):
+                    n = min(int(n_in), int(n_tgt), features.shape[1], frame_targets.shape[1])   # a frame with its target
+                    feats.append(features[b, :n])
+                    feat_targets.append(frame_targets[b, :n])
             if criterion is not None:
                 losses.append(_loss(model, outputs, criterion, targets, input_lengths, target_lengths, True, True).item())
             norm_outputs = model.get_normalized_outputs(outputs)
@@ -279,6 +319,8 @@ def run_test(model, dataloader, fn_metrics, target, feature=Feature.MELSPEC, use
         np.save(os.path.join(save_dir, "substitution_matrix.npy"), normalize_counts(sub_counts.cpu().numpy(), "true"))
     if conf_counts is not None:
         np.save(os.path.join(save_dir, "confusion_matrix.npy"), _finish_confusion(conf_counts.cpu().numpy(), "true"))
+    if model_features is not None:
+        _save_model_features(torch.cat(feats), torch.cat(feat_targets), vocabulary, groups, dict(model_features), save_dir)
     info = {name: float(np.mean(v)) for name, v in metrics_values.items()}
     if criterion is not None:
         info["loss"] = float(np.mean(losses))

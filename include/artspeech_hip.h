@@ -1042,6 +1042,42 @@ int as_contour_spline(const float* contours, int64_t s_contour, int64_t s_coord,
                       int32_t K, int32_t degree, double lambda, int32_t M, const int64_t* lengths, int32_t T, int32_t A, float* out,
                       int64_t out_pitch, int32_t* status, void* stream);
 
+/* Exact t-SNE of the recogniser's features (artspeech_amd/csrc/tsne.hip).  The reference draws model_features.pdf with
+ * sklearn.manifold.TSNE(n_components=2).fit_transform (phoneme_recognition/__init__.py:355-356); the four entry points below are
+ * that routine's device work, stage by stage.  No float atomics; every sum that crosses a workgroup goes through the workspace
+ * and is added in an order that depends on N alone: equal inputs give equal bits.  One workspace of as_tsne_workspace_bytes(N)
+ * bytes (16-byte aligned; too small: AS_ERR_WORKSPACE) serves as_tsne_joint_p and as_tsne_iterate; it need not be cleared and
+ * nothing in it has to survive between calls.  2 <= N <= 16384 (two (N, N) float32 matrices of 1 GiB each at the limit); a
+ * larger N is refused with AS_ERR_BAD_ARG before anything is launched -- there is no second path.  Only the rows of one slab
+ * of Y (at most 2048 points, 16 KiB) are ever staged in LDS, so the limit is the matrices', not the LDS's.
+ *
+ * as_tsne_sqdist (:355-356; sklearn.metrics.pairwise_distances(X, metric="euclidean", squared=True) of TSNE._fit):
+ *     dist[i][j] = sum_k (x[i ldx + k] - x[j ldx + k])^2 by direct differences, one float32 chain over k = 0 .. D-1 (not the
+ *     Gram form, which cancels for near-duplicate frames).  dist is (N, N) contiguous, exactly symmetric, its diagonal exactly 0.
+ * as_tsne_joint_p (:355-356; sklearn.manifold._t_sne._joint_probabilities and _utils._binary_search_perplexity):
+ *     per row the bisection on the precision beta in float64 (beta = 1 first, at most 100 steps, |H - log perplexity| <= 1e-5,
+ *     scikit-learn's doubling / halving while an end of the interval is open), then
+ *     P = max((C + C') / max(sum(C + C'), eps), eps), eps = 2^-52, stored as (N, N) float32, exactly symmetric, diagonal 0.
+ *     dist must be symmetric (as as_tsne_sqdist writes it).  beta [N], entropy [N] (H in nats at the last step: the value of the
+ *     stopping rule) are float64, steps [N] int32 (evaluations of H, 1 .. 100).  0 < perplexity < N.
+ * as_tsne_iterate (:355-356; sklearn.manifold._t_sne._kl_divergence and _gradient_descent):
+ *     n_iters iterations of  grad_i = 4 (exaggeration sum_j p_ij num_ij (y_i - y_j) - sum_j num_ij^2 (y_i - y_j) / Z),
+ *     num_ij = 1 / (1 + |y_i - y_j|^2), Z = sum_{i != j} num_ij;  gains += 0.2 where update grad < 0, else gains *= 0.8, clipped at
+ *     min_gain;  update = momentum update - learning_rate gains grad;  Y += update -- two launches per iteration on `stream`, no host
+ *     synchronisation.  P (as as_tsne_joint_p writes it: symmetric) is read once per iteration and never rescaled.  Y, update and
+ *     gains are (N, 2) float32 and updated in place.  log is (n_iters, 3) float64: |grad|_2, |gains grad|_2 (the norm
+ *     scikit-learn's min_grad_norm test sees: it scales grad in place first) and the KL divergence
+ *     2 sum_{i<j} p_ij log(max(p_ij, eps) / max(num_ij / Z, eps)) of the UNexaggerated P at the Y the iteration started from, or
+ *     NaN: the KL is a pass of its own (two more launches) on iteration k of the call where (it0 + k + 1) % kl_every == 0
+ *     (kl_every > 0) or, with kl_last, k == n_iters - 1.  grad (N, 2), optional: the last iteration's gradient. */
+int64_t as_tsne_workspace_bytes(int32_t N);
+int as_tsne_sqdist(const float* x, int64_t ldx, int32_t N, int32_t D, float* dist, void* stream);
+int as_tsne_joint_p(const float* dist, int32_t N, double perplexity, float* P, double* beta, double* entropy, int32_t* steps,
+                    void* ws, int64_t ws_bytes, void* stream);
+int as_tsne_iterate(const float* P, float* Y, float* update, float* gains, int32_t N, int32_t n_iters, int32_t it0,
+                    int32_t kl_every, int32_t kl_last, float exaggeration, float momentum, float learning_rate, float min_gain,
+                    float* grad, double* log, void* ws, int64_t ws_bytes, void* stream);
+
 /* Optional per-kernel-phase timing with HIP events recorded on the launch stream (for bench.py's
  * roofline object).  as_profile_report writes "name count total_ms\n" lines (NUL terminated, truncated
  * to buflen) and returns the untruncated length; it waits for the recorded events to complete. */
