@@ -17,7 +17,8 @@ COMMON = ["-O3", "-fPIC", "-std=c++17", f"-I{os.path.join(ROOT, 'include')}", f"
 # function must be bit-reproducible), so no fused multiply-add contraction there; pc_eval.hip likewise (its denormalisation
 # is torch's multiply, then add); p2cp_loss.hip finds its closest points with metrics.hip's arithmetic, so it is built alike;
 # report.hip rounds x * scale before it centres it, like the reference's table in mm; contours.hip's results are selections
-# and op-by-op float32 arithmetic ((p - u) + 0.3, (x - mean) / std), bit-equal to the reference's torch expressions.
+# and op-by-op float32 arithmetic ((p - u) + 0.3, (x - mean) / std), bit-equal to the reference's torch expressions;
+# vocal_tract_tube.hip picks its junctions with metrics.hip's closest-point arithmetic and lerps as numpy does.
 SOURCES = {
     "error.cpp": [],
     "prof.hip": [],
@@ -50,6 +51,7 @@ SOURCES = {
     "resample_plan.cpp": [],
     "resample.hip": [],
     "contour_spline.hip": [],
+    "vocal_tract_tube.hip": ["-ffp-contract=off"],
     "tsne.hip": [],
     "artspeech.hip": [],
 }

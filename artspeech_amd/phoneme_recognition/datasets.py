@@ -1,11 +1,14 @@
 """Data of the phoneme recogniser (reference ``phoneme_recognition/datasets.py``, ``synthetic_shapes.py``): the collate function
 (:253-302), a seeded synthetic data set with the reference's item layout (synthetic_shapes.py:146-158), and the real-data class,
-which needs the reference's MRI data stack and raises without it.  For the speech signal: seeded synthetic waveforms, WAV
+which needs the reference's MRI data stack and raises without it, and ``ShapeTreeRecognitionDataset``, which reads the tree that
+``generate_vocal_tract_shape.py`` writes with ``air_column: true`` (the reference's synthetic_shapes.py).  For the speech signal: seeded synthetic waveforms, WAV
 recordings listed in a manifest (``read_wav``, ``RecordedAcousticRecognitionDataset``), and ``acoustic_collate_fn``, which brings
 a batch to the model's rate (:124-126) and computes its log-mel features on the device."""
 import json
+import logging
 import os
 import wave
+from glob import glob
 
 import numpy as np
 import torch
@@ -66,6 +69,71 @@ class SyntheticPhonemeRecognitionDataset(Dataset):
             "vocal_tract_length": T,
             "articulatory_target": sentence,
             "articulatory_target_length": T,
+            "voicing": voicing,
+            "ctc_target": ctc_target,
+            "ctc_target_length": len(ctc_target),
+        }
+
+
+class ShapeTreeRecognitionDataset(Dataset):
+    """The reference's ``synthetic_shapes.SyntheticPhonemeRecognitionDataset`` (that name is taken here by the seeded data set
+    above): the recogniser's data read from synthesised shapes, ``<datadir>/<subject>/<sentence>/`` with target_sequence.txt,
+    air_column/<frame>.npy and inference_contours/<frame>_<articulator>.npy -- the tree of ``generate_vocal_tract_shape.py`` with
+    ``air_column: true``, or of ``shape_to_air_column.py``.  Same constructor arguments (:39-47); the frame ids come from
+    air_column/*.npy (:58-62) and a sequence without frames is skipped with a warning (:69-71).  Items carry the reference's nine
+    keys (:146-158): ``air_column`` (2, 2 Nw, T) and ``vocal_tract`` (2, A N, T) over the sorted articulators, float32.  The
+    articulators are the reference's ten (:24-35) unless ``articulators`` names others; the point count is read from the files
+    (the reference fixes 50, :112)."""
+    ARTICULATORS = ("arytenoid-cartilage", "epiglottis", "lower-incisor", "lower-lip", "pharynx", "soft-palate-midline",
+                    "thyroid-cartilage", "tongue", "upper-lip", "vocal-folds")
+
+    def __init__(self, database_name, datadir, vocabulary, sequences, voiced_tokens=None, articulators=None, **kwargs):
+        from ..settings import DATASET_CONFIG
+        self.datadir = datadir
+        self.database_config = DATASET_CONFIG[database_name]
+        self.articulators = sorted(articulators or self.ARTICULATORS)
+        self.vocabulary = vocabulary
+        self.voiced_tokens = voiced_tokens or []
+        self.data = self._collect_data(sequences)
+
+    def __len__(self):
+        return len(self.data)
+
+    def get_frame_ids(self, subject, sentence_name):
+        filepaths = glob(os.path.join(self.datadir, subject, sentence_name, "air_column", "*.npy"))
+        return sorted(os.path.basename(f).split(".")[0] for f in filepaths)
+
+    def _collect_data(self, sequences):
+        data = []
+        for subject, sentence_name in sequences:
+            frame_ids = self.get_frame_ids(subject, sentence_name)
+            if len(frame_ids) == 0:
+                logging.warning(f"Skipping {subject}/{sentence_name} - Empty frame sequence")
+                continue
+            with open(os.path.join(self.datadir, subject, sentence_name, "target_sequence.txt")) as f:
+                phonemes = f.read().strip().split()
+            data.append({"subject": subject, "sentence_name": sentence_name, "phonemes": phonemes, "frame_ids": frame_ids})
+        return data
+
+    def __getitem__(self, index):
+        item = self.data[index]
+        sequence_dir = os.path.join(self.datadir, item["subject"], item["sentence_name"])
+        frame_ids, phonemes = item["frame_ids"], item["phonemes"]
+        sentence = torch.tensor([self.vocabulary.get(p, 0) for p in phonemes], dtype=torch.long)   # :93-96: unknown -> 0
+        air = np.stack([np.load(os.path.join(sequence_dir, "air_column", f"{f}.npy")) for f in frame_ids])   # (T, walls, 2, Nw)
+        shapes = np.stack([np.stack([np.load(os.path.join(sequence_dir, "inference_contours", f"{f}_{a}.npy"))
+                                     for a in self.articulators]) for f in frame_ids])                       # (T, A, 2, N)
+        air = torch.from_numpy(air).float().permute(2, 1, 3, 0)        # (2, walls, Nw, T), :129-131
+        shapes = torch.from_numpy(shapes).float().permute(2, 1, 3, 0)  # (2, A, N, T), :133-135
+        voicing = torch.tensor([p in self.voiced_tokens for p in phonemes], dtype=torch.float)
+        ctc_target = torch.unique_consecutive(sentence)
+        return {
+            "air_column": air.reshape(2, -1, len(frame_ids)),
+            "air_column_length": len(frame_ids),
+            "vocal_tract": shapes.reshape(2, -1, len(frame_ids)),
+            "vocal_tract_length": len(frame_ids),
+            "articulatory_target": sentence,
+            "articulatory_target_length": len(sentence),
             "voicing": voicing,
             "ctc_target": ctc_target,
             "ctc_target_length": len(ctc_target),

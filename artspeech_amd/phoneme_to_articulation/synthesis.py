@@ -7,10 +7,12 @@ by length and batched; a batch takes one forward pass of the model and one as_co
 (``regularize_contours`` with the batch's lengths).  The smoothing is this project's own definition (regularization.py): parity
 with ``vt_tools.bs_regularization.regularize_Bsplines`` is unpinned.
 
-Left out, with the reference's line numbers: the vocal-tract tube and what depends on it (``generate_vocal_tract_tube``, an external
-generator without source here, v2 :425-439: air_column/ and xarticul/ -- a user with vt_shape_gen runs scripts/shape_to_air_column.py
-on the tree), the jpg / pdf / avi rendering (:190-241) and TextGrid parsing (:124-158, ``tgt`` is absent: the ``<index>_phonemes.txt``
-files of align_phoneme_recognition.py stand in)."""
+With ``air_column`` the batch takes one more launch, as_vocal_tract_tube over its (B, T) frames (``vocal_tract_tube`` with the
+batch's lengths), and every sentence gains air_column/%04d.npy and xarticul/%04d.txt (v2 :425-439).  The tube is this project's own
+definition too (vocal_tract_tube.py): parity with ``vt_shape_gen.vocal_tract_tube.generate_vocal_tract_tube`` is unpinned.
+
+Left out, with the reference's line numbers: the jpg / pdf / avi rendering (:190-241) and TextGrid parsing (:124-158, ``tgt`` is
+absent: the ``<index>_phonemes.txt`` files of align_phoneme_recognition.py stand in)."""
 import json
 import os
 import re
@@ -18,9 +20,11 @@ import re
 import numpy as np
 import torch
 
+from ..helpers import npy_to_xarticul
 from ..settings import UNKNOWN
 from .regularization import STATUS_NON_FINITE, STATUS_ZERO_LENGTH, regularize_contours
 from .tail_clipper import UPPER_INCISOR
+from .vocal_tract_tube import vocal_tract_tube
 
 METHODS = ("encoder_decoder", "mean_contour", "autoencoder")
 
@@ -153,13 +157,48 @@ def synthesize_batch(model, token_rows, regularize_outputs=True, degree=3, n_ctr
     return contours, status, lengths
 
 
-def save_sentence(save_dir, tokens, contours, articulators, upper_incisor=None, save_frames=True):
+def tube_channels(contours, articulators, upper_incisor=None):
+    """The contours (..., A, 2, n) and channel names that the tube is built from: the configured upper incisor joined as one more
+    channel when the articulators lack one (v2 :244-267 saves it beside every frame for the same reason)."""
+    articulators = list(articulators)
+    if upper_incisor is None or UPPER_INCISOR in articulators:
+        return contours, articulators
+    incisor = torch.as_tensor(np.asarray(upper_incisor, dtype=np.float32))
+    if incisor.shape != (2, contours.shape[-1]):
+        raise ValueError(f"the upper incisor has {tuple(incisor.shape)} coordinates, the contours {contours.shape[-1]} points each: "
+                         "give it the contours' point count (n_out)")
+    incisor = incisor.to(contours.device).expand(contours.shape[:-3] + (1, 2, contours.shape[-1]))
+    return torch.cat([contours.float(), incisor], dim=-3), articulators + [UPPER_INCISOR]
+
+
+def save_air_columns(save_dir, air_columns, res=1.0):
+    """air_columns (T, 2, 2, n_wall) float64 -> air_column/%04d.npy in ``save_air_column``'s layout and xarticul/%04d.txt,
+    ``npy_to_xarticul(internal * res) + npy_to_xarticul(external * res)`` (v2 :425-439), numbered from 1."""
+    air_dir, xarticul_dir = os.path.join(save_dir, "air_column"), os.path.join(save_dir, "xarticul")
+    os.makedirs(air_dir, exist_ok=True)
+    os.makedirs(xarticul_dir, exist_ok=True)
+    for i_frame, air in enumerate(np.asarray(air_columns, dtype=np.float64), start=1):
+        np.save(os.path.join(air_dir, f"{'%04d' % i_frame}.npy"), air)
+        lines = npy_to_xarticul(air[0].T * res) + npy_to_xarticul(air[1].T * res)
+        with open(os.path.join(xarticul_dir, f"{'%04d' % i_frame}.txt"), "w") as f:
+            f.write("\n".join(lines))
+
+
+def save_sentence(save_dir, tokens, contours, articulators, upper_incisor=None, save_frames=True, air_column=False, n_wall=100,
+                  res=1.0):
     """One sentence's files (v2 :244-267, :391-392): target_sequence.txt, contours.npy (T, A, 2, n) and, with ``save_frames``,
-    inference_contours/%04d_<articulator>.npy numbered from 1, plus the upper incisor's when given and not an articulator."""
+    inference_contours/%04d_<articulator>.npy numbered from 1, plus the upper incisor's when given and not an articulator.
+    ``air_column``: False writes nothing more; a (T, 2, 2, n_wall) array (the caller's batched launch) is written as
+    air_column/ and xarticul/ (``save_air_columns``); True builds the walls of ``n_wall`` points here, one launch for the sentence."""
     os.makedirs(save_dir, exist_ok=True)
     with open(os.path.join(save_dir, "target_sequence.txt"), "w") as f:
         f.write(" ".join(tokens))
     np.save(os.path.join(save_dir, "contours.npy"), contours)
+    if air_column is True:
+        x, names = tube_channels(torch.as_tensor(np.asarray(contours, dtype=np.float32)).cuda(), articulators, upper_incisor)
+        air_column = vocal_tract_tube(x, names, n_out=n_wall).cpu().numpy()
+    if air_column is not False and air_column is not None:
+        save_air_columns(save_dir, air_column, res)
     if not save_frames:
         return
     frames_dir = os.path.join(save_dir, "inference_contours")
@@ -172,14 +211,22 @@ def save_sentence(save_dir, tokens, contours, articulators, upper_incisor=None, 
 
 
 def synthesize(model, sentences, vocabulary, articulators, save_to, batch_size=32, regularize_outputs=True, degree=3, n_ctrl=12,
-               smoothing=1e-3, n_out=None, upper_incisor=None, save_frames=True):
+               smoothing=1e-3, n_out=None, upper_incisor=None, save_frames=True, air_column=False, n_wall=100, res=1.0):
     """Every sentence of ``sentences`` [(name, phonemes)] through ``model`` and the smoothing, written under ``save_to/<name>/``;
-    returns the summary that main() writes to synthesis.json."""
+    returns the summary that main() writes to synthesis.json.  ``air_column``: one vocal_tract_tube launch per batch after the
+    smoothing, walls of ``n_wall`` points, air_column/ and xarticul/ (scaled by ``res``, the data set's image resolution) beside
+    the contours, and the count of flagged walls in the summary."""
     flagged = {"zero_length": 0, "non_finite": 0}
+    flagged_walls = {"zero_length": 0, "non_finite": 0}
     report = []
     for batch in make_batches(sentences, batch_size):
         rows = [numerize(sentences[i][1], vocabulary) for i in batch]
         contours, status, lengths = synthesize_batch(model, rows, regularize_outputs, degree, n_ctrl, smoothing, n_out)
+        air = wall_status = None
+        if air_column:
+            x, names = tube_channels(contours, articulators, upper_incisor)
+            air, wall_status = vocal_tract_tube(x, names, n_out=n_wall, lengths=lengths, return_status=True)
+            air, wall_status = air.cpu().numpy(), wall_status.cpu().numpy()
         contours = contours.cpu().numpy()   # one copy per batch
         status = status.cpu().numpy() if status is not None else None
         for b, i in enumerate(batch):
@@ -191,11 +238,19 @@ def synthesize(model, sentences, vocabulary, articulators, save_to, batch_size=3
                 entry["zero_length"], entry["non_finite"] = int((s & STATUS_ZERO_LENGTH != 0).sum()), int((s & STATUS_NON_FINITE != 0).sum())
                 flagged["zero_length"] += entry["zero_length"]
                 flagged["non_finite"] += entry["non_finite"]
-            save_sentence(os.path.join(save_to, name), tokens, contours[b, :length], articulators, upper_incisor, save_frames)
+            if wall_status is not None:
+                s = wall_status[b, :length]
+                flagged_walls["zero_length"] += int((s & STATUS_ZERO_LENGTH != 0).sum())
+                flagged_walls["non_finite"] += int((s & STATUS_NON_FINITE != 0).sum())
+            save_sentence(os.path.join(save_to, name), tokens, contours[b, :length], articulators, upper_incisor, save_frames,
+                          air[b, :length] if air is not None else False, n_wall, res)
             report.append(entry)
     position = {name: i for i, (name, _) in enumerate(sentences)}
     report.sort(key=lambda e: position[e["name"]])
-    return {"sentences": report, "frames": sum(e["frames"] for e in report), "flagged_contours": flagged if regularize_outputs else None}
+    info = {"sentences": report, "frames": sum(e["frames"] for e in report), "flagged_contours": flagged if regularize_outputs else None}
+    if air_column:
+        info["flagged_walls"] = flagged_walls
+    return info
 
 
 def write_summary(save_to, info):

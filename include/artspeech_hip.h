@@ -1042,6 +1042,36 @@ int as_contour_spline(const float* contours, int64_t s_contour, int64_t s_coord,
                       int32_t K, int32_t degree, double lambda, int32_t M, const int64_t* lengths, int32_t T, int32_t A, float* out,
                       int64_t out_pitch, int32_t* status, void* stream);
 
+/* The vocal-tract tube (artspeech_amd/csrc/vocal_tract_tube.hip): the internal and the external wall of every frame, from the
+ * frame's articulator contours, in one launch.  The reference calls vt_shape_gen.vocal_tract_tube.generate_vocal_tract_tube at
+ * generate_vocal_tract_shape_v2.py:426, generate_vocal_tract_shape.py:34 and scripts/shape_to_air_column.py:77.  vt_shape_gen is
+ * neither vendored nor pinned: the definition is THIS PROJECT'S OWN, stated in full at the top of the .hip file, an
+ * ASSUMPTION whose parity with vt_shape_gen is unpinned.  In short, per wall and its chain of K contours of N points:
+ *   junctions   (i_k, j_k) = the first minimum in row-major order of |c_k[i] - c_{k+1}[j]|^2, float32, dx*dx + dy*dy uncontracted
+ *   runs        contour k from its entry (the junction with k-1) to its exit (the junction with k+1); the first and the last
+ *               contour start / end at the end that leaves them more points; K = 1: the whole contour
+ *   resampling  float64: M points at equal arc-length steps along the concatenated runs, the two ends copied
+ *   contours            coordinate xy of point i of articulator a of frame f at contours[f s_frame + a s_art + xy s_coord +
+ *                       i s_point] (element strides): (B, T, A, 2, N) model outputs and (F, A, N, 2) raw contours go in as they lie
+ *   chains [2][8] int32 ON THE HOST (read before the launch and handed to the kernel by value, so that an index outside [0, A)
+ *                       is refused here): row 0 the internal wall's articulator indices, row 1 the external wall's, k_int and
+ *                       k_ext of them used; the unused ones are not looked at (-1 by convention)
+ *   lengths [B] int64   optional, on the device, with T and frames = B T (frame f = b T + t): a frame t >= lengths[b] gets zeros
+ *                       in air, status 0, junctions -1 and length 0, and is not read
+ *   air                 coordinate xy of point m of wall w (0 internal, 1 external) of frame f at air[((2 f + w) 2 + xy) ld_out
+ *                       + m]: the air-column file layout; the M outputs of every row are written and nothing behind them
+ *   status [frames][2]  optional int32: bit 0 = zero length (every output is the first point), bit 1 = a non-finite coordinate
+ *                       in a chain contour (this wall's outputs and length are NaN, its junctions -1)
+ *   junctions [frames][2][7][2] optional int32: (i_k, j_k), the unused ones -1
+ *   wall_length [frames][2]     optional float64: L
+ * No atomics, every sum in a fixed order: two launches give equal bits, a frame alone or in a batch gives equal bits.  Limits,
+ * refused with AS_ERR_BAD_ARG before any launch (never truncated): 2 <= N <= 128, 1 <= k_int, k_ext <= 8, 2 <= M <= 1024,
+ * ld_out >= M, every used chain index in [0, A). */
+int as_vocal_tract_tube(const float* contours, int64_t s_frame, int64_t s_art, int64_t s_coord, int64_t s_point, int64_t frames,
+                        int32_t A, int32_t N, const int32_t* chains, int32_t k_int, int32_t k_ext, const int64_t* lengths, int32_t T,
+                        int32_t M, double* air, int64_t ld_out, int32_t* status, int32_t* junctions, double* wall_length,
+                        void* stream);
+
 /* Exact t-SNE of the recogniser's features (artspeech_amd/csrc/tsne.hip).  The reference draws model_features.pdf with
  * sklearn.manifold.TSNE(n_components=2).fit_transform (phoneme_recognition/__init__.py:355-356); the four entry points below are
  * that routine's device work, stage by stage.  No float atomics; every sum that crosses a workgroup goes through the workspace

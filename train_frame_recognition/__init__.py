@@ -42,7 +42,7 @@ from train_phoneme_recognition import VOICING_WITH_MELSPEC, _make_dataset, build
 def main(database_name, datadir, num_epochs, batch_size, patience, learning_rate, weight_decay, feature, target, vocab_filepath,
          train_seq_dict, valid_seq_dict, test_seq_dict, model_params, loss, plot_target=None, loss_params=None, num_workers=0,
          logits_large_margins=0.0, pretrained=False, voicing_filepath=None, state_dict_filepath=None, checkpoint_filepath=None,
-         seed=0, synthetic=None, results_dir=None, melspec=None):
+         seed=0, synthetic=None, results_dir=None, dataset=None, melspec=None):
     if loss != "CE":
         raise NotImplementedError(f"train_frame_recognition: loss {loss!r} is not this script's; it trains the frame classifier "
                                   f"(loss: CE) -- CTC is trained by train_phoneme_recognition.py")
@@ -76,7 +76,7 @@ def main(database_name, datadir, num_epochs, batch_size, patience, learning_rate
     gen.manual_seed(seed)
 
     def loader(seq_dict, ds_seed):
-        ds = _make_dataset(datadir, database_name, seq_dict, vocabulary, feature, voiced_tokens, synthetic, ds_seed, melspec)
+        ds = _make_dataset(datadir, database_name, seq_dict, vocabulary, feature, voiced_tokens, synthetic, ds_seed, melspec, dataset)
         return DataLoader(ds, batch_size=batch_size, shuffle=True, num_workers=num_workers, worker_init_fn=set_seeds,
                           collate_fn=make_collate_fn(datadir, feature, num_workers, ds), generator=gen)
 

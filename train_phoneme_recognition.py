@@ -6,7 +6,9 @@
 #          --run_id ID --run_name NAME --checkpoint checkpoint.pt]
 # The YAML keys are the keyword arguments of main() (the reference's), plus the extras `datadir: synthetic`
 # (SyntheticPhonemeRecognitionDataset, sized by `synthetic:` and the sequence dicts' `num_sentences`) and
-# `results_dir`.  With `feature: melspec` the synthetic data set is SyntheticAcousticRecognitionDataset
+# `results_dir`; `dataset: shape_tree` reads datadir as a tree of synthesised shapes (ShapeTreeRecognitionDataset, the
+# reference's phoneme_recognition/synthetic_shapes.py; test_phoneme_recognition.py, whose main() has no such keyword, takes
+# `synthetic: {dataset: shape_tree}`).  With `feature: melspec` the synthetic data set is SyntheticAcousticRecognitionDataset
 # (waveforms) and a batch's log-mel features are computed on the device while collating
 # (datasets.acoustic_collate_fn); `melspec:` holds the MelSpectrogram keywords (default
 # the reference's: 16 kHz, n_fft 1024, win_length 1024, hop_length 256, 80 mels; `synthetic: {melspec: ...}`
@@ -33,8 +35,8 @@ from artspeech_amd.helpers import sequences_from_dict, set_seeds
 from artspeech_amd.phoneme_recognition import (BLANK, SIL, UNKNOWN, Criterion, Feature, Target, TrainableDeepSpeech2, run_epoch,
                                                run_test)
 from artspeech_amd.phoneme_recognition.datasets import (PhonemeRecognitionDataset, RecordedAcousticRecognitionDataset,
-                                                        SyntheticAcousticRecognitionDataset, SyntheticPhonemeRecognitionDataset,
-                                                        acoustic_collate_fn, collate_fn)
+                                                        ShapeTreeRecognitionDataset, SyntheticAcousticRecognitionDataset,
+                                                        SyntheticPhonemeRecognitionDataset, acoustic_collate_fn, collate_fn)
 from artspeech_amd.phoneme_recognition.features import MelSpectrogram
 from artspeech_amd.phoneme_recognition.decoders import GreedyCTCDecoder
 from artspeech_amd.phoneme_recognition.metrics import EditDistance
@@ -52,13 +54,26 @@ MELSPEC_DEFAULTS = dict(sample_rate=16000, n_fft=1024, win_length=1024, hop_leng
 VOICING_WITH_MELSPEC = "feature: melspec takes no voicing_filepath: voicing is per articulatory frame, not per spectrogram frame"
 
 
-def _make_dataset(datadir, database_name, seq_dict, vocabulary, feature, voiced_tokens, synthetic, seed, melspec=None):
+def _make_dataset(datadir, database_name, seq_dict, vocabulary, feature, voiced_tokens, synthetic, seed, melspec=None, dataset=None):
     """The split's data set.  With datadir: synthetic and feature: melspec it is the waveform data set, carrying the MelSpectrogram
     that collate_fn launches on its batches: MELSPEC_DEFAULTS, overridden by `synthetic: {melspec: {...}}` (the way
     test_phoneme_recognition.py passes it, whose main() has no melspec keyword), then by `melspec`.  `synthetic: {orig_sample_rate:
     44100}` generates the waveforms at that rate, and `datadir: recordings` reads the WAV files of the sequence dict's `manifest:`
     (RecordedAcousticRecognitionDataset; `synthetic:` then holds its keywords and `melspec`): either way the collate function
-    resamples a batch to the transform's rate on the device before the log-mel launch."""
+    resamples a batch to the transform's rate on the device before the log-mel launch.  `dataset: shape_tree` reads datadir as a
+    tree of synthesised shapes (ShapeTreeRecognitionDataset: the output of generate_vocal_tract_shape.py with air_column: true);
+    `synthetic: {dataset: shape_tree}` says the same, for test_phoneme_recognition.py and the scripts whose main() follows its
+    keywords (decode_, embed_), which have no dataset keyword -- the way they pass `melspec`."""
+    options = dict(synthetic or {})
+    nested = options.pop("dataset", None)
+    if dataset is not None and nested is not None and nested != dataset:
+        raise ValueError(f"dataset: {dataset!r} and synthetic: {{dataset: {nested!r}}} disagree")
+    dataset = nested if dataset is None else dataset
+    if dataset == "shape_tree":
+        return ShapeTreeRecognitionDataset(database_name, datadir, vocabulary, sequences_from_dict(datadir, seq_dict), voiced_tokens,
+                                           **options)
+    if dataset is not None:
+        raise ValueError(f"dataset: {dataset!r} (shape_tree, or leave it out)")
     if datadir == "synthetic":
         n, cfg = synthetic_size(seq_dict, synthetic, "num_sentences", 32)
         mel_kw = {**MELSPEC_DEFAULTS, **(cfg.pop("melspec", None) or {}), **(melspec or {})}
@@ -96,7 +111,7 @@ def make_collate_fn(datadir, feature, num_workers, dataset=None):
 def main(database_name, datadir, num_epochs, batch_size, patience, learning_rate, weight_decay, feature, target, vocab_filepath,
          train_seq_dict, valid_seq_dict, test_seq_dict, model_params, loss, plot_target=None, loss_params=None, num_workers=0,
          logits_large_margins=0.0, pretrained=False, voicing_filepath=None, state_dict_filepath=None, checkpoint_filepath=None,
-         seed=0, synthetic=None, results_dir=None, melspec=None):
+         seed=0, synthetic=None, results_dir=None, dataset=None, melspec=None):
     criterion = Criterion[loss]
     if criterion != Criterion.CTC:
         raise NotImplementedError(f"train_phoneme_recognition: loss {loss!r} is not supported; only CTC is ported")
@@ -127,7 +142,7 @@ def main(database_name, datadir, num_epochs, batch_size, patience, learning_rate
     gen.manual_seed(seed)
 
     def loader(seq_dict, ds_seed):
-        ds = _make_dataset(datadir, database_name, seq_dict, vocabulary, feature, voiced_tokens, synthetic, ds_seed, melspec)
+        ds = _make_dataset(datadir, database_name, seq_dict, vocabulary, feature, voiced_tokens, synthetic, ds_seed, melspec, dataset)
         return DataLoader(ds, batch_size=batch_size, shuffle=True, num_workers=num_workers, worker_init_fn=set_seeds,
                           collate_fn=make_collate_fn(datadir, feature, num_workers, ds), generator=gen)
 
