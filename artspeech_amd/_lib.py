@@ -125,7 +125,6 @@ PROTOTYPES = {
     "as_attention_fwd_causal": (_I32, [_P, _P, _P, _P, _P, _P, _P, _P, _I32, _I32, _I32, _I32, _I32, _I32, _F, _S]),
     "as_attention_bwd_ds": (_I32, [_P, _P, _P, _P, _P, _I32, _I32, _I32, _I32, _I32, _I32, _F, _S]),
     "as_attention_bwd_ds_causal": (_I32, [_P, _P, _P, _P, _P, _I32, _I32, _I32, _I32, _I32, _I32, _F, _S]),
-    "as_attn_softmax_bwd_t": (_I32, [_P, _P, _P, _P, _P, _I32, _I32, _I32, _I32, _I32, _I32, _F, _S]),
     "as_group_reduce": (_I32, [_P, _P, _I32, _I32, _I64, _P, _S]),
     "as_layernorm_bwd": (_I32, [_P, _P, _P, _P, _P, _I64, _I32, _S]),
     "as_unfold_ln": (_I32, [_P, _P, _P, _P, _P, _P, _P, _P, _I32, _I32, _I32, _S]),

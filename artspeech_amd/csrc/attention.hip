@@ -532,77 +532,6 @@ int launch_attn_ds_causal(const AttnDsK& k, long Z, hipStream_t st) {
     return 0;
 }
 
-// softmax backward on key-major tensors, two launches:
-//  (1) D[z][q] = sum_c dctx[q][c] ctx[q][c] over the head's columns: a quarter-wave per query row (16 lanes x float4 = 64
-//      floats), consecutive quarter-waves on consecutive heads of the same row -> a wave reads one contiguous 1 KB row;
-//  (2) the [Z][Tk][T] tensors are walked as ONE flat array in float4s (z, q from the index): full aligned 16-byte
-//      accesses per lane whatever T is, no per-slice barrier.  (A thread per query walking 800-byte rows measured 2.07 ms,
-//      one workgroup per slice with D in LDS 2.25 ms, against 1.3 ms for the row-major kernel this replaces.)
-__global__ __launch_bounds__(256) void attn_dsum_kernel(const float* __restrict__ ctx, const float* __restrict__ dctx, long rows,
-                                                        int heads, int T, int B, int d, float* __restrict__ D) {
-    // item = (row r = (g*B + b)*T + q, head h); D index = ((g*B + b)*heads + h)*T + q
-    const int dh = d / heads;
-    const int per = dh / 4;                      // lanes per item (float4 each): 4, 8 or 16
-    const long gt = (long)blockIdx.x * 256 + threadIdx.x;
-    const long item = gt / per;
-    const int part = (int)(gt - item * per);
-    const bool ok = item < rows * heads;
-    const long r = ok ? item / heads : 0;
-    const int h = ok ? (int)(item - r * heads) : 0;
-    const float4 a = *reinterpret_cast<const float4*>(ctx + r * d + (long)h * dh + part * 4);
-    const float4 g = *reinterpret_cast<const float4*>(dctx + r * d + (long)h * dh + part * 4);
-    float s = a.x * g.x + a.y * g.y + a.z * g.z + a.w * g.w;
-    for (int o = per / 2; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
-    if (ok && part == 0) {
-        const long gb = r / T;
-        const int q = (int)(r - gb * T);
-        D[(gb * heads + h) * T + q] = s;
-    }
-}
-
-__global__ __launch_bounds__(256) void attn_softmax_bwd_t_kernel(const float* __restrict__ pt, float* __restrict__ dpt,
-                                                                 const float* __restrict__ D, long total4, int T, int Tp, long plane,
-                                                                 float scale) {
-    const long stride = (long)gridDim.x * 256;
-    for (long i0 = (long)blockIdx.x * 256 + threadIdx.x; i0 < total4; i0 += 4 * stride) {  // four float4 pairs in flight
-        float4 pv[4], dv[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            const long i = i0 + u * stride < total4 ? i0 + u * stride : total4 - 1;
-            pv[u] = reinterpret_cast<const float4*>(pt)[i];
-            dv[u] = reinterpret_cast<const float4*>(dpt)[i];
-        }
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            const long i = i0 + u * stride;
-            if (i < total4) {
-                const long e = 4 * i;                     // T % 4 == 0: the float4 is q .. q + 3 of one key row (row pitch Tp)
-                const long z = e / plane;
-                const int q = (int)((e - z * plane) % Tp);
-                if (q >= T) continue;                     // the row's padding up to the pitch
-                const float4 dq = *reinterpret_cast<const float4*>(D + z * T + q);
-                float4 r;
-                r.x = pv[u].x * (dv[u].x - dq.x) * scale;
-                r.y = pv[u].y * (dv[u].y - dq.y) * scale;
-                r.z = pv[u].z * (dv[u].z - dq.z) * scale;
-                r.w = pv[u].w * (dv[u].w - dq.w) * scale;
-                reinterpret_cast<float4*>(dpt)[i] = r;
-            }
-        }
-    }
-}
-
-__global__ __launch_bounds__(256) void attn_softmax_bwd_t_scalar_kernel(const float* __restrict__ pt, float* __restrict__ dpt,
-                                                                        const float* __restrict__ D, long total, int T, int Tp, long plane,
-                                                                        float scale) {
-    const long stride = (long)gridDim.x * 256;
-    for (long e = (long)blockIdx.x * 256 + threadIdx.x; e < total; e += stride) {
-        const long z = e / plane;
-        const int q = (int)((e - z * plane) % Tp);
-        if (q < T) dpt[e] = pt[e] * (dpt[e] - D[z * T + q]) * scale;
-    }
-}
-
 template <int DH, int NB>
 int launch_attn(const AttnK& k, long Z, hipStream_t st) {
     constexpr size_t shm = (size_t)(2 * 32 * NB * (DH + 4) + 32 * NB) * sizeof(float);
@@ -663,34 +592,6 @@ extern "C" int as_attention_fwd_causal(const float* Q, const float* K, const flo
                                        const float* key_padding_mask, float* out, float* lse, float* probs_t, int32_t G, int32_t B,
                                        int32_t heads, int32_t T, int32_t Tk, int32_t d, float scale, void* stream) {
     return attention_fwd(Q, K, V, attn_mask_t, key_padding_mask, out, lse, probs_t, G, B, heads, T, Tk, d, scale, 1, stream);
-}
-
-extern "C" int as_attn_softmax_bwd_t(const float* probs_t, float* dprobs_t, const float* ctx, const float* dctx, float* dsum, int32_t G,
-                                     int32_t B, int32_t heads, int32_t T, int32_t Tk, int32_t d, float scale, void* stream) {
-    AS_REQUIRE(probs_t && dprobs_t && ctx && dctx && dsum && G > 0 && B > 0 && heads > 0 && T > 0 && Tk > 0 && d > 0 && d % heads == 0,
-               AS_ERR_BAD_ARG, "as_attn_softmax_bwd_t: bad argument");
-    const int dh = d / heads;
-    AS_REQUIRE(dh == 16 || dh == 32 || dh == 64, AS_ERR_UNSUPPORTED, "as_attn_softmax_bwd_t: head width %d not in {16, 32, 64}", dh);
-    AS_REQUIRE(as_aligned16(ctx) && as_aligned16(dctx), AS_ERR_BAD_ARG, "as_attn_softmax_bwd_t: ctx / dctx must be 16-byte aligned");
-    hipStream_t st = (hipStream_t)stream;
-    const long rows = (long)G * B * T, Z = (long)G * B * heads;
-    const long lanes = rows * heads * (dh / 4);
-    hipLaunchKernelGGL(attn_dsum_kernel, dim3((unsigned)as_cdiv(lanes, 256)), dim3(256), 0, st, ctx, dctx, rows, heads, T, B, d, dsum);
-    AS_LAUNCH_CHECK("as_attn_softmax_bwd_t(dsum)");
-    const int Tp = (T + 31) / 32 * 32;   // row pitch of the key-major tensors (as_attention_fwd)
-    const long plane = (long)Tk * Tp, total = Z * plane;
-    const bool vec = T % 4 == 0 && as_aligned16(probs_t) && as_aligned16(dprobs_t) && as_aligned16(dsum);
-    if (vec) {
-        long blocks = as_cdiv(total / 4, 4 * 256);
-        if (blocks > 16384) blocks = 16384;
-        hipLaunchKernelGGL(attn_softmax_bwd_t_kernel, dim3((unsigned)blocks), dim3(256), 0, st, probs_t, dprobs_t, dsum, total / 4, T, Tp, plane, scale);
-    } else {
-        long blocks = as_cdiv(total, 256);
-        if (blocks > 16384) blocks = 16384;
-        hipLaunchKernelGGL(attn_softmax_bwd_t_scalar_kernel, dim3((unsigned)blocks), dim3(256), 0, st, probs_t, dprobs_t, dsum, total, T, Tp, plane, scale);
-    }
-    AS_LAUNCH_CHECK("as_attn_softmax_bwd_t");
-    return 0;
 }
 
 static int attention_bwd_ds(const float* V, const float* dctx, const float* ctx, const float* probs_t, float* ds_t, int32_t G,

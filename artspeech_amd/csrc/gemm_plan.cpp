@@ -4,8 +4,7 @@
 //   1. weight-gradient shapes (both operands reduction-strided, no k_tri): gemm_s6.hip with precision == 3 and >= 256 tiles,
 //      else wgrad_f32.hip (whole tiles or stream-K) where its contract holds;
 //   2. forward and input-gradient shapes with precision == 3: gemm_s6.hip where its contract holds;
-//   3. precision 1 / 2 on float4-clean forward shapes: the on-the-fly split kernel;
-//   4. everything else: the general kernel on 128 x 128 tiles once they fill the chip, else on 64 x 64 tiles, either with its
+//   3. everything else: the general kernel on 128 x 128 tiles once they fill the chip, else on 64 x 64 tiles, either with its
 //      split-K rule.
 #define AS_HOST_ONLY
 #include "gemm_plan.h"
@@ -143,21 +142,21 @@ int as_gemm_plan_make(const as_gemm* g, const as_gemm_env* env, as_gemm_plan* p,
     PLAN_REQUIRE((g->b_j == 1) != (g->b_k == 1) || (g->b_j == 1 && g->b_k == 1 && (g->N == 1 || g->K == 1)),
                  AS_ERR_BAD_ARG, "as_gemm_f32: exactly one of b_j/b_k must be 1 (b_j=%ld b_k=%ld)", (long)g->b_j, (long)g->b_k);
     PLAN_REQUIRE(g->act >= 0 && g->act <= 3, AS_ERR_BAD_ARG, "as_gemm_f32: act=%d", g->act);
-    PLAN_REQUIRE(g->precision >= 0 && g->precision <= 3, AS_ERR_BAD_ARG, "as_gemm_f32: precision=%d", g->precision);
-    const int prec = g->precision == 3 ? 0 : g->precision;   // 3 = "the library's matrix arithmetic, at any size" (below)
+    // 3 = "the library's matrix arithmetic, at any size" (below)
+    PLAN_REQUIRE(g->precision == 0 || g->precision == 3, AS_ERR_BAD_ARG, "as_gemm_f32: precision=%d (accepted: 0 and 3)", g->precision);
     // (M == 1 with both strides of A equal to 1 reads the same either way: output-contiguous then, the form the column sums take)
     const bool a_kc = g->a_k == 1 && !(g->a_i == 1 && g->colsum), b_kc = g->b_k == 1;
     PLAN_REQUIRE(!(g->b_kT > 0 && b_kc), AS_ERR_BAD_ARG, "as_gemm_f32: b_kshift needs a reduction-strided B operand");
     const long a_ld = a_kc ? g->a_i : g->a_k, b_ld = b_kc ? g->b_j : g->b_k;
     PLAN_REQUIRE(g->k_tri >= 0 && g->k_tri <= 2, AS_ERR_BAD_ARG, "as_gemm_f32: k_tri=%d", g->k_tri);
-    PLAN_REQUIRE(g->k_tri == 0 || (!g->colsum && !g->splitk_ws && prec == 0 && g->k_seg == 0 && !g->accumulate && g->act <= 1 &&
+    PLAN_REQUIRE(g->k_tri == 0 || (!g->colsum && !g->splitk_ws && g->k_seg == 0 && !g->accumulate && g->act <= 1 &&
                                    !g->bias_off && (long)g->M * g->ldc < (1L << 31)),
-                 AS_ERR_BAD_ARG, "as_gemm_f32: k_tri goes with the extended general kernel only (no colsum, splitk_ws, split precision, "
-                 "k_seg, accumulate, act > 1)");
+                 AS_ERR_BAD_ARG, "as_gemm_f32: k_tri goes with the extended general kernel only (no colsum, splitk_ws, k_seg, accumulate, "
+                 "act > 1)");
     const bool epi_ops = g->res || g->mask_bits || g->relu_bits, segmented = g->k_seg > 0;
-    PLAN_REQUIRE(!(epi_ops || segmented) || (!g->colsum && !g->splitk_ws && !g->accumulate && prec == 0 && (a_kc || b_kc)),
+    PLAN_REQUIRE(!(epi_ops || segmented) || (!g->colsum && !g->splitk_ws && !g->accumulate && (a_kc || b_kc)),
                  AS_ERR_BAD_ARG, "as_gemm_f32: res / mask_bits / relu_bits / k_seg go with the general kernel only (no colsum, splitk_ws, "
-                 "accumulate, split precision or weight-gradient shape)");
+                 "accumulate or weight-gradient shape)");
     PLAN_REQUIRE(!g->relu_bits || g->act == 1, AS_ERR_BAD_ARG, "as_gemm_f32: relu_bits is the bit image of a ReLU epilogue (act == 1)");
     PLAN_REQUIRE(!(epi_ops || segmented) || (a_kc && as_aligned16(g->A) && as_aligned16(g->B) && a_ld % 4 == 0 && b_ld % 4 == 0 && g->K % 4 == 0 &&
                                              (b_kc || g->N % 4 == 0) && g->act <= 1 && (g->a_off || segmented || g->a_batch % 4 == 0) &&
@@ -193,14 +192,6 @@ int as_gemm_plan_make(const as_gemm* g, const as_gemm_env* env, as_gemm_plan* p,
     // alignment of table offsets is the caller's contract (multiples of 4 floats) -- see header
     p->a_vec = as_aligned16(g->A) && a_ld % 4 == 0 && (grouped || segmented || g->a_batch % 4 == 0);
     p->b_vec = as_aligned16(g->B) && b_ld % 4 == 0 && (grouped || segmented || g->b_batch % 4 == 0);
-    // split-precision request (forward linears only): both operands reduction-contiguous and float4-clean, else exact fp32
-    if (prec != 0 && a_kc && b_kc && p->a_vec && p->b_vec && g->K % 4 == 0 && !g->colsum) {
-        p->family = AS_GEMM_SPLIT;
-        p->planes = prec == 2 ? 3 : 2;
-        p->tile_m = p->tile_n = 128;
-        p->work = (long)as_cdiv(g->M, 128) * as_cdiv(g->N, 128) * g->batch;
-        return 0;
-    }
     p->family = AS_GEMM_GENERAL;
     // FAST needs whole float4s: aligned operands and contiguous extents that are multiples of 4
     p->fast = p->a_vec && p->b_vec && (a_kc ? g->K % 4 == 0 : g->M % 4 == 0) && (b_kc ? g->K % 4 == 0 : g->N % 4 == 0);

@@ -32,7 +32,6 @@ struct as_gemm_env {
 
 enum as_gemm_family {
     AS_GEMM_GENERAL,         // gemm_f32.hip: gemm_f32_kernel<tile, tile, a_kc, b_kc, fast | ext>
-    AS_GEMM_SPLIT,           // gemm_f32.hip: gemm_split_nt_kernel<128, 128, planes> (as_gemm.precision 1 / 2)
     AS_GEMM_S6,              // gemm_s6.hip:  gemm_s6_kernel<anc, bnc, ext>
     AS_GEMM_WGRAD,           // wgrad_f32.hip: wgrad_f32_kernel<tile_n, false, split_arith>, whole tiles per workgroup
     AS_GEMM_WGRAD_STREAMK,   // wgrad_f32.hip: wgrad_f32_kernel<tile_n, true, split_arith>
@@ -50,8 +49,7 @@ enum as_gemm_reduce {
 struct as_gemm_plan {
     int family;
     int tile_m, tile_n;          // output tile of a workgroup
-    int planes;                  // AS_GEMM_SPLIT: bf16 pieces per element (2 or 3)
-    bool a_kc, b_kc;             // general / split kernel: the operand is reduction-contiguous
+    bool a_kc, b_kc;             // general kernel: the operand is reduction-contiguous
     bool anc, bnc;               // gemm_s6: the operand is row-contiguous (X[k][row])
     bool fast, ext;              // general kernel: whole-float4 loads; the instantiation with res / mask_bits / relu_bits / k_seg / k_tri
     bool split_arith;            // the products run on the bf16 matrix instruction in the library's split arithmetic

@@ -432,7 +432,7 @@ __global__ __launch_bounds__(NT, 4) void lin_f32_kernel(LinK g) {
 // sum of nine plane products with exact operands; the three smallest (lo.lo, lo.mid, mid.lo, each <= 2^-24 |a||b|) are
 // dropped: six MFMAs per 16-deep k-step.  Against an fp64 product of the same fp32 operands this is MORE accurate than the
 // fp32 matrix instruction (rms 2.4e-7 vs 2.9e-7 of rms C: the bf16 instruction adds 16 products before it rounds, the fp32
-// one two; tools/bench_split_gemm.py, tests/test_gpu_parity.py::test_split_matrix_arithmetic_*).
+// one two; profiles/r03_split_gemm_probe.log, tests/test_gpu_parity.py::test_split_matrix_arithmetic_*).
 //   * B (the folded weights) arrives as planes, emitted once per step by as_emit_planes (rowops.hip) k-step-major:
 //     [plane][head][K / 16][rows][16] bf16, so that the fragment of a wave (32 columns x 8 k x 2 lane halves) is 1 KiB of
 //     consecutive bytes.  A wave's columns are its own: B fragments go from L2 straight to registers (global_load_dwordx4,

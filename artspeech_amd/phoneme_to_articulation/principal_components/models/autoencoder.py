@@ -6,11 +6,10 @@ and seed-for-seed initial weights.
 A ``MultiEncoder`` / ``MultiDecoder`` runs all its articulators in ONE launch per direction (``as_multi_mlp_fwd`` /
 ``as_multi_mlp_bwd``, artspeech_amd/csrc/multi_mlp.hip): the encoder reads its slices of the (rows, A, in_features) input and
 takes the maximum over the articulators that own each latent index inside the kernel (tanh fused when the autoencoder applies
-it), the decoder gathers its latent indices and stacks its outputs.  Widths beyond the kernel's LDS budget, or
-``ARTSPEECH_PC_MLP=grouped`` (A/B runs), take the per-articulator path: every Linear a ``GroupedLinear`` GEMM, the slicing /
-max over articulators torch glue.
+it), the decoder gathers its latent indices and stacks its outputs.  Widths beyond the kernel's LDS budget, or every width
+while ``FUSED_MLP`` is set to False (A/B runs), take the per-articulator path: every Linear a ``GroupedLinear`` GEMM, the
+slicing / max over articulators torch glue.
 """
-import os
 from enum import Enum
 
 import torch
@@ -21,8 +20,7 @@ from ....helpers import make_indices_dict
 from ...transformer.ops import GroupedLinear
 
 
-def _fused_enabled():
-    return os.environ.get("ARTSPEECH_PC_MLP", "fused") != "grouped"
+FUSED_MLP = True  # False: the per-articulator GEMM path at every width (A/B hook of the tests and tools/bench_pc_training.py)
 
 
 def _linear(x, W, b, relu):
@@ -320,7 +318,7 @@ class _MultiMlpFn(torch.autograd.Function):
 
 def _single(x, W, b):
     """One projection x [..., K] -> [..., N] (a PCAEncoder / PCADecoder on its own): the fused kernel with one group."""
-    if not _fused_enabled():
+    if not FUSED_MLP:
         return _linear(x.reshape(-1, x.shape[-1]).float(), W, b, False).reshape(*x.shape[:-1], W.shape[0])
     N, K = W.shape
     plan = _single_plan(K, N)
@@ -363,7 +361,7 @@ class MultiEncoder(nn.Module):
 
     def _forward(self, x, tanh):
         _lib.require_gpu(x, "x")
-        if _fused_enabled() and self._plan.supported:
+        if FUSED_MLP and self._plan.supported:
             modules = [self.encoders[a] for a in self.sorted_articulators]
             return _MultiMlpFn.apply(self._plan, 1.0, int(tanh), x, *_fused_params(modules))
         lead = x.shape[:-2]
@@ -394,7 +392,7 @@ class MultiDecoder(nn.Module):
         """x (..., latent_size) -> (..., n_articulators, in_features); ``scale`` multiplies the input inside the kernel
         (AutoencoderLoss2's rescale_factor)."""
         _lib.require_gpu(x, "x")
-        if _fused_enabled() and self._plan.supported:
+        if FUSED_MLP and self._plan.supported:
             modules = [self.decoders[a] for a in self.sorted_articulators]
             return _MultiMlpFn.apply(self._plan, float(scale), 0, x, *_fused_params(modules))
         if scale != 1.0:

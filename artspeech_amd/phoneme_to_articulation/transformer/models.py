@@ -97,8 +97,8 @@ def _reference_order_state(vocab_size, A, d, heads, L, nf):
 
 
 # generate(): reuse the step-invariant memory-side K/V and restrict the last layer to the newest frame (both exact);
-# ARTSPEECH_GENERATE_PLAIN=1 (or setting this to False) re-decodes everything like the reference, for A/B timing.
-GENERATE_SAVINGS = os.environ.get("ARTSPEECH_GENERATE_PLAIN") is None
+# setting this to False re-decodes everything like the reference, for A/B timing.
+GENERATE_SAVINGS = True
 
 
 class ArtSpeechTransformer(nn.Module):

@@ -18,14 +18,21 @@ SLAB_FLOATS = 20 << 20   # split-K slabs / stream-K pieces (80 MB); as_gemm_f32 
 _c = _lib.contiguous
 
 # Precision of the forward linears of the modules built on these ops (as_gemm.precision): "f32" = exact fp32 MFMA,
-# "bf16x6" / "bf16x3" = fp32 operands split on the fly into 3 / 2 bf16 pieces on the bf16 MFMA, fp32 accumulation.
 # "lib" = the library's matrix arithmetic (as_set_matrix_arith: split fp32 on the bf16 matrix instruction unless the process chose
 # the exact fp32 one) for the forward linears, at any size.  Measured at configs[3] (d=256, L=6, B=32, T=200): forward + backward
 # 186.8 -> 172.7 ms; the full-width model's contours against the REFERENCE fixture then sit at 1.19 x the 1e-4 bound (0.89 x with
 # "f32": two correct fp32 roundings of a 6-layer network differ by about that much), so the default stays "f32": by default only
 # the backward's GEMMs (input and weight gradients, GRAD_PRECISION below) use the split arithmetic.
-PRECISIONS = {"f32": 0, "bf16x3": 1, "bf16x6": 2, "lib": 3}
-GEMM_PRECISION = PRECISIONS[os.environ.get("ARTSPEECH_GEMM_PRECISION", "f32")]
+PRECISIONS = {"f32": 0, "lib": 3}
+
+
+def _precision(name, what):
+    if name not in PRECISIONS:
+        raise ValueError(f"{what}={name!r}: accepted values are {', '.join(PRECISIONS)}")
+    return PRECISIONS[name]
+
+
+GEMM_PRECISION = _precision(os.environ.get("ARTSPEECH_GEMM_PRECISION", "f32"), "ARTSPEECH_GEMM_PRECISION")
 
 
 # Precision of the backward's GEMMs -- input gradients (dx = dz W, with their residual / ReLU-mask / segmented-reduction operands)
@@ -33,14 +40,14 @@ GEMM_PRECISION = PRECISIONS[os.environ.get("ARTSPEECH_GEMM_PRECISION", "f32")]
 # (configs[3]: 218 ms all-fp32 -> 186.8 ms).  The parity tests hold gradients to a yardstick relative to their own magnitude and the split
 # product is at least as accurate as the fp32 instruction's (tests/test_gpu_parity.py::test_split_matrix_arithmetic_error_vs_fp64),
 # so nothing a forward value is compared with depends on this.  ARTSPEECH_GRAD_PRECISION=f32 keeps them on the fp32 instruction.
-GRAD_PRECISION = PRECISIONS[os.environ.get("ARTSPEECH_GRAD_PRECISION", "lib")]
+GRAD_PRECISION = _precision(os.environ.get("ARTSPEECH_GRAD_PRECISION", "lib"), "ARTSPEECH_GRAD_PRECISION")
 
 
 def set_gemm_precision(name, grad=None):
     global GEMM_PRECISION, GRAD_PRECISION
-    GEMM_PRECISION = PRECISIONS[name]
-    if grad is not None:
-        GRAD_PRECISION = PRECISIONS[grad]
+    gemm = _precision(name, "set_gemm_precision: name")
+    grad = GRAD_PRECISION if grad is None else _precision(grad, "set_gemm_precision: grad")   # both checked before either is set
+    GEMM_PRECISION, GRAD_PRECISION = gemm, grad
 
 
 def _gemm(**kw):
@@ -237,8 +244,7 @@ class GroupedLinear(torch.autograd.Function):
         return dx, dW, db, None, None
 
 
-FUSED_DS = os.environ.get("ARTSPEECH_UNFUSED_DS") is None  # ablation: dP GEMM + as_attn_softmax_bwd_t instead of as_attention_bwd_ds
-FUSED_ATTENTION = os.environ.get("ARTSPEECH_UNFUSED_ATTENTION") is None  # ablation switch (tools/bench_attention.py)
+FUSED_ATTENTION = True  # False: scores GEMM -> softmax -> PV GEMM at every shape (A/B hook of the tests and tools/bench_attention.py)
 _MASK_T = {}  # id(mask tensor) -> (weak reference to it, (version, Tk, T), key-major copy)
 
 
@@ -332,13 +338,8 @@ def attention_backward(saved, B, heads, scale, dctx, dQ=None, dK=None, dV=None, 
         upper = dict(k_tri=2, precision=0) if causal else {}   # reduction over keys, rows = q: zero for key > q
         # dV = P^T dctx
         _gemm(A=Pt, B=dctx, C=dV, M=Tk, N=dh, K=T, a_i=Tp, a_k=1, b_j=1, b_k=d, ldc=d, batch=Z, a_off=zp, b_off=zq, c_off=zk, **lower)
-        if FUSED_DS:
-            # dS^T = P^T o (V dctx^T - D) * scale in one kernel: dP is never formed
-            _lib.call("as_attention_bwd_ds_causal" if causal else "as_attention_bwd_ds", V, dctx, out, Pt, dPt, G, B, heads, T, Tk, d, scale)
-        else:
-            _gemm(A=V, B=dctx, C=dPt, M=Tk, N=T, K=dh, a_i=d, a_k=1, b_j=d, b_k=1, ldc=Tp, batch=Z, a_off=zk, b_off=zq, c_off=zp)
-            dsum = torch.empty((Z, T), dtype=torch.float32, device=dev)
-            _lib.call("as_attn_softmax_bwd_t", Pt, dPt, out, dctx, dsum, G, B, heads, T, Tk, d, scale)
+        # dS^T = P^T o (V dctx^T - D) * scale in one kernel: dP is never formed
+        _lib.call("as_attention_bwd_ds_causal" if causal else "as_attention_bwd_ds", V, dctx, out, Pt, dPt, G, B, heads, T, Tk, d, scale)
         # dQ = dS K (dS read through its transpose) ; dK = dS^T Q
         _gemm(A=dPt, B=K, C=dQ, M=T, N=dh, K=Tk, a_i=1, a_k=Tp, b_j=1, b_k=d, ldc=d, batch=Z, a_off=zp, b_off=zk, c_off=zq, **upper)
         _gemm(A=dPt, B=Q, C=dK, M=Tk, N=dh, K=T, a_i=Tp, a_k=1, b_j=1, b_k=d, ldc=d, batch=Z, a_off=zp, b_off=zq, c_off=zk, **lower)
@@ -411,9 +412,8 @@ def channel_blocks_forward(xt, xs, q_w, q_b, k_w, k_b, v_w, v_b, in_w, in_b, o_w
     ncb = (d + 31) // 32
     qbits = torch.empty((G, R, ncb), dtype=torch.int32, device=dev) if training else None
     kvbits = torch.empty((2 * G, Rs, ncb), dtype=torch.int32, device=dev) if training else None
-    lib_or_exact = 3 if GEMM_PRECISION == 3 else 0   # (the on-the-fly split kernels of as_gemm.precision 1 / 2 have no bit-image epilogue)
-    bq = dict(relu_bits=qbits, relu_bits_batch=R * ncb, precision=lib_or_exact) if training else {}
-    bkv = dict(relu_bits=kvbits, relu_bits_batch=Rs * ncb, precision=lib_or_exact) if training else {}
+    bq = dict(relu_bits=qbits, relu_bits_batch=R * ncb) if training else {}
+    bkv = dict(relu_bits=kvbits, relu_bits_batch=Rs * ncb) if training else {}
     _gemm(A=xt, B=W3, C=q, bias=b3, M=R, N=d, K=d, a_i=d, a_k=1, b_j=d, b_k=1, ldc=d, batch=G, a_off=t_off, b_batch=d * d,
           c_batch=R * d, bias_batch=d, act=1, **bq)
     # MHA in-projection: slice j of the stacked [G, 3d, d] weight, read in place

@@ -238,9 +238,7 @@ typedef struct as_gemm {
        multi-channel transformer decoder, whose 132 attention blocks per layer read/write irregular
        (channel, head) slices. */
     const int64_t* a_off; const int64_t* b_off; const int64_t* c_off; const int64_t* bias_off;
-    /* 0: exact fp32 on the f32 MFMA (default).  1 / 2: forward linears (a_k == b_k == 1, float4-clean operands) may run on
-       the bf16 MFMA with every fp32 element split on the fly into 2 / 3 bf16 pieces and the product rebuilt from 3 / 6
-       cross terms with fp32 accumulation (error ~2^-16 / ~2^-23 of sum |a||b|); other shapes silently stay exact.
+    /* 0: exact fp32 on the f32 MFMA (default).
        3: the library's current matrix arithmetic (as_set_matrix_arith): in mode 1 the shapes gemm_s6.hip's kernel takes run on
        the bf16 matrix instruction with both operands split exactly into three planes inside the kernel, whatever their size --
        forward (a_k == b_k == 1; plain or relu_bits epilogue), input gradient (a_k == 1, b_j == 1; with res / mask_bits / k_seg)
@@ -248,7 +246,7 @@ typedef struct as_gemm {
        K % 16 == 0, float4-clean operands.  Anything else, and mode 0, as 0.  The transformer modules use it for every backward
        GEMM (ARTSPEECH_GRAD_PRECISION, default "lib": 218 -> 187 ms at configs[3]) and offer it for the forward ones
        (ARTSPEECH_GEMM_PRECISION=lib: 173 ms; the full-width contours then sit at 1.19 x the 1e-4 bound against the reference
-       fixture, 0.89 x with 0: default 0). */
+       fixture, 0.89 x with 0: default 0).  Any other value is refused (AS_ERR_BAD_ARG). */
     int32_t precision;
     int32_t b_kshift_batch;
     /* optional hint for weight-gradient shapes (a_i == b_j == 1 with splitk_ws): the number of CUs the launch can expect to
@@ -256,7 +254,7 @@ typedef struct as_gemm {
        split-K factor depends on it, never the result's summation order for a given factor. */
     int32_t cu_budget;
     /* optional extra operands of the general kernel (forward / input-gradient shapes with a reduction-contiguous A; refused
-       together with colsum, splitk_ws, accumulate, split precision and weight-gradient shapes):
+       together with colsum, splitk_ws, accumulate and weight-gradient shapes):
            C = keep ? act(res + acc + bias) : 0
        res       [.][M][N] through (res_ld, res_batch | res_off): the INITIAL VALUE of the accumulators (loaded while the
                  first operand tiles are staged: no extra pass, no epilogue loads); the sum is (res + sum_k in k order) +
@@ -438,7 +436,8 @@ int as_attn_softmax_bwd(const float* probs, float* dprobs, int64_t Z, int32_t Tq
  *   lse              : optional [G*B*heads][T] log-sum-exp of every score row (what a recomputing backward needs), or NULL
  *   probs_t          : optional [G*B*heads][Tk][Tp] the probabilities, KEY-major, rows padded to Tp = T rounded up to a multiple
  *                      of 32 floats (columns >= T are not written; a 32-query segment of a row is then one 128-byte line)
- *                      (training: consumed by the grouped GEMMs of the backward and by as_attn_softmax_bwd_t), or NULL
+ *                      (training: as_attention_bwd_ds forms dS^T = P^T o (V dctx^T - D) * scale from it and the grouped GEMMs of
+ *                      the backward consume both), or NULL
  *                      (inference: nothing but `out` is written)
  * Scores and probabilities stay in registers (the unfused path writes G*B*heads*T*Tk floats twice).  A fully masked query
  * row yields NaN, as in PyTorch. */
@@ -454,17 +453,10 @@ int as_attention_fwd_causal(const float* Q, const float* K, const float* V, cons
                             float* out, float* lse, float* probs_t, int32_t G, int32_t B, int32_t heads, int32_t T, int32_t Tk,
                             int32_t d, float scale, void* stream);
 
-/* Softmax backward on KEY-major tensors, in place on dprobs_t:  dS^T[k][q] = P^T[k][q] * (dP^T[k][q] - D[q]) * scale with
- * D[q] = sum_c dctx[q][c] * ctx[q][c] over the head's dh columns (= sum_k P dP, without a second pass over the scores).
- *   probs_t, dprobs_t : [G*B*heads][Tk][Tp], Tp = T rounded up to 32      ctx, dctx : [G][B*T][d] (attention output and its gradient)
- *   dsum              : workspace of G*B*heads*T floats (receives D); dh = d / heads in {16, 32, 64} */
-int as_attn_softmax_bwd_t(const float* probs_t, float* dprobs_t, const float* ctx, const float* dctx, float* dsum, int32_t G,
-                          int32_t B, int32_t heads, int32_t T, int32_t Tk, int32_t d, float scale, void* stream);
-
-/* Backward of the attention core, first half, without a dP tensor:
+/* Backward of the attention core, first half, without a dP tensor:  dS^T = P^T o (V dctx^T - D) * scale, that is
  *   ds_t[z][k][q] = probs_t[z][k][q] * (sum_c V_h[k][c] dctx[q][h*dh + c] - D[q]) * scale,   D[q] = sum_c dctx[q][c] ctx[q][c]
- * (= as_attn_softmax_bwd_t applied to dP^T = V dctx^T).  Shapes as as_attention_fwd; ds_t [G*B*heads][Tk][Tp] is what the
- * two remaining grouped GEMMs (dQ = dS K, dK = dS^T Q) read. */
+ * over the head's dh columns (D = sum_k P dP, without a second pass over the scores).  Shapes as as_attention_fwd; ds_t
+ * [G*B*heads][Tk][Tp] is what the two remaining grouped GEMMs (dQ = dS K, dK = dS^T Q) read. */
 int as_attention_bwd_ds(const float* V, const float* dctx, const float* ctx, const float* probs_t, float* ds_t, int32_t G, int32_t B,
                         int32_t heads, int32_t T, int32_t Tk, int32_t d, float scale, void* stream);
 /* The same when the forward's additive mask was -inf above the diagonal for every utterance (both decoder masks of

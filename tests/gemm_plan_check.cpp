@@ -2,7 +2,7 @@
 //   gemm_plan_check ROWS   ROWS: one descriptor per line, `name field=value ...`; a pointer field's value is 0 (absent) or 16 + the
 //                          low four bits of its address
 // Part 1 prints, for every row in both matrix arithmetics, the kernel the plan names as the kernel trace would show it, the reduce
-// kernel behind it, the work items, the weight-gradient kernels' items per XCD, splitk and kchunk.  Part 2 plans 20 000 seeded
+// kernel behind it, the work items, the weight-gradient kernels' items per XCD, splitk and kchunk.  Part 2 plans 30 000 seeded
 // random descriptors and checks what must hold for every one of them; the first violation is printed and the exit status is 1.
 #include <stdint.h>
 #include <stdio.h>
@@ -29,7 +29,6 @@ std::string kernel_name(const as_gemm_plan& p) {
             if (p.ext) snprintf(s, sizeof s, "gemm_f32_kernel<%d, %d, %s, %s, true, true>", p.tile_m, p.tile_n, tf(p.a_kc), tf(p.a_kc && p.b_kc));
             else snprintf(s, sizeof s, "gemm_f32_kernel<%d, %d, %s, %s, %s, false>", p.tile_m, p.tile_n, tf(p.a_kc), tf(p.b_kc), tf(p.fast));
             break;
-        case AS_GEMM_SPLIT: snprintf(s, sizeof s, "gemm_split_nt_kernel<%d, %d, %d>", p.tile_m, p.tile_n, p.planes); break;
         case AS_GEMM_S6: snprintf(s, sizeof s, "gemm_s6_kernel<%s, %s, %s>", tf(p.anc), tf(p.anc || p.bnc), tf(!p.anc && p.ext)); break;
         default: snprintf(s, sizeof s, "wgrad_f32_kernel<%d, %s, %s>", p.tile_n, tf(p.family == AS_GEMM_WGRAD_STREAMK), tf(p.split_arith));
     }
@@ -50,7 +49,7 @@ std::string reduce_name(const as_gemm_plan& p, int kind) {
 // every field of a plan, for comparing two plans
 std::string dump(const as_gemm_plan& p) {
     char s[512];
-    snprintf(s, sizeof s, "%d %d %d %d %d%d%d%d%d%d%d%d%d%d%d %d %d %d %d %d %d %d %d %d %d %ld %ld", p.family, p.tile_m, p.tile_n, p.planes, p.a_kc,
+    snprintf(s, sizeof s, "%d %d %d %d%d%d%d%d%d%d%d%d%d%d %d %d %d %d %d %d %d %d %d %d %ld %ld", p.family, p.tile_m, p.tile_n, p.a_kc,
              p.b_kc, p.anc, p.bnc, p.fast, p.ext, p.split_arith, p.a_vec, p.b_vec, p.c_vec, p.vec_epi, p.k_tri, p.splitk, p.kchunk, p.reduce,
              p.reduce_fallback, p.xcd_panels, p.xcd_chunks, p.xcd_group, p.nkt, p.per_xcd, p.unit_per_wg, p.work);
     return s;
@@ -132,8 +131,8 @@ long stride(Rng& r, long least) {   // >= least: tight, padded to a multiple of 
 
 int sweep() {
     Rng r{0x9E3779B97F4A7C15ull};
-    long plans = 0, errors = 0, by_family[5] = {}, by_reduce[6] = {};
-    for (int i = 0; i < 20000; ++i) {
+    long plans = 0, errors = 0, by_family[4] = {}, by_reduce[6] = {};
+    for (int i = 0; i < 30000; ++i) {   // a third of the draws ask for a precision that is refused
         as_gemm g{};
         const bool wshape = r.chance(35), fwd = !wshape && r.chance(50);
         g.M = size(r); g.N = size(r); g.K = size(r);
@@ -188,6 +187,7 @@ int sweep() {
             p.family = -1;
             char err[512] = "";
             const int rc = as_gemm_plan_make(&g, &ENV[arith], &p, err, sizeof err);
+            if (g.precision != 0 && g.precision != 3) CHECK(rc == AS_ERR_BAD_ARG);   // 1 and 2 (once the on-the-fly split kernels) included
             if (rc != 0) {   // exactly one of an error or a plan
                 CHECK(rc == AS_ERR_BAD_ARG && err[0] != 0 && strncmp(err, "as_gemm_f32: ", 13) == 0 && p.family == -1);
                 ++errors;
@@ -198,11 +198,9 @@ int sweep() {
             char err2[512] = "";
             CHECK(as_gemm_plan_make(&g, &ENV[arith], &q, err2, sizeof err2) == 0 && dump(p) == dump(q));   // planning is a pure function
             ++plans; ++by_family[p.family]; ++by_reduce[p.reduce];
-            // the fp32 arithmetic never runs the library's split arithmetic (the on-the-fly kernels of precision 1 / 2 are asked
-            // for by name and run in either mode)
+            // the fp32 arithmetic never runs the library's split arithmetic
             if (arith == AS_ARITH_FP32) CHECK(p.family != AS_GEMM_S6 && !p.split_arith);
             CHECK(p.family != AS_GEMM_S6 || g.precision == 3);
-            CHECK(p.family != AS_GEMM_SPLIT || ((g.precision == 1 || g.precision == 2) && p.planes == g.precision + 1));
             const bool wgrad = p.family == AS_GEMM_WGRAD || p.family == AS_GEMM_WGRAD_STREAMK;
             const int ktile = wgrad ? AS_WGRAD_BK : AS_GEMM_BK;
             CHECK(p.splitk >= 1 && (g.splitk_ws || (p.splitk == 1 && p.family != AS_GEMM_WGRAD_STREAMK)));
@@ -223,8 +221,8 @@ int sweep() {
             if (p.k_tri) CHECK(p.family == AS_GEMM_GENERAL && p.ext && p.k_tri == g.k_tri);
         }
     }
-    printf("sweep: %ld plans, %ld refusals; families %ld %ld %ld %ld %ld; reduces %ld %ld %ld %ld %ld %ld\n", plans, errors, by_family[0], by_family[1],
-           by_family[2], by_family[3], by_family[4], by_reduce[0], by_reduce[1], by_reduce[2], by_reduce[3], by_reduce[4], by_reduce[5]);
+    printf("sweep: %ld plans, %ld refusals; families %ld %ld %ld %ld; reduces %ld %ld %ld %ld %ld %ld\n", plans, errors, by_family[0], by_family[1],
+           by_family[2], by_family[3], by_reduce[0], by_reduce[1], by_reduce[2], by_reduce[3], by_reduce[4], by_reduce[5]);
     for (long n : by_family) if (n < 20) { printf("sweep: a kernel family was planned fewer than 20 times\n"); return 1; }
     for (long n : by_reduce) if (n < 20) { printf("sweep: a reduce kind was planned fewer than 20 times\n"); return 1; }
     if (errors < 1000) { printf("sweep: fewer than 1000 refusals\n"); return 1; }

@@ -242,18 +242,18 @@ def test_ds_kernels(dev, T, Tk, dh, causal):
             assert (got[:, above] == 0).all(), f"{fn.__name__}: dS^T above the diagonal"
 
 
-_ROUTES = (("fused", True, True), ("unfused dS", True, False), ("unfused", False, True))
+_ROUTES = (("fused", True), ("unfused", False))
 
 
 @pytest.mark.parametrize("T,Tk,dh,causal", [(80, 80, 32, True), (150, 150, 16, True), (200, 200, 64, True), (33, 33, 64, True),
                                             (300, 256, 32, True), (300, 300, 16, True), (70, 150, 64, False), (96, 80, 16, False),
                                             (129, 129, 32, False), (300, 513, 16, False), (64, 1024, 32, False), (257, 257, 64, True),
                                             (40, 700, 24, False)])
-def test_attention_gradients_three_routes(dev, T, Tk, dh, causal):
-    """(dQ, dK, dV) of ops.Attention against float64 autograd by the fused dS kernel, by the dP GEMM + as_attn_softmax_bwd_t
-    (its float4 kernel at T % 4 == 0, its scalar one otherwise) and by the unfused forward and backward.  Where
-    as_attention_supported says no -- Tk > 256 (every utterance longer than 256 frames: as_attn_softmax at NW = 8 and 16) or a
-    head width outside {16, 32, 64} (dh = 24) -- all three settings take the unfused route, the only one there is."""
+def test_attention_gradients_both_routes(dev, T, Tk, dh, causal):
+    """(dQ, dK, dV) of ops.Attention against float64 autograd by the fused forward with the fused dS kernel and by the unfused
+    forward and backward.  Where as_attention_supported says no -- Tk > 256 (every utterance longer than 256 frames:
+    as_attn_softmax at NW = 8 and 16) or a head width outside {16, 32, 64} (dh = 24) -- both settings take the unfused route,
+    the only one there is."""
     ops = _ops()
     _lib, L = _L()
     G, B, h = 1, 3, 2
@@ -266,8 +266,8 @@ def test_attention_gradients_three_routes(dev, T, Tk, dh, causal):
     gref = torch.autograd.grad(_ref(Qd, Kd, Vd, am, kpm, B, h)[0], (Qd, Kd, Vd), go.double())
     fusable = bool(L.as_attention_supported(T, Tk, d, h))
     assert fusable == (Tk <= 256 and dh in (16, 32, 64))
-    for route, fused_att, fused_ds in _ROUTES:
-        ops.FUSED_ATTENTION, ops.FUSED_DS = fused_att, fused_ds
+    for route, fused_att in _ROUTES:
+        ops.FUSED_ATTENTION = fused_att
         try:
             q, k, v = (t.clone().requires_grad_() for t in (Q, K, V))
             out = ops.Attention.apply(q, k, v, am, kpm, B, h)
@@ -275,7 +275,7 @@ def test_attention_gradients_three_routes(dev, T, Tk, dh, causal):
             assert out.grad_fn.causal == (causal and fused_att and fusable), route
             got = torch.autograd.grad(out, (q, k, v), go)
         finally:
-            ops.FUSED_ATTENTION, ops.FUSED_DS = True, True
+            ops.FUSED_ATTENTION = True
         for name, a_, r_ in zip("QKV", got, gref):
             _close(a_, r_, 2e-5, f"{route} T={T} Tk={Tk} dh={dh}: d{name}")
 

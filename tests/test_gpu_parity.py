@@ -115,29 +115,6 @@ def test_gemm_nn_tn(dev, M, N, K):
                  atol=2e-5 * np.sqrt(K), what="tn+acc")
 
 
-@pytest.mark.parametrize("M,N,K", [(500, 200, 264), (128, 128, 32), (1, 5, 4), (6400, 256, 256)])
-def test_gemm_split_precision(dev, M, N, K):
-    """as_gemm.precision: fp32 operands split into bf16 pieces on the bf16 MFMA.  Three pieces (six cross terms) are
-    fp32-grade, two pieces (three terms) ~2^-16; shapes the split kernel does not take (K % 4 != 0) stay exact."""
-    rng = np.random.RandomState(M + N + K)
-    a, b, bias = rng.randn(M, K).astype(np.float32), rng.randn(N, K).astype(np.float32), rng.randn(N).astype(np.float32)
-    ref = np.maximum(a.astype(np.float64) @ b.astype(np.float64).T + bias, 0)
-    scale = (np.abs(a).astype(np.float64) @ np.abs(b).astype(np.float64).T).max()
-    for precision, tol in ((2, 5e-7), (1, 8e-6)):
-        c = run_gemm(dev, T_(a, dev), T_(b, dev), M, N, K, K, 1, K, 1, bias=T_(bias, dev), act=1, precision=precision)
-        err = np.abs(c.cpu().numpy().reshape(M, N) - ref).max()
-        assert err <= tol * scale, (precision, err / scale)
-    # accumulate + batched through the split kernel
-    c0 = T_(rng.randn(M * N).astype(np.float32), dev)
-    c = run_gemm(dev, T_(a, dev), T_(b, dev), M, N, K, K, 1, K, 1, accumulate=1, C0=c0, precision=2)
-    want = a.astype(np.float64) @ b.astype(np.float64).T + c0.cpu().numpy().reshape(M, N)
-    assert np.abs(c.cpu().numpy().reshape(M, N) - want).max() <= 5e-7 * scale
-    # a reduction-strided operand keeps the exact kernel whatever the request
-    bt = np.ascontiguousarray(b.T)
-    c = run_gemm(dev, T_(a, dev), T_(bt, dev), M, N, K, K, 1, 1, N, precision=1)
-    assert_close(c.cpu().numpy().reshape(M, N), a.astype(np.float64) @ bt, rtol=2e-5, atol=2e-5 * np.sqrt(K), what="nn exact")
-
-
 @pytest.fixture
 def matrix_arith():
     """tests that switch the library's matrix arithmetic restore the default (1 = split) afterwards"""

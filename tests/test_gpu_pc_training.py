@@ -249,7 +249,7 @@ def test_widths_beyond_the_lds_budget_take_the_grouped_path(dev):
 # ------------------------------------------------------------------------------------------------ 3. fused vs grouped
 def test_autoencoder_fused_matches_grouped(dev, monkeypatch):
     from artspeech_amd.phoneme_to_articulation.principal_components.losses import RegularizedLatentsMSELoss2
-    from artspeech_amd.phoneme_to_articulation.principal_components.models import MultiArticulatorAutoencoder
+    from artspeech_amd.phoneme_to_articulation.principal_components.models import MultiArticulatorAutoencoder, autoencoder
     torch.manual_seed(4)
     comps = {a: c for a, c in zip(ARTS, (3, 2, 4, 12, 3))}
     m = MultiArticulatorAutoencoder(100, comps, hidden_features=50).to(dev)
@@ -258,7 +258,7 @@ def test_autoencoder_fused_matches_grouped(dev, monkeypatch):
     w = torch.rand(700, device=dev)
     results = {}
     for mode in ("fused", "grouped"):
-        monkeypatch.setenv("ARTSPEECH_PC_MLP", mode)
+        monkeypatch.setattr(autoencoder, "FUSED_MLP", mode == "fused")
         m.zero_grad(set_to_none=True)
         out, lat = m(x)
         loss = crit(out, lat, x, w)

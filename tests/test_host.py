@@ -557,6 +557,24 @@ def test_key_major_mask_is_transposed_padded_and_cached():
     assert mt2 is not mt and mt2[0, 0, 0] == 7.0
 
 
+def test_unknown_gemm_precision_name_is_refused_by_name():
+    """ARTSPEECH_GEMM_PRECISION accepts `f32` and `lib`; a retired or misspelt name stops the import of transformer.ops with a
+    ValueError that lists both, and so does set_gemm_precision."""
+    import subprocess
+    import sys
+    from artspeech_amd.phoneme_to_articulation.transformer import ops
+    run = subprocess.run([sys.executable, "-c", "import artspeech_amd.phoneme_to_articulation.transformer.ops"], cwd=ROOT,
+                         env={**os.environ, "ARTSPEECH_GEMM_PRECISION": "bf16x6"}, capture_output=True, text=True)
+    assert run.returncode != 0
+    last = run.stderr.strip().splitlines()[-1]
+    assert last.startswith("ValueError: ARTSPEECH_GEMM_PRECISION='bf16x6'") and "f32" in last and "lib" in last, run.stderr[-2000:]
+    keep = ops.GEMM_PRECISION, ops.GRAD_PRECISION
+    for args in (("bf16",), ("lib", "bf16x6")):
+        with pytest.raises(ValueError, match=r"f32, lib"):
+            ops.set_gemm_precision(*args)
+        assert (ops.GEMM_PRECISION, ops.GRAD_PRECISION) == keep   # a refused call changes neither
+
+
 def test_bench_self_launch_builds_a_child_torchrun_command(monkeypatch):
     """`python bench.py --gpus N` outside torchrun: the parent spawns `python -m torch.distributed.run --nnodes=1
     --nproc-per-node N --master-addr 127.0.0.1 ... bench.py <same flags>` as a CHILD (subprocess, never exec), falls back to the

@@ -1,6 +1,6 @@
 #!/usr/bin/env python
 """Step times of the principal-components method's training at thesis sizes, fused multi-articulator MLP kernel against the
-per-articulator GEMM path (ARTSPEECH_PC_MLP=grouped), the two arms alternating in one process:
+per-articulator GEMM path (autoencoder.FUSED_MLP = False), the two arms alternating in one process:
 
   (a) AutoencoderLoss2 forward + backward: B=12, T=200, 10 articulators, in 100 / hidden 50 (25 in the middle),
       35 components, TVs LA / TTCD / TBCD, frozen encoder and decoder;
@@ -98,25 +98,26 @@ def main():
     ap.add_argument("--rounds", type=int, default=5)
     args = ap.parse_args()
     assert torch.cuda.is_available(), "bench_pc_training measures on an MI355X"
+    from artspeech_amd.phoneme_to_articulation.principal_components.models import autoencoder
     dev = torch.device("cuda:0")
     with tempfile.TemporaryDirectory() as tmp:
         wl = workloads(dev, tmp)
         for name, fn in wl.items():
             times = {"fused": [], "grouped": []}
             for mode in times:
-                os.environ["ARTSPEECH_PC_MLP"] = mode
+                autoencoder.FUSED_MLP = mode == "fused"
                 for _ in range(args.warmup):
                     fn()
             for _ in range(args.rounds):
                 for mode in times:
-                    os.environ["ARTSPEECH_PC_MLP"] = mode
+                    autoencoder.FUSED_MLP = mode == "fused"
                     times[mode].append(timed(fn, args.iters))
             for mode, ts in times.items():
                 ts = sorted(ts)
                 print(json.dumps({"workload": name, "path": mode, "ms_median": round(ts[len(ts) // 2], 4),
                                   "ms_min": round(ts[0], 4), "ms_max": round(ts[-1], 4), "iters": args.iters,
                                   "rounds": args.rounds}), flush=True)
-        os.environ.pop("ARTSPEECH_PC_MLP", None)
+        autoencoder.FUSED_MLP = True
 
 
 if __name__ == "__main__":
