@@ -4,12 +4,15 @@
 // Part 1 prints, for every row in both matrix arithmetics, the kernel the plan names as the kernel trace would show it, the reduce
 // kernel behind it, the work items, the weight-gradient kernels' items per XCD, splitk and kchunk.  Part 2 plans 30 000 seeded
 // random descriptors and checks what must hold for every one of them; the first violation is printed and the exit status is 1.
+// It then prints the distinct (kernel, reduce kernel) pairs the sweep planned, one `pair: KERNEL | REDUCE` line each (a plan that
+// sums by arrival counters as `counters/FALLBACK`), ahead of its summary line: the test requires a device-tested row for each.
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
 
 #include <fstream>
+#include <set>
 #include <sstream>
 #include <string>
 #include <type_traits>
@@ -132,6 +135,7 @@ long stride(Rng& r, long least) {   // >= least: tight, padded to a multiple of 
 int sweep() {
     Rng r{0x9E3779B97F4A7C15ull};
     long plans = 0, errors = 0, by_family[4] = {}, by_reduce[6] = {};
+    std::set<std::string> pairs;
     for (int i = 0; i < 30000; ++i) {   // a third of the draws ask for a precision that is refused
         as_gemm g{};
         const bool wshape = r.chance(35), fwd = !wshape && r.chance(50);
@@ -198,6 +202,7 @@ int sweep() {
             char err2[512] = "";
             CHECK(as_gemm_plan_make(&g, &ENV[arith], &q, err2, sizeof err2) == 0 && dump(p) == dump(q));   // planning is a pure function
             ++plans; ++by_family[p.family]; ++by_reduce[p.reduce];
+            pairs.insert(kernel_name(p) + " | " + reduce_name(p, p.reduce));
             // the fp32 arithmetic never runs the library's split arithmetic
             if (arith == AS_ARITH_FP32) CHECK(p.family != AS_GEMM_S6 && !p.split_arith);
             CHECK(p.family != AS_GEMM_S6 || g.precision == 3);
@@ -221,6 +226,7 @@ int sweep() {
             if (p.k_tri) CHECK(p.family == AS_GEMM_GENERAL && p.ext && p.k_tri == g.k_tri);
         }
     }
+    for (const std::string& pair : pairs) printf("pair: %s\n", pair.c_str());
     printf("sweep: %ld plans, %ld refusals; families %ld %ld %ld %ld; reduces %ld %ld %ld %ld %ld %ld\n", plans, errors, by_family[0], by_family[1],
            by_family[2], by_family[3], by_reduce[0], by_reduce[1], by_reduce[2], by_reduce[3], by_reduce[4], by_reduce[5]);
     for (long n : by_family) if (n < 20) { printf("sweep: a kernel family was planned fewer than 20 times\n"); return 1; }

@@ -6,7 +6,9 @@ tests in test_gpu_parity.py and the descriptors the Python call sites pose at th
 the same rows on the GPU) -- in both matrix arithmetics; EXPECTED below is what the kernel trace of those rows showed on an
 MI355X (256 CUs; 768 resident workgroups of the 128 x 128 kernel; 8192 arrival counters) BEFORE the planner existed
 (profiles/gemm_plan_equivalence.log): kernel name, reduce kernel, grid in workgroups, and where the grid shows it the split-K
-factor with the chunk length that follows from it (every row has both: see the note above the table).  Its second part is a seeded sweep of 30 000 random descriptors."""
+factor with the chunk length that follows from it (every row has both: see the note above the table).  Its second part is a seeded
+sweep of 30 000 random descriptors, which also lists every (kernel, reduce kernel) pair it planned: each must be the plan of a row
+that a device test runs (the gemm_plans[...] rows of test_gpu_gemm_plans.py and the rows named after tests of test_gpu_parity.py)."""
 import json
 import os
 import re
@@ -18,7 +20,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 # A row without a workspace cannot split: splitk 1, kchunk K, whatever its grid.  Four rows with a workspace have grids that do not
 # show the split (gemm_split_k_paths[6400-256-768-1]/*: a grid clamped to the resident slots, slabs summed by arrival counters;
 # ops.py:226#1, #3: a weight-gradient grid rounded up to whole XCD rounds); theirs was printed by the code before the planner, built
-# with one fprintf in front of those launches (profiles/gemm_plan_equivalence.log).
+# with one fprintf in front of those launches (profiles/gemm_plan_equivalence.log).  The gemm_plans[...] entries at the end of the table
+# are of another kind: the planner's own output, recorded when the rows were added (see the note above them).
 EXPECTED = {
     "gemm_nt[64-64-32]": ("gemm_f32_kernel<64, 64, true, true, true, false> - 1 1 32",),
     "gemm_nt[200-100-128]": ("gemm_f32_kernel<64, 64, true, true, true, false> - 8 1 128",),
@@ -324,6 +327,65 @@ EXPECTED = {
     "rnn_ops.py:84": ("gemm_f32_kernel<64, 64, false, false, true, false> - 768 16 416",),
     "rnn_ops.py:89": ("gemm_f32_kernel<64, 64, false, false, true, false> splitk_reduce4_kernel 600 50 128",),
     "rnn_ops.py:89#1": ("gemm_f32_kernel<64, 64, false, false, true, false> splitk_reduce4_kernel 600 50 128",),
+    # gemm_plans[...]: the rows tests/test_gpu_gemm_plans.py runs on the device, one per (kernel, reduce kernel) pair the planner can
+    # name and per path inside one (tile numbering, epilogue, shifted operand).  No trace stands behind these: each entry is what the
+    # planner printed for the row in the commit that added the row, so they pin the planner to itself from then on.
+    "gemm_plans[otkc_slow]": ("gemm_f32_kernel<64, 64, false, true, false, false> - 2 1 33",),
+    "gemm_plans[otkc_fast]": ("gemm_f32_kernel<64, 64, false, true, true, false> - 1 1 64",),
+    "gemm_plans[otkc_colsum]": ("gemm_f32_kernel<64, 64, false, true, true, false> - 6 1 64",),
+    "gemm_plans[t128_nt_fast]": ("gemm_f32_kernel<128, 128, true, true, true, false> - 512 1 32",),
+    "gemm_plans[t128_nt_slow]": ("gemm_f32_kernel<128, 128, true, true, false, false> - 512 1 33",),
+    "gemm_plans[t128_nn]": ("gemm_f32_kernel<128, 128, true, false, true, false> - 512 1 40",),
+    "gemm_plans[t128_tn]": ("gemm_f32_kernel<128, 128, false, false, true, false> - 512 1 40",),
+    "gemm_plans[t128_otkc]": ("gemm_f32_kernel<128, 128, false, true, true, false> - 512 1 40",),
+    "gemm_plans[t128_splitk]": ("gemm_f32_kernel<128, 128, true, true, true, false> splitk_reduce_kernel 1536 3 704",),
+    "gemm_plans[t128_splitk_tn]": ("gemm_f32_kernel<128, 128, false, false, false, false> splitk_reduce_kernel 1536 3 704",),
+    "gemm_plans[panels]": ("gemm_f32_kernel<128, 128, true, true, true, false> - 2058 1 32",),
+    "gemm_plans[sk_counters]": ("gemm_f32_kernel<64, 64, false, false, false, false> - 16 8 64",),
+    "gemm_plans[sk_counters_dx]": ("gemm_f32_kernel<64, 64, true, false, true, false> - 60 10 64",),
+    "gemm_plans[sk_r4]": ("gemm_f32_kernel<64, 64, false, false, true, false> splitk_reduce4_kernel 136 34 64",),
+    "gemm_plans[sk_shift]": ("gemm_f32_kernel<64, 64, false, false, true, false> - 12 6 96",),
+    "gemm_plans[wg128_sk]": ("wgrad_f32_kernel<128, true, false> wgrad_reduce_sk_kernel<128> 16 1 3328",
+        "wgrad_f32_kernel<128, true, true> wgrad_reduce_sk_kernel<128> 16 1 3328"),
+    "gemm_plans[wg256_sk]": ("wgrad_f32_kernel<256, true, false> wgrad_reduce_sk_kernel<256> 16 1 3328",
+        "wgrad_f32_kernel<256, true, true> wgrad_reduce_sk_kernel<256> 16 1 3328"),
+    "gemm_plans[wg_split]": ("wgrad_f32_kernel<256, false, false> wgrad_reduce_kernel 64 4 1056",
+        "wgrad_f32_kernel<256, false, true> wgrad_reduce_kernel 64 4 1056"),
+    "gemm_plans[wg_split128]": ("wgrad_f32_kernel<128, false, false> wgrad_reduce_kernel 64 4 1056",
+        "wgrad_f32_kernel<128, false, true> wgrad_reduce_kernel 64 4 1056"),
+    "gemm_plans[wg_whole]": ("wgrad_f32_kernel<128, false, false> - 64 1 1056",
+        "wgrad_f32_kernel<128, false, true> - 64 1 1056"),
+    "gemm_plans[wg_shift]": ("wgrad_f32_kernel<256, false, false> wgrad_reduce_kernel 64 4 1056",
+        "wgrad_f32_kernel<256, false, true> wgrad_reduce_kernel 64 4 1056"),
+    "gemm_plans[wg_shift_nows]": ("wgrad_f32_kernel<256, false, false> - 16 1 4160",
+        "wgrad_f32_kernel<256, false, true> - 16 1 4160"),
+    "gemm_plans[s6_anc]": ("gemm_f32_kernel<64, 64, false, false, true, false> - 768 1 48",
+        "gemm_s6_kernel<true, true, false> - 256 1 48"),
+    "gemm_plans[s6_anc_novec]": ("gemm_f32_kernel<64, 64, false, false, true, false> - 768 1 48",
+        "gemm_s6_kernel<true, true, false> - 256 1 48"),
+    "gemm_plans[s6_bnc]": ("gemm_f32_kernel<64, 64, true, false, true, false> - 6 1 48",
+        "gemm_s6_kernel<false, true, false> - 3 1 48"),
+    "gemm_plans[tri1_128]": ("gemm_f32_kernel<128, 128, true, false, true, true> - 512 1 256",),
+    "gemm_plans[tri2_128]": ("gemm_f32_kernel<128, 128, false, false, true, true> - 512 1 256",),
+    "gemm_plans[ext128_ragged]": ("gemm_f32_kernel<128, 128, true, true, true, true> - 512 1 64",),
+    "gemm_plans[ext64_tri2]": ("gemm_f32_kernel<64, 64, false, false, true, true> - 6 1 72",),
+    "gemm_plans[ext64_dx_mask]": ("gemm_f32_kernel<64, 64, true, false, true, true> - 6 1 64",),
+    "gemm_plans[t128_tn_slow]": ("gemm_f32_kernel<128, 128, false, false, false, false> - 512 1 40",),
+    "gemm_plans[t128_nn_slow]": ("gemm_f32_kernel<128, 128, true, false, false, false> - 512 1 40",),
+    "gemm_plans[t128_splitk_nn_slow]": ("gemm_f32_kernel<128, 128, true, false, false, false> splitk_reduce_kernel 1536 3 704",),
+    "gemm_plans[t128_splitk_nn]": ("gemm_f32_kernel<128, 128, true, false, true, false> splitk_reduce_kernel 1536 3 704",),
+    "gemm_plans[t128_splitk_nt_slow]": ("gemm_f32_kernel<128, 128, true, true, false, false> splitk_reduce_kernel 1536 3 704",),
+    "gemm_plans[sk_nn_slow_c]": ("gemm_f32_kernel<64, 64, true, false, false, false> - 16 8 64",),
+    "gemm_plans[sk_nt_slow_c]": ("gemm_f32_kernel<64, 64, true, true, false, false> - 16 8 64",),
+    "gemm_plans[sk_nt_c]": ("gemm_f32_kernel<64, 64, true, true, true, false> - 32 8 64",),
+    "gemm_plans[sk_tn_slow_c4]": ("gemm_f32_kernel<64, 64, false, false, false, false> - 32 16 64",),
+    "gemm_plans[sk_nn_slow_c4]": ("gemm_f32_kernel<64, 64, true, false, false, false> - 32 16 64",),
+    "gemm_plans[sk_nt_slow_c4]": ("gemm_f32_kernel<64, 64, true, true, false, false> - 32 16 64",),
+    "gemm_plans[sk_nt_c4]": ("gemm_f32_kernel<64, 64, true, true, true, false> - 64 16 64",),
+    "gemm_plans[sk_tn_slow_r4]": ("gemm_f32_kernel<64, 64, false, false, false, false> splitk_reduce4_kernel 68 34 64",),
+    "gemm_plans[sk_nn_slow_r4]": ("gemm_f32_kernel<64, 64, true, false, false, false> splitk_reduce4_kernel 68 34 64",),
+    "gemm_plans[sk_nt_slow_r4]": ("gemm_f32_kernel<64, 64, true, true, false, false> splitk_reduce4_kernel 68 34 64",),
+    "gemm_plans[sk_nt_r4]": ("gemm_f32_kernel<64, 64, true, true, true, false> splitk_reduce4_kernel 136 34 64",),
 }
 
 
@@ -348,8 +410,12 @@ def test_planner_decision_table_and_sweep(tmp_path):
     assert run.returncode == 0 and run.stderr == "", run.stdout[-2000:] + run.stderr[-4000:]
     lines = run.stdout.splitlines()
     assert re.fullmatch(r"sweep: \d+ plans, \d+ refusals; .*", lines[-1]), lines[-1]
+    swept = {line[len("pair: "):] for line in lines if line.startswith("pair: ")}
+    assert len(swept) >= 40, sorted(swept)
     got = {}
     for line in lines[:-1]:
+        if line.startswith("pair: "):
+            continue
         name, rest = line.split(" arith=")
         got[(name, int(rest[0]))] = rest[2:]
     assert len(got) == 2 * len(rows)
@@ -379,3 +445,52 @@ def test_planner_decision_table_and_sweep(tmp_path):
             if not ok:
                 wrong.append((name, arith, w, g))
     assert not wrong, wrong[:10]
+    # closure: whatever the planner can name for a legal descriptor runs on the device in a kernel-level test.  The call-site rows
+    # (file.py:line) do not count: the suite reaches them only inside whole-model checks.
+    tested = set()
+    for (name, arith), g in got.items():
+        m = re.fullmatch(r"(.*) reduce=(\S+) work=.*", g)
+        if m and not re.match(r"\w+\.py:\d+", name):
+            tested.add(m.group(1) + " | " + m.group(2))
+    assert not swept - tested, sorted(swept - tested)
+
+
+def test_fp64_reference_against_a_scalar_loop():
+    """tests/gemm_fp64.py, the yardstick of test_gpu_gemm_plans.py, against the header's formula written out element by element of C:
+    strides, overlapping batch windows, the shifted B operand and its zeros.  Every legal row of modest size poses, and no NaN
+    (an element the descriptor does not address) reaches its reference."""
+    import numpy as np
+
+    import gemm_fp64 as G
+    with open(os.path.join(ROOT, "tests", "golden", "gemm_plan_rows.json")) as f:
+        rows = {r["name"]: r for r in json.load(f)}
+    for name in ("gemm_plans[sk_shift]", "gemm_shift_batched", "gemm_plans[otkc_slow]"):
+        r = rows[name]
+        ops = G.pose(r, np.random.RandomState(2))
+        A, B = ops["A"], ops["B"]
+        want = np.zeros((r["batch"], r["M"], r["N"]))
+        for g in range(r["batch"]):
+            s = r["b_kshift"] + g * r["b_kshift_batch"]
+            k = np.arange(r["K"])
+            live = (k % r["b_kT"] + s >= 0) & (k % r["b_kT"] + s < r["b_kT"]) if r["b_kT"] > 0 else np.ones(r["K"], bool)
+            kb = k[live] + (s if r["b_kT"] > 0 else 0)
+            for i in range(r["M"]):
+                for j in range(r["N"]):
+                    a = A.data[A.start + g * r["a_batch"] + i * r["a_i"] + k[live] * r["a_k"]].astype(np.float64)
+                    b = B.data[B.start + g * r["b_batch"] + j * r["b_j"] + kb * r["b_k"]].astype(np.float64)
+                    want[g, i, j] = float(np.dot(a, b))
+        got = G.reference(r, ops)["C"]
+        assert not np.isnan(want).any() and np.abs(got - want).max() <= 1e-12 * np.abs(want).max(), name
+    posed = 0
+    for name, want in EXPECTED.items():
+        r = rows[name]
+        if want[0] == "refused" or 2.0 * r["M"] * r["N"] * r["K"] * r["batch"] > 2e6:
+            continue
+        ops = G.pose(r, np.random.RandomState(posed))
+        ref = G.reference(r, ops)
+        assert not np.isnan(ref["C"]).any() and (ref["colsum"] is None or not np.isnan(ref["colsum"]).any()), name
+        for k, o in ops.items():
+            if isinstance(o, G.Operand):
+                assert o.start * 4 % 16 == r[k] % 16 and o.data.size - int(np.flatnonzero(o.addressed)[-1]) > 4, (name, k)
+        posed += 1
+    assert posed >= 30
