@@ -202,6 +202,8 @@ PROTOTYPES = {
     "as_resample_fwd": (_I32, [_P, _I32, _I64, _P, _I32, _I32, _I32, _P, _P, _I32, _I32, _I32, _I32, _F, _P, _I64, _I64, _P, _S]),
     "as_contour_spline": (_I32, [_P, _I64, _I64, _I64, _I64, _I32, _I32, _I32, _D, _I32, _P, _I32, _I32, _P, _I64, _P, _S]),
     "as_vocal_tract_tube": (_I32, [_P, _I64, _I64, _I64, _I64, _I64, _I32, _I32, _P, _I32, _I32, _P, _I32, _I32, _P, _I64, _P, _P, _P, _S]),
+    "as_vt_acoustics": (_I32, [_P, _I64, _I64, _P, _I64, _I64, _P, _I64, _I32, _D, _D, _I32, _I32, _D, _D, _D, _I32, _I32, _P, _P, _P, _P,
+                              _P, _P, _S]),
     "as_tsne_workspace_bytes": (_I64, [_I32]),
     "as_tsne_sqdist": (_I32, [_P, _I64, _I32, _I32, _P, _S]),
     "as_tsne_joint_p": (_I32, [_P, _I32, _D, _P, _P, _P, _P, _P, _I64, _S]),

@@ -52,6 +52,7 @@ SOURCES = {
     "resample.hip": [],
     "contour_spline.hip": [],
     "vocal_tract_tube.hip": ["-ffp-contract=off"],
+    "vt_acoustics.hip": [],
     "tsne.hip": [],
     "artspeech.hip": [],
 }

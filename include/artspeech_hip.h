@@ -1064,6 +1064,38 @@ int as_vocal_tract_tube(const float* contours, int64_t s_frame, int64_t s_art, i
                         int32_t M, double* air, int64_t ld_out, int32_t* status, int32_t* junctions, double* wall_length,
                         void* stream);
 
+/* Vocal-tract acoustics (artspeech_amd/csrc/vt_acoustics.hip): the volume-velocity transfer function and the formants of every
+ * frame's tube, in one launch.  The reference has no acoustic stage (its area_function.py is imported by nothing): the
+ * definition is THIS PROJECT'S OWN, an ASSUMPTION whose parity with any other synthesiser is unpinned.  It has closed-form
+ * answers instead: a uniform tube closed at the glottis resonates at (2n - 1) c / 4L.  Lossless walls, float64 throughout:
+ *   sections    K per frame, glottis -> lips: area A_i (cm^2) at areas[f a_frame + i a_sec], length l_i (cm) at lengths[f l_frame
+ *               + i l_sec] (element strides; l_frame = 0 shares one row of lengths among the frames)
+ *   counts [frames] int32, optional, on the device: frame f uses its first counts[f] sections (all K without it; a count above
+ *               K reads K)
+ *   grid        f_j = f0 + j df, j = 0 .. F-1, f0 > 0, df > 0
+ *   chain       k = 2 pi f / c, z_i = rho c / A_i, M_i = [[cos k l_i, j z_i sin k l_i], [j sin(k l_i) / z_i, cos k l_i]],
+ *               [[A, B], [C, D]] = M_1 M_2 ... M_K with the glottis on the left
+ *   radiation   0: ideal open end, Z = 0.  1: Flanagan's piston in a baffle on the last section, a = sqrt(A_K / pi),
+ *               ka = 2 pi f a / c, Z = (rho c / A_K) ((ka)^2 / 2 + j 8 ka / (3 pi))
+ *   den, transfer [frames][F] complex128 (real, imaginary; 16-byte aligned): den = C Z + D and H = U_lips / U_glottis = 1 / den
+ *   formants    on g = |den|^2.  Coarse minima: bins j in 1 .. F-2 with g_j < g_{j-1} and g_j <= g_{j+1}, in increasing j, the
+ *               first n_formants.  Refinement, `rounds` times: the bracket starts as [f_{j-1}, f_{j+1}]; g at lo + (hi - lo) m /
+ *               65, m = 1 .. 64; the lowest value wins, among equals the lowest m; the new bracket is that point +- (hi - lo) /
+ *               65.  freq [frames][n_formants]: the last bracket's midpoint, i.e. the last winner (f_j when rounds = 0; the
+ *               bracket is 2 df (2 / 65)^rounds wide); level: -10 log10 g there, the value that won (g_j when rounds = 0);
+ *               found [frames] int32; the slots not found hold NaN
+ *   status [frames] int32: bit 0 = some used A_i < min_area (a closure, as in a stop consonant: computed as min_area; not an
+ *               error), bit 1 = a non-finite area or length, a length <= 0 or counts[f] < 1 (every output of the frame is NaN,
+ *               found = 0; no other frame is touched by it)
+ * Every output pointer is optional.  No atomics, every choice in a fixed order: two launches give equal bits, a frame alone or
+ * in a batch gives equal bits.  Limits, refused with AS_ERR_BAD_ARG before any launch: 1 <= K <= 1024 (the area function's own),
+ * 3 <= F <= 4096, 0 <= n_formants <= 8, 0 <= rounds <= 6, radiation 0 or 1, c, rho, min_area > 0; frames = 0 launches nothing.
+ * Left out: wall, viscous and heat losses, formant bandwidths, a nasal branch, a time-domain waveform. */
+int as_vt_acoustics(const double* areas, int64_t a_frame, int64_t a_sec, const double* lengths, int64_t l_frame, int64_t l_sec,
+                    const int32_t* counts, int64_t frames, int32_t K, double f0, double df, int32_t F, int32_t radiation, double c,
+                    double rho, double min_area, int32_t n_formants, int32_t rounds, double* den, double* transfer, double* freq,
+                    double* level, int32_t* found, int32_t* status, void* stream);
+
 /* Exact t-SNE of the recogniser's features (artspeech_amd/csrc/tsne.hip).  The reference draws model_features.pdf with
  * sklearn.manifold.TSNE(n_components=2).fit_transform (phoneme_recognition/__init__.py:355-356); the four entry points below are
  * that routine's device work, stage by stage.  No float atomics; every sum that crosses a workgroup goes through the workspace
