@@ -204,6 +204,9 @@ PROTOTYPES = {
     "as_vocal_tract_tube": (_I32, [_P, _I64, _I64, _I64, _I64, _I64, _I32, _I32, _P, _I32, _I32, _P, _I32, _I32, _P, _I64, _P, _P, _P, _S]),
     "as_vt_acoustics": (_I32, [_P, _I64, _I64, _P, _I64, _I64, _P, _I64, _I32, _D, _D, _I32, _I32, _D, _D, _D, _I32, _I32, _P, _P, _P, _P,
                               _P, _P, _S]),
+    "as_vt_glottal_source": (_I32, [_P, _P, _P, _P, _I32, _I32, _I32, _D, C.c_uint64, _D, _D, _P, _I64, _P, _S]),
+    "as_vt_waveguide": (_I32, [_P, _I64, _I64, _I64, _P, _P, _I32, _I32, _I32, _I32, _P, _P, _P, C.c_uint64, _D, _D, _D, _D, _I32, _P, _P,
+                              _I64, _P, _S]),
     "as_tsne_workspace_bytes": (_I64, [_I32]),
     "as_tsne_sqdist": (_I32, [_P, _I64, _I32, _I32, _P, _S]),
     "as_tsne_joint_p": (_I32, [_P, _I32, _D, _P, _P, _P, _P, _P, _I64, _S]),

@@ -53,6 +53,7 @@ SOURCES = {
     "contour_spline.hip": [],
     "vocal_tract_tube.hip": ["-ffp-contract=off"],
     "vt_acoustics.hip": [],
+    "vt_synth.hip": [],
     "tsne.hip": [],
     "artspeech.hip": [],
 }

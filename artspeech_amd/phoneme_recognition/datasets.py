@@ -236,6 +236,28 @@ def read_wav(path):
     return torch.from_numpy(samples.astype(np.int16)), rate
 
 
+def write_wav(path, samples, sample_rate):
+    """Write (n,) samples as a mono 16-bit PCM WAV file with the standard library's ``wave`` and return ``path``.  int16 samples go
+    out as they are, so ``read_wav(write_wav(path, x, rate))`` gives x back; floating-point samples are read as full scale = 1:
+    round(value x 32768) to the nearest, halves to even, clipped to [-32768, 32767] (read_wav's value / 32768, inverted).
+    ``sample_rate`` must be a whole number of Hz, which is all the format holds."""
+    samples = torch.as_tensor(samples).detach().cpu().reshape(-1)
+    if samples.dtype != torch.int16:
+        if not samples.dtype.is_floating_point:
+            raise ValueError(f"write_wav: samples are int16 or floating point, got {samples.dtype}")
+        if not bool(torch.isfinite(samples).all()):
+            raise ValueError(f"write_wav: {path}: non-finite samples")
+        samples = torch.round(samples.double() * 32768.0).clamp(-32768, 32767).to(torch.int16)
+    if int(sample_rate) != sample_rate or sample_rate <= 0:
+        raise ValueError(f"write_wav: a WAV file holds a whole positive sample rate, got {sample_rate}")
+    with wave.open(str(path), "wb") as f:
+        f.setnchannels(1)
+        f.setsampwidth(2)
+        f.setframerate(int(sample_rate))
+        f.writeframes(samples.numpy().astype("<i2").tobytes())
+    return path
+
+
 class RecordedAcousticRecognitionDataset(Dataset):
     """Recordings with phoneme intervals, for ``feature: melspec``: ``manifest`` is a JSON file (or the list itself) of
     ``{"audio_filepath": a 16-bit PCM WAV, relative paths taken from the manifest's folder, "phonemes": [[token, start, end], ...]}``

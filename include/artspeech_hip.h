@@ -1096,6 +1096,64 @@ int as_vt_acoustics(const double* areas, int64_t a_frame, int64_t a_sec, const d
                     double rho, double min_area, int32_t n_formants, int32_t rounds, double* den, double* transfer, double* freq,
                     double* level, int32_t* found, int32_t* status, void* stream);
 
+/* Speech from the tube (artspeech_amd/csrc/vt_synth.hip): a glottal source and a time-domain Kelly-Lochbaum waveguide whose
+ * sections vary in time.  The reference has no acoustic stage: the definition is THIS PROJECT'S OWN, an ASSUMPTION whose parity
+ * with any other synthesiser is unpinned.  Its closed forms: a uniform ladder of K sections resonates at (2n - 1) fs / 4K, and
+ * a static ladder's impulse response is the direct solve of its 2K steady-state equations.  All arithmetic and state: float64.
+ * Conventions of both entry points:
+ *   B utterances of T frame slots, (B, T) arrays contiguous; frames [B] int32 on the device, read into [0, T]: utterance b uses
+ *   frames[b] frames.  S >= 1 samples per frame: frame t sits at sample t S, utterance b has n_b = frames[b] S samples, and the
+ *   sample rate is fs = S x the frame rate.  A per-frame control x is read at sample n as x[n] = x_t + (x_t' - x_t) (s / S),
+ *   t = n div S, s = n mod S, t' = min(t + 1, frames[b] - 1): the last frame is held.  Output rows have a pitch >= T S; the
+ *   samples n_b .. pitch - 1 are written as 0 and nothing behind the pitch is written.  T S < 2^31, S <= 2^24.
+ *   noise       nu(seed, stream, b, n): idx = ((2 b + stream) << 40) | n, z = seed + (idx + 1) 0x9E3779B97F4A7C15 mod 2^64,
+ *               z = (z ^ (z >> 30)) 0xBF58476D1CE4E5B9, z = (z ^ (z >> 27)) 0x94D049BB133111EB, z ^= z >> 31 (the splitmix64
+ *               finaliser of as_dropout_fwd), u = (z >> 11) 2^-53, nu = 2 u - 1 in [-1, 1): exact in float64.  Stream 0 is
+ *               aspiration, stream 1 frication.
+ * as_vt_glottal_source: f0 (Hz), voiced_amp, asp_amp (B, T) float64 -> source (B, pitch) float64.
+ *   phase       g_t = max(f0_t, 0) per frame, g[n] interpolated as above (so g[n] = max(g[n], 0): never negative);
+ *               phase[n] = sum_{m < n} g[m] / fs, evaluated as base_t + (g_t s + (g_t' - g_t) (s (s - 1) / 2) / S) / fs with
+ *               base_t = sum_{u < t} (g_u S + (g_u' - g_u) (S - 1) / 2) / fs: a scan over frames and a closed form per sample
+ *   pulse       theta = phase - floor(phase); Rosenberg: theta < rise: (1 - cos(pi theta / rise)) / 2; rise <= theta < rise +
+ *               fall: cos(pi (theta - rise) / (2 fall)); otherwise 0.  Continuous everywhere, the wrap included.
+ *   source[n] = voiced_amp[n] pulse(theta) + asp_amp[n] nu(seed, 0, b, n)
+ *   status [B]  optional int32: bit 1 = a non-finite f0, voiced_amp or asp_amp in a used frame: the row's n_b samples are NaN
+ *               and no other row is touched.  rise, fall > 0, rise + fall <= 1 (defaults of the package: 0.40, 0.16).
+ * as_vt_waveguide: section 0 is the glottis, K_b - 1 the lips; every section is c / fs long, one sample of delay each way (the
+ * length appears nowhere else).
+ *   areas       A (cm^2) of section j of frame t of utterance b at areas[b a_utt + t a_frame + j a_sec] (element strides),
+ *               rows of Kmax sections; sections [B] int32 on the device: K_b in [1, min(64, Kmax)]
+ *   per frame   A = max(A, min_area), k_j = (A_j - A_{j+1}) / (A_j + A_{j+1}), j = 0 .. K-2.  The reflection coefficients, not
+ *               the areas, are interpolated per sample (a convex combination keeps |k| < 1 and the division off the sample path)
+ *   state       right-going R_i and left-going L_i pressure waves, zero at n = 0.  Per sample, the right-hand sides from the
+ *               state before:   y = (1 + r_l) R_{K-1};  out[n] = y - y_prev (radiation 1, "difference"; y_prev = 0 at n = 0)
+ *               or y (radiation 0, "none");
+ *                 w_j      = k_j[n] (R_j - L_{j+1})                 j = 0 .. K-2
+ *                 R'_{j+1} = mu ((R_j + w_j) + e_{j+1}[n])
+ *                 L'_j     = mu (L_{j+1} + w_j)
+ *                 R'_0     = mu (source[n] + r_g L_0)
+ *                 L'_{K-1} = mu (r_l R_{K-1})
+ *   frication   inject_section (B, T) int32 and inject_gain (B, T) float64, both or neither: e_i[n] = inject_gain[n] nu(seed,
+ *               1, b, n) when i == inject_section[t] and 0 otherwise; the section is constant over a frame (-1: none, and the
+ *               gain is not multiplied in), the gain is interpolated
+ *   out64 (B, pitch) float64, out32 (B, pitch) float32 = out64 rounded; either may be NULL
+ *   status [B]  optional int32: bit 0 = some used area below min_area, computed as min_area (a closure, not an error); bit 1 =
+ *               a non-finite or non-positive area, or a non-finite source sample or gain, in a used frame: that utterance's
+ *               n_b samples are NaN and no other utterance is touched
+ * Refused before any launch, never truncated: K_b outside [1, 64] (AS_ERR_UNSUPPORTED); K_b > Kmax, an inject_section of a used
+ * frame outside {-1} and [1, K_b - 1], a pitch below T S (AS_ERR_BAD_ARG).  To refuse, as_vt_waveguide reads sections, frames
+ * and inject_section back and waits for `stream` once before its launch.  B = 0 launches nothing; frames[b] = 0 writes the zeros
+ * alone.  No atomics: two launches give equal bits, an utterance alone or in a batch gives equal bits.  Defaults of the package,
+ * plausible but this project's own: r_g = 0.75, r_l = -0.85, mu = 0.999, min_area = 1e-4.
+ * Left out: a nasal branch, wall vibration and frequency-dependent losses, a two-mass glottis, more than 64 sections. */
+int as_vt_glottal_source(const double* f0, const double* voiced_amp, const double* asp_amp, const int32_t* frames, int32_t B,
+                         int32_t T, int32_t S, double sample_rate, uint64_t seed, double rise, double fall, double* source,
+                         int64_t pitch, int32_t* status, void* stream);
+int as_vt_waveguide(const double* areas, int64_t a_utt, int64_t a_frame, int64_t a_sec, const int32_t* sections,
+                    const int32_t* frames, int32_t B, int32_t T, int32_t Kmax, int32_t S, const double* source,
+                    const int32_t* inject_section, const double* inject_gain, uint64_t seed, double r_g, double r_l, double mu,
+                    double min_area, int32_t radiation, double* out64, float* out32, int64_t pitch, int32_t* status, void* stream);
+
 /* Exact t-SNE of the recogniser's features (artspeech_amd/csrc/tsne.hip).  The reference draws model_features.pdf with
  * sklearn.manifold.TSNE(n_components=2).fit_transform (phoneme_recognition/__init__.py:355-356); the four entry points below are
  * that routine's device work, stage by stage.  No float atomics; every sum that crosses a workgroup goes through the workspace
